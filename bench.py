@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- particle-steps/s of the particle-robot update loop on MI355X: the headline line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2]): 10^6 oscillating bots on a square lattice (pitch 0.155:
 jammed and dense for the whole run, ~57 candidate pairs per bot; DESIGN.md section 5 says why not the hexagonal one) in
@@ -14,15 +14,25 @@ the form that writes everything the reference's collideD writes (particlebot_ker
 sums, `attraction_sums: 1`).  `value` is over the wall clock of the K steps (barrier + device synchronisation on both
 sides, MAX over ranks); `roofline.avg_launch_us` is the HIP-event time of those same K launches on the simulation's
 stream / K, priced at SURVEY 8(d)'s 64 algorithmic bytes per particle-step.  The library's DEFAULT form for the
-reference's default parameters (constrained_contraction 0: Sum|F_attr| has no reader and is not computed, 56 B) is
-timed right after it and reported as `default_form`.
+reference's default parameters (constrained_contraction 0: Sum|F_attr| has no reader and is not computed, 56 B) is,
+with --full, timed right after it and reported as `default_form`.
 
 N > 1 (torch.distributed.run, one rank per GPU; a bare `python bench.py --gpus N` starts the N ranks itself as a child
 process): a single arena does not shard (neighbour forces couple every cell each step), so every rank steps its own
 arena -- an ensemble member with its own seed -- with no collective in the timed region; the per-arena summaries are
-gathered over RCCL afterwards (`collective`).  At every N the line also carries BASELINE configs[3] as written -- 256 +
-256 Monte-Carlo seeds of the obstacle and object-transport examples at full length, member k on rank k mod N, summary
-rows gathered over RCCL -- end to end (`ensemble`).
+gathered over RCCL afterwards (`collective`).  With --full, at every N the line also carries BASELINE configs[3] as
+written -- 256 + 256 Monte-Carlo seeds of the obstacle and object-transport examples at full length, member k on rank
+k mod N, summary rows gathered over RCCL -- end to end (`ensemble`).
+
+A plain run does only what its headline needs: set-up, the pre-warm, W warm-up steps, the K timed steps, the outputs
+(--dump-outputs) and the line.  Everything else it measures runs with --full only: the default form (`default_form`),
+the CPU baseline (`cpu_baseline`), configs[3] end to end (`ensemble`) and the second timed region of >= 100 ms behind a
+region under 50 ms (`roofline.long`).
+
+--dump-outputs DIR: what the K timed steps computed, as a caller of the path receives it (pbSimGetState: pos, vel, rad,
+phase, dead, absForce_a, absForce_r of rank 0's arena after its last timed step), written as DIR/<name>.npy in float32
+-- a fixed, seeded sample of the bots when the whole state exceeds 64 MB.  The inputs depend on the arguments only, so
+two builds can be compared output for output.
 
 The line stays under 4 KB; everything else goes to bench_detail.json (and stderr).  Every other leg -- streamlined
 kernel, 8 x 10^6 bots, random blob, host round trip, the configs[3]/[4] workloads on their own -- is
@@ -74,10 +84,12 @@ def timed_arena(pb, args, rank, world, dist, torch, warm):
     s1 = sim.stats()
     assert done == args.steps, (done, args.steps)
     launches = (s1["fused_launches"] - s0["fused_launches"]) + (s1["plain_launches"] - s0["plain_launches"])
-    # a timed region under 50 ms of device time (the driver's --steps 20 is ~2 ms) is followed at once by one of
-    # >= 100 ms of the same simulation, reported beside it (`long`)
+    # what the K timed steps computed, read back before anything else steps this simulation (--dump-outputs)
+    outputs = sim.get_state() if args.dump_outputs and rank == 0 else None
+    # with --full, a timed region under 50 ms of device time (the driver's --steps 20 is ~2 ms) is followed at once by
+    # one of >= 100 ms of the same simulation, reported beside it (`long`)
     long = None
-    if dev_ms < K.SHORT_MS:
+    if args.full and dev_ms < K.SHORT_MS:
         k = min(int(K.LONG_MS / max(dev_ms / done, 1e-6)) + 1, 400000)
         d2, ms2 = sim.step_timed(k)
         long = {"steps": d2, "avg_launch_us": ms2 * 1e3 / max(d2, 1)}
@@ -86,7 +98,33 @@ def timed_arena(pb, args, rank, world, dist, torch, warm):
     summary = [sim.time, cx, cy]
     sim.close()
     return {"wall": wall, "dev_ms": dev_ms, "launches": launches, "long": long, "summary": summary, "cfg": cfg,
-            "kernel": kernel, "prewarm": prewarm}
+            "kernel": kernel, "prewarm": prewarm}, outputs
+
+
+DUMP_MAX_BYTES = 60_000_000   # (under 64 MB however counted, .npy headers included)
+
+
+def dump_outputs(state, out_dir, max_bytes=DUMP_MAX_BYTES):
+    """state (Sim.get_state) -> out_dir/<name>.npy in float32, every bot when the arrays fit max_bytes, else the same
+    fixed, seeded sample of bots in every array (its indices in bot_index.npy, float64).  Returns what was written."""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in state.items() if v is not None}
+    n = len(next(iter(arrays.values())))
+    per_bot = sum(a[0].size for a in arrays.values()) * 4
+    idx = None
+    if n * per_bot > max_bytes:
+        keep = max_bytes // (per_bot + 8)   # (the index array counts towards the budget too)
+        idx = np.sort(np.random.default_rng(20240601).choice(n, size=keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in sorted(arrays.items()):
+        a = np.ascontiguousarray((a if idx is None else a[idx]).astype(np.float32))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    if idx is not None:
+        np.save(os.path.join(out_dir, "bot_index.npy"), idx.astype(np.float64))
+        written["bot_index"] = [len(idx)]
+    return written
 
 
 def default_form_leg(pb, n, steps, warmup, warm):
@@ -127,8 +165,12 @@ def main():
                     help="device time of scratch work right before every timed leg (clock ramp; never timed); 0 disables")
     ap.add_argument("--cpu-seconds", type=float, default=4.0,
                     help="time budget of the cpu_baseline sample on all usable cores (+ a quarter of it on one thread)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ensemble", action="store_true", help="skip the configs[3] end-to-end run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: default_form, cpu_baseline, ensemble, roofline.long")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the K timed steps computed (rank 0's arena) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline sample")
+    ap.add_argument("--no-ensemble", action="store_true", help="with --full: skip the configs[3] end-to-end run")
     ap.add_argument("--e2e-steps", type=int, default=None, help="bound the timesteps per member of the configs[3] run")
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the long record goes")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL even with one rank (the N>1 code path)")
@@ -156,8 +198,9 @@ def main():
     n = args.bots
     K.HEADLINE_FORCE_SUMS = 1   # the scratch arena runs the headline's kernel
     warm = K.DevicePrewarm(pb, min(n, 1_000_000), K.LATTICE_PITCH, args.prewarm_ms)
-    h = timed_arena(pb, args, rank, world, dist, torch, warm)
+    h, state = timed_arena(pb, args, rank, world, dist, torch, warm)
     phases["headline"] = time.perf_counter() - t_start
+    dumped = dump_outputs(state, args.dump_outputs) if state is not None else None
     wall, summaries, coll = h["wall"], [h["summary"]], None
     if dist is not None:
         t = torch.tensor([wall], dtype=torch.float64, device=K.dist_device())
@@ -171,8 +214,10 @@ def main():
         coll = K.collective_info(dist, torch, local_rank, dev)
     warm.done()
     # (the arenas are closed before the ensemble: with their streams alive the two batches land on one hardware queue)
-    ens, ens_detail = (None, None) if args.no_ensemble else configs3_end_to_end(rank, world, dist, torch, args.e2e_steps)
-    phases["ensemble"] = time.perf_counter() - t_start
+    ens, ens_detail = None, None
+    if args.full and not args.no_ensemble:
+        ens, ens_detail = configs3_end_to_end(rank, world, dist, torch, args.e2e_steps)
+        phases["ensemble"] = time.perf_counter() - t_start
 
     if rank == 0:
         avg_us = h["dev_ms"] * 1e3 / max(h["launches"], 1)
@@ -200,16 +245,18 @@ def main():
                           "parallelism": "single arena" if world == 1 else f"{world} independent arenas, one per GPU"},
                "roofline": roof, "device_ms_timed_region": h["dev_ms"], "collective": coll}
         detail = {"headline": h, "summaries_time_comx_comy": summaries, "host": K.host_info(),
-                  "build": K.loaded_build_stamp(), "profile_both_sums": tr, "ensemble": ens_detail}
-        K.HEADLINE_FORCE_SUMS = 0
-        warm = K.DevicePrewarm(pb, min(n, 1_000_000), K.LATTICE_PITCH, args.prewarm_ms)
-        out["default_form"], detail["default_form"] = default_form_leg(pb, n, min(args.steps, 400),
-                                                                       max(args.warmup, 100), warm)
-        warm.done()
-        phases["default_form"] = time.perf_counter() - t_start
+                  "build": K.loaded_build_stamp(), "profile_both_sums": tr, "ensemble": ens_detail,
+                  "outputs": {"dir": args.dump_outputs, "arrays": dumped} if dumped else None}
+        if args.full:
+            K.HEADLINE_FORCE_SUMS = 0
+            warm = K.DevicePrewarm(pb, min(n, 1_000_000), K.LATTICE_PITCH, args.prewarm_ms)
+            out["default_form"], detail["default_form"] = default_form_leg(pb, n, min(args.steps, 400),
+                                                                           max(args.warmup, 100), warm)
+            warm.done()
+            phases["default_form"] = time.perf_counter() - t_start
         if ens is not None:
             out["ensemble"] = ens
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             c = K.cpu_baseline(n, K.LATTICE_PITCH, args.cpu_seconds)
             detail["cpu_baseline"] = c
             out["cpu_baseline"] = {k: c[k] for k in ("value", "unit", "cores", "value_1_thread", "kind", "sample")}

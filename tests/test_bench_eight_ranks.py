@@ -97,8 +97,8 @@ def test_eight_rank_configs4_line(tmp_path):
 def test_eight_rank_headline_line_is_small_and_names_eight_devices(tmp_path):
     """The driver's SCALE form of bench.py on eight ranks: the line obeys the 4 KB limit, the process group reports
     eight ranks, and every rank sits on its own LOCAL_RANK."""
-    p = run_bench("--gpus", "8", "--steps", "20", "--warmup", "5", "--dry-run-device", "--e2e-steps", "50", "--detail",
-                  str(tmp_path / "d.json"), env=fake_quota(tmp_path), timeout=900)
+    p = run_bench("--gpus", "8", "--steps", "20", "--warmup", "5", "--dry-run-device", "--full", "--e2e-steps", "50",
+                  "--detail", str(tmp_path / "d.json"), env=fake_quota(tmp_path), timeout=900)
     d = check_headline_line(p, 8)
     c = d["collective"]
     assert c["ranks"] == 8 and sorted(x[0] for x in c["local_rank_device"]) == list(range(8))

@@ -79,8 +79,8 @@ def test_gather_puts_every_member_in_its_place(two_rank_ensemble):
 
 
 def check_headline_line(p, world):
-    """bench.py's line: ONE line under 4 KB carrying the contract keys, one kernel per headline, the process group's
-    own rank count, the configs[3] run; the long record goes to the --detail file."""
+    """bench.py --full's line: ONE line under 4 KB carrying the contract keys, one kernel per headline, the process
+    group's own rank count, the configs[3] run; the long record goes to the --detail file."""
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1 and len(lines[0].encode()) + 1 < MAX_LINE_BYTES, (len(lines), len(lines[0]))
@@ -101,7 +101,7 @@ def check_headline_line(p, world):
 
 def test_two_rank_arena_line(tmp_path):
     detail = tmp_path / "detail.json"
-    p = run_bench("--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run-device", "--e2e-steps", "100",
+    p = run_bench("--gpus", "2", "--steps", "20", "--warmup", "5", "--dry-run-device", "--full", "--e2e-steps", "100",
                   "--detail", str(detail))
     d = check_headline_line(p, 2)
     assert d["steps"] == 20 and d["warmup"] == 5 and "2 independent arenas" in d["config"]["parallelism"]
@@ -119,7 +119,7 @@ def test_two_rank_arena_line(tmp_path):
 
 
 def test_one_rank_line_has_no_process_group():
-    d = check_headline_line(run_bench("--steps", "20", "--warmup", "5", "--dry-run-device", "--no-ensemble",
+    d = check_headline_line(run_bench("--steps", "20", "--warmup", "5", "--dry-run-device", "--full", "--no-ensemble",
                                       "--no-cpu-baseline", "--detail", ""), 1)
     assert d["collective"] is None and "ensemble" not in d and d["detail"] is None
     assert d["config"]["parallelism"] == "single arena"

@@ -1,7 +1,7 @@
 """CPU tests of the .cfg loader (main.cpp:594-816, 832-939): the product's C++ loader
 (libparticlebot_host.so) against the oracle's C restatement, field by field, on every shipped
-example, on the loader's documented quirks, and -- when the reference checkout is present -- on the
-reference's own examples/*.cfg."""
+example, on the loader's documented quirks, and on the reference's own examples/*.cfg (stored under
+tests/golden/ref_examples)."""
 import glob
 import os
 
@@ -9,7 +9,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXAMPLES = sorted(glob.glob(os.path.join(ROOT, "examples", "example*.cfg")))
-REF_EXAMPLES = sorted(glob.glob("/root/reference/examples/*.cfg"))
+REF_EXAMPLES = sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "ref_examples", "*.cfg")))
 
 
 @pytest.fixture(scope="module")
@@ -42,7 +42,11 @@ def test_examples_resolve_identically(host, orc, path):
     assert abs(flat.cellSizeX - 0.235) < 1e-6
 
 
-@pytest.mark.skipif(not REF_EXAMPLES, reason="reference checkout not present")
+def test_reference_examples_are_stored():
+    assert [os.path.basename(p) for p in REF_EXAMPLES] == ["example.cfg", "example_dead_cells.cfg", "example_gap.cfg",
+                                                           "example_object_transport.cfg", "example_obstacle.cfg"]
+
+
 @pytest.mark.parametrize("path", REF_EXAMPLES, ids=[os.path.basename(p) for p in REF_EXAMPLES])
 def test_shipped_examples_equal_reference_examples(host, path):
     """examples/*.cfg in this repo carry the reference's parameter sets (own comments)."""

@@ -13,12 +13,12 @@ LEGS = os.path.join(ROOT, "tools", "bench_legs.py")
 
 
 def test_headline_line_is_small_and_describes_one_kernel(tmp_path):
-    """`python bench.py`: value, ms_per_step and roofline are the SAME K launches of the both-sums kernel (everything
-    collideD writes, impl.cuh:828-830); the default (dead-sum) form, the CPU baseline and configs[3] ride along; the
-    line is under 4 KB and the long record is in the --detail file."""
+    """`python bench.py --full`: value, ms_per_step and roofline are the SAME K launches of the both-sums kernel
+    (everything collideD writes, impl.cuh:828-830); the default (dead-sum) form, the CPU baseline and configs[3] ride
+    along; the line is under 4 KB and the long record is in the --detail file."""
     n, k = 200000, 60
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bots", str(n), "--steps", str(k), "--warmup",
-                          "20", "--cpu-seconds", "1", "--e2e-steps", "1500", "--detail", str(tmp_path / "d.json")],
+                          "20", "--full", "--cpu-seconds", "1", "--e2e-steps", "1500", "--detail", str(tmp_path / "d.json")],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -59,11 +59,39 @@ def test_headline_line_is_small_and_describes_one_kernel(tmp_path):
     assert long["default_form"]["timed"]["device_prewarm_ms"] >= 100.0
 
 
+def test_plain_run_dumps_what_the_timed_steps_computed(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the headline only, EXACTLY K timed launches, and DIR holds
+    the state after the W + K steps, bit for bit what the same arena stepped W + K times in this process holds."""
+    import numpy as np
+    n, k, w = 100000, 30, 5
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bots", str(n), "--steps", str(k), "--warmup",
+                          str(w), "--dump-outputs", str(tmp_path / "out"), "--detail", ""], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads(out.stdout.strip().splitlines()[-1])
+    assert d["steps"] == k and d["roofline"]["launches"] == k and "long" not in d["roofline"]
+    for key in ("default_form", "cpu_baseline", "ensemble"):
+        assert key not in d, key
+    import bench
+    import particlerobotsimulations_amd as pb
+    pb.legacy.cudaInit(0, None)
+    sim = bench.make_sim(pb, n, bench.LATTICE_PITCH, seed=1, force_sums=1)
+    assert sim.step(w + k) == w + k
+    st = sim.get_state()
+    sim.close()
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f"{key}.npy" for key in st)
+    for key, a in st.items():
+        got = np.load(tmp_path / "out" / f"{key}.npy")
+        assert got.dtype == np.float32 and got.shape == a.shape, key
+        assert np.array_equal(got.view(np.uint32), a.astype(np.float32).view(np.uint32)), key
+
+
 def test_headline_line_through_rccl_with_one_rank(tmp_path):
     """--force-dist: the N > 1 code path on one GPU -- RCCL communicator, barriers, MAX all-reduce, gather of the arena
     summaries and of the configs[3] rows -- and `collective` says what the communicator saw."""
     raw = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bots", "150000", "--steps", "40", "--warmup",
-                          "10", "--force-dist", "--no-cpu-baseline", "--e2e-steps", "300", "--detail", str(tmp_path / "d.json")],
+                          "10", "--full", "--force-dist", "--no-cpu-baseline", "--e2e-steps", "300", "--detail",
+                          str(tmp_path / "d.json")],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert raw.returncode == 0, raw.stderr[-2000:]
     lines = [l for l in raw.stdout.splitlines() if l.strip()]

@@ -92,6 +92,13 @@ class _DrySim:
     def centroid(self):
         return 0.0, 0.0
 
+    def get_state(self):
+        import numpy as np
+        n, t = self.n, np.float32(self.time)
+        bot = np.arange(n, dtype=np.float32)
+        return {"pos": np.stack([bot, bot + t], axis=1), "vel": np.zeros((n, 2), np.float32), "rad": bot * 0 + t,
+                "phase": bot, "dead": np.zeros(n, np.int32), "absForce_a": bot, "absForce_r": bot}
+
     def stats(self):
         return {"steps": self._steps, "fused_launches": self._steps, "plain_launches": 0, "state_launches": 0, "resorts": 0,
                 "phase_updates": 0, "resident_launches": 0}
