@@ -150,6 +150,24 @@ class Particlebot {
    * (The display_shadow tint is not drawn.)  Returns false on I/O errors. */
   bool writeFramePPM(const char *path, int width, int height, float centerX, float centerY, float halfExtent,
                      float lightRadius = 0.25f);
+  /* The same view in the reference's display colours: bots in the device colours of updateCol_k (getColorArray,
+   * display_shadow tint included), each channel lrintf(c * 255) clamped to 0..255; then the centroid trail in slot
+   * order as red discs of centroid_radius at (x, y - 2000), slots still at x = -5000 skipped (trail only with
+   * setDisplay(true)).  Returns false on I/O errors. */
+  bool writeFramePPMReference(const char *path, int width, int height, float centerX, float centerY,
+                              float halfExtent, float lightRadius = 0.25f);
+  /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
+   * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
+   * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at
+   * the reference's two places (particlebot.cpp:207-209, 254); getColorBuffer / getCudaColorVBO return it.  Fused
+   * engine: the engine's centroid trail (pbSimSetCentroidTrail).  The dynamics are the same either way. */
+  void setDisplay(bool on);
+  bool displayOn() const { return display; }
+  /* nCells x 4 floats (RGBA, original order): the colours updateCol gives the current state */
+  const float *getColorArray();
+  /* the centroid ring (2 centroid_steps floats, y still + 2000), the start time of the step that wrote each slot (NaN:
+   * never) and the records made so far; false when setDisplay(true) was not called.  Not carried by checkpoints. */
+  bool getCentroidTrail(std::vector<float> &xy, std::vector<float> &times, unsigned &records);
   /* HostOnly engines follow an external clock */
   void setHostTime(float t) { time = t; }
   /* The private placement / dead-draw generator's state and the host mirrors of a HostOnly instance: what an
@@ -186,6 +204,9 @@ class Particlebot {
   void drawDeadBots();
   void pullState(bool pos, bool vel, bool rad);
   void legacyUpdate(float deltaTime, float sort_interval);
+  bool writeFrame(const char *path, int width, int height, float centerX, float centerY, float halfExtent,
+                  float lightRadius, bool referenceStyle);
+  void resetDisplayRing();
 
   /* host mirrors (original bot order) */
   std::vector<float> hPosV, hVelV, hRadV, hPhaseV, hFreqV;
@@ -219,6 +240,12 @@ class Particlebot {
   bool fastBlob = false;
   int rngKindV = 0; /* PB_RNG_COUNTER */
   PbLibcRand rng; /* seeded with params.seed at construction */
+  /* display (setDisplay) */
+  bool display = false;
+  struct pbGraphicsResource *colRes = nullptr;
+  float *dTempPos1 = nullptr, *dTempPos2 = nullptr; /* calcCOG's temporaries (legacy) */
+  std::vector<float> hColV, trailTimesV;
+  unsigned trailRecords = 0;
 };
 
 #endif /* PARTICLEBOT_H */

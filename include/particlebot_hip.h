@@ -109,13 +109,18 @@ void curand_setup(pbRngState *state, int N);
 void add_normal_noise(pbRngState *state, float *val, float std, int N);
 /* particlebot.cuh:80-85 */
 void updatePhase(float *pos, float *phase, float spacing, float max_d, float min_d, int nCells);
-/* particlebot.cuh:89-94 (display only: feeds the renderer; exported, does nothing) */
+/* particlebot.cuh:89-94 (display only: feeds the renderer).  rgb of col[4i .. 4i+2] for i < nCells, bit for bit
+ * the reference's updateCol_k (display_shadow tint included); alpha and everything past nCells untouched. */
 void updateCol(float *rad, float *col, int nCells, float *pos, float *phase, int *dead);
 /* particlebot.cuh:96-107 */
 void collide(float *newVel, float *absForce_a, float *absForce_r, float *sortedPos, float *sortedVel,
              float *sortedRad, uint *gridParticlebotIndex, uint *cellStart, uint *cellEnd, uint nCells,
              uint numCells, float deltaTime);
-/* particlebot.cuh:109-115 (display only: centroid trail; exported, does nothing) */
+/* particlebot.cuh:109-115 (display only: centroid trail).  Writes exactly the two floats at pos + 2 (ind + nCells),
+ * ind = (int)(time / hist_int) % hist_steps: the centroid of pos[0 .. nCells) in the reference's summation order,
+ * y + 2000.  temppos / temppos1 (nCells float2 each) hold unspecified values afterwards.  Deviation: writes nothing
+ * for nCells <= 0, hist_steps <= 0, hist_int <= 0 or a negative ind (negative time), where the reference writes in
+ * front of the ring or divides by zero. */
 void calcCOG(float *pos, float *temppos, float *temppos1, int nCells, float time, int hist_steps,
              float hist_int);
 /* particlebot.cuh:117-119 */
@@ -199,6 +204,20 @@ int pbSimCentroids(pbSim *sim, double *cxcy);
  * serially in original order as dumpParticlebot does (particlebot.cpp:335-338) -- bit for bit what its CSV's
  * "Centroid X, Centroid Y" columns are divided from (pbSimCentroids above is the accurately rounded mean). */
 int pbSimCentroidSums(pbSim *sim, float *sumxy);
+/* Display (the reference's updateCol / calcCOG on the engine's state; the dynamics are untouched either way).
+ * GetColorsOf: one member's RGBA (4 n floats, ORIGINAL order) computed now from its state, bit for bit the legacy
+ * updateCol on the same state with alpha 1.
+ * SetCentroidTrail(1): one ring of centroid_steps float2 per member, reset to (-5000, 0); from then on every step
+ * whose start time t passes the reference's gate t - centroid_int floorf(t / centroid_int) < dt records calcCOG of
+ * the positions at the start of that step into slot (int)(t / centroid_int) % centroid_steps.  PB_ERR_ARG when the
+ * members disagree on centroid_int or centroid_steps, or either is <= 0.  SetCentroidTrail(0) (the default) frees
+ * it: no allocation, no launch.
+ * GetCentroidTrailOf: xy = the ring verbatim (2 centroid_steps floats, y still + 2000), times = the fp32 start time of
+ * the step that wrote each slot (NaN: never written), records = the records made so far; NULL pointers are skipped.
+ * The trail is not part of a checkpoint: a resumed run starts a fresh ring. */
+int pbSimGetColorsOf(pbSim *sim, unsigned member, float *rgba);
+int pbSimSetCentroidTrail(pbSim *sim, int on);
+int pbSimGetCentroidTrailOf(pbSim *sim, unsigned member, float *xy, float *times, unsigned *records);
 
 /* Host arrays in ORIGINAL bot order; NULL pointers leave that array unchanged.
  * pos, vel: 2*n floats; rad, phase: n floats; dead: n ints. */

@@ -352,6 +352,28 @@ class Sim:
     def set_resort_every_step(self, on):
         _capi.check(_capi.lib().pbSimSetResortEveryStep(self._h, 1 if on else 0))
 
+    def colors(self, member=0):
+        """The reference's updateCol colours of one member, (n, 4) float32 RGBA in original order, computed now from
+        its state (alpha 1)."""
+        out = np.empty((self.n, 4), np.float32)
+        _capi.check(_capi.lib().pbSimGetColorsOf(self._h, int(member), _capi.np_ptr(out)), "pbSimGetColorsOf")
+        return out
+
+    def set_centroid_trail(self, on):
+        """Record the reference's centroid trail (calcCOG) every centroid_int seconds into a ring of centroid_steps."""
+        _capi.check(_capi.lib().pbSimSetCentroidTrail(self._h, 1 if on else 0), "pbSimSetCentroidTrail")
+
+    def centroid_trail(self, member=0):
+        """(xy, times, records): the ring verbatim ((centroid_steps, 2) float32, y still + 2000), the fp32 start time of
+        the step that wrote each slot (NaN: never written) and the number of records so far."""
+        steps = int(self.params.centroid_steps)
+        xy = np.empty((steps, 2), np.float32)
+        times = np.empty(steps, np.float32)
+        rec = C.c_uint(0)
+        _capi.check(_capi.lib().pbSimGetCentroidTrailOf(self._h, int(member), _capi.np_ptr(xy), _capi.np_ptr(times),
+                                                        C.byref(rec)), "pbSimGetCentroidTrailOf")
+        return xy, times, int(rec.value)
+
 
 class Ensemble(Sim):
     """A batch of independent simulations of equal size stepped by the same launches

@@ -127,6 +127,9 @@ SYMBOLS = {
     "pbSimGetStateOf": (_I, [_VP, _U] + [_VP] * 7),
     "pbSimCentroids": (_I, [_VP, C.POINTER(C.c_double)]),
     "pbSimCentroidSums": (_I, [_VP, C.POINTER(C.c_float)]),
+    "pbSimGetColorsOf": (_I, [_VP, _U, _VP]),
+    "pbSimSetCentroidTrail": (_I, [_VP, _I]),
+    "pbSimGetCentroidTrailOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_U)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <cstring>
+#include <limits>
 #include <new>
 #include <string>
 
@@ -460,6 +461,13 @@ void Particlebot::_finalize() {
     unregisterGLBufferObject(radRes);
     pbDeleteBuffer(posVbo);
     pbDeleteBuffer(radVbo);
+    if (colorVBO) {
+      freeArray(dTempPos1);
+      freeArray(dTempPos2);
+      unregisterGLBufferObject(colRes);
+      pbDeleteBuffer(colorVBO);
+      colorVBO = 0;
+    }
     dVel = nullptr;
   }
 }
@@ -507,12 +515,24 @@ void Particlebot::drawDeadBots() {
 }
 
 void Particlebot::legacyUpdate(float deltaTime, float sort_interval) {
-  // particlebot.cpp:196-299, call for call (minus calcCOG/updateCol, which only feed the renderer)
+  // particlebot.cpp:196-299, call for call (calcCOG / updateCol, which only feed the renderer, with setDisplay(true))
   float *dPos = (float *)mapGLBufferObject(&posRes);
   float *dRad = (float *)mapGLBufferObject(&radRes);
   unmapGLBufferObject(posRes);
   unmapGLBufferObject(radRes);
   const uint n = params.nCells;
+  if (display && everyGate(time, params.centroid_int, deltaTime)) {
+    calcCOG(dPos, dTempPos1, dTempPos2, (int)n, time, params.centroid_steps, params.centroid_int);
+    // the slot calcCOG wrote, if any (it writes nothing where the reference's index is undefined)
+    const float q = time / params.centroid_int;
+    if (n > 0 && params.centroid_steps > 0 && params.centroid_int > 0.0f && q > -2147483648.0f && q < 2147483648.0f) {
+      const int ind = ((int)q) % params.centroid_steps;
+      if (ind >= 0) {
+        trailTimesV[ind] = time;
+        trailRecords++;
+      }
+    }
+  }
   if (params.control == LIGHT_WAVE) {
     if (everyGate(time, params.phase_update_interval, deltaTime)) {
       copyArrayFromDevice(hPos, dPos, 0, (int)(sizeof(float) * 2 * n));
@@ -534,6 +554,7 @@ void Particlebot::legacyUpdate(float deltaTime, float sort_interval) {
     if (time >= 0) updateRad_light_wave(dPos, dAbsForce_a, dAbsForce_r, dRad, dphase, time, deltaTime, dDead, (int)n);
   }
   integrateSystem(dPos, dVel, dRad, deltaTime, n, time);
+  if (display) updateCol(dRad, cudaColorVBO, (int)n, dPos, dphase, dDead);
   if (everyGate(time, sort_interval, deltaTime)) {
     calcHash(dGridParticleHash, dGridParticleIndex, dPos, (int)n);
     sortParticlebots(dGridParticleHash, dGridParticleIndex, n);
@@ -1092,6 +1113,102 @@ void Particlebot::reset() {
     setArray(POSITION, hPos, 0, n);
     setArray(VELOCITY, hVel, 0, n);
   }
+  if (display) resetDisplayRing();
+}
+
+// ---- display (extension; include/particlebot.h) ------------------------------------------------------------------
+
+void Particlebot::setDisplay(bool on) {
+  if (engineKind == Engine::HostOnly) die("setDisplay: a HostOnly instance has no device state");
+  display = on;
+  if (engineKind == Engine::Fused) {
+    if (pbSimSetCentroidTrail(sim, on ? 1 : 0) != PB_OK) die("pbSimSetCentroidTrail");
+    return;
+  }
+  if (!on || colorVBO) return;
+  // the reference's display buffers (particlebot.cpp:101-141): POSITION / RADII with centroid_steps + 1 more entries,
+  // the colour buffer with its fills.  What the smaller buffers held so far moves over.
+  const size_t n = params.nCells, cs = params.centroid_steps > 0 ? (size_t)params.centroid_steps : 0;
+  std::vector<float> pos(2 * n), rad(n);
+  copyArrayFromDevice(pos.data(), 0, &posRes, (int)(sizeof(float) * 2 * n));
+  copyArrayFromDevice(rad.data(), 0, &radRes, (int)(sizeof(float) * n));
+  unregisterGLBufferObject(posRes);
+  unregisterGLBufferObject(radRes);
+  pbDeleteBuffer(posVbo);
+  pbDeleteBuffer(radVbo);
+  posVbo = pbCreateBuffer(sizeof(float) * 2 * (n + cs + 1));
+  registerGLBufferObject(posVbo, &posRes);
+  radVbo = pbCreateBuffer(sizeof(float) * (n + cs + 1));
+  registerGLBufferObject(radVbo, &radRes);
+  cudaPosVBO = (float *)mapGLBufferObject(&posRes);
+  cudaRadVBO = (float *)mapGLBufferObject(&radRes);
+  if (n) {
+    pbBufferSubData(posVbo, 0, sizeof(float) * 2 * n, pos.data());
+    pbBufferSubData(radVbo, 0, sizeof(float) * n, rad.data());
+  }
+  std::vector<float> col(4 * (n + cs + 1));
+  float *c = col.data();
+  for (size_t i = 0; i < n; i++) *c++ = 1.0f, *c++ = 1.0f, *c++ = 1.0f, *c++ = 1.0f;
+  for (size_t i = 0; i < cs; i++) *c++ = 1.0f, *c++ = 0.0f, *c++ = 0.0f, *c++ = 0.8f;
+  *c++ = 1.0f, *c++ = 0.0f, *c++ = 0.0f, *c++ = 1.0f;
+  colorVBO = pbCreateBuffer(sizeof(float) * col.size());
+  pbBufferSubData(colorVBO, 0, sizeof(float) * col.size(), col.data());
+  registerGLBufferObject(colorVBO, &colRes);
+  cudaColorVBO = (float *)mapGLBufferObject(&colRes);
+  allocateArray((void **)&dTempPos1, sizeof(float) * 2 * n);
+  allocateArray((void **)&dTempPos2, sizeof(float) * 2 * n);
+  resetDisplayRing();
+}
+
+void Particlebot::resetDisplayRing() {
+  // particlebot.cpp:776-780: every trail slot at x = -5000 (off screen) with radius centroid_radius, the last entry 0
+  if (engineKind == Engine::Fused) {
+    if (pbSimSetCentroidTrail(sim, 0) != PB_OK || pbSimSetCentroidTrail(sim, 1) != PB_OK) die("pbSimSetCentroidTrail");
+    return;
+  }
+  const size_t n = params.nCells, cs = params.centroid_steps > 0 ? (size_t)params.centroid_steps : 0;
+  std::vector<float> pos(2 * cs), rad(cs + 1, params.centroid_radius);
+  for (size_t i = 0; i < cs; i++) pos[2 * i] = -5000.0f, pos[2 * i + 1] = 0.0f;
+  rad[cs] = 0.0f;
+  if (cs) pbBufferSubData(posVbo, sizeof(float) * 2 * n, sizeof(float) * 2 * cs, pos.data());
+  pbBufferSubData(radVbo, sizeof(float) * n, sizeof(float) * (cs + 1), rad.data());
+  trailTimesV.assign(cs, std::numeric_limits<float>::quiet_NaN());
+  trailRecords = 0;
+}
+
+const float *Particlebot::getColorArray() {
+  const size_t n = params.nCells;
+  hColV.assign(4 * n, 1.0f);
+  if (engineKind == Engine::HostOnly) die("getColorArray: a HostOnly instance has no device state");
+  if (engineKind == Engine::Fused) {
+    if (pbSimGetColorsOf(sim, 0, hColV.data()) != PB_OK) die("pbSimGetColorsOf");
+    return hColV.data();
+  }
+  if (!n) return hColV.data();
+  // updateCol on the current state into a scratch buffer with the reference's alpha fill (the display buffer, when
+  // there is one, holds the same values after every update)
+  float *d = nullptr;
+  allocateArray((void **)&d, sizeof(float) * 4 * n);
+  copyArrayToDevice(d, hColV.data(), 0, (int)(sizeof(float) * 4 * n));
+  float *dPos = (float *)mapGLBufferObject(&posRes);
+  float *dRad = (float *)mapGLBufferObject(&radRes);
+  updateCol(dRad, d, (int)n, dPos, dphase, dDead);
+  copyArrayFromDevice(hColV.data(), d, 0, (int)(sizeof(float) * 4 * n));
+  freeArray(d);
+  return hColV.data();
+}
+
+bool Particlebot::getCentroidTrail(std::vector<float> &xy, std::vector<float> &times, unsigned &records) {
+  if (!display) return false;
+  const size_t n = params.nCells, cs = params.centroid_steps > 0 ? (size_t)params.centroid_steps : 0;
+  xy.resize(2 * cs);
+  times.resize(cs);
+  if (engineKind == Engine::Fused)
+    return pbSimGetCentroidTrailOf(sim, 0, xy.data(), times.data(), &records) == PB_OK;
+  if (cs) copyArrayFromDevice(xy.data(), cudaPosVBO + 2 * n, 0, (int)(sizeof(float) * 2 * cs));
+  times = trailTimesV;
+  records = trailRecords;
+  return true;
 }
 
 // ---- one placement for several members (extension; include/particlebot.h) --------------------------
@@ -1151,9 +1268,21 @@ bool getv(FILE *fp, T *p, size_t count) { return fread(p, sizeof(T), count, fp) 
 
 bool Particlebot::writeFramePPM(const char *path, int width, int height, float centerX, float centerY,
                                 float halfExtent, float lightRadius) {
+  return writeFrame(path, width, height, centerX, centerY, halfExtent, lightRadius, false);
+}
+
+bool Particlebot::writeFramePPMReference(const char *path, int width, int height, float centerX, float centerY,
+                                         float halfExtent, float lightRadius) {
+  return writeFrame(path, width, height, centerX, centerY, halfExtent, lightRadius, true);
+}
+
+bool Particlebot::writeFrame(const char *path, int width, int height, float centerX, float centerY, float halfExtent,
+                             float lightRadius, bool referenceStyle) {
   if (!path || width <= 0 || height <= 0 || !(halfExtent > 0)) return false;
   pullState(true, false, true);
   const int *deadNow = getDeadArray();
+  const float *col = referenceStyle ? getColorArray() : nullptr;
+  auto channel = [](float c) { return (unsigned char)std::min(255L, std::max(0L, lrintf(c * 255.0f))); };
   std::vector<unsigned char> img((size_t)width * height * 3, 245);
   const float scale = 0.5f * (float)height / halfExtent;  // pixels per world unit
   // world -> pixel: x mirrored (the reference translates by -x), y up
@@ -1188,7 +1317,11 @@ bool Particlebot::writeFramePPM(const char *path, int width, int height, float c
   for (uint i = 0; i < params.nCells; i++) {
     const float r = hRad[i];
     unsigned char R = 0, G = 0, B = 0;
-    if (!deadNow[i]) {  // updateCol_k, impl.cuh:413-417
+    if (col) {  // the device colours (updateCol_k)
+      R = channel(col[4 * i]);
+      G = channel(col[4 * i + 1]);
+      B = channel(col[4 * i + 2]);
+    } else if (!deadNow[i]) {  // updateCol_k, impl.cuh:413-417
       const float g = span > 0 ? (params.max_radius - r) / span : 0.0f;
       const float b = span > 0 ? (r - params.min_radius) / span : 0.0f;
       R = 30;
@@ -1197,6 +1330,11 @@ bool Particlebot::writeFramePPM(const char *path, int width, int height, float c
     }
     disc(hPos[2 * i], hPos[2 * i + 1], r, R, G, B);
   }
+  std::vector<float> trail, trailTimes;
+  unsigned records = 0;
+  if (referenceStyle && getCentroidTrail(trail, trailTimes, records))  // the shader's centroid marker (y + 2000)
+    for (size_t k = 0; k < trailTimes.size(); k++)
+      if (trail[2 * k] != -5000.0f) disc(trail[2 * k], trail[2 * k + 1] - 2000.0f, params.centroid_radius, 255, 0, 0);
   FILE *fp = fopen(path, "wb");
   if (!fp) return false;
   fprintf(fp, "P6\n%d %d\n255\n", width, height);

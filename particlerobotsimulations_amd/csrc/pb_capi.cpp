@@ -262,6 +262,31 @@ int pbHostWriteFrame(void *hv, const char *path, int width, int height, float cx
   return h->bot->writeFramePPM(path, width, height, cx, cy, half, h->cfg.light_radius) ? 0 : -1;
 }
 
+// style 0: writeFramePPM, 1: writeFramePPMReference (the device colours and the centroid trail)
+int pbHostWriteFrameStyle(void *hv, const char *path, int width, int height, float cx, float cy, float half, int style) {
+  HostSim *h = (HostSim *)hv;
+  if (style == 0) return pbHostWriteFrame(hv, path, width, height, cx, cy, half);
+  if (!(half > 0)) {
+    cx = h->cfg.camera_x;
+    cy = 0.0f;
+    half = h->cfg.camera_y * 0.57735027f;
+  }
+  return h->bot->writeFramePPMReference(path, width, height, cx, cy, half, h->cfg.light_radius) ? 0 : -1;
+}
+
+void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
+
+// the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off
+int pbHostCentroidTrail(void *hv, float *xy, float *times, unsigned *records) {
+  std::vector<float> a, b;
+  unsigned r = 0;
+  if (!((HostSim *)hv)->bot->getCentroidTrail(a, b, r)) return -1;
+  if (xy) memcpy(xy, a.data(), sizeof(float) * a.size());
+  if (times) memcpy(times, b.data(), sizeof(float) * b.size());
+  if (records) *records = r;
+  return 0;
+}
+
 int pbHostSaveCheckpoint(void *hv, const char *path) {
   FILE *fp = fopen(path, "wb");
   if (!fp) return -1;
@@ -296,6 +321,7 @@ int pbHostGetArray(void *hv, int which, void *out) {
     case 2: memcpy(out, h->bot->getArray(RADII), 4 * n); return 0;
     case 3: memcpy(out, h->bot->getArray(PHASE), 4 * n); return 0;
     case 5: memcpy(out, h->bot->getDeadArray(), 4 * n); return 0;
+    case 6: memcpy(out, h->bot->getColorArray(), 16 * n); return 0;  // RGBA (Particlebot::getColorArray)
     default: return -1;
   }
 }
@@ -1797,5 +1823,6 @@ void pbHostXorwowJumpMatrix(unsigned k, unsigned *rows) {
 void *pbHostEngineHandle(void *hv) { return ((HostSim *)hv)->bot->engineHandle(); }
 
 unsigned pbHostNumBots(void *hv) { return ((HostSim *)hv)->bot->getParams().nCells; }
+int pbHostCentroidSteps(void *hv) { return ((HostSim *)hv)->bot->getParams().centroid_steps; }
 
 }  // extern "C"

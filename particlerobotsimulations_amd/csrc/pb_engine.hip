@@ -593,6 +593,24 @@ int phaseUpdate(pbSim *S) {
   return PB_OK;
 }
 
+// calcCOG of every member's positions at the start of the step at time t into its ring (particlebot.cpp:207-209)
+int trailRecord(pbSim *S, float t) {
+  const float q = t / S->trailInt;
+  if (!(q > -2147483648.0f && q < 2147483648.0f)) return PB_OK;
+  const int ind = ((int)q) % S->trailSteps;
+  if (ind < 0) return PB_OK;  // negative time: the reference would write in front of the ring (calcCOG)
+  const uint32_t n = S->n;
+  const int c = S->cur;
+  hipLaunchKernelGGL(k_com_scatter, gridOf(S), dim3(TILE), 0, S->stream, S->orig[c], S->pr[c], S->comPos, n);
+  const size_t tmpStride = cdiv(n, 64);
+  pbLaunchCentroid((const float *)S->comPos, n, n, (float *)S->trailTmp, (float *)(S->trailTmp + S->nsims * tmpStride),
+                   tmpStride, (float *)(S->trail + ind), (size_t)S->trailSteps, S->nsims, S->stream);
+  PB_TRY(hipGetLastError());
+  S->trailTimes[ind] = t;
+  S->trailRecords++;
+  return PB_OK;
+}
+
 int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const uint32_t n = S->n;
   const dim3 gA = gridOf(S), b(TILE);
@@ -600,11 +618,17 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const bool lightWave = (S->host.control == LIGHT_WAVE);
   bool ahead = false;  // true: radius+integration of the coming step are already applied
   const bool resident = pbResidentWanted(S);
+  const bool trail = S->trail != nullptr;
+  const float ci = S->trailInt;
   int k = 0;
   for (; k < nsteps; k++) {
     const float t = S->time;
     if (t > S->host.max_time) break;  // particlebot.cpp:174-176 (the reference exits the process)
     if (!ahead) {
+      if (trail && gate(t, ci, dt)) {
+        const int rc = trailRecord(S, t);
+        if (rc) return rc;
+      }
       if (lightWave && gate(t, pui, dt)) {
         const int rc = phaseUpdate(S);
         if (rc) return rc;
@@ -615,7 +639,7 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
         int m = 1;
         float tt = t + dt;
         while (k + m < nsteps && !(tt > S->host.max_time) && !(lightWave && gate(tt, pui, dt)) &&
-               !gate(tt, sortInterval, dt)) {
+               !(trail && gate(tt, ci, dt)) && !gate(tt, sortInterval, dt)) {
           m++;
           tt += dt;
         }
@@ -641,6 +665,10 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     // positions of THIS step's integration, which are final now, so it runs before the launch.
     // (resident form: never run ahead, so that the next step can start a resident stretch)
     const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time);
+    if (fuse && trail && gate(tNext, ci, dt)) {
+      const int rc = trailRecord(S, tNext);
+      if (rc) return rc;
+    }
     if (fuse && lightWave && gate(tNext, pui, dt)) {
       const int rc = phaseUpdate(S);
       if (rc) return rc;
@@ -712,6 +740,9 @@ void pbSimDestroy(pbSim *S) {
   (void)hipFree(S->comPartial);
   (void)hipFree(S->comOut);
   (void)hipFree(S->walkTrips);
+  (void)hipFree(S->colors);
+  (void)hipFree(S->trail);
+  (void)hipFree(S->trailTmp);
   if (S->hMin) (void)hipHostFree(S->hMin);
   if (S->hMinD) (void)hipHostFree(S->hMinD);
   if (S->hCom) (void)hipHostFree(S->hCom);
@@ -781,6 +812,9 @@ int pbSimCreateBatch(pbSim **out, const SimParams *params, int nsims, float wall
     S->fastOk = S->fastOk && pbFastMathAllowed(S->hP[k]);
     S->magOk = S->magOk && pbAttractionMagnitudeSafe(S->hP[k]);
     S->anyConstrained = S->anyConstrained || S->hP[k].constrained_contraction != 0u;
+    S->displayShadow.push_back(params[k].display_shadow);
+    S->centroidInt.push_back(params[k].centroid_int);
+    S->centroidSteps.push_back(params[k].centroid_steps);
   }
   // A/B switches for tools/ab_bench.py: honoured only under PB_ALLOW_ENV_OVERRIDES=1 and through the
   // same range checks as the setters, so a stray variable cannot silently change what a caller runs
@@ -1174,6 +1208,72 @@ int pbSimCentroid(pbSim *S, double *cx, double *cy) {
   if (rc) return rc;
   if (cx) *cx = v[0];
   if (cy) *cy = v[1];
+  return PB_OK;
+}
+
+int pbSimGetColorsOf(pbSim *S, unsigned sim, float *rgba) {
+  if (!S || !rgba || sim >= S->nsims) {
+    pbLastError() = "pbSimGetColorsOf: null argument or member out of range";
+    return PB_ERR_ARG;
+  }
+  useDevice(S);
+  if (!S->colors) PB_TRY(hipMalloc((void **)&S->colors, sizeof(float4) * S->n));
+  const int c = S->cur;
+  pbLaunchEngineColors(S->dP, sim, S->displayShadow[sim], S->pr[c], S->dead[c], S->orig[c], S->n, S->colors, S->stream);
+  PB_TRY(hipGetLastError());
+  PB_TRY(hipMemcpyAsync(rgba, S->colors, sizeof(float4) * S->n, hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  return PB_OK;
+}
+
+int pbSimSetCentroidTrail(pbSim *S, int on) {
+  if (!S) {
+    pbLastError() = "pbSimSetCentroidTrail: null handle";
+    return PB_ERR_ARG;
+  }
+  useDevice(S);
+  if (!on) {
+    if (S->stream) PB_TRY(hipStreamSynchronize(S->stream));
+    PB_TRY(hipFree(S->trail));
+    PB_TRY(hipFree(S->trailTmp));
+    S->trail = S->trailTmp = nullptr;
+    S->trailTimes.clear();
+    S->trailRecords = 0;
+    return PB_OK;
+  }
+  if (S->trail) return PB_OK;
+  const float ci = S->centroidInt[0];
+  const int cs = S->centroidSteps[0];
+  for (uint32_t k = 0; k < S->nsims; k++)
+    if (!(S->centroidInt[k] > 0.0f) || S->centroidSteps[k] <= 0 || S->centroidInt[k] != ci || S->centroidSteps[k] != cs) {
+      pbLastError() = "pbSimSetCentroidTrail: every member needs the same centroid_int > 0 and centroid_steps > 0";
+      return PB_ERR_ARG;
+    }
+  const size_t ring = (size_t)S->nsims * (size_t)cs;
+  std::vector<float2> init(ring, make_float2(-5000.0f, 0.0f));  // particlebot.cpp:776-779
+  PB_TRY(hipMalloc((void **)&S->trail, sizeof(float2) * ring));
+  PB_TRY(hipMalloc((void **)&S->trailTmp, sizeof(float2) * 2 * (size_t)S->nsims * cdiv(S->n, 64)));
+  PB_TRY(hipMemcpy(S->trail, init.data(), sizeof(float2) * ring, hipMemcpyHostToDevice));
+  S->trailInt = ci;
+  S->trailSteps = cs;
+  S->trailTimes.assign((size_t)cs, std::numeric_limits<float>::quiet_NaN());
+  S->trailRecords = 0;
+  return PB_OK;
+}
+
+int pbSimGetCentroidTrailOf(pbSim *S, unsigned sim, float *xy, float *times, unsigned *records) {
+  if (!S || sim >= S->nsims || !S->trail) {
+    pbLastError() = "pbSimGetCentroidTrailOf: null handle, member out of range or trail off";
+    return PB_ERR_ARG;
+  }
+  useDevice(S);
+  if (xy) {
+    PB_TRY(hipMemcpyAsync(xy, S->trail + (size_t)sim * S->trailSteps, sizeof(float2) * S->trailSteps,
+                          hipMemcpyDeviceToHost, S->stream));
+    PB_TRY(hipStreamSynchronize(S->stream));
+  }
+  if (times) memcpy(times, S->trailTimes.data(), sizeof(float) * S->trailSteps);
+  if (records) *records = S->trailRecords;
   return PB_OK;
 }
 

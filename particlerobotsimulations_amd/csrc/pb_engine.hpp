@@ -92,6 +92,17 @@ struct pbSim {
   std::vector<float> hostPos;  // mode 1: one simulation's positions, original order
   int forceSums = 0;    // 0: Sum|F_attr| only when a member reads it (constrained_contraction), 1: always
   bool anyConstrained = false;  // some member has constrained_contraction != 0
+  // display (pb_display.hip): per-member display_shadow, and the centroid trail when on (pbSimSetCentroidTrail)
+  std::vector<uint32_t> displayShadow;
+  std::vector<float> centroidInt;
+  std::vector<int> centroidSteps;
+  float4 *colors = nullptr;      // n, allocated by the first pbSimGetColorsOf
+  float2 *trail = nullptr;       // nsims x trailSteps rings; nullptr: trail off
+  float2 *trailTmp = nullptr;    // 2 x nsims x ceil(n / 64): the tree's temporaries
+  float trailInt = 0.0f;
+  int trailSteps = 0;
+  std::vector<float> trailTimes;  // start time of the step that wrote each slot (NaN: never)
+  unsigned trailRecords = 0;
   pbSimStats stats{};
 };
 

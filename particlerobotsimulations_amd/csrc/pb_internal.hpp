@@ -35,3 +35,16 @@ static inline int pbKeyBits(uint32_t numKeys) {
 // ---- XORWOW jump table (pb_xorwow.hpp) on the CURRENT device: built on the host once per process,
 // uploaded once per device; returns nullptr and sets *err after a HIP error (pb_legacy.hip)
 const uint32_t *pbXorwowDeviceTable(hipError_t *err);
+
+// ---- the reference's display kernels (pb_display.hip); strides count float2 / float4 elements, n >= 1 ---------
+struct PbDevParams;
+// updateCol_k over caller arrays in original order: rgb of col[i] for i < n, alpha untouched
+void pbLaunchUpdateCol(const PbDevParams &P, uint32_t displayShadow, const float *rad, float *col, const float *pos,
+                       const int *dead, uint32_t n, hipStream_t stream);
+// one member's colours from the engine's cell-sorted slots, written to out[orig] with alpha 1
+void pbLaunchEngineColors(const PbDevParams *params, uint32_t member, uint32_t displayShadow, const float4 *pr,
+                          const int *dead, const uint32_t *orig, uint32_t n, float4 *out, hipStream_t stream);
+// calcCOG's tree for `members` inputs of n float2 each (member k at pos + 2 k posStride): the centroid, y + 2000, to
+// dst + 2 k dstStride.  tmp0 / tmp1: scratch of ceil(n / 64) float2 per member (member k at + 2 k tmpStride)
+void pbLaunchCentroid(const float *pos, size_t posStride, uint32_t n, float *tmp0, float *tmp1, size_t tmpStride,
+                      float *dst, size_t dstStride, uint32_t members, hipStream_t stream);

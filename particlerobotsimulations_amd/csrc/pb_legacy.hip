@@ -421,7 +421,13 @@ void updatePhase(float *pos, float *phase, float spacing, float, float min_d, in
   PB_CHECK_ABORT(hipGetLastError());
 }
 
-void updateCol(float *, float *, int, float *, float *, int *) {}  // display only
+// impl.cuh:401-443 (pb_display.hip): display only, the dynamics never read it
+void updateCol(float *rad, float *col, int nCells, float *pos, float *, int *dead) {
+  requireParams("updateCol");
+  if (nCells <= 0) return;
+  pbLaunchUpdateCol(g_P, g_hostParams.display_shadow, rad, col, pos, dead, (uint32_t)nCells, 0);
+  PB_CHECK_ABORT(hipGetLastError());
+}
 
 void collide(float *newVel, float *absForce_a, float *absForce_r, float *sortedPos, float *sortedVel,
              float *sortedRad, uint *index, uint *cellStart, uint *cellEnd, uint nCells, uint, float deltaTime) {
@@ -438,7 +444,19 @@ void collide(float *newVel, float *absForce_a, float *absForce_r, float *sortedP
   PB_CHECK_ABORT(hipGetLastError());
 }
 
-void calcCOG(float *, float *, float *, int, float, int, float) {}  // display only
+// particlebot_cuda.cu:241-281 (pb_display.hip): the centroid of pos[0 .. n) with y + 2000 into ring slot
+// ind = (int)(time / hist_int) % hist_steps, i.e. the two floats at pos + 2 (ind + n).  Deviation: nothing is written
+// for n <= 0, hist_steps <= 0, hist_int <= 0 or an index that is negative or has no int value (negative or non-finite
+// time), where the reference writes in front of the ring or divides by zero.
+void calcCOG(float *pos, float *temppos, float *temppos1, int nCells, float time, int hist_steps, float hist_int) {
+  if (nCells <= 0 || hist_steps <= 0 || !(hist_int > 0.0f)) return;
+  const float q = time / hist_int;
+  if (!(q > -2147483648.0f && q < 2147483648.0f)) return;
+  const int ind = ((int)q) % hist_steps;
+  if (ind < 0) return;
+  pbLaunchCentroid(pos, 0, (uint32_t)nCells, temppos, temppos1, 0, pos + 2 * ((size_t)ind + (size_t)nCells), 0, 1, 0);
+  PB_CHECK_ABORT(hipGetLastError());
+}
 
 void sortParticlebots(uint *hash, uint *index, uint nCells) {
   if (!nCells) return;

@@ -1,7 +1,7 @@
 // pb_runner.cpp -- headless replacement for the reference's GLUT main loop.
 //
 //   particlebot_run [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet]
-//                   [--frames DIR [--frame-size PIXELS]]
+//                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference]] [--trail FILE]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -21,8 +21,12 @@
 // (display(), main.cpp:354-361).  Between dump rows the steps are handed to the engine in one
 // batch so that it can keep one fused kernel per timestep.  --frames DIR writes a PPM of the arena
 // every VIDEO_INTERVAL timesteps (the reference's video cadence, main.cpp:455-470), viewed like the
-// reference's camera: centred on (camera_x, 0), half extent camera_y * tan(30 deg).
+// reference's camera: centred on (camera_x, 0), half extent camera_y * tan(30 deg); --frame-style reference draws them
+// in the device colours of updateCol with the centroid trail (Particlebot::writeFramePPMReference).  --trail FILE
+// records the reference's centroid trail (Particlebot::setDisplay) and writes it at the end of the run as
+// `slot,time,x,y` rows (slots holding a record; fp32 time and x to 9 digits), y as the double (stored y) - 2000, without the shader's +2000 (a resumed run starts a fresh trail).
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -76,6 +80,8 @@ int main(int argc, char **argv) {
   bool quiet = false, overwriteCsv = false;
   std::string framesDir, resumePath, ckptPath, finalCkptPath;
   int frameSize = 800;
+  bool referenceFrames = false;
+  std::string trailPath;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
   for (int i = 1; i < argc; i++) {
@@ -92,6 +98,11 @@ int main(int argc, char **argv) {
       framesDir = argv[++i];
     } else if (!strcmp(argv[i], "--frame-size") && i + 1 < argc) {
       frameSize = atoi(argv[++i]);
+    } else if (!strcmp(argv[i], "--frame-style") && i + 1 < argc &&
+               (!strcmp(argv[i + 1], "plain") || !strcmp(argv[i + 1], "reference"))) {
+      referenceFrames = !strcmp(argv[++i], "reference");
+    } else if (!strcmp(argv[i], "--trail") && i + 1 < argc) {
+      trailPath = argv[++i];
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -109,7 +120,7 @@ int main(int argc, char **argv) {
     } else {
       fprintf(stderr,
               "usage: %s [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet] "
-              "[--frames DIR [--frame-size PIXELS]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
+              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference]] [--trail FILE] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
               "[--checkpoint-every SECONDS] [--checkpoint-steps N]] [--final-checkpoint FILE]\n",
               argv[0]);
       return 2;
@@ -139,6 +150,7 @@ int main(int argc, char **argv) {
   sim.setFastBlob(cfg.fast_blob);
   sim.setRng(cfg.rng_kind);
   sim.setForceVariant(cfg.force_variant);
+  if (!trailPath.empty() || referenceFrames) sim.setDisplay(true);
   sim.reset();
   const SimParams &p = sim.getParams();
   const int frameEvery = cfg.video_interval > 0 ? cfg.video_interval : 100;
@@ -225,8 +237,12 @@ int main(int argc, char **argv) {
     if (!framesDir.empty() && stepsDone % frameEvery == 0) {
       char name[64];
       snprintf(name, sizeof name, "/frame_%06ld.ppm", frames++);
-      if (!sim.writeFramePPM((framesDir + name).c_str(), frameSize, frameSize, cfg.camera_x, 0.0f,
-                             cfg.camera_y * 0.57735027f, cfg.light_radius)) {
+      const std::string fpath = framesDir + name;
+      const float half = cfg.camera_y * 0.57735027f;
+      if (!(referenceFrames ? sim.writeFramePPMReference(fpath.c_str(), frameSize, frameSize, cfg.camera_x, 0.0f, half,
+                                                         cfg.light_radius)
+                            : sim.writeFramePPM(fpath.c_str(), frameSize, frameSize, cfg.camera_x, 0.0f, half,
+                                                cfg.light_radius))) {
         fprintf(stderr, "cannot write %s%s\n", framesDir.c_str(), name);
         return 1;
       }
@@ -244,5 +260,20 @@ int main(int argc, char **argv) {
   }
   if (!finalCkptPath.empty() && !writeCheckpoint(finalCkptPath)) return 1;
   fclose(fp);
+  if (!trailPath.empty()) {
+    std::vector<float> xy, times;
+    unsigned records = 0;
+    FILE *tf = fopen(trailPath.c_str(), "w");
+    if (!tf || !sim.getCentroidTrail(xy, times, records)) {
+      fprintf(stderr, "cannot write %s\n", trailPath.c_str());
+      if (tf) fclose(tf);
+      return 1;
+    }
+    fprintf(tf, "slot,time,x,y\n");
+    for (size_t k = 0; k < times.size(); k++)
+      if (!std::isnan(times[k]))  // a slot that holds a record
+        fprintf(tf, "%zu,%.9g,%.9g,%.17g\n", k, (double)times[k], (double)xy[2 * k], (double)xy[2 * k + 1] - 2000.0);
+    if (fclose(tf) != 0) return 1;
+  }
   return 0;
 }

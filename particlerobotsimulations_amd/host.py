@@ -87,6 +87,14 @@ def lib():
     L.pbHostLibcRandDraws.argtypes = [C.c_uint, C.c_int, C.c_void_p]
     L.pbHostNumBots.argtypes = [C.c_void_p]
     L.pbHostNumBots.restype = C.c_uint
+    L.pbHostCentroidSteps.argtypes = [C.c_void_p]
+    L.pbHostCentroidSteps.restype = C.c_int
+    L.pbHostSetDisplay.argtypes = [C.c_void_p, C.c_int]
+    L.pbHostCentroidTrail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint)]
+    L.pbHostCentroidTrail.restype = C.c_int
+    L.pbHostWriteFrameStyle.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
+                                        C.c_int]
+    L.pbHostWriteFrameStyle.restype = C.c_int
     _lib = L
     return L
 
@@ -166,10 +174,38 @@ class HostSim:
         lib().pbHostDrawDead(self._h, out.ctypes.data_as(C.c_void_p))
         return out
 
-    def write_frame(self, path, size=800, center=(0.0, 0.0), half_extent=0.0):
-        """Binary PPM of the arena seen from above (Particlebot::writeFramePPM).  half_extent <= 0:
+    def reset(self):
+        lib().pbHostReset(self._h)
+
+    def set_display(self, on):
+        """Particlebot::setDisplay: the reference's colour buffer and centroid trail (create with reset=False, call
+        this, then reset())."""
+        lib().pbHostSetDisplay(self._h, 1 if on else 0)
+
+    def centroid_trail(self):
+        """(xy, times, records): the centroid ring ((centroid_steps, 2) float32, y still + 2000), the start time of the
+        step that wrote each slot (NaN: never) and the records made so far.  Needs set_display(True)."""
+        steps = max(0, lib().pbHostCentroidSteps(self._h))
+        xy = np.empty((steps, 2), np.float32)
+        times = np.empty(steps, np.float32)
+        rec = C.c_uint(0)
+        if lib().pbHostCentroidTrail(self._h, xy.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p),
+                                     C.byref(rec)) != 0:
+            raise RuntimeError("centroid_trail: set_display(True) first")
+        return xy, times, int(rec.value)
+
+    def write_frame(self, path, size=800, center=(0.0, 0.0), half_extent=0.0, style="plain"):
+        """Binary PPM of the arena seen from above (Particlebot::writeFramePPM; style "reference":
+        writeFramePPMReference, the device colours and the centroid trail).  half_extent <= 0:
         the reference's camera, centred on (camera_x, 0), half extent camera_y * tan(30 deg)."""
         L = lib()
+        if style != "plain":
+            if style != "reference":
+                raise ValueError(style)
+            if L.pbHostWriteFrameStyle(self._h, os.fsencode(path), int(size), int(size), center[0], center[1],
+                                       half_extent, 1) != 0:
+                raise OSError(f"writeFramePPMReference({path}) failed")
+            return
         L.pbHostWriteFrame.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
         if L.pbHostWriteFrame(self._h, os.fsencode(path), int(size), int(size), center[0], center[1],
                               half_extent) != 0:
@@ -187,7 +223,7 @@ class HostSim:
 
     def get(self, name):
         which, dt, w = {"pos": (0, np.float32, 2), "vel": (1, np.float32, 2), "rad": (2, np.float32, 1),
-                        "phase": (3, np.float32, 1), "dead": (5, np.int32, 1)}[name]
+                        "phase": (3, np.float32, 1), "dead": (5, np.int32, 1), "col": (6, np.float32, 4)}[name]
         out = np.empty((self.n, w) if w > 1 else self.n, dtype=dt)
         assert lib().pbHostGetArray(self._h, which, out.ctypes.data_as(C.c_void_p)) == 0
         return out
