@@ -305,6 +305,16 @@ int pbSimSetForceSums(pbSim *sim, int mode);
  * 64 up to 1280 bots in the batch, 32 up to 2560, 16 up to 8192, 8 up to 40960, 4 up to 131072, else 1).
  * Results do not depend on it. */
 int pbSimSetLanesPerBot(pbSim *sim, int lanes);
+/* Split-lane tail of the throughput form (one lane per bot, 32-bit offsets): the last `tiles` tiles of every
+ * XCD's share of the grid -- the last workgroups to be dispatched -- run with PB_TAIL_LANES lanes per bot, so
+ * that the launch's final workgroups have shorter serial neighbour chains.  -1 = automatic (default: the rule
+ * of pbTailTiles, pb_force.hip), 0 = off, else that many tiles per XCD (capped at the XCD's share).  What the
+ * next launch uses is pbSimConfig.tail_tiles.  Results do not depend on it. */
+int pbSimSetTailTiles(pbSim *sim, int tiles);
+/* The throughput grid's workgroup -> bots mapping (no device needed): workgroup `workgroup` of a grid with
+ * `per_xcd` tiles per XCD, `tail_tiles` of them split, covers bots [*first_bot, *first_bot + *bots).  PB_ERR_ARG
+ * for a workgroup beyond the grid (8 * (per_xcd + tail_tiles * (lanes - 1)) workgroups) or tail_tiles > per_xcd. */
+int pbForceXcdTile(unsigned workgroup, unsigned per_xcd, unsigned tail_tiles, unsigned *first_bot, unsigned *bots);
 /* Resident form for simulations of at most 1024 bots: one workgroup per simulation keeps the state
  * in registers/LDS and runs every timestep up to the next re-sort, phase update or end of the
  * pbSimStep call in ONE launch.  0 = automatic (default: a cost model fitted to MI355X measurements
@@ -373,6 +383,8 @@ typedef struct pbSimConfig {
   int attraction_sums; /* 1: absForce_a is maintained (pbSimSetForceSums) */
   int dead_sum_form;   /* 1: the force kernel that runs is a form without Sum|F_attr| */
   int stream_walk;     /* 1: the streamlined kernel runs and walks its stencil flattened (pbSimSetStreamWalk) */
+  int tail_tiles;      /* split-lane tail tiles per XCD of the next force launch (pbSimSetTailTiles; 0: none) */
+  int tail_lanes;      /* lanes per bot of those tail tiles (0 when there are none) */
 } pbSimConfig;
 int pbSimGetConfig(pbSim *sim, pbSimConfig *cfg);
 

@@ -345,6 +345,11 @@ class Sim:
     def set_lanes_per_bot(self, lanes):
         _capi.check(_capi.lib().pbSimSetLanesPerBot(self._h, int(lanes)))
 
+    def set_tail_tiles(self, tiles):
+        """Split-lane tail tiles per XCD of the throughput form: -1 automatic (default), 0 off, else that many
+        (pbSimSetTailTiles; bit-identical either way).  config()["tail_tiles"] is what the next step uses."""
+        _capi.check(_capi.lib().pbSimSetTailTiles(self._h, int(tiles)), "pbSimSetTailTiles")
+
     def set_resident(self, mode):
         """0 automatic, 1 never, 2 whenever the simulation fits one workgroup (<= 1024 bots)."""
         _capi.check(_capi.lib().pbSimSetResident(self._h, int(mode)))

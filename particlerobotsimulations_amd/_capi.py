@@ -74,7 +74,8 @@ class pbSimStats(C.Structure):
 class pbSimConfig(C.Structure):
     _fields_ = [("force_variant", C.c_int), ("force_kind", C.c_int), ("lanes_per_bot", C.c_int),
                 ("resident", C.c_int), ("fast_math_ok", C.c_int), ("payload", C.c_int), ("rng", C.c_int), ("offsets64", C.c_int),
-                ("attraction_sums", C.c_int), ("dead_sum_form", C.c_int), ("stream_walk", C.c_int)]
+                ("attraction_sums", C.c_int), ("dead_sum_form", C.c_int), ("stream_walk", C.c_int),
+                ("tail_tiles", C.c_int), ("tail_lanes", C.c_int)]
 
 
 class pbForceForm(C.Structure):
@@ -152,6 +153,8 @@ SYMBOLS = {
     "pbHostSqrtThreshold": (C.c_float, [C.c_float]),
     "pbSimSetForceVariant": (_I, [_VP, _I]),
     "pbSimSetLanesPerBot": (_I, [_VP, _I]),
+    "pbSimSetTailTiles": (_I, [_VP, _I]),
+    "pbForceXcdTile": (_I, [_U, _U, _U, C.POINTER(_U), C.POINTER(_U)]),
     "pbSimSetResident": (_I, [_VP, _I]),
     "pbSimGetConfig": (_I, [_VP, C.POINTER(pbSimConfig)]),
     "pbSimSetForceSums": (_I, [_VP, _I]),

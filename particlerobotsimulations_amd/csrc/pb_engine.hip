@@ -1326,6 +1326,12 @@ int pbSimSetLanesPerBot(pbSim *S, int lanes) {
   return PB_OK;
 }
 
+int pbSimSetTailTiles(pbSim *S, int tiles) {
+  if (!S || tiles < -1) return PB_ERR_ARG;
+  S->tailTiles = tiles;
+  return PB_OK;
+}
+
 int pbSimSetResident(pbSim *S, int mode) {
   if (!S || mode < 0 || mode > 2) {
     pbLastError() = "pbSimSetResident: mode must be 0 (automatic), 1 (never) or 2 (whenever it fits)";
@@ -1349,6 +1355,8 @@ int pbSimGetConfig(pbSim *S, pbSimConfig *cfg) {
   cfg->attraction_sums = attractionSumsKept(S) ? 1 : 0;
   cfg->dead_sum_form = ((cfg->resident || p.stream) ? !attractionSumsKept(S) : !p.asum) ? 1 : 0;
   cfg->stream_walk = (p.stream && pbStreamWalk(S)) ? 1 : 0;
+  cfg->tail_tiles = (int)pbForceTailTiles(S);
+  cfg->tail_lanes = cfg->tail_tiles ? PB_TAIL_LANES : 0;
   return PB_OK;
 }
 

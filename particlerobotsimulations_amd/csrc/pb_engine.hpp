@@ -85,6 +85,8 @@ struct pbSim {
   int streamWalk = -1;
   bool streamWalkAuto = false;
   unsigned long long *walkTrips = nullptr, walkTripsHost[2] = {0, 0};
+  uint32_t cuCount = 0;  // compute units of the device (pbTailTiles; 0 until first asked)
+  int tailTiles = -1;  // split-lane tail tiles per XCD of the throughput form: -1 automatic (pbTailTiles), else that many
   bool wideOffsets = false;  // run the 64-bit-offset throughput sweep on a batch below 2^28 bots (pbSimSelectForceForm, tests)
   unsigned debugLdsBytes = 0;  // PB_DEBUG_LDS_BYTES under PB_ALLOW_ENV_OVERRIDES=1 (tools/occupancy_sweep.py --lds)
   int rng = 0;          // phase noise: 0 PB-RNG v1 (counter based), 1 cuRAND-compatible XORWOW (pb_xorwow.hpp)
@@ -128,6 +130,24 @@ struct PbForcePlan {
   bool big;   // 64-bit byte offsets in the throughput sweep
 };
 PbForcePlan pbForcePlan(const pbSim *S);
+#ifndef PB_TAIL_LANES
+#define PB_TAIL_LANES 2  // lanes per bot of the throughput form's split-lane tail workgroups (k_force)
+#endif
+// Workgroup tileX of a throughput-form grid in XCD order with perXcd tiles per XCD, the last `tail` of them split
+// (8 * (perXcd + tail * (PB_TAIL_LANES - 1)) workgroups; round-robin dispatch puts workgroups b, b+8, ... on one
+// XCD): its first bot, and whether it is a tail workgroup (TILE / PB_TAIL_LANES bots, PB_TAIL_LANES lanes each;
+// else TILE bots, one lane each).  Together the workgroups cover bots [0, 8 * perXcd * TILE) once each.
+__host__ __device__ inline bool pbXcdTile(uint32_t tileX, uint32_t perXcd, uint32_t tail, uint32_t &first) {
+  const uint32_t x = tileX & 7u, k = tileX >> 3, mainK = perXcd - tail;
+  if (k < mainK) {
+    first = (x * perXcd + k) * TILE;
+    return false;
+  }
+  first = (x * perXcd + mainK) * TILE + (k - mainK) * (TILE / PB_TAIL_LANES);
+  return true;
+}
+// split-lane tail tiles per XCD of the next per-step force launch (0: none; pbSimSetTailTiles)             pb_force.hip
+uint32_t pbForceTailTiles(pbSim *S);
 
 // step n's forces + kick into the other copy of posrad/vel; fuse: also step n+1's radius + integration
 void pbLaunchForce(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int doRadiusNext);          // pb_force.hip

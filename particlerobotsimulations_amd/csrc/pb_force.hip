@@ -40,7 +40,7 @@ namespace {
 // ASUM: maintain absForce_a.  false (throughput form, batches without constrained contraction):
 // the attraction magnitudes are dead values and are neither computed nor stored (pbPairEvalXY).
 template <bool PAYLOAD, bool FLAT, int L, int NB, bool BIG, bool ASUM>
-__global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : PB_FORCE_WAVES)) void k_force(const PbDevParams *__restrict__ params,
+__global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : (L == 1 && FLAT && !BIG && !PAYLOAD) ? PB_TAIL_FORM_WAVES : PB_FORCE_WAVES)) void k_force(const PbDevParams *__restrict__ params,
                                                 const float4 *__restrict__ prIn, const float2 *__restrict__ velIn,
                                                 const uint32_t *__restrict__ cellSAll, float *__restrict__ absR,
                                                 uint32_t n, uint32_t perXcd, uint32_t memberTiles, uint32_t nsims,
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : PB_FORCE_WAVES)) vo
   // one GPU: 32 + 32 members 7.75 -> 7.31 us per step, 64 + 64 members 10.22 -> 9.40, 8 + 8 unchanged
   // (tools/experiments/ab_xcd_members.sh); the results do not depend on the mapping.
   uint32_t member = blockIdx.y, tileX = blockIdx.x;
-  if (memberTiles) {
+  if (memberTiles && !perXcd) {
     const uint32_t r = blockIdx.x >> 3;
     member = (r / memberTiles) * 8u + (blockIdx.x & 7u);
     tileX = r % memberTiles;
@@ -70,9 +70,24 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : PB_FORCE_WAVES)) vo
   // XCD-aware tile order (large simulations): workgroups b, b+8, b+16, ... share an XCD
   // (round-robin dispatch); give each XCD one contiguous eighth of the tiles (gridDim.x = 8*perXcd).
   // perXcd == 0: plain order (small simulations, a handful of tiles each).
-  const uint32_t tile = perXcd ? (tileX & 7u) * perXcd + (tileX >> 3) : tileX;
-  const uint32_t l = tile * (TILE / L) + threadIdx.x / L;  // all L lanes of a group share the bot
-  const uint32_t sub = threadIdx.x % L;
+  uint32_t tile = perXcd ? (tileX & 7u) * perXcd + (tileX >> 3) : tileX;
+  uint32_t l = tile * (TILE / L) + threadIdx.x / L;  // all L lanes of a group share the bot
+  uint32_t sub = threadIdx.x % L;
+  // Split-lane tail (throughput form, perXcd != 0): memberTiles is then the number of tiles at the END of every
+  // XCD's eighth that run as workgroups of TILE / PB_TAIL_LANES bots with PB_TAIL_LANES lanes each (pbXcdTile).
+  // Dispatch is ascending within an XCD, so they are the last workgroups to start: a bot's serial neighbour chain
+  // there is about half as long (at ~1.4x the VALU work per bot, which the draining SIMDs have spare), and the
+  // launch ends sooner.  The choice is per workgroup, so it is wave-uniform, and both sweeps give the same bits.
+  constexpr bool TAILABLE = L == 1 && FLAT && NB == 1 && !BIG;
+  bool tailWg = false;
+  if (TAILABLE && perXcd && memberTiles) {
+    uint32_t first;
+    tailWg = pbXcdTile(tileX, perXcd, memberTiles, first);
+    if (tailWg) {
+      l = first + threadIdx.x / PB_TAIL_LANES;
+      sub = threadIdx.x % PB_TAIL_LANES;
+    }
+  }
 #ifdef PB_TIMELINE
   // (stored at once: a start stamp kept in registers to the end cost the kernel a wave per SIMD)
   PB_TL_STAMP(0);
@@ -100,10 +115,17 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : PB_FORCE_WAVES)) vo
   constexpr bool REPLIST = L == 1 && FLAT && NB == 1 && (!ASUM || PB_ASUM_XY);
   __shared__ float repLds[REPLIST ? (PB_REP_CAP + 1) * TILE : 1];
   float *const repCol = &repLds[REPLIST ? threadIdx.x : 0];
-  if (FLAT && fastOk && __all(pbLaneFastMathOk(me.x, me.y)))
-    pbSweep<PAYLOAD, FLAT, true, L, NB, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, repCol);
+  auto sweep = [&](auto lanes) __attribute__((always_inline)) {
+    constexpr int LS = decltype(lanes)::value;
+    if (FLAT && fastOk && __all(pbLaneFastMathOk(me.x, me.y)))
+      pbSweep<PAYLOAD, FLAT, true, LS, NB, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, repCol);
+    else
+      pbSweep<PAYLOAD, FLAT, false, LS, NB, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, repCol);
+  };
+  if (TAILABLE && tailWg)
+    sweep(std::integral_constant<int, TAILABLE ? PB_TAIL_LANES : L>{});
   else
-    pbSweep<PAYLOAD, FLAT, false, L, NB, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, repCol);
+    sweep(std::integral_constant<int, L>{});
   pbObstacles(P, me.x, me.y, v.x, v.y, me.z, F);
   pbFrictionAndKick(P, selfPayload, F.fx, F.fy, dt, v.x, v.y);
 
@@ -128,19 +150,39 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : PB_FORCE_WAVES)) vo
 #endif
 }
 
+// Split-lane tail tiles per XCD for a throughput-form launch with perXcd tiles per XCD.  Rule: the last round of
+// workgroups is spread over every CU, and the tail gives each CU one tile of it, split into PB_TAIL_LANES workgroups:
+// CUs per XCD tiles, for launches of at least one full round (perXcd >= CUs per XCD x workgroups per CU).
+// Measured on MI355X at 10^6 bots (1.91 rounds), us/step for 0/16/24/32/40/48 tail tiles per XCD: both sums
+// 89.8/86.4/85.7/85.6/85.6/86.2, dead sums 74.9/72.3/73.0/72.6/72.6/72.6 (profiles/r7_tail_sweep.txt).
+// Smaller launches (a single partial round: every workgroup starts at once) are left alone.
+uint32_t pbTailTiles(pbSim *S, uint32_t perXcd) {
+  if (S->tailTiles >= 0) return std::min((uint32_t)S->tailTiles, perXcd);
+  if (S->cuCount == 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, S->device) != hipSuccess || cus <= 0) cus = 256;
+    S->cuCount = (uint32_t)cus;
+  }
+  const uint32_t cusPerXcd = std::max(S->cuCount / 8u, 1u);
+  const uint32_t wgPerCu = PB_TAIL_FORM_WAVES * 4u / (TILE / 64u);  // 4 SIMDs per CU, TILE / 64 waves per workgroup
+  return perXcd >= cusPerXcd * wgPerCu ? cusPerXcd : 0u;
+}
+
 template <bool PAYLOAD, bool FLAT, int L, bool BIG, bool ASUM>
 void launchForceT(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int doRadiusNext) {
   const uint32_t tiles = cdiv(S->n, TILE / L);
   // XCD-aware order only pays when a simulation spans many tiles.  (Round 5: for the multi-lane forms too -- one
   // simulation of 4 000 ... 10^5 bots steps 1-4 % faster in its automatic form, profiles/r5_xcd_tiles_all.txt.)
   const uint32_t perXcd = ((L == 1 || S->xcdTilesAll) && tiles >= 64u) ? cdiv(tiles, 8u) : 0u;
-  dim3 grid(perXcd ? perXcd * 8u : tiles, S->nsims);
-  uint32_t memberTiles = 0u;
+  constexpr int NB = (FLAT && L == 1 && !BIG && ASUM) ? PB_THROUGHPUT_NB : 1;
+  // split-lane tail tiles per XCD (k_force; 0 for the forms without one)
+  const uint32_t tail = (FLAT && L == 1 && NB == 1 && !BIG && perXcd) ? pbTailTiles(S, perXcd) : 0u;
+  dim3 grid(perXcd ? (perXcd + tail * (PB_TAIL_LANES - 1)) * 8u : tiles, S->nsims);
+  uint32_t memberTiles = tail;
   if (S->xcdMembers && !perXcd && S->nsims >= 8u) {
     memberTiles = tiles;
     grid = dim3(cdiv(S->nsims, 8u) * 8u * tiles, 1u);
   }
-  constexpr int NB = (FLAT && L == 1 && !BIG && ASUM) ? PB_THROUGHPUT_NB : 1;
   // (the both-sums throughput form roots its attraction magnitudes without a domain check: pbAttractionMagnitudeSafe)
   const bool magNeeded = ASUM && FLAT && L == 1 && PB_ASUM_XY;
   const int fastOk = (S->variant >= 2 && S->fastOk && (!magNeeded || S->magOk)) ? 1 : 0;
@@ -193,6 +235,13 @@ const FormRow kForms[] = {
 constexpr int kNumForms = (int)(sizeof(kForms) / sizeof(kForms[0]));
 
 }  // namespace
+
+uint32_t pbForceTailTiles(pbSim *S) {
+  const PbForcePlan p = pbForcePlan(S);
+  if (p.stream || p.kind == 0 || p.form != 1 || p.big || pbResidentWanted(S)) return 0u;
+  const uint32_t tiles = cdiv(S->n, TILE);
+  return tiles >= 64u ? pbTailTiles(S, cdiv(tiles, 8u)) : 0u;
+}
 
 PbForcePlan pbForcePlan(const pbSim *S) {
   PbForcePlan p{false, 0, 1, true, false};
@@ -253,6 +302,15 @@ void pbLaunchForce(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int
 }
 
 extern "C" {
+
+int pbForceXcdTile(unsigned workgroup, unsigned per_xcd, unsigned tail_tiles, unsigned *first_bot, unsigned *bots) {
+  if (!first_bot || !bots || tail_tiles > per_xcd || workgroup >= 8u * (per_xcd + tail_tiles * (PB_TAIL_LANES - 1u)))
+    return PB_ERR_ARG;
+  uint32_t first;
+  *bots = pbXcdTile(workgroup, per_xcd, tail_tiles, first) ? TILE / PB_TAIL_LANES : TILE;
+  *first_bot = first;
+  return PB_OK;
+}
 
 int pbForceFormCount(void) { return kNumForms; }
 

@@ -30,6 +30,9 @@
 // (64 VGPRs, 28 spilled), 120.8 at 7 (72), 119.8 at 6 (80), 121.4 at 5 (81, no bound) against 114.0
 // for NB = 1 (63 VGPRs, 8 waves/SIMD): waves, not ILP inside a wave, are what fills the VALU pipe.
 
+#ifndef PB_TAIL_FORM_WAVES
+#define PB_TAIL_FORM_WAVES 8  // waves per SIMD the one-lane throughput forms (with their tail body) are compiled for
+#endif
 #ifndef PB_ASUM_XY
 #define PB_ASUM_XY 1  // throughput form with both sums: 1 = the dead-sum trip + the attraction magnitude (round 5), 0 = pbPairEvalK
 #endif

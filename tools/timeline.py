@@ -21,6 +21,8 @@ def main():
     ap.add_argument("--libdir", required=True)
     ap.add_argument("--bots", type=int, default=1_000_000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--force-sums", type=int, default=1, help="1: both magnitude sums (the headline kernel), 0: dead sums")
+    ap.add_argument("--tail", type=int, default=-1, help="split-lane tail tiles per XCD (-1: the automatic share, 0: off)")
     args = ap.parse_args()
     from particlerobotsimulations_amd import _capi
     _capi.LIB_DIR = os.path.abspath(args.libdir)
@@ -28,12 +30,18 @@ def main():
     import particlerobotsimulations_amd as pb
     pb.legacy.cudaInit(0, None)
     n = args.bots
-    sim = bench.make_sim(pb, n, bench.LATTICE_PITCH, seed=1)
+    sim = bench.make_sim(pb, n, bench.LATTICE_PITCH, seed=1, force_sums=args.force_sums)
     sim.set_lanes_per_bot(1)
+    if hasattr(sim, "set_tail_tiles"):
+        sim.set_tail_tiles(args.tail)
     sim.step(200)
     sim.synchronize()  # (the pointer below must not change under running kernels)
+    cfg = sim.config()
+    print("kernel:", sim.force_kernel_name().split("(")[0], "tail tiles per XCD:", cfg.get("tail_tiles"), "lanes:", cfg.get("tail_lanes"))
     tiles = (n + 255) // 256
     grid = ((tiles + 7) // 8) * 8 if tiles >= 64 else tiles
+    if tiles >= 64 and cfg.get("tail_tiles"):   # split-lane tail: tail_lanes workgroups per tail tile
+        grid = ((tiles + 7) // 8 + cfg["tail_tiles"] * (cfg["tail_lanes"] - 1)) * 8
     buf = pb.DeviceArray((grid + 64, 8), np.uint64, fill=0)  # (+64 rows of slack)
     L = _capi.lib()
     L.pbDebugSetTimeline.argtypes = [C.c_void_p]
@@ -61,6 +69,15 @@ def main():
     print("time(us)  resident  started  finished")
     for a in np.arange(0, end.max() + 5, 5.0):
         print(f"{a:7.0f} {int(((start <= a) & (end > a)).sum()):9d} {int((start <= a).sum()):8d} {int((end <= a).sum()):9d}")
+    fine = np.arange(0, end.max() + 0.25, 0.25)
+    res = np.array([int(((start <= a) & (end > a)).sum()) for a in fine])
+    below = fine[(res < 256) & (fine > 5.0)]
+    print(f"last workgroup start -> launch end: {end.max() - start.max():.1f} us; "
+          f"fewer than 256 workgroups resident (after the ramp): {0.25 * len(below):.1f} us"
+          + (f" (from {below.min():.1f} us)" if len(below) else ""))
+    ends = np.sort(end)
+    print("last workgroups to finish (us before the launch end): 1%% %.1f, 5%% %.1f, 10%% %.1f" % tuple(
+        end.max() - ends[int(len(ends) * (1 - f))] for f in (0.01, 0.05, 0.10)))
     order = np.argsort(start)
     print("lifetime by start-time decile (us):", [round(float(life[order[i::10]].mean()), 1) for i in range(10)][:1],
           [round(float(np.mean(life[(start >= lo) & (start < lo + 10)])), 1) if ((start >= lo) & (start < lo + 10)).any() else None
