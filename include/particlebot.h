@@ -156,6 +156,18 @@ class Particlebot {
    * setDisplay(true)).  Returns false on I/O errors. */
   bool writeFramePPMReference(const char *path, int width, int height, float centerX, float centerY,
                               float halfExtent, float lightRadius = 0.25f);
+  /* The same pictures rasterised on the device from the engine's resident state (pbSimRenderOf): only the
+   * 3 * width * height bytes of the frame leave the device, no state copy.  renderFrame fills `rgb` (rows top to
+   * bottom, R G B); writeFramePPMDevice writes the header and payload bytes writeFramePPM / writeFramePPMReference
+   * write for the same state.  Fused engine only: Legacy and HostOnly instances return false with a message on
+   * stderr.  Also false on a bad size or extent, and on I/O errors. */
+  bool renderFrame(std::vector<unsigned char> &rgb, int width, int height, float centerX, float centerY,
+                   float halfExtent, float lightRadius = 0.25f, bool referenceStyle = false);
+  bool writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY, float halfExtent,
+                           float lightRadius = 0.25f, bool referenceStyle = false);
+  /* frames rendered on the device so far and the device time of the last one's launches in milliseconds
+   * (pbSimGetRenderStats); false unless the engine is the fused one */
+  bool renderStats(unsigned long long &frames, float &lastDeviceMs);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at
@@ -245,6 +257,7 @@ class Particlebot {
   struct pbGraphicsResource *colRes = nullptr;
   float *dTempPos1 = nullptr, *dTempPos2 = nullptr; /* calcCOG's temporaries (legacy) */
   std::vector<float> hColV, trailTimesV;
+  std::vector<unsigned char> frameV; /* writeFramePPMDevice's frame, kept between calls */
   unsigned trailRecords = 0;
 };
 

@@ -327,6 +327,32 @@ int pbSimSetResident(pbSim *sim, int mode);
  * constants are outside the fast forms' domain), the effective lanes per bot of the per-step kernel,
  * whether the resident multi-step kernel is used, and the phase-noise generator.  bench.py echoes it
  * into its JSON line so a reader can see which kernel a number belongs to. */
+/* One frame of one member, rasterised on the device from the resident state (csrc/pb_render.hip): byte for byte the
+ * picture Particlebot::writeFramePPM (style 0) / writeFramePPMReference (style 1) paints on the host from the same
+ * state -- background 245, rectangle obstacles, circle obstacles, the light disc of lightRadius, the bots in ORIGINAL
+ * index order (a pixel keeps the highest index that covers it), and in style 1 with the centroid trail on
+ * (pbSimSetCentroidTrail) the recorded trail slots as red discs of centroid_radius on top.  scale =
+ * 0.5f * height / halfExtent pixels per world unit, x mirrored, y up.  `rgb` is a host buffer of 3 * width * height
+ * bytes, rows top to bottom, R G B per pixel.  Only the picture leaves the device.
+ * Rendering reads the state and changes nothing: not the slot layout, not the counters of pbSimStats.  Buffers
+ * (4 + 3 bytes per pixel, 4 per bot) are allocated by the first call, kept, and freed by pbSimDestroy.
+ * PB_ERR_ARG, before the device is touched: NULL handle, view or buffer; member out of range; width or height <= 0 or
+ * width * height > PB_RENDER_MAX_PIXELS; halfExtent not > 0; style other than 0 or 1.
+ * Non-finite positions or radii are outside the contract (the host writer's conversion of them to int is undefined):
+ * the device does not fault on them and draws nothing for such a bot.  The lanes per bot are chosen from
+ * max_radius * scale; a bot far larger than that is drawn correctly, but by too few lanes.
+ * pbSimGetRenderStats: frames rendered so far, and the device time of the last frame's launches (clear, scatter,
+ * resolve; without the copy to the host) in milliseconds.  Either pointer may be NULL. */
+#define PB_RENDER_MAX_PIXELS 67108864ull /* 2^26 */
+typedef struct pbRenderView {
+  int width, height;                  /* > 0, width * height <= PB_RENDER_MAX_PIXELS */
+  float centerX, centerY, halfExtent; /* halfExtent > 0: world units from the centre to the top edge */
+  float lightRadius;
+  int style;                          /* 0 plain, 1 reference (device colours + centroid trail) */
+} pbRenderView;
+int pbSimRenderOf(pbSim *sim, unsigned member, const pbRenderView *view, unsigned char *rgb);
+int pbSimGetRenderStats(pbSim *sim, unsigned long long *renders, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

@@ -379,6 +379,24 @@ class Sim:
                                                         C.byref(rec)), "pbSimGetCentroidTrailOf")
         return xy, times, int(rec.value)
 
+    def render(self, width, height, center=(0.0, 0.0), half_extent=1.0, light_radius=0.25, style="plain", member=0):
+        """One frame of `member` rasterised on the device from the resident state (pbSimRenderOf): uint8
+        [height, width, 3], byte for byte the host frame writer's picture of the same state.  style "reference": the
+        device colours, and the centroid trail when set_centroid_trail(True)."""
+        if style not in ("plain", "reference"):
+            raise ValueError(style)
+        view = _capi.pbRenderView(int(width), int(height), float(center[0]), float(center[1]), float(half_extent),
+                                  float(light_radius), 1 if style == "reference" else 0)
+        out = np.empty((int(height), int(width), 3), np.uint8)
+        _capi.check(_capi.lib().pbSimRenderOf(self._h, int(member), C.byref(view), _capi.np_ptr(out)), "pbSimRenderOf")
+        return out
+
+    def render_stats(self):
+        """(frames rendered, device milliseconds of the last frame's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetRenderStats(self._h, C.byref(n), C.byref(ms)), "pbSimGetRenderStats")
+        return int(n.value), float(ms.value)
+
 
 class Ensemble(Sim):
     """A batch of independent simulations of equal size stepped by the same launches

@@ -78,6 +78,11 @@ class pbSimConfig(C.Structure):
                 ("tail_tiles", C.c_int), ("tail_lanes", C.c_int)]
 
 
+class pbRenderView(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("centerX", C.c_float), ("centerY", C.c_float),
+                ("halfExtent", C.c_float), ("lightRadius", C.c_float), ("style", C.c_int)]
+
+
 class pbForceForm(C.Structure):
     _fields_ = [("flat", C.c_int), ("lanes_per_bot", C.c_int), ("attraction_sums", C.c_int), ("offsets64", C.c_int)]
 
@@ -131,6 +136,8 @@ SYMBOLS = {
     "pbSimGetColorsOf": (_I, [_VP, _U, _VP]),
     "pbSimSetCentroidTrail": (_I, [_VP, _I]),
     "pbSimGetCentroidTrailOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_U)]),
+    "pbSimRenderOf": (_I, [_VP, _U, C.POINTER(pbRenderView), _VP]),
+    "pbSimGetRenderStats": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -683,6 +683,7 @@ void Particlebot::setArray(ParticlebotArray array, const float *data, int start,
   if (start < 0 || start >= n || count <= 0) return;
   if (start + count > n) count = n - start;
   const bool fused = engineKind == Engine::Fused;
+  const bool hostOnly = engineKind == Engine::HostOnly;  // no device state: the host mirrors are the state
   switch (array) {
     default:
     case POSITION:
@@ -690,7 +691,7 @@ void Particlebot::setArray(ParticlebotArray array, const float *data, int start,
       if (fused) {
         if (pbSimSetStateRangeOf(sim, 0, (unsigned)start, (unsigned)count, data, nullptr, nullptr, nullptr, nullptr) != PB_OK)
           die("pbSimSetStateRangeOf");
-      } else {
+      } else if (!hostOnly) {
         pbBufferSubData(posVbo, sizeof(float) * 2 * start, sizeof(float) * 2 * count, data);
       }
       break;
@@ -699,7 +700,7 @@ void Particlebot::setArray(ParticlebotArray array, const float *data, int start,
       if (fused) {
         if (pbSimSetStateRangeOf(sim, 0, (unsigned)start, (unsigned)count, nullptr, data, nullptr, nullptr, nullptr) != PB_OK)
           die("pbSimSetStateRangeOf");
-      } else {
+      } else if (!hostOnly) {
         copyArrayToDevice(dVel, data, (int)(start * 2 * sizeof(float)), (int)(count * 2 * sizeof(float)));
       }
       break;
@@ -708,7 +709,7 @@ void Particlebot::setArray(ParticlebotArray array, const float *data, int start,
       if (fused) {
         if (pbSimSetStateRangeOf(sim, 0, (unsigned)start, (unsigned)count, nullptr, nullptr, nullptr, data, nullptr) != PB_OK)
           die("pbSimSetStateRangeOf");
-      } else {
+      } else if (!hostOnly) {
         copyArrayToDevice(dphase, data, (int)(start * sizeof(float)), (int)(count * sizeof(float)));
       }
       break;
@@ -720,7 +721,7 @@ void Particlebot::setArray(ParticlebotArray array, const float *data, int start,
       if (fused) {
         if (pbSimSetStateRangeOf(sim, 0, (unsigned)start, (unsigned)count, nullptr, nullptr, data, nullptr, nullptr) != PB_OK)
           die("pbSimSetStateRangeOf");
-      } else {
+      } else if (!hostOnly) {
         pbBufferSubData(radVbo, sizeof(float) * start, sizeof(float) * count, data);
       }
       break;
@@ -1339,6 +1340,42 @@ bool Particlebot::writeFrame(const char *path, int width, int height, float cent
   if (!fp) return false;
   fprintf(fp, "P6\n%d %d\n255\n", width, height);
   const bool ok = fwrite(img.data(), 1, img.size(), fp) == img.size();
+  return fclose(fp) == 0 && ok;
+}
+
+bool Particlebot::renderFrame(std::vector<unsigned char> &rgb, int width, int height, float centerX, float centerY,
+                              float halfExtent, float lightRadius, bool referenceStyle) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::renderFrame: the device rasteriser needs the fused engine\n");
+    return false;
+  }
+  if (width <= 0 || height <= 0 || !(halfExtent > 0)) return false;
+  pbRenderView view;
+  view.width = width, view.height = height;
+  view.centerX = centerX, view.centerY = centerY, view.halfExtent = halfExtent;
+  view.lightRadius = lightRadius;
+  view.style = referenceStyle ? 1 : 0;
+  if ((unsigned long long)width * (unsigned long long)height > PB_RENDER_MAX_PIXELS) return false;
+  rgb.resize((size_t)width * height * 3);
+  if (pbSimRenderOf(sim, 0, &view, rgb.data()) != PB_OK) {
+    fprintf(stderr, "Particlebot::renderFrame: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::renderStats(unsigned long long &frames, float &lastDeviceMs) {
+  return engineKind == Engine::Fused && pbSimGetRenderStats(sim, &frames, &lastDeviceMs) == PB_OK;
+}
+
+bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
+                                      float halfExtent, float lightRadius, bool referenceStyle) {
+  if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))
+    return false;
+  FILE *fp = fopen(path, "wb");
+  if (!fp) return false;
+  fprintf(fp, "P6\n%d %d\n255\n", width, height);
+  const bool ok = fwrite(frameV.data(), 1, frameV.size(), fp) == frameV.size();
   return fclose(fp) == 0 && ok;
 }
 

@@ -274,6 +274,35 @@ int pbHostWriteFrameStyle(void *hv, const char *path, int width, int height, flo
   return h->bot->writeFramePPMReference(path, width, height, cx, cy, half, h->cfg.light_radius) ? 0 : -1;
 }
 
+// the same frames rasterised on the device (Particlebot::renderFrame / writeFramePPMDevice; fused engine only):
+// path != NULL writes the PPM, rgb != NULL receives the 3 * width * height bytes.  half <= 0: the reference's camera.
+int pbHostRenderFrame(void *hv, const char *path, unsigned char *rgb, int width, int height, float cx, float cy,
+                      float half, int style) {
+  HostSim *h = (HostSim *)hv;
+  if (!(half > 0)) {
+    cx = h->cfg.camera_x;
+    cy = 0.0f;
+    half = h->cfg.camera_y * 0.57735027f;
+  }
+  if (path && !h->bot->writeFramePPMDevice(path, width, height, cx, cy, half, h->cfg.light_radius, style != 0)) return -1;
+  if (rgb) {
+    std::vector<unsigned char> img;
+    if (!h->bot->renderFrame(img, width, height, cx, cy, half, h->cfg.light_radius, style != 0)) return -1;
+    memcpy(rgb, img.data(), img.size());
+  }
+  return 0;
+}
+
+// frames rendered on the device and the last one's device milliseconds; -1 unless the engine is the fused one
+int pbHostRenderStats(void *hv, unsigned long long *frames, float *last_device_ms) {
+  unsigned long long f = 0;
+  float ms = 0.0f;
+  if (!((HostSim *)hv)->bot->renderStats(f, ms)) return -1;
+  if (frames) *frames = f;
+  if (last_device_ms) *last_device_ms = ms;
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

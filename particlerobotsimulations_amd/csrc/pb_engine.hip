@@ -743,6 +743,11 @@ void pbSimDestroy(pbSim *S) {
   (void)hipFree(S->colors);
   (void)hipFree(S->trail);
   (void)hipFree(S->trailTmp);
+  (void)hipFree(S->renderIds);
+  (void)hipFree(S->renderOut);
+  (void)hipFree(S->renderRgb8);
+  if (S->renderEv0) (void)hipEventDestroy(S->renderEv0);
+  if (S->renderEv1) (void)hipEventDestroy(S->renderEv1);
   if (S->hMin) (void)hipHostFree(S->hMin);
   if (S->hMinD) (void)hipHostFree(S->hMinD);
   if (S->hCom) (void)hipHostFree(S->hCom);
@@ -815,6 +820,7 @@ int pbSimCreateBatch(pbSim **out, const SimParams *params, int nsims, float wall
     S->displayShadow.push_back(params[k].display_shadow);
     S->centroidInt.push_back(params[k].centroid_int);
     S->centroidSteps.push_back(params[k].centroid_steps);
+    S->centroidRadius.push_back(params[k].centroid_radius);
   }
   // A/B switches for tools/ab_bench.py: honoured only under PB_ALLOW_ENV_OVERRIDES=1 and through the
   // same range checks as the setters, so a stray variable cannot silently change what a caller runs
@@ -1274,6 +1280,76 @@ int pbSimGetCentroidTrailOf(pbSim *S, unsigned sim, float *xy, float *times, uns
   }
   if (times) memcpy(times, S->trailTimes.data(), sizeof(float) * S->trailSteps);
   if (records) *records = S->trailRecords;
+  return PB_OK;
+}
+
+int pbSimRenderOf(pbSim *S, unsigned sim, const pbRenderView *view, unsigned char *rgb) {
+  if (!S || !view || !rgb) {
+    pbLastError() = "pbSimRenderOf: null handle, view or buffer";
+    return PB_ERR_ARG;
+  }
+  if (sim >= S->nsims) {
+    pbLastError() = "pbSimRenderOf: member out of range";
+    return PB_ERR_ARG;
+  }
+  if (view->width <= 0 || view->height <= 0 ||
+      (unsigned long long)view->width * (unsigned long long)view->height > PB_RENDER_MAX_PIXELS) {
+    pbLastError() = "pbSimRenderOf: width and height must be > 0 and width * height <= PB_RENDER_MAX_PIXELS";
+    return PB_ERR_ARG;
+  }
+  if (!(view->halfExtent > 0.0f) || (view->style != 0 && view->style != 1)) {
+    pbLastError() = "pbSimRenderOf: halfExtent must be > 0 and style 0 (plain) or 1 (reference)";
+    return PB_ERR_ARG;
+  }
+  useDevice(S);
+  const size_t pixels = (size_t)view->width * (size_t)view->height;
+  if (pixels > S->renderPixels) {
+    PB_TRY(hipStreamSynchronize(S->stream));
+    (void)hipFree(S->renderIds);
+    (void)hipFree(S->renderOut);
+    S->renderIds = S->renderOut = nullptr;
+    S->renderPixels = 0;
+    PB_TRY(hipMalloc((void **)&S->renderIds, sizeof(uint32_t) * pixels));
+    PB_TRY(hipMalloc((void **)&S->renderOut, 12 * ((pixels + 3) / 4)));
+    S->renderPixels = pixels;
+  }
+  if (!S->renderRgb8) PB_TRY(hipMalloc((void **)&S->renderRgb8, sizeof(uint32_t) * S->n));
+  if (!S->renderEv0) PB_TRY(hipEventCreate(&S->renderEv0));
+  if (!S->renderEv1) PB_TRY(hipEventCreate(&S->renderEv1));
+  // the host writer's view, in its operations (Particlebot::writeFrame)
+  PbRenderParams V;
+  V.width = view->width, V.height = view->height;
+  V.centerX = view->centerX, V.centerY = view->centerY;
+  V.scale = 0.5f * (float)view->height / view->halfExtent;
+  V.halfW = 0.5f * (float)view->width, V.halfH = 0.5f * (float)view->height;
+  V.lightRadius = view->lightRadius;
+  V.style = view->style;
+  V.displayShadow = S->displayShadow[sim];
+  const int c = S->cur;
+  PB_TRY(hipEventRecord(S->renderEv0, S->stream));
+  PB_TRY(hipMemsetAsync(S->renderIds, 0, sizeof(uint32_t) * pixels, S->stream));
+  pbLaunchRenderBots(S->dP, sim, V, S->hP[sim].max_radius, S->pr[c], S->dead[c], S->orig[c], S->n, S->renderIds,
+                     S->renderRgb8, S->stream);
+  if (view->style == 1 && S->trail)
+    pbLaunchRenderTrail(V, S->trail + (size_t)sim * S->trailSteps, (uint32_t)S->trailSteps, S->centroidRadius[sim],
+                        S->renderIds, S->stream);
+  pbLaunchRenderResolve(S->dP, sim, V, S->renderIds, S->renderRgb8, (uint32_t)pixels, S->renderOut, S->stream);
+  PB_TRY(hipGetLastError());
+  PB_TRY(hipEventRecord(S->renderEv1, S->stream));
+  PB_TRY(hipMemcpyAsync(rgb, S->renderOut, 3 * pixels, hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  PB_TRY(hipEventElapsedTime(&S->lastRenderMs, S->renderEv0, S->renderEv1));
+  S->renders++;
+  return PB_OK;
+}
+
+int pbSimGetRenderStats(pbSim *S, unsigned long long *renders, float *last_device_ms) {
+  if (!S) {
+    pbLastError() = "pbSimGetRenderStats: null handle";
+    return PB_ERR_ARG;
+  }
+  if (renders) *renders = S->renders;
+  if (last_device_ms) *last_device_ms = S->lastRenderMs;
   return PB_OK;
 }
 

@@ -5,6 +5,8 @@
 //   pb_force.hip     k_force: the exact per-step force kernel in all its forms + the forms table
 //   pb_stream.hip    k_force_stream: the opt-in streamlined (tolerance) force kernel
 //   pb_resident.hip  k_resident: the multi-step one-workgroup-per-simulation kernel
+//   pb_display.hip   the reference's display kernels (colours, centroid trail)
+//   pb_render.hip    the frame rasteriser behind pbSimRenderOf
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 #pragma once
@@ -105,6 +107,15 @@ struct pbSim {
   int trailSteps = 0;
   std::vector<float> trailTimes;  // start time of the step that wrote each slot (NaN: never)
   unsigned trailRecords = 0;
+  // frame rasteriser (pb_render.hip, pbSimRenderOf): allocated by the first render, re-allocated when the frame grows
+  std::vector<float> centroidRadius;
+  uint32_t *renderIds = nullptr;   // one key per pixel
+  uint32_t *renderOut = nullptr;   // packed RGB8, padded to whole groups of four pixels
+  uint32_t *renderRgb8 = nullptr;  // n: a member's bot colours in original order
+  size_t renderPixels = 0;         // capacity of renderIds / renderOut
+  hipEvent_t renderEv0 = nullptr, renderEv1 = nullptr;
+  unsigned long long renders = 0;
+  float lastRenderMs = 0.0f;
   pbSimStats stats{};
 };
 

@@ -48,3 +48,25 @@ void pbLaunchEngineColors(const PbDevParams *params, uint32_t member, uint32_t d
 // dst + 2 k dstStride.  tmp0 / tmp1: scratch of ceil(n / 64) float2 per member (member k at + 2 k tmpStride)
 void pbLaunchCentroid(const float *pos, size_t posStride, uint32_t n, float *tmp0, float *tmp1, size_t tmpStride,
                       float *dst, size_t dstStride, uint32_t members, hipStream_t stream);
+
+// ---- the frame rasteriser (pb_render.hip) --------------------------------------------------------------------------
+// One view, flattened on the host with the host writer's fp32 operations (Particlebot::writeFrame):
+// scale = 0.5f * height / halfExtent, halfW = 0.5f * width, halfH = 0.5f * height.
+struct PbRenderParams {
+  int width, height;
+  float centerX, centerY, scale, halfW, halfH;
+  float lightRadius;
+  int style;                // 0 plain, 1 reference (updateCol_k's colours)
+  uint32_t displayShadow;   // the member's display_shadow (style 1)
+};
+// ids: one key per pixel, cleared by the caller; rgb8: n packed colours, written at [orig] for every bot that is drawn.
+// maxRadius (world units) picks the lanes per bot.
+void pbLaunchRenderBots(const PbDevParams *params, uint32_t member, const PbRenderParams &V, float maxRadius,
+                        const float4 *pr, const int *dead, const uint32_t *orig, uint32_t n, uint32_t *ids,
+                        uint32_t *rgb8, hipStream_t stream);
+// the recorded slots of one member's centroid ring as discs of `radius` at (x, y - 2000), above every bot
+void pbLaunchRenderTrail(const PbRenderParams &V, const float2 *ring, uint32_t slots, float radius, uint32_t *ids,
+                         hipStream_t stream);
+// keys -> packed RGB8 (3 * pixels bytes, `out` padded to a multiple of 12), the analytic items where no key is set
+void pbLaunchRenderResolve(const PbDevParams *params, uint32_t member, const PbRenderParams &V, const uint32_t *ids,
+                           const uint32_t *rgb8, uint32_t pixels, uint32_t *out, hipStream_t stream);

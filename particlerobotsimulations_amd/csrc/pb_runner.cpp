@@ -1,7 +1,8 @@
 // pb_runner.cpp -- headless replacement for the reference's GLUT main loop.
 //
 //   particlebot_run [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet]
-//                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference]] [--trail FILE]
+//                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]]
+//                   [--trail FILE]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -22,7 +23,9 @@
 // batch so that it can keep one fused kernel per timestep.  --frames DIR writes a PPM of the arena
 // every VIDEO_INTERVAL timesteps (the reference's video cadence, main.cpp:455-470), viewed like the
 // reference's camera: centred on (camera_x, 0), half extent camera_y * tan(30 deg); --frame-style reference draws them
-// in the device colours of updateCol with the centroid trail (Particlebot::writeFramePPMReference).  --trail FILE
+// in the device colours of updateCol with the centroid trail (Particlebot::writeFramePPMReference).
+// --frame-render device rasterises the frames on the GPU from the engine's resident state (Particlebot::writeFramePPMDevice:
+// the same bytes, no state copy; fused engine only); host (default) is the class's CPU writer.  --trail FILE
 // records the reference's centroid trail (Particlebot::setDisplay) and writes it at the end of the run as
 // `slot,time,x,y` rows (slots holding a record; fp32 time and x to 9 digits), y as the double (stored y) - 2000, without the shader's +2000 (a resumed run starts a fresh trail).
 #include <algorithm>
@@ -80,7 +83,7 @@ int main(int argc, char **argv) {
   bool quiet = false, overwriteCsv = false;
   std::string framesDir, resumePath, ckptPath, finalCkptPath;
   int frameSize = 800;
-  bool referenceFrames = false;
+  bool referenceFrames = false, deviceFrames = false;
   std::string trailPath;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -101,6 +104,9 @@ int main(int argc, char **argv) {
     } else if (!strcmp(argv[i], "--frame-style") && i + 1 < argc &&
                (!strcmp(argv[i + 1], "plain") || !strcmp(argv[i + 1], "reference"))) {
       referenceFrames = !strcmp(argv[++i], "reference");
+    } else if (!strcmp(argv[i], "--frame-render") && i + 1 < argc &&
+               (!strcmp(argv[i + 1], "host") || !strcmp(argv[i + 1], "device"))) {
+      deviceFrames = !strcmp(argv[++i], "device");
     } else if (!strcmp(argv[i], "--trail") && i + 1 < argc) {
       trailPath = argv[++i];
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
@@ -120,7 +126,7 @@ int main(int argc, char **argv) {
     } else {
       fprintf(stderr,
               "usage: %s [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet] "
-              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference]] [--trail FILE] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
+              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
               "[--checkpoint-every SECONDS] [--checkpoint-steps N]] [--final-checkpoint FILE]\n",
               argv[0]);
       return 2;
@@ -239,7 +245,13 @@ int main(int argc, char **argv) {
       snprintf(name, sizeof name, "/frame_%06ld.ppm", frames++);
       const std::string fpath = framesDir + name;
       const float half = cfg.camera_y * 0.57735027f;
-      if (!(referenceFrames ? sim.writeFramePPMReference(fpath.c_str(), frameSize, frameSize, cfg.camera_x, 0.0f, half,
+      if (deviceFrames) {
+        if (!sim.writeFramePPMDevice(fpath.c_str(), frameSize, frameSize, cfg.camera_x, 0.0f, half, cfg.light_radius,
+                                     referenceFrames)) {
+          fprintf(stderr, "cannot write %s%s\n", framesDir.c_str(), name);
+          return 1;
+        }
+      } else if (!(referenceFrames ? sim.writeFramePPMReference(fpath.c_str(), frameSize, frameSize, cfg.camera_x, 0.0f, half,
                                                          cfg.light_radius)
                             : sim.writeFramePPM(fpath.c_str(), frameSize, frameSize, cfg.camera_x, 0.0f, half,
                                                 cfg.light_radius))) {

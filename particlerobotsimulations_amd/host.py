@@ -95,6 +95,11 @@ def lib():
     L.pbHostWriteFrameStyle.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
                                         C.c_int]
     L.pbHostWriteFrameStyle.restype = C.c_int
+    L.pbHostRenderFrame.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
+                                    C.c_float, C.c_int]
+    L.pbHostRenderFrame.restype = C.c_int
+    L.pbHostRenderStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)]
+    L.pbHostRenderStats.restype = C.c_int
     _lib = L
     return L
 
@@ -194,22 +199,50 @@ class HostSim:
             raise RuntimeError("centroid_trail: set_display(True) first")
         return xy, times, int(rec.value)
 
-    def write_frame(self, path, size=800, center=(0.0, 0.0), half_extent=0.0, style="plain"):
+    def write_frame(self, path, size=800, center=(0.0, 0.0), half_extent=0.0, style="plain", renderer="host"):
         """Binary PPM of the arena seen from above (Particlebot::writeFramePPM; style "reference":
         writeFramePPMReference, the device colours and the centroid trail).  half_extent <= 0:
-        the reference's camera, centred on (camera_x, 0), half extent camera_y * tan(30 deg)."""
+        the reference's camera, centred on (camera_x, 0), half extent camera_y * tan(30 deg).
+        size: pixels of a square frame, or (width, height).  renderer "device": the same bytes rasterised on the GPU
+        from the resident state (Particlebot::writeFramePPMDevice; fused engine only)."""
         L = lib()
+        width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        if style not in ("plain", "reference"):
+            raise ValueError(style)
+        if renderer not in ("host", "device"):
+            raise ValueError(renderer)
+        if renderer == "device":
+            if L.pbHostRenderFrame(self._h, os.fsencode(path), None, width, height, center[0], center[1], half_extent,
+                                   1 if style == "reference" else 0) != 0:
+                raise OSError(f"writeFramePPMDevice({path}) failed")
+            return
         if style != "plain":
-            if style != "reference":
-                raise ValueError(style)
-            if L.pbHostWriteFrameStyle(self._h, os.fsencode(path), int(size), int(size), center[0], center[1],
+            if L.pbHostWriteFrameStyle(self._h, os.fsencode(path), width, height, center[0], center[1],
                                        half_extent, 1) != 0:
                 raise OSError(f"writeFramePPMReference({path}) failed")
             return
         L.pbHostWriteFrame.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
-        if L.pbHostWriteFrame(self._h, os.fsencode(path), int(size), int(size), center[0], center[1],
+        if L.pbHostWriteFrame(self._h, os.fsencode(path), width, height, center[0], center[1],
                               half_extent) != 0:
             raise OSError(f"writeFramePPM({path}) failed")
+
+    def render(self, width, height, center=(0.0, 0.0), half_extent=0.0, style="plain"):
+        """The frame write_frame(..., renderer="device") writes, as a uint8 array [height, width, 3] (fused engine
+        only; Particlebot::renderFrame)."""
+        if style not in ("plain", "reference"):
+            raise ValueError(style)
+        out = np.empty((int(height), int(width), 3), np.uint8)
+        if lib().pbHostRenderFrame(self._h, None, out.ctypes.data_as(C.c_void_p), int(width), int(height), center[0],
+                                   center[1], half_extent, 1 if style == "reference" else 0) != 0:
+            raise RuntimeError("renderFrame failed (the device rasteriser needs the fused engine and a valid view)")
+        return out
+
+    def render_stats(self):
+        """(frames rendered on the device, device milliseconds of the last frame's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        if lib().pbHostRenderStats(self._h, C.byref(n), C.byref(ms)) != 0:
+            raise RuntimeError("render_stats: the device rasteriser needs the fused engine")
+        return int(n.value), float(ms.value)
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
