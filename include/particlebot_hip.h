@@ -440,6 +440,9 @@ int pbSelfTest(unsigned long long div_samples, unsigned long long *sqrt_checked,
 /* The static-friction hold's squared-length threshold for the constant c (pbHostSqrtThreshold) against the device's
  * IEEE sqrtf: `sqrtf(x) < c` and `x < T(c)` compared for EVERY non-negative float bit pattern x (2^31, NaNs included). */
 int pbSelfTestHoldThreshold(float c, unsigned long long *checked, unsigned long long *mismatches);
+/* The root of the both-sums throughput form's attraction magnitude (one v_rsq_f32, one Newton step, no clamp) against
+ * sqrtf for every float of [2^-96, FLT_MAX) -- a superset of what that form can hand it: 1 879 048 191 values. */
+int pbSelfTestMagnitudeRoot(unsigned long long *checked, unsigned long long *mismatches);
 int pbSelfTestPairGeometry(unsigned first_slice, unsigned slices, unsigned long long *checked,
                            unsigned long long *mismatches);
 /* The same for pbDiv2Fast (the division of the attraction term by gap^2): every denominator mantissa of

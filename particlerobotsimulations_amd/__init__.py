@@ -32,6 +32,14 @@ def self_test_hold_threshold(c):
     return {"checked": checked.value, "mismatches": bad.value}
 
 
+def self_test_magnitude_root():
+    """pbSelfTestMagnitudeRoot: the unclamped one-Newton-step root of the both-sums form's attraction magnitude
+    against sqrtf on the GPU for every float of [2^-96, FLT_MAX)."""
+    checked, bad = C.c_ulonglong(), C.c_ulonglong()
+    _capi.check(_capi.lib().pbSelfTestMagnitudeRoot(C.byref(checked), C.byref(bad)), "pbSelfTestMagnitudeRoot")
+    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+
+
 def self_test_pair_geometry(first_slice=0, slices=64):
     """pbSelfTestPairGeometry: pbDistUnitFast against sqrtf and IEEE division on EVERY (d2, numerator)
     mantissa pair of `slices` of the 64 slices of d2 in [1, 4) (all 64: 2^47 pairs, ~90 s of one MI355X)."""

@@ -152,12 +152,13 @@ static inline bool pbFastMathAllowed(const PbDevParams &d) {
 }
 
 // Precondition of the both-sums throughput form's attraction magnitude (pbPairEvalXY<FAST, true>): the root of
-// |term|^2 comes from pbRootNewton, exact for 0 and for [2^-96, FLT_MAX).  A non-contact term is the 2.5 N band or
-// A * n / gap^2 with gap^2 < 2^27 (above) and max(|nx|, |ny|) >= 2^-0.5, so |term|^2 >= A^2 * 2^-55: inside the domain
-// when every attraction constant a pair can see is 0 or >= 2^-20 (the reference's default is 4.8e-5 = 2^-14.4).  A batch
-// that fails it runs that form's plain IEEE path.
+// |term|^2 comes from pbRootNewtonPositive, exact for [2^-96, FLT_MAX) and NaN at 0 (no clamp).  A non-contact term is
+// the 2.5 N band or A * n / gap^2 with gap^2 < 2^27 (above) and max(|nx|, |ny|) >= 2^-0.5, so |term|^2 >= A^2 * 2^-55:
+// inside the domain when every attraction constant a pair can see is >= 2^-20 (the reference's default is
+// 4.8e-5 = 2^-14.4).  A constant of exactly 0 makes every far term (0, 0) and |term|^2 = 0, which the unclamped root
+// does not survive, so it fails the check too.  A batch that fails it runs that form's plain IEEE path.
 static inline bool pbAttractionMagnitudeSafe(const PbDevParams &d) {
-  auto okA = [](float a) { return a == 0.0f || a >= 0x1p-20f; };
+  auto okA = [](float a) { return a >= 0x1p-20f; };
   bool ok = okA(d.attraction);
   if (d.nDead == -1) {
     const float a1 = d.attraction * d.attractionFactor;
@@ -176,6 +177,17 @@ static_assert(offsetof(SimParams, worldOrigin) == 16 && offsetof(SimParams, nCel
               "SimParams layout drifted from the reference struct");
 
 #define PB_DEV __device__ __forceinline__
+
+// Bookkeeping taken out of the throughput sweep's pair trip (pbSweepC, FLAT && NB == 1; pbPairEvalXY), one bit each,
+// kept as ONE build-time switch for A/B runs (profiles/r8_trip_trim.txt).  Neither touches a floating-point operation
+// that reaches an output.
+//   1  own slot: a segment that holds the bot's own slot is walked as [lo, self) and (self, hi) instead of every
+//      trip comparing its offset with the own slot's and masking the accumulation
+//   4  the attraction magnitude's root without the clamp (pbRootNewtonPositive)
+// (2 was the contact mask of Sum|F_attr| moved into the near block: measured slower, removed, see the same file.)
+#ifndef PB_TRIP_TRIM
+#define PB_TRIP_TRIM 5
+#endif
 
 // helper_math.h:1244/1287 semantics: dot = ax*bx + ay*by (two roundings), length = sqrtf(dot)
 PB_DEV float pbDot(float ax, float ay, float bx, float by) { return ax * bx + ay * by; }
@@ -366,6 +378,31 @@ PB_DEV float pbRootNewton(float x, float &s) {
   // GPU test session
   const float e = __builtin_fmaf(-y, y, x);
   return __builtin_fmaf(e, h, y);
+}
+
+// pbRootNewton without the clamp: the same v_rsq_f32, the same Newton step, one VALU instruction less.  The clamp is the
+// identity unless v_rsq_f32 returns +inf (x == 0), NaN (x < 0, NaN) or 0 (x == +inf, where both forms end in NaN), so
+// this equals sqrtf(x) for every x in [2^-96, FLT_MAX) (pbSelfTestMagnitudeRoot: every float of the range) and must not
+// see 0.  Its one caller is the attraction magnitude of the both-sums throughput form, which roots
+// m2 = tx^2 + ty^2 of a term that is NOT a contact, in a batch that passed pbAttractionMagnitudeSafe and
+// pbFastMathAllowed:
+//   * m2 >= A^2 * 2^-55 >= 2^-95 > 0 (see pbAttractionMagnitudeSafe; a band coefficient lies between 2.5 and
+//     A / near2^2 >= 2^-20 / 3.61e-6 > 0.26, and one component of n is >= 2^-0.5);
+//   * m2 is finite: a far term is at most A / near2^2 <= 2^30 / 3.61e-6 < 2^49 per component, a band term at most
+//     max(2.5, A / near2^2), so m2 < 2^99;
+//   * m2 is not NaN: the components are quotients and products of finite values with a nonzero finite divisor.
+// A contact lane's m2 (possibly 0: coincident bots at rest) is rooted here too, and the result is dropped.
+PB_DEV float pbRootNewtonPositive(float x) {
+#if PB_TRIP_TRIM & 4
+  const float s = __builtin_amdgcn_rsqf(x);
+  const float h = 0.5f * s;
+  const float y = x * s;
+  const float e = __builtin_fmaf(-y, y, x);
+  return __builtin_fmaf(e, h, y);
+#else
+  float s;
+  return pbRootNewton(x, s);
+#endif
 }
 
 PB_DEV void pbDistUnitFast(float rx, float ry, float d2, float &dist, float &nx, float &ny) {
@@ -627,14 +664,21 @@ struct PbPairXY {
   float tx, ty;
 };
 
-// WANT_A (round 5: the throughput form that keeps BOTH sums): also return, in magA, the magnitude of the term of a
-// lane that is NOT in contact -- length(tempforce) of the attraction branches (impl.cuh:580-592), the root of the
-// uncontracted dot product of the rounded components, as pbPairEvalK forms it -- and the lane's contact flag; a
-// contact's magnitude still goes through pushRep.  magA of a contact lane or of a lane that is not live is garbage.
+// WANT_A (round 5: the throughput form that keeps BOTH sums): also add to *fa the magnitude of the term of a live lane
+// that is NOT in contact -- length(tempforce) of the attraction branches (impl.cuh:580-592), the root of the
+// uncontracted dot product of the rounded components, as pbPairEvalK forms it; a contact's magnitude still goes through
+// pushRep.
+template <bool FAST>
+PB_DEV float pbAttractionMagnitude(float tx, float ty) {
+  const float m2 = pbDot(tx, ty, tx, ty);
+  // (FAST: no check for a tiny m2 -- the caller only takes the FAST path for batches that pass pbAttractionMagnitudeSafe)
+  return FAST ? pbRootNewtonPositive(m2) : sqrtf(m2);
+}
+
 template <bool FAST, bool WANT_A = false, class VelFetch, class PushRep>
 PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay, float avx, float avy, float ra,
                              float bx, float by, float rb, VelFetch velB, float attraction, float slope,
-                             PushRep pushRep, float *magA = nullptr, bool *isContact = nullptr) {
+                             PushRep pushRep, float *fa = nullptr) {
   const float near1 = 0.0009f, near2 = 0.0019f, fmin_attr = 2.5f;
   const float rx = bx - ax, ry = by - ay;
   const float d2 = pbDot(rx, ry, rx, ry);
@@ -647,7 +691,6 @@ PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay,
     ny = ry / dist;
   }
   const float reach = ra + rb;
-  const bool contact = dist < reach;
   const float gap = dist - reach;
   const float g2 = gap * gap;
   float tx, ty;
@@ -662,6 +705,7 @@ PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay,
   // some live lane passes it works out which lanes are which.
   const unsigned long long mNear = __builtin_amdgcn_ballot_w64(live) & __builtin_amdgcn_ballot_w64(gap < near2);
   if (mNear != 0ull) {
+    const bool contact = dist < reach;
     const unsigned long long mContact = __builtin_amdgcn_ballot_w64(contact);
     if ((mNear & ~mContact) != 0ull) {
       const float band = gap < near1 ? fmin_attr : fmin_attr + slope * (gap - near1);
@@ -687,17 +731,8 @@ PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay,
     }
   }
   if (WANT_A) {
-    const float m2 = pbDot(tx, ty, tx, ty);
-    float mag;
-    if (FAST) {
-      // (no check for a tiny m2: the caller only takes the FAST path for batches that pass pbAttractionMagnitudeSafe)
-      float s;
-      mag = pbRootNewton(m2, s);
-    } else {
-      mag = sqrtf(m2);
-    }
-    *magA = mag;
-    *isContact = contact;
+    const float mag = pbAttractionMagnitude<FAST>(tx, ty);
+    if (live && !(dist < reach)) *fa += mag;
   }
   PbPairXY r;
   r.tx = tx;

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : (L == 1 && FLAT && 
   using OffT = typename std::conditional<BIG, uint64_t, uint32_t>::type;
   static_assert(ASUM || (FLAT && NB == 1), "the dead-sum form exists for the branch-free sweeps only");
   // (L > 1: magnitudes are rooted inside the contact block; the both-sums throughput form has the list since round 5)
-  constexpr bool REPLIST = L == 1 && FLAT && NB == 1 && (!ASUM || PB_ASUM_XY);
+  constexpr bool REPLIST = L == 1 && FLAT && NB == 1;
   __shared__ float repLds[REPLIST ? (PB_REP_CAP + 1) * TILE : 1];
   float *const repCol = &repLds[REPLIST ? threadIdx.x : 0];
   auto sweep = [&](auto lanes) __attribute__((always_inline)) {
@@ -184,7 +184,7 @@ void launchForceT(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int 
     grid = dim3(cdiv(S->nsims, 8u) * 8u * tiles, 1u);
   }
   // (the both-sums throughput form roots its attraction magnitudes without a domain check: pbAttractionMagnitudeSafe)
-  const bool magNeeded = ASUM && FLAT && L == 1 && PB_ASUM_XY;
+  const bool magNeeded = ASUM && FLAT && L == 1;
   const int fastOk = (S->variant >= 2 && S->fastOk && (!magNeeded || S->magOk)) ? 1 : 0;
   // (debugLdsBytes: an occupancy experiment -- unused dynamic LDS that only limits workgroups per CU)
   hipLaunchKernelGGL((k_force<PAYLOAD, FLAT, L, NB, BIG, ASUM>), grid, dim3(TILE), S->debugLdsBytes, S->stream, S->dP,

@@ -24,7 +24,7 @@ __global__ __launch_bounds__(1024) void k_resident(const PbDevParams *__restrict
   constexpr int CAP = 1024 / L;
   __shared__ float4 sPr[2][CAP + 1];  // +1: the sweep prefetches one slot past a range
   __shared__ float2 sVel[2][CAP + 1];
-  constexpr bool REPLIST = L == 1 && (!ASUM || PB_ASUM_XY);  // (as k_force: the one-lane-per-bot sweep parks contact magnitudes)
+  constexpr bool REPLIST = L == 1;  // (as k_force: the one-lane-per-bot sweep parks contact magnitudes)
   __shared__ float repLds[REPLIST ? (PB_REP_CAP + 1) * 1024 : 1];
   // L == 1 (members of 513 ... 1024 bots): 32.8 + 16.4 + 36.9 = 86 KB of the CU's 160 KB, i.e. ONE workgroup per CU.
   // Registers allow a second one only below 768 bots (>= 71 VGPRs: 6 waves per SIMD) and only a batch of more than
@@ -156,7 +156,7 @@ void pbLaunchResident(pbSim *S, float dt, float t0, int m, int lightWave) {
   const bool asum = attractionSumsKept(S);
   // (with both sums kept the ONE-lane-per-bot sweep roots its attraction magnitudes without a domain check,
   //  pbAttractionMagnitudeSafe; the multi-lane forms do not and keep the fast path whatever magOk says -- as k_force)
-  const bool magNeeded = asum && residentLanes(S->n) == 1 && PB_ASUM_XY;
+  const bool magNeeded = asum && residentLanes(S->n) == 1;
   const bool fast = S->variant >= 2 && S->fastOk && (!magNeeded || S->magOk);
 #define PB_RESL(PL, FA)                                                   \
   do {                                                                    \

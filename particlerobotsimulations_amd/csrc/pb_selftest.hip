@@ -30,6 +30,25 @@ __global__ __launch_bounds__(256) void k_selftest_sqrt(unsigned long long *__res
   if (seen) atomicAdd(checked, (unsigned long long)seen);
 }
 
+// the attraction magnitude's root without the clamp (pbRootNewtonPositive) against hipcc's sqrtf for EVERY float of
+// [2^-96, FLT_MAX): a superset of what the both-sums throughput form can hand it, [2^-95, 2^99) -- the lower bound is
+// pbAttractionMagnitudeSafe's (every attraction constant >= 2^-20, |term|^2 >= A^2 * 2^-55), the upper one
+// pbFastMathAllowed's (A <= 2^30 over near2^2, squared, two components)
+__global__ __launch_bounds__(256) void k_selftest_magroot(unsigned long long *__restrict__ mismatches,
+                                                          unsigned long long *__restrict__ checked) {
+  const uint32_t base = (blockIdx.x * 256u + threadIdx.x) * 16u;
+  uint32_t bad = 0, seen = 0;
+  for (uint32_t k = 0; k < 16u; k++) {
+    const uint32_t bits = base + k;
+    if (bits < 0x0F800000u || bits >= 0x7F7FFFFFu) continue;
+    const float x = __uint_as_float(bits);
+    seen++;
+    if (__float_as_uint(pbRootNewtonPositive(x)) != __float_as_uint(sqrtf(x))) bad++;
+  }
+  if (bad) atomicAdd(mismatches, (unsigned long long)bad);
+  if (seen) atomicAdd(checked, (unsigned long long)seen);
+}
+
 // the static-friction hold (pb_device.hpp PbDevParams::holdV2 / holdF2): `sqrtf(x) < c` against `x < T(c)` for EVERY
 // non-negative float bit pattern x (infinities and NaNs included), T computed on the host (pbSqrtThreshold)
 __global__ __launch_bounds__(256) void k_selftest_hold(float c, float T, unsigned long long *__restrict__ mismatches,
@@ -213,6 +232,20 @@ int pbSelfTestHoldThreshold(float c, unsigned long long *checked, unsigned long 
   PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_selftest_hold, dim3(1u << 19), dim3(256), 0, 0, c, pbSqrtThreshold(c), d + 1, d + 0);
+  PB_TRY(hipGetLastError());
+  unsigned long long h[2];
+  PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
+  PB_TRY(hipFree(d));
+  if (checked) *checked = h[0];
+  if (mismatches) *mismatches = h[1];
+  return PB_OK;
+}
+
+int pbSelfTestMagnitudeRoot(unsigned long long *checked, unsigned long long *mismatches) {
+  unsigned long long *d = nullptr;
+  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(k_selftest_magroot, dim3(1u << 19), dim3(256), 0, 0, d + 1, d + 0);  // 2^31 bit patterns
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));

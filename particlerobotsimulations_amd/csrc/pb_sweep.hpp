@@ -17,9 +17,6 @@
 #ifndef PB_THROUGHPUT_NB
 #define PB_THROUGHPUT_NB 1
 #endif
-#ifndef PB_PREFETCH_DEPTH
-#define PB_PREFETCH_DEPTH 1  // neighbours in flight ahead of the one being evaluated (throughput sweep)
-#endif
 #ifndef PB_REP_CAP
 #define PB_REP_CAP 8  // pending contact magnitudes per lane before the wave flushes (PbRepList)
 #endif
@@ -32,15 +29,6 @@
 
 #ifndef PB_TAIL_FORM_WAVES
 #define PB_TAIL_FORM_WAVES 8  // waves per SIMD the one-lane throughput forms (with their tail body) are compiled for
-#endif
-#ifndef PB_ASUM_XY
-#define PB_ASUM_XY 1  // throughput form with both sums: 1 = the dead-sum trip + the attraction magnitude (round 5), 0 = pbPairEvalK
-#endif
-#ifndef PB_LAZY_VEL
-#define PB_LAZY_VEL 1  // (0: the round-2 form, the neighbour's velocity prefetched with every posrad)
-#endif
-#ifndef PB_SWEEP_EXPERIMENT
-#define PB_SWEEP_EXPERIMENT 0
 #endif
 #ifndef PB_TL_STAMP
 #define PB_TL_STAMP(word) do { } while (0)  // (pb_force.hip defines it in the -DPB_TIMELINE diagnostic build)
@@ -281,80 +269,47 @@ __device__ __forceinline__ void pbSweepC(const PbDevParams &P, PR prIn, VL velIn
     //  * Inside a segment the next neighbour's posrad is already in flight, the loop is unrolled
     //    by two with the two registers swapping roles (no copy at the back-edge), and it runs on
     //    32-bit BYTE offsets from the array base (one add and one compare per trip; the
-    //    neighbour's velocity sits at half the offset).  One slot past a range is still inside
-    //    the array (spare elements) and is never evaluated.
+    //    neighbour's velocity sits at half the offset and is fetched inside the contact block).  One
+    //    slot past a range is still inside the array (spare elements) and is never evaluated.
+    //  * The bot's own slot is never evaluated either (the reference skips j == index, impl.cuh:638): a
+    //    segment [lo, hi) that holds it is walked as [lo, self) and, in one more turn of the segment loop,
+    //    (self, hi), so the pair trip carries no test for it.  The slot is found by its index, not by the
+    //    bot's position: the lists are stale, so it may sit in any segment or in none, and in a grid fewer
+    //    than 5 cells high in more than one.  It contributed nothing, so the order of the sums is unchanged.
     const char *const prBytes = (const char *)&prIn[0];
     const char *const velBytes = (const char *)&velIn[0];
     // OffT: 32-bit byte offsets (batches below 2^28 bots: one add and one compare per trip, loads with a
     // scalar base + 32-bit vector offset) or 64-bit ones (larger batches, up to 2^32 slots)
+    constexpr bool SPLIT = (PB_TRIP_TRIM & 1) != 0;
     const OffT selfOff = (OffT)s * 16u;
+    const OffT selfOff16 = selfOff + 16u;
     auto at = [&](OffT off) __attribute__((always_inline)) { return *(const float4 *)(prBytes + off); };
-    auto vat = [&](OffT off) __attribute__((always_inline)) { return *(const float2 *)(velBytes + (off >> 1)); };
-    // (round 5: the form that keeps both sums parks its contact magnitudes in LDS too; PB_ASUM_XY 0 = the former
-    //  pbPairEvalK + pbPairAdd path, kept for A/B)
-    constexpr bool REPL = !ASUM || PB_ASUM_XY;
+    // contact magnitudes wait in the lane's LDS column (both forms since round 5)
     PbRepList<FAST, PB_REP_CAP, REPSTRIDE> rep;
-    if (REPL) rep.init(repCol);
+    rep.init(repCol);
     // (64-bit address arithmetic with a constant displacement: the displacement becomes the load's
     //  immediate offset, so the look-ahead loads need no address instructions of their own)
-#if PB_SWEEP_EXPERIMENT >= 2
-    // timing experiment (wrong results): no neighbour posrad loads at all
-    auto atI = [&](OffT off, int imm) __attribute__((always_inline)) {
-      float4 q = me;
-      asm volatile("" : "+v"(q.x), "+v"(q.y), "+v"(q.z) : "v"(off));
-      q.x += 0.3f;
-      return q;
-    };
-#else
     auto atI = [&](OffT off, int imm) __attribute__((always_inline)) {
       return *(const float4 *)(prBytes + (uint64_t)off + imm);
     };
-#endif
-#if PB_SWEEP_EXPERIMENT >= 1
-    // timing experiment (wrong results): no neighbour velocity loads
-    auto vatI = [&](OffT hoff, int imm) __attribute__((always_inline)) {
-      float2 w = v;
-      asm volatile("" : "+v"(w.x), "+v"(w.y) : "v"(hoff));
-      return w;
-    };
-#else
     auto vatI = [&](OffT hoff, int imm) __attribute__((always_inline)) {
       return *(const float2 *)(velBytes + (uint64_t)hoff + imm);
     };
-#endif
-    const OffT selfOff16 = selfOff + 16u;
-    auto one = [&](const float4 &q, auto velOf, bool isLive) __attribute__((always_inline)) {
-      const bool live[1] = {isLive};
-      const float bx[1] = {q.x}, by[1] = {q.y}, rb[1] = {q.z};
-      const float A[1] = {PAYLOAD ? attraction0 * q.w * att1 : attraction0};
-      const float K[1] = {PAYLOAD ? pbBandSlope(A[0]) : slope0};
-      if (ASUM && !PB_ASUM_XY) {
-        PbPairTerm t[1];
-        pbPairEvalK<FAST, 1>(CK, live, me.x, me.y, v.x, v.y, me.z, bx, by, rb, A, K, [&](int) { return velOf(); }, t);
-        pbPairAdd(live[0], t[0], F);
-      } else if (ASUM) {
-        // both sums: the dead-sum trip + the magnitude of the lane's attraction term (Sum|F_attr| in list order, as
-        // absforce_a += length(tempforce), impl.cuh:580-592); contact magnitudes through the LDS list as below
-        float magA;
-        bool contact;
-        const PbPairXY t = pbPairEvalXY<FAST, true>(CK, live[0], me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A[0],
-                                                    K[0], [&](bool mine, float m2) { rep.push(mine, m2, F.fr); }, &magA,
-                                                    &contact);
-        if (live[0]) {
-          asm volatile("");
-          F.fx += t.tx;
-          F.fy += t.ty;
-          if (!contact) F.fa += magA;
-        }
-      } else {
-        const PbPairXY t = pbPairEvalXY<FAST>(CK, live[0], me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A[0],
-                                              K[0], [&](bool mine, float m2) { rep.push(mine, m2, F.fr); });
-        if (live[0]) {
-          // (a real exec-masked block -- two scalar instructions -- instead of two selects per trip)
-          asm volatile("");
-          F.fx += t.tx;
-          F.fy += t.ty;
-        }
+    auto one = [&](const float4 &q, auto velOf, bool live) __attribute__((always_inline)) {
+      const float A = PAYLOAD ? attraction0 * q.w * att1 : attraction0;
+      const float K = PAYLOAD ? pbBandSlope(A) : slope0;
+      // the dead-sum trip; with ASUM also the magnitude of the lane's attraction term (Sum|F_attr| in list order, as
+      // absforce_a += length(tempforce), impl.cuh:580-592)
+      const PbPairXY t = pbPairEvalXY<FAST, ASUM>(CK, live, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A, K,
+                                                  [&](bool mine, float m2) { rep.push(mine, m2, F.fr); }, &F.fa);
+      if (SPLIT) {
+        F.fx += t.tx;
+        F.fy += t.ty;
+      } else if (live) {
+        // (a real exec-masked block -- two scalar instructions -- instead of two selects per trip)
+        asm volatile("");
+        F.fx += t.tx;
+        F.fy += t.ty;
       }
     };
     // byte offsets [lo, hi) of segment si; empty beyond the last one and for the second range of a
@@ -374,76 +329,38 @@ __device__ __forceinline__ void pbSweepC(const PbDevParams &P, PR prIn, VL velIn
     bounds(0, loA, hiA);
     bounds(stride, loB, hiB);
     float4 qA = at(loA);
-    float2 vA = vat(loA);
     PB_TL_STAMP(4);
 #pragma unroll 1
-    for (int si = 0; si < 10; si += stride) {
+    for (int si = 0; si < 10;) {
       if (si == 4) PB_TL_STAMP(5);
-      const OffT lo = loA, end = hiA;
+      const OffT lo = loA;
+      // own slot inside [lo, hiA): this turn stops short of it, the next one starts behind it with the same si
+      const bool cut = SPLIT && (OffT)(selfOff - lo) < (OffT)(hiA - lo);
+      const OffT end = cut ? selfOff : hiA;
       float4 q0 = qA;
-      float2 v0 = vA;
-      loA = loB;
-      hiA = hiB;
-      qA = at(loA);                        // first posrad of the next segment
-      vA = vat(loA);
-      bounds(si + 2 * stride, loB, hiB);   // bounds of the one after
+      loA = cut ? selfOff16 : loB;
+      hiA = cut ? hiA : hiB;
+      qA = at(loA);                                    // first posrad of the next turn's range
+      if (!cut) bounds(si + 2 * stride, loB, hiB);     // bounds of the segment after the next
+      si += cut ? 0 : stride;
       if (lo < end) {
-#if PB_PREFETCH_DEPTH == 2
-        // look-ahead of TWO neighbours (three register sets rotating through a loop unrolled by three); velocities
-        // fetched inside the contact block
-        OffT off = lo, hoff = lo >> 1;
-        const OffT endm16 = end - 16u, endm32 = end > 32u ? end - 32u : 0u, endm48 = end > 48u ? end - 48u : 0u;
-        float4 q1 = atI(off, 16);
-        for (;;) {
-          const float4 q2 = atI(off, 32);
-          one(q0, [&]() { return vatI(hoff, 0); }, off != selfOff);
-          if (off >= endm16) break;
-          q0 = atI(off, 48);
-          one(q1, [&]() { return vatI(hoff, 8); }, off != selfOff - 16u);
-          if (off >= endm32) break;
-          q1 = atI(off, 64);
-          one(q2, [&]() { return vatI(hoff, 16); }, off != selfOff - 32u);
-          if (off >= endm48) break;
-          off += 48u;
-          hoff += 24u;
-        }
-#else
         // two neighbours per turn of the loop: `off` is the even one's byte offset, hoff = off / 2 the
         // offset of its velocity
         OffT off = lo, hoff = lo >> 1;
         const OffT endm = end - 16u;
-#if PB_LAZY_VEL
-        // experiment: the neighbour's velocity fetched inside the contact block (22 % of the trips on the bench
-        // lattice) instead of with every posrad: one vector-memory instruction per trip instead of two
-        (void)v0;
         for (;;) {
           const float4 q1 = atI(off, 16);
-          one(q0, [&]() { return vatI(hoff, 0); }, off != selfOff);
+          one(q0, [&]() { return vatI(hoff, 0); }, SPLIT || off != selfOff);
           if (off >= endm) break;
           off += 32u;
           hoff += 16u;
           q0 = atI(off, 0);
-          one(q1, [&]() { return vatI(hoff, -8); }, off != selfOff16);
+          one(q1, [&]() { return vatI(hoff, -8); }, SPLIT || off != selfOff16);
           if (off >= end) break;
         }
-#else
-        for (;;) {
-          const float4 q1 = atI(off, 16);
-          const float2 v1 = vatI(hoff, 8);
-          one(q0, [&]() { return v0; }, off != selfOff);
-          if (off >= endm) break;
-          off += 32u;
-          hoff += 16u;
-          q0 = atI(off, 0);
-          v0 = vatI(hoff, 0);
-          one(q1, [&]() { return v1; }, off != selfOff16);
-          if (off >= end) break;
-        }
-#endif
-#endif
       }
     }
-    if (REPL) rep.flush(F.fr);
+    rep.flush(F.fr);
     return;
   }
   if (FLAT && NB == 2) {
