@@ -178,17 +178,6 @@ static_assert(offsetof(SimParams, worldOrigin) == 16 && offsetof(SimParams, nCel
 
 #define PB_DEV __device__ __forceinline__
 
-// Bookkeeping taken out of the throughput sweep's pair trip (pbSweepC, FLAT && NB == 1; pbPairEvalXY), one bit each,
-// kept as ONE build-time switch for A/B runs (profiles/r8_trip_trim.txt).  Neither touches a floating-point operation
-// that reaches an output.
-//   1  own slot: a segment that holds the bot's own slot is walked as [lo, self) and (self, hi) instead of every
-//      trip comparing its offset with the own slot's and masking the accumulation
-//   4  the attraction magnitude's root without the clamp (pbRootNewtonPositive)
-// (2 was the contact mask of Sum|F_attr| moved into the near block: measured slower, removed, see the same file.)
-#ifndef PB_TRIP_TRIM
-#define PB_TRIP_TRIM 5
-#endif
-
 // helper_math.h:1244/1287 semantics: dot = ax*bx + ay*by (two roundings), length = sqrtf(dot)
 PB_DEV float pbDot(float ax, float ay, float bx, float by) { return ax * bx + ay * by; }
 PB_DEV float pbLen(float x, float y) { return sqrtf(pbDot(x, y, x, y)); }
@@ -393,16 +382,11 @@ PB_DEV float pbRootNewton(float x, float &s) {
 //   * m2 is not NaN: the components are quotients and products of finite values with a nonzero finite divisor.
 // A contact lane's m2 (possibly 0: coincident bots at rest) is rooted here too, and the result is dropped.
 PB_DEV float pbRootNewtonPositive(float x) {
-#if PB_TRIP_TRIM & 4
   const float s = __builtin_amdgcn_rsqf(x);
   const float h = 0.5f * s;
   const float y = x * s;
   const float e = __builtin_fmaf(-y, y, x);
   return __builtin_fmaf(e, h, y);
-#else
-  float s;
-  return pbRootNewton(x, s);
-#endif
 }
 
 PB_DEV void pbDistUnitFast(float rx, float ry, float d2, float &dist, float &nx, float &ny) {
@@ -456,98 +440,23 @@ PB_DEV float pbBandSlope(float attraction) {
 // every lane of the wave + the per-simulation check pbFastMathAllowed), except for the force
 // magnitude's square root, whose input is checked here wave-wide and sent to sqrtf if tiny.
 //
-// Split in two so that a loop can evaluate several neighbours' forces as independent instruction
-// streams (the evaluation is one long dependent chain) and then add them in the reference's order.
+// The term and its accumulation (pbGroupSum, pbPairAdd) are separate steps: the multi-lane forms evaluate
+// one candidate per lane and then add the group's terms in the reference's order.
 struct PbPairTerm {
   float tx, ty, mag;
   bool contact;
 };
 
-template <bool FAST, class VelFetch>
-PB_DEV PbPairTerm pbPairEval(const PbDevParams &P, bool live, float ax, float ay, float avx, float avy, float ra,
-                             float bx, float by, float rb, float attraction, float slope, VelFetch velB) {
-  const float near1 = 0.0009f, near2 = 0.0019f, fmin_attr = 2.5f;
-  const float rx = bx - ax, ry = by - ay;
-  const float d2 = pbDot(rx, ry, rx, ry);
-  float dist, nx, ny;
-  if (FAST) {
-    dist = pbSqrtFast(d2);  // d2 is 0 or >= 2^-88 here (coordinate differences are 0 or >= 2^-44)
-    pbDiv2Fast(rx, ry, dist, nx, ny);
-  } else {
-    dist = sqrtf(d2);
-    nx = rx / dist;
-    ny = ry / dist;
-  }
-  const float reach = ra + rb;
-  const bool contact = dist < reach;
-  // no contact: constant band, linear band, inverse-square tail
-  const float gap = dist - reach;
-  const float g2 = gap * gap;
-  float farx, fary;
-  if (FAST) {
-    pbDiv2Fast(attraction * nx, attraction * ny, g2, farx, fary);
-  } else {
-    farx = attraction * nx / g2;
-    fary = attraction * ny / g2;
-  }
-  const float band = gap < near1 ? fmin_attr : fmin_attr + slope * (gap - near1);
-  float tx = gap < near2 ? band * nx : farx;
-  float ty = gap < near2 ? band * ny : fary;
-  // contact: spring + dashpot + shear
-  if (__builtin_amdgcn_ballot_w64(contact && live) != 0ull) {
-    float2 vb = make_float2(0.0f, 0.0f);
-    if (contact) vb = velB();
-    const float rvx = vb.x - avx, rvy = vb.y - avy;
-    const float vn = pbDot(rvx, rvy, nx, ny);
-    const float tvx = rvx - vn * nx, tvy = rvy - vn * ny;
-    const float ks = -P.spring * (reach - dist);
-    float cx = 0.0f, cy = 0.0f;
-    cx += ks * nx;
-    cy += ks * ny;
-    cx += P.damping * rvx;
-    cy += P.damping * rvy;
-    cx += P.shear * tvx;
-    cy += P.shear * tvy;
-    if (contact) {
-      tx = cx;
-      ty = cy;
-    } else {
-      tx = 0.0f + tx;
-      ty = 0.0f + ty;
-    }
-  } else {
-    tx = 0.0f + tx;  // `tempforce += ...` onto (0,0): turns -0 into +0
-    ty = 0.0f + ty;
-  }
-  const float m2 = pbDot(tx, ty, tx, ty);
-  float mag;
-  if (FAST) {
-    mag = pbSqrtFast(m2);
-    if (__builtin_expect(__builtin_amdgcn_ballot_w64(live && pbTinyNonzero(m2)) != 0ull, 0)) {
-      // a real branch, not a select: the empty asm keeps hipcc from computing both roots every time
-      asm volatile("; rare: force magnitude below 2^-48, full sqrtf" ::: "memory");
-      mag = sqrtf(m2);
-    }
-  } else {
-    mag = sqrtf(m2);
-  }
-  PbPairTerm r;
-  r.tx = tx;
-  r.ty = ty;
-  r.mag = mag;
-  r.contact = contact;
-  return r;
-}
-
-// K neighbours evaluated side by side in the same basic blocks (one shared contact branch, one
-// shared rare-sqrt branch), so the scheduler can interleave K independent dependency chains.
-// Each term equals pbPairEval's for that neighbour.
 // the three contact constants, copied out of the parameter block once per kernel (the block lives
 // in device memory; left to itself hipcc re-reads it inside the neighbour loop)
 struct PbContactK {
   float spring, damping, shear;
 };
 
+// The terms of K neighbours, evaluated side by side in the same basic blocks (one shared contact branch, one shared
+// rare-sqrt branch).  Every caller passes K = 1 (the group sweep, pb_legacy.hip).  The array form stays: a scalar
+// restatement -- the same operations in the same order -- compiles to other code in k_force's headline forms (their
+// tail workgroups run the group sweep), which a clean-up must not do.
 template <bool FAST, int K, class VelFetch>
 PB_DEV void pbPairEvalK(const PbContactK &P, const bool (&live)[K], float ax, float ay, float avx, float avy,
                         float ra, const float (&bx)[K], const float (&by)[K], const float (&rb)[K],
@@ -785,13 +694,6 @@ PB_DEV void pbPairAdd(bool live, const PbPairTerm &t, PbForce &F) {
     if (t.contact) F.fr += t.mag;
     else F.fa += t.mag;
   }
-}
-
-template <bool FAST, class VelFetch>
-PB_DEV void pbPairFlat(const PbDevParams &P, bool live, float ax, float ay, float avx, float avy, float ra,
-                       float bx, float by, float rb, float attraction, float slope, VelFetch velB,
-                       PbForce &F) {
-  pbPairAdd(live, pbPairEval<FAST>(P, live, ax, ay, avx, avy, ra, bx, by, rb, attraction, slope, velB), F);
 }
 
 // ---- streamlined pair force (force variant 3; NOT bit-identical) ----

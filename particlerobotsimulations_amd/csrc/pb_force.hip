@@ -40,7 +40,7 @@ namespace {
 // ASUM: maintain absForce_a.  false (throughput form, batches without constrained contraction):
 // the attraction magnitudes are dead values and are neither computed nor stored (pbPairEvalXY).
 template <bool PAYLOAD, bool FLAT, int L, int NB, bool BIG, bool ASUM>
-__global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : (L == 1 && FLAT && !BIG && !PAYLOAD) ? PB_TAIL_FORM_WAVES : PB_FORCE_WAVES)) void k_force(const PbDevParams *__restrict__ params,
+__global__ __launch_bounds__(TILE, ((L == 1 && FLAT && !BIG && !PAYLOAD) ? PB_TAIL_FORM_WAVES : PB_FORCE_WAVES)) void k_force(const PbDevParams *__restrict__ params,
                                                 const float4 *__restrict__ prIn, const float2 *__restrict__ velIn,
                                                 const uint32_t *__restrict__ cellSAll, float *__restrict__ absR,
                                                 uint32_t n, uint32_t perXcd, uint32_t memberTiles, uint32_t nsims,
@@ -59,6 +59,7 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : (L == 1 && FLAT && 
   // reads of a member's tiles -- the same few KB -- meet in one L2 instead of missing in eight.  BASELINE configs[3] on
   // one GPU: 32 + 32 members 7.75 -> 7.31 us per step, 64 + 64 members 10.22 -> 9.40, 8 + 8 unchanged
   // (tools/experiments/ab_xcd_members.sh); the results do not depend on the mapping.
+  static_assert(NB == 1, "one neighbour per trip");  // the slot is kept for the kernel's recorded name only
   uint32_t member = blockIdx.y, tileX = blockIdx.x;
   if (memberTiles && !perXcd) {
     const uint32_t r = blockIdx.x >> 3;
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : (L == 1 && FLAT && 
   // Dispatch is ascending within an XCD, so they are the last workgroups to start: a bot's serial neighbour chain
   // there is about half as long (at ~1.4x the VALU work per bot, which the draining SIMDs have spare), and the
   // launch ends sooner.  The choice is per workgroup, so it is wave-uniform, and both sweeps give the same bits.
-  constexpr bool TAILABLE = L == 1 && FLAT && NB == 1 && !BIG;
+  constexpr bool TAILABLE = L == 1 && FLAT && !BIG;
   bool tailWg = false;
   if (TAILABLE && perXcd && memberTiles) {
     uint32_t first;
@@ -110,17 +111,20 @@ __global__ __launch_bounds__(TILE, (NB == 2 ? PB_NB2_WAVES : (L == 1 && FLAT && 
 
   // wave-uniform choice: the fast exact forms need every lane's coordinates away from zero
   using OffT = typename std::conditional<BIG, uint64_t, uint32_t>::type;
-  static_assert(ASUM || (FLAT && NB == 1), "the dead-sum form exists for the branch-free sweeps only");
+  static_assert(ASUM || FLAT, "the dead-sum form exists for the branch-free sweeps only");
   // (L > 1: magnitudes are rooted inside the contact block; the both-sums throughput form has the list since round 5)
-  constexpr bool REPLIST = L == 1 && FLAT && NB == 1;
+  constexpr bool REPLIST = L == 1 && FLAT;
   __shared__ float repLds[REPLIST ? (PB_REP_CAP + 1) * TILE : 1];
   float *const repCol = &repLds[REPLIST ? threadIdx.x : 0];
   auto sweep = [&](auto lanes) __attribute__((always_inline)) {
     constexpr int LS = decltype(lanes)::value;
+    PbSegCache none;  // (a per-step launch keeps no list)
     if (FLAT && fastOk && __all(pbLaneFastMathOk(me.x, me.y)))
-      pbSweep<PAYLOAD, FLAT, true, LS, NB, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, repCol);
+      pbSweep<PAYLOAD, FLAT, true, LS, false, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, none,
+                                                          repCol);
     else
-      pbSweep<PAYLOAD, FLAT, false, LS, NB, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, repCol);
+      pbSweep<PAYLOAD, FLAT, false, LS, false, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, none,
+                                                           repCol);
   };
   if (TAILABLE && tailWg)
     sweep(std::integral_constant<int, TAILABLE ? PB_TAIL_LANES : L>{});
@@ -174,9 +178,8 @@ void launchForceT(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int 
   // XCD-aware order only pays when a simulation spans many tiles.  (Round 5: for the multi-lane forms too -- one
   // simulation of 4 000 ... 10^5 bots steps 1-4 % faster in its automatic form, profiles/r5_xcd_tiles_all.txt.)
   const uint32_t perXcd = ((L == 1 || S->xcdTilesAll) && tiles >= 64u) ? cdiv(tiles, 8u) : 0u;
-  constexpr int NB = (FLAT && L == 1 && !BIG && ASUM) ? PB_THROUGHPUT_NB : 1;
   // split-lane tail tiles per XCD (k_force; 0 for the forms without one)
-  const uint32_t tail = (FLAT && L == 1 && NB == 1 && !BIG && perXcd) ? pbTailTiles(S, perXcd) : 0u;
+  const uint32_t tail = (FLAT && L == 1 && !BIG && perXcd) ? pbTailTiles(S, perXcd) : 0u;
   dim3 grid(perXcd ? (perXcd + tail * (PB_TAIL_LANES - 1)) * 8u : tiles, S->nsims);
   uint32_t memberTiles = tail;
   if (S->xcdMembers && !perXcd && S->nsims >= 8u) {
@@ -187,7 +190,7 @@ void launchForceT(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int 
   const bool magNeeded = ASUM && FLAT && L == 1;
   const int fastOk = (S->variant >= 2 && S->fastOk && (!magNeeded || S->magOk)) ? 1 : 0;
   // (debugLdsBytes: an occupancy experiment -- unused dynamic LDS that only limits workgroups per CU)
-  hipLaunchKernelGGL((k_force<PAYLOAD, FLAT, L, NB, BIG, ASUM>), grid, dim3(TILE), S->debugLdsBytes, S->stream, S->dP,
+  hipLaunchKernelGGL((k_force<PAYLOAD, FLAT, L, 1, BIG, ASUM>), grid, dim3(TILE), S->debugLdsBytes, S->stream, S->dP,
                      S->pr[c], S->vel[c], S->cellS, S->absR[c], S->n, perXcd, memberTiles, S->nsims, dt, fastOk, S->pr[o],
                      S->vel[o], S->phase[c], S->dead[c], S->absA[c], S->orig[c], tNext, doRadiusNext, (int)fuse);
 }
@@ -198,10 +201,9 @@ void launchForceT(pbSim *S, bool fuse, int c, int o, float dt, float tNext, int 
 // template parameter makes the counters another kernel's).
 template <bool PAYLOAD, bool FLAT, int L, bool BIG, bool ASUM>
 std::string forceNameT() {
-  constexpr int NB = (FLAT && L == 1 && !BIG && ASUM) ? PB_THROUGHPUT_NB : 1;
   auto b = [](bool v) { return std::string(v ? "true" : "false"); };
-  return "k_force<" + b(PAYLOAD) + ", " + b(FLAT) + ", " + std::to_string(L) + ", " + std::to_string(NB) + ", " + b(BIG) +
-         ", " + b(ASUM) + ">" + pbKernelArgs(typeid(&k_force<PAYLOAD, FLAT, L, NB, BIG, ASUM>).name());
+  return "k_force<" + b(PAYLOAD) + ", " + b(FLAT) + ", " + std::to_string(L) + ", 1, " + b(BIG) +
+         ", " + b(ASUM) + ">" + pbKernelArgs(typeid(&k_force<PAYLOAD, FLAT, L, 1, BIG, ASUM>).name());
 }
 
 // ---- the forms table ---------------------------------------------------------------------------
@@ -275,7 +277,7 @@ PbForcePlan pbForcePlan(const pbSim *S) {
     else if (want == 4 || (want == 0 && S->total <= 131072u)) p.form = 4;
     else if (want == 2) p.form = 2;
     // the dead-sum forms exist for the branch-free kernels
-    if (PB_THROUGHPUT_NB == 1 && !attractionSumsKept(S)) p.asum = false;
+    if (!attractionSumsKept(S)) p.asum = false;
   }
   return p;
 }

@@ -70,14 +70,12 @@ __global__ __launch_bounds__(1024) void k_resident(const PbDevParams *__restrict
       F.fr = 0.0f * fr;  // impl.cuh:688
       const float4 *prIn = sPr[cur];
       const float2 *velIn = sVel[cur];
-      using PR = const float4 *;
-      using VL = const float2 *;
       if (FASTOK && __all(pbLaneFastMathOk(me.x, me.y)))
-        pbSweepC<PAYLOAD, true, true, L, 1, (L > 1), PR, VL, uint32_t, ASUM, 1024>(P, prIn, velIn, cellS, base, l, sub, me,
-                                                                                 v, att1, F, segCache, repCol);
+        pbSweep<PAYLOAD, true, true, L, (L > 1), uint32_t, ASUM, 1024>(P, prIn, velIn, cellS, base, l, sub, me, v, att1, F,
+                                                               segCache, repCol);
       else
-        pbSweepC<PAYLOAD, true, false, L, 1, (L > 1), PR, VL, uint32_t, ASUM, 1024>(P, prIn, velIn, cellS, base, l, sub,
-                                                                                  me, v, att1, F, segCache, repCol);
+        pbSweep<PAYLOAD, true, false, L, (L > 1), uint32_t, ASUM, 1024>(P, prIn, velIn, cellS, base, l, sub, me, v, att1, F,
+                                                                segCache, repCol);
       pbObstacles(P, me.x, me.y, v.x, v.y, me.z, F);
       pbFrictionAndKick(P, selfPayload, F.fx, F.fy, dt, v.x, v.y);
       fa = F.fa;

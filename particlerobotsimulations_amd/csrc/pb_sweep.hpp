@@ -11,22 +11,9 @@
 #ifndef PB_FORCE_WAVES
 #define PB_FORCE_WAVES 1
 #endif
-#ifndef PB_NB2_WAVES
-#define PB_NB2_WAVES 8  // minimum waves per SIMD the two-neighbours-per-trip form is compiled for
-#endif
-#ifndef PB_THROUGHPUT_NB
-#define PB_THROUGHPUT_NB 1
-#endif
 #ifndef PB_REP_CAP
 #define PB_REP_CAP 8  // pending contact magnitudes per lane before the wave flushes (PbRepList)
 #endif
-// NB (template parameter of k_force): neighbours evaluated side by side per loop trip of the
-// one-lane-per-bot form.  1 is what ships.  2 (two independent dependency chains per wave, the
-// software-pipelined two-wide loop in pbSweepC) is a build-time experiment: measured on MI355X at
-// 10^6 bots it is bit-identical and SLOWER at every register budget -- 124.9 us/step at 8 waves/SIMD
-// (64 VGPRs, 28 spilled), 120.8 at 7 (72), 119.8 at 6 (80), 121.4 at 5 (81, no bound) against 114.0
-// for NB = 1 (63 VGPRs, 8 waves/SIMD): waves, not ILP inside a wave, are what fills the VALU pipe.
-
 #ifndef PB_TAIL_FORM_WAVES
 #define PB_TAIL_FORM_WAVES 8  // waves per SIMD the one-lane throughput forms (with their tail body) are compiled for
 #endif
@@ -150,25 +137,17 @@ struct PbSegCache {
   int gx, gy;
 };
 
-// Neighbour sweep of one bot: the 25-cell stencil as 5 grid rows x up to 2 slot ranges (x-wrap), in
-// the reference's order (impl.cuh:617-655).  prIn/velIn are indexed by (global slot - base): the
-// per-step kernel passes the HBM arrays and base 0, the resident kernel its LDS copy and the
-// simulation's first slot.  s is the bot's own index into prIn.
-// L: lanes per bot.  L == 1 is the throughput form (one bot per lane).  L > 1 (small batches that
-// cannot fill the chip) gives each bot L adjacent lanes: they evaluate L candidates of the bot's
-// flattened neighbour list at a time, then every lane of the group adds the L terms in list order
-// (ds_swizzle broadcasts inside the group), so the sums -- and their order -- are those of L == 1.
-// The serial chain per bot shrinks ~L/2-fold at ~2x the total VALU work.
-// ASUM: maintain Sum|F_attr| (F.fa).  false (branch-free forms; the caller guarantees that no
-// simulation of the batch has constrained_contraction set, see pbPairEvalXY): F.fa is left alone;
-// in the throughput form the contact magnitudes go through the lane's LDS column repCol
-// (PbRepList, columns REPSTRIDE floats apart).
-template <bool PAYLOAD, bool FLAT, bool FAST, int L, int NB, bool CACHED, class PR, class VL, class OffT = uint32_t,
-          bool ASUM = true, int REPSTRIDE = TILE>
-__device__ __forceinline__ void pbSweepC(const PbDevParams &P, PR prIn, VL velIn,
-                                        const uint32_t *__restrict__ cellS, uint32_t base, uint32_t s,
-                                         uint32_t sub, const float4 &me, const float2 &v, float att1, PbForce &F,
-                                         PbSegCache &cache, float *repCol = nullptr) {
+// The three sweeps below start with the same few lines: the bot's cell (gx, gy) and its 25-cell stencil as 5 grid rows
+// x up to 2 slot ranges -- mx0 the first column (wrapped), `first` the cells of a row before the x-wrap (5 away from
+// it), nseg the ranges per row.  (Repeated, not shared: the order of these lines reaches the generated code.)
+
+// ---- group sweep: L > 1 lanes per bot, flattened candidate list, L candidates per trip, ordered group sum ----
+// CACHED: keep the flattened list in `cache` across calls (resident kernel); otherwise `cache` is not touched.
+template <bool PAYLOAD, bool FAST, int L, bool CACHED, bool ASUM, class PR, class VL>
+__device__ __forceinline__ void pbSweepGroup(const PbDevParams &P, PR prIn, VL velIn,
+                                             const uint32_t *__restrict__ cellS, uint32_t base, uint32_t s, uint32_t sub,
+                                             const float4 &me, const float2 &v, float att1, PbForce &F,
+                                             PbSegCache &cache) {
   const int gx = pbCellX(P, me.x), gy = pbCellY(P, me.y);
   const float slope0 = pbBandSlope(P.attraction);
   const float attraction0 = P.attraction;
@@ -177,259 +156,209 @@ __device__ __forceinline__ void pbSweepC(const PbDevParams &P, PR prIn, VL velIn
   const uint32_t mx0 = (uint32_t)(gx - 2) & (GX - 1u);
   const uint32_t first = (GX - mx0) < 5u ? (GX - mx0) : 5u;  // cells before the x-wrap
   const int nseg = first < 5u ? 2 : 1;
-  if (L > 1) {
-    // ---- flattened candidate list, L candidates per trip, ordered group sum --------------------
-    // 5 grid rows x up to 2 ranges (x-wrap) = 10 list segments; segment r covers list positions
-    // [c[r], c[r+1]) and maps position k to slot k + o[r].
-    PbSegList SL;
-    uint32_t m;
-    // (wave-uniform) rebuild unless every lane's cached list is still for the cell it is in
-    if (!CACHED || __any(cache.gx != gx || cache.gy != gy)) {
-      uint32_t cum = 0;
+  // 5 grid rows x up to 2 ranges (x-wrap) = 10 list segments; segment r covers list positions
+  // [c[r], c[r+1]) and maps position k to slot k + o[r].
+  PbSegList SL;
+  uint32_t m;
+  // (wave-uniform) rebuild unless every lane's cached list is still for the cell it is in
+  if (!CACHED || __any(cache.gx != gx || cache.gy != gy)) {
+    uint32_t cum = 0;
 #pragma unroll
-      for (int si = 0; si < 10; si++) {
-        const int sg = si & 1;
-        const uint32_t row = ((uint32_t)(gy + (si >> 1) - 2) & (P.gridY - 1u)) << P.gridXLog2;
-        uint32_t lo = 0, hi = 0;
-        if (sg < nseg) {
-          lo = cellS[row + (sg == 0 ? mx0 : 0u)] - base;
-          hi = cellS[row + (sg == 0 ? mx0 + first : 5u - first)] - base;
-        }
-        SL.set(si, lo - cum, cum);
-        cum += hi - lo;
+    for (int si = 0; si < 10; si++) {
+      const int sg = si & 1;
+      const uint32_t row = ((uint32_t)(gy + (si >> 1) - 2) & (P.gridY - 1u)) << P.gridXLog2;
+      uint32_t lo = 0, hi = 0;
+      if (sg < nseg) {
+        lo = cellS[row + (sg == 0 ? mx0 : 0u)] - base;
+        hi = cellS[row + (sg == 0 ? mx0 + first : 5u - first)] - base;
       }
-      m = cum;
-      if (CACHED) {
-        cache.SL = SL;
-        cache.m = m;
-        cache.gx = gx;
-        cache.gy = gy;
-      }
-    } else {
-      SL = cache.SL;
-      m = cache.m;
+      SL.set(si, lo - cum, cum);
+      cum += hi - lo;
     }
-    // wave-uniform: away from the x-wrap (nearly always) the position -> slot chain has 5 links, not 10
-    auto run = [&](auto wrapTag) __attribute__((always_inline)) {
-      constexpr bool WRAP = decltype(wrapTag)::value;
-      auto slotOf = [=](uint32_t k) __attribute__((always_inline)) {
-        return WRAP ? pbSegSlot(SL, m, s, k) : pbSegSlot5(SL, m, s, k);
-      };
-      uint32_t jn = slotOf(sub);
-      float4 qn = prIn[jn];
-      float2 wn = velIn[jn];
-      for (uint32_t b0 = 0; b0 < m; b0 += L) {
-        const uint32_t j = jn;
-        const float4 q = qn;
-        const float2 w = wn;
-        jn = slotOf(b0 + L + sub);
-        qn = prIn[jn];
-        wn = velIn[jn];
-        const bool live[1] = {j != s};
-        const float bx[1] = {q.x}, by[1] = {q.y}, rb[1] = {q.z};
-        const float A[1] = {PAYLOAD ? attraction0 * q.w * att1 : attraction0};
-        const float K[1] = {PAYLOAD ? pbBandSlope(A[0]) : slope0};
-        if (ASUM) {
-          PbPairTerm t[1];
-          pbPairEvalK<FAST, 1>(CK, live, me.x, me.y, v.x, v.y, me.z, bx, by, rb, A, K, [&](int) { return w; }, t);
-          // the group's L terms join the running sums in list order
-          pbGroupSum<L>(live[0], t[0], F);
-        } else {
-          // dead-sum form: no Sum|F_attr|; a contact's magnitude and the Sum|F_rep| chain only in the
-          // trips in which some lane of the wave is in contact
-          const PbPairXY t = pbPairEvalXY<FAST>(
-              CK, live[0], me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, [&]() { return w; }, A[0], K[0], [&](bool mine, float m2) {
-                float mag;
-                if (FAST) {
-                  mag = pbSqrtFast(m2);
-                  if (__builtin_expect(__builtin_amdgcn_ballot_w64(mine && pbTinyNonzero(m2)) != 0ull, 0)) {
-                    asm volatile("; rare: a contact magnitude below 2^-48, full sqrtf" ::: "memory");
-                    mag = sqrtf(m2);
-                  }
-                } else {
+    m = cum;
+    if (CACHED) {
+      cache.SL = SL;
+      cache.m = m;
+      cache.gx = gx;
+      cache.gy = gy;
+    }
+  } else {
+    SL = cache.SL;
+    m = cache.m;
+  }
+  // wave-uniform: away from the x-wrap (nearly always) the position -> slot chain has 5 links, not 10
+  auto run = [&](auto wrapTag) __attribute__((always_inline)) {
+    constexpr bool WRAP = decltype(wrapTag)::value;
+    auto slotOf = [=](uint32_t k) __attribute__((always_inline)) {
+      return WRAP ? pbSegSlot(SL, m, s, k) : pbSegSlot5(SL, m, s, k);
+    };
+    uint32_t jn = slotOf(sub);
+    float4 qn = prIn[jn];
+    float2 wn = velIn[jn];
+    for (uint32_t b0 = 0; b0 < m; b0 += L) {
+      const uint32_t j = jn;
+      const float4 q = qn;
+      const float2 w = wn;
+      jn = slotOf(b0 + L + sub);
+      qn = prIn[jn];
+      wn = velIn[jn];
+      const bool live[1] = {j != s};
+      const float bx[1] = {q.x}, by[1] = {q.y}, rb[1] = {q.z};
+      const float A[1] = {PAYLOAD ? attraction0 * q.w * att1 : attraction0};
+      const float K[1] = {PAYLOAD ? pbBandSlope(A[0]) : slope0};
+      if (ASUM) {
+        PbPairTerm t[1];
+        pbPairEvalK<FAST, 1>(CK, live, me.x, me.y, v.x, v.y, me.z, bx, by, rb, A, K, [&](int) { return w; }, t);
+        // the group's L terms join the running sums in list order
+        pbGroupSum<L>(live[0], t[0], F);
+      } else {
+        // dead-sum form: no Sum|F_attr|; a contact's magnitude and the Sum|F_rep| chain only in the
+        // trips in which some lane of the wave is in contact
+        const PbPairXY t = pbPairEvalXY<FAST>(
+            CK, live[0], me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, [&]() { return w; }, A[0], K[0], [&](bool mine, float m2) {
+              float mag;
+              if (FAST) {
+                mag = pbSqrtFast(m2);
+                if (__builtin_expect(__builtin_amdgcn_ballot_w64(mine && pbTinyNonzero(m2)) != 0ull, 0)) {
+                  asm volatile("; rare: a contact magnitude below 2^-48, full sqrtf" ::: "memory");
                   mag = sqrtf(m2);
                 }
-                pbGroupSum1<L>(mine ? mag : 0.0f, F.fr);
-              });
-          pbGroupSumXY<L>(live[0], t, F);
-        }
-      }
-    };
-    if (__all(nseg == 1)) run(std::false_type{});
-    else run(std::true_type{});
-    return;
-  }
-  if (FLAT && NB == 1) {
-    // One bot per lane, one neighbour per trip (the throughput form).
-    //  * The loop over the 10 segments is rolled (one copy of the pair loop in the binary) and
-    //    software-pipelined two deep: while segment si runs, the cell-table bounds of segment
-    //    si + 2 and the first posrad of segment si + 1 are in flight.  Loaded just in time they are
-    //    two dependent memory round trips per segment, ~20 per bot, that only other waves can hide
-    //    -- and at the start and the end of a launch there are none.
-    //  * Inside a segment the next neighbour's posrad is already in flight, the loop is unrolled
-    //    by two with the two registers swapping roles (no copy at the back-edge), and it runs on
-    //    32-bit BYTE offsets from the array base (one add and one compare per trip; the
-    //    neighbour's velocity sits at half the offset and is fetched inside the contact block).  One
-    //    slot past a range is still inside the array (spare elements) and is never evaluated.
-    //  * The bot's own slot is never evaluated either (the reference skips j == index, impl.cuh:638): a
-    //    segment [lo, hi) that holds it is walked as [lo, self) and, in one more turn of the segment loop,
-    //    (self, hi), so the pair trip carries no test for it.  The slot is found by its index, not by the
-    //    bot's position: the lists are stale, so it may sit in any segment or in none, and in a grid fewer
-    //    than 5 cells high in more than one.  It contributed nothing, so the order of the sums is unchanged.
-    const char *const prBytes = (const char *)&prIn[0];
-    const char *const velBytes = (const char *)&velIn[0];
-    // OffT: 32-bit byte offsets (batches below 2^28 bots: one add and one compare per trip, loads with a
-    // scalar base + 32-bit vector offset) or 64-bit ones (larger batches, up to 2^32 slots)
-    constexpr bool SPLIT = (PB_TRIP_TRIM & 1) != 0;
-    const OffT selfOff = (OffT)s * 16u;
-    const OffT selfOff16 = selfOff + 16u;
-    auto at = [&](OffT off) __attribute__((always_inline)) { return *(const float4 *)(prBytes + off); };
-    // contact magnitudes wait in the lane's LDS column (both forms since round 5)
-    PbRepList<FAST, PB_REP_CAP, REPSTRIDE> rep;
-    rep.init(repCol);
-    // (64-bit address arithmetic with a constant displacement: the displacement becomes the load's
-    //  immediate offset, so the look-ahead loads need no address instructions of their own)
-    auto atI = [&](OffT off, int imm) __attribute__((always_inline)) {
-      return *(const float4 *)(prBytes + (uint64_t)off + imm);
-    };
-    auto vatI = [&](OffT hoff, int imm) __attribute__((always_inline)) {
-      return *(const float2 *)(velBytes + (uint64_t)hoff + imm);
-    };
-    auto one = [&](const float4 &q, auto velOf, bool live) __attribute__((always_inline)) {
-      const float A = PAYLOAD ? attraction0 * q.w * att1 : attraction0;
-      const float K = PAYLOAD ? pbBandSlope(A) : slope0;
-      // the dead-sum trip; with ASUM also the magnitude of the lane's attraction term (Sum|F_attr| in list order, as
-      // absforce_a += length(tempforce), impl.cuh:580-592)
-      const PbPairXY t = pbPairEvalXY<FAST, ASUM>(CK, live, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A, K,
-                                                  [&](bool mine, float m2) { rep.push(mine, m2, F.fr); }, &F.fa);
-      if (SPLIT) {
-        F.fx += t.tx;
-        F.fy += t.ty;
-      } else if (live) {
-        // (a real exec-masked block -- two scalar instructions -- instead of two selects per trip)
-        asm volatile("");
-        F.fx += t.tx;
-        F.fy += t.ty;
-      }
-    };
-    // byte offsets [lo, hi) of segment si; empty beyond the last one and for the second range of a
-    // row away from the x-wrap
-    auto bounds = [&](int si, OffT &lo, OffT &hi) __attribute__((always_inline)) {
-      lo = hi = selfOff;
-      if (si < 10) {
-        const uint32_t row = ((uint32_t)(gy + (si >> 1) - 2) & (P.gridY - 1u)) << P.gridXLog2;
-        lo = (OffT)(cellS[row + ((si & 1) ? 0u : mx0)] - base) * 16u;
-        hi = (OffT)(cellS[row + ((si & 1) ? 5u - first : mx0 + first)] - base) * 16u;
-      }
-    };
-    // segment numbers advance by 2 (one range per grid row) except for a lane at the x-wrap, whose
-    // rows split into two ranges: per-lane stride, the wave runs until its last lane is done
-    const int stride = nseg == 1 ? 2 : 1;
-    OffT loA, hiA, loB, hiB;
-    bounds(0, loA, hiA);
-    bounds(stride, loB, hiB);
-    float4 qA = at(loA);
-    PB_TL_STAMP(4);
-#pragma unroll 1
-    for (int si = 0; si < 10;) {
-      if (si == 4) PB_TL_STAMP(5);
-      const OffT lo = loA;
-      // own slot inside [lo, hiA): this turn stops short of it, the next one starts behind it with the same si
-      const bool cut = SPLIT && (OffT)(selfOff - lo) < (OffT)(hiA - lo);
-      const OffT end = cut ? selfOff : hiA;
-      float4 q0 = qA;
-      loA = cut ? selfOff16 : loB;
-      hiA = cut ? hiA : hiB;
-      qA = at(loA);                                    // first posrad of the next turn's range
-      if (!cut) bounds(si + 2 * stride, loB, hiB);     // bounds of the segment after the next
-      si += cut ? 0 : stride;
-      if (lo < end) {
-        // two neighbours per turn of the loop: `off` is the even one's byte offset, hoff = off / 2 the
-        // offset of its velocity
-        OffT off = lo, hoff = lo >> 1;
-        const OffT endm = end - 16u;
-        for (;;) {
-          const float4 q1 = atI(off, 16);
-          one(q0, [&]() { return vatI(hoff, 0); }, SPLIT || off != selfOff);
-          if (off >= endm) break;
-          off += 32u;
-          hoff += 16u;
-          q0 = atI(off, 0);
-          one(q1, [&]() { return vatI(hoff, -8); }, SPLIT || off != selfOff16);
-          if (off >= end) break;
-        }
+              } else {
+                mag = sqrtf(m2);
+              }
+              pbGroupSum1<L>(mine ? mag : 0.0f, F.fr);
+            });
+        pbGroupSumXY<L>(live[0], t, F);
       }
     }
-    rep.flush(F.fr);
-    return;
-  }
-  if (FLAT && NB == 2) {
-    // The same sweep with TWO neighbours per trip, evaluated side by side in the same basic blocks
-    // (pbPairEvalK<FAST, 2>: two independent dependency chains for the scheduler to interleave) and
-    // added in slot order.  The one-per-trip form above leaves ~a third of the SIMD's issue slots
-    // empty (a wave's pair evaluation is one long dependent chain and a launch's last waves run
-    // nearly alone); this form trades registers (<= 64, still 8 waves per SIMD) for ILP.  A range of
-    // odd length evaluates one slot past its end (spare elements; never accumulated).
-    const char *const prBytes = (const char *)&prIn[0];
-    const char *const velBytes = (const char *)&velIn[0];
-    const uint32_t selfOff = s * 16u;
-    auto at = [&](uint32_t off) __attribute__((always_inline)) { return *(const float4 *)(prBytes + off); };
-    auto vat = [&](uint32_t off) __attribute__((always_inline)) { return *(const float2 *)(velBytes + (off >> 1)); };
-    auto two = [&](const float4 &qa, const float2 &va, const float4 &qb, const float2 &vb, uint32_t off,
-                   uint32_t end) __attribute__((always_inline)) {
-      const bool live[2] = {off != selfOff, (off + 16u != selfOff) && (off + 16u < end)};
-      const float bx[2] = {qa.x, qb.x}, by[2] = {qa.y, qb.y}, rb[2] = {qa.z, qb.z};
-      const float A[2] = {PAYLOAD ? attraction0 * qa.w * att1 : attraction0,
-                          PAYLOAD ? attraction0 * qb.w * att1 : attraction0};
-      const float K[2] = {PAYLOAD ? pbBandSlope(A[0]) : slope0, PAYLOAD ? pbBandSlope(A[1]) : slope0};
-      PbPairTerm t[2];
-      pbPairEvalK<FAST, 2>(CK, live, me.x, me.y, v.x, v.y, me.z, bx, by, rb, A, K,
-                           [&](int k) { return k == 0 ? va : vb; }, t);
-      pbPairAdd(live[0], t[0], F);
-      pbPairAdd(live[1], t[1], F);
-    };
-    auto bounds = [&](int si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
-      lo = hi = selfOff;
-      if (si < 10) {
-        const uint32_t row = ((uint32_t)(gy + (si >> 1) - 2) & (P.gridY - 1u)) << P.gridXLog2;
-        lo = (cellS[row + ((si & 1) ? 0u : mx0)] - base) * 16u;
-        hi = (cellS[row + ((si & 1) ? 5u - first : mx0 + first)] - base) * 16u;
-      }
-    };
-    const int stride = nseg == 1 ? 2 : 1;
-    uint32_t loA, hiA, loB, hiB;
-    bounds(0, loA, hiA);
-    bounds(stride, loB, hiB);
-    float4 qA = at(loA);
-    float2 vA = vat(loA);
+  };
+  if (__all(nseg == 1)) run(std::false_type{});
+  else run(std::true_type{});
+}
+
+// ---- lane sweep: one bot per lane, one neighbour per trip (the throughput form) ----
+// The contact magnitudes go through the lane's LDS column repCol (PbRepList, columns REPSTRIDE floats apart).
+template <bool PAYLOAD, bool FAST, class OffT, bool ASUM, int REPSTRIDE, class PR, class VL>
+__device__ __forceinline__ void pbSweepLane(const PbDevParams &P, PR prIn, VL velIn,
+                                            const uint32_t *__restrict__ cellS, uint32_t base, uint32_t s,
+                                            const float4 &me, const float2 &v, float att1, PbForce &F, float *repCol) {
+  const int gx = pbCellX(P, me.x), gy = pbCellY(P, me.y);
+  const float slope0 = pbBandSlope(P.attraction);
+  const float attraction0 = P.attraction;
+  const PbContactK CK{P.spring, P.damping, P.shear};
+  const uint32_t GX = P.gridX;
+  const uint32_t mx0 = (uint32_t)(gx - 2) & (GX - 1u);
+  const uint32_t first = (GX - mx0) < 5u ? (GX - mx0) : 5u;  // cells before the x-wrap
+  const int nseg = first < 5u ? 2 : 1;
+  // How the walk is laid out:
+  //  * The loop over the 10 segments is rolled (one copy of the pair loop in the binary) and
+  //    software-pipelined two deep: while segment si runs, the cell-table bounds of segment
+  //    si + 2 and the first posrad of segment si + 1 are in flight.  Loaded just in time they are
+  //    two dependent memory round trips per segment, ~20 per bot, that only other waves can hide
+  //    -- and at the start and the end of a launch there are none.
+  //  * Inside a segment the next neighbour's posrad is already in flight, the loop is unrolled
+  //    by two with the two registers swapping roles (no copy at the back-edge), and it runs on
+  //    32-bit BYTE offsets from the array base (one add and one compare per trip; the
+  //    neighbour's velocity sits at half the offset and is fetched inside the contact block).  One
+  //    slot past a range is still inside the array (spare elements) and is never evaluated.
+  //  * The bot's own slot is never evaluated either (the reference skips j == index, impl.cuh:638): a
+  //    segment [lo, hi) that holds it is walked as [lo, self) and, in one more turn of the segment loop,
+  //    (self, hi), so the pair trip carries no test for it.  The slot is found by its index, not by the
+  //    bot's position: the lists are stale, so it may sit in any segment or in none, and in a grid fewer
+  //    than 5 cells high in more than one.  It contributed nothing, so the order of the sums is unchanged.
+  const char *const prBytes = (const char *)&prIn[0];
+  const char *const velBytes = (const char *)&velIn[0];
+  // OffT: 32-bit byte offsets (batches below 2^28 bots: one add and one compare per trip, loads with a
+  // scalar base + 32-bit vector offset) or 64-bit ones (larger batches, up to 2^32 slots)
+  const OffT selfOff = (OffT)s * 16u;
+  const OffT selfOff16 = selfOff + 16u;
+  auto at = [&](OffT off) __attribute__((always_inline)) { return *(const float4 *)(prBytes + off); };
+  // contact magnitudes wait in the lane's LDS column (both forms since round 5)
+  PbRepList<FAST, PB_REP_CAP, REPSTRIDE> rep;
+  rep.init(repCol);
+  // (64-bit address arithmetic with a constant displacement: the displacement becomes the load's
+  //  immediate offset, so the look-ahead loads need no address instructions of their own)
+  auto atI = [&](OffT off, int imm) __attribute__((always_inline)) {
+    return *(const float4 *)(prBytes + (uint64_t)off + imm);
+  };
+  auto vatI = [&](OffT hoff, int imm) __attribute__((always_inline)) {
+    return *(const float2 *)(velBytes + (uint64_t)hoff + imm);
+  };
+  auto one = [&](const float4 &q, auto velOf) __attribute__((always_inline)) {
+    const float A = PAYLOAD ? attraction0 * q.w * att1 : attraction0;
+    const float K = PAYLOAD ? pbBandSlope(A) : slope0;
+    // the dead-sum trip; with ASUM also the magnitude of the lane's attraction term (Sum|F_attr| in list order, as
+    // absforce_a += length(tempforce), impl.cuh:580-592)
+    const PbPairXY t = pbPairEvalXY<FAST, ASUM>(CK, true, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A, K,
+                                                [&](bool mine, float m2) { rep.push(mine, m2, F.fr); }, &F.fa);
+    F.fx += t.tx;
+    F.fy += t.ty;
+  };
+  // byte offsets [lo, hi) of segment si; empty beyond the last one and for the second range of a
+  // row away from the x-wrap
+  auto bounds = [&](int si, OffT &lo, OffT &hi) __attribute__((always_inline)) {
+    lo = hi = selfOff;
+    if (si < 10) {
+      const uint32_t row = ((uint32_t)(gy + (si >> 1) - 2) & (P.gridY - 1u)) << P.gridXLog2;
+      lo = (OffT)(cellS[row + ((si & 1) ? 0u : mx0)] - base) * 16u;
+      hi = (OffT)(cellS[row + ((si & 1) ? 5u - first : mx0 + first)] - base) * 16u;
+    }
+  };
+  // segment numbers advance by 2 (one range per grid row) except for a lane at the x-wrap, whose
+  // rows split into two ranges: per-lane stride, the wave runs until its last lane is done
+  const int stride = nseg == 1 ? 2 : 1;
+  OffT loA, hiA, loB, hiB;
+  bounds(0, loA, hiA);
+  bounds(stride, loB, hiB);
+  float4 qA = at(loA);
+  PB_TL_STAMP(4);
 #pragma unroll 1
-    for (int si = 0; si < 10; si += stride) {
-      const uint32_t lo = loA, end = hiA;
-      float4 q0 = qA, q1 = at(lo + 16u);
-      float2 v0 = vA, v1 = vat(lo + 16u);
-      loA = loB;
-      hiA = hiB;
-      qA = at(loA);  // first posrad of the next segment
-      vA = vat(loA);
-      bounds(si + 2 * stride, loB, hiB);  // bounds of the one after
-      if (lo < end) {
-        uint32_t off = lo;
-        for (;;) {
-          const float4 n0 = at(off + 32u), n1 = at(off + 48u);
-          const float2 w0 = vat(off + 32u), w1 = vat(off + 48u);
-          two(q0, v0, q1, v1, off, end);
-          if ((off += 32u) >= end) break;
-          q0 = at(off + 32u);
-          q1 = at(off + 48u);
-          v0 = vat(off + 32u);
-          v1 = vat(off + 48u);
-          two(n0, w0, n1, w1, off, end);
-          if ((off += 32u) >= end) break;
-        }
+  for (int si = 0; si < 10;) {
+    if (si == 4) PB_TL_STAMP(5);
+    const OffT lo = loA;
+    // own slot inside [lo, hiA): this turn stops short of it, the next one starts behind it with the same si
+    const bool cut = (OffT)(selfOff - lo) < (OffT)(hiA - lo);
+    const OffT end = cut ? selfOff : hiA;
+    float4 q0 = qA;
+    loA = cut ? selfOff16 : loB;
+    hiA = cut ? hiA : hiB;
+    qA = at(loA);                                    // first posrad of the next turn's range
+    if (!cut) bounds(si + 2 * stride, loB, hiB);     // bounds of the segment after the next
+    si += cut ? 0 : stride;
+    if (lo < end) {
+      // two neighbours per turn of the loop: `off` is the even one's byte offset, hoff = off / 2 the
+      // offset of its velocity
+      OffT off = lo, hoff = lo >> 1;
+      const OffT endm = end - 16u;
+      for (;;) {
+        const float4 q1 = atI(off, 16);
+        one(q0, [&]() { return vatI(hoff, 0); });
+        if (off >= endm) break;
+        off += 32u;
+        hoff += 16u;
+        q0 = atI(off, 0);
+        one(q1, [&]() { return vatI(hoff, -8); });
+        if (off >= end) break;
       }
     }
-    return;
   }
+  rep.flush(F.fr);
+}
+
+// ---- reference-shaped sweep: pbPair (divergent branches, force variant 0) over the ten ranges ----
+template <bool PAYLOAD, class PR, class VL>
+__device__ __forceinline__ void pbSweepRef(const PbDevParams &P, PR prIn, VL velIn,
+                                           const uint32_t *__restrict__ cellS, uint32_t base, uint32_t s,
+                                           const float4 &me, const float2 &v, float att1, PbForce &F) {
+  const int gx = pbCellX(P, me.x), gy = pbCellY(P, me.y);
+  // Not used below, and not dead: it is the expression of pbPair's linear band for A == P.attraction, the compiler
+  // merges the two, and the band's divisions leave the pair loop with it.
+  const float slope0 = pbBandSlope(P.attraction);
+  (void)slope0;
+  const uint32_t GX = P.gridX;
+  const uint32_t mx0 = (uint32_t)(gx - 2) & (GX - 1u);
+  const uint32_t first = (GX - mx0) < 5u ? (GX - mx0) : 5u;  // cells before the x-wrap
+  const int nseg = first < 5u ? 2 : 1;
   // rolled on purpose: one copy of the pair loop in the binary (unrolling the five rows made ten)
 #pragma unroll 1
   for (int si = 0; si < 10; si++) {
@@ -437,67 +366,38 @@ __device__ __forceinline__ void pbSweepC(const PbDevParams &P, PR prIn, VL velIn
     const uint32_t row = ((uint32_t)(gy + (si >> 1) - 2) & (P.gridY - 1u)) << P.gridXLog2;
     const uint32_t lo = cellS[row + ((si & 1) ? 0u : mx0)] - base;
     const uint32_t hi = cellS[row + ((si & 1) ? 5u - first : mx0 + first)] - base;
-    if (FLAT) {
-      // NB neighbours per trip, evaluated side by side (independent dependency chains for the
-      // scheduler to interleave) and then summed in slot order.  The next trip's posrad loads
-      // are already in flight (software pipeline).  Out-of-range slots alias the lane's own
-      // slot s, which is never accumulated.  With NB > 1 (latency form) the neighbours'
-      // velocities travel with their posrad instead of being fetched inside the contact branch.
-      constexpr bool PREVEL = NB > 1;
-      float4 q[NB];
-      float2 vq[NB];
-#pragma unroll
-      for (int k = 0; k < NB; k++) {
-        const uint32_t i0 = lo + k < hi ? lo + k : s;
-        q[k] = prIn[i0];
-        if (PREVEL) vq[k] = velIn[i0];
-      }
-      for (uint32_t j = lo; j < hi; j += NB) {
-        bool live[NB];
-        uint32_t idx[NB];
-        float bx[NB], by[NB], rb[NB], A[NB], K[NB];
-        float2 vb[NB];
-#pragma unroll
-        for (int k = 0; k < NB; k++) {
-          idx[k] = j + k < hi ? j + k : s;
-          live[k] = idx[k] != s;
-          bx[k] = q[k].x;
-          by[k] = q[k].y;
-          rb[k] = q[k].z;
-          if (PREVEL) vb[k] = vq[k];
-          // payload factors ride in q.w / att1 (impl.cuh:629-633, 640-649)
-          A[k] = PAYLOAD ? attraction0 * q[k].w * att1 : attraction0;
-          K[k] = PAYLOAD ? pbBandSlope(A[k]) : slope0;
-        }
-#pragma unroll
-        for (int k = 0; k < NB; k++) {
-          // NB == 1: plain j + 1, no clamp -- one slot past the range is still inside the array
-          // (spare element at the end) and is never evaluated
-          const uint32_t i1 = (NB == 1 || j + NB + k < hi) ? j + NB + k : s;
-          q[k] = prIn[i1];
-          if (PREVEL) vq[k] = velIn[i1];
-        }
-        PbPairTerm t[NB];
-        pbPairEvalK<FAST, NB>(CK, live, me.x, me.y, v.x, v.y, me.z, bx, by, rb, A, K,
-                              [&](int k) { return PREVEL ? vb[k] : velIn[idx[k]]; }, t);
-#pragma unroll
-        for (int k = 0; k < NB; k++) pbPairAdd(live[k], t[k], F);
-      }
-    } else {
-      for (uint32_t j = lo; j < hi; j++) {
-        const float4 q = prIn[j];
-        const float A = PAYLOAD ? P.attraction * q.w * att1 : P.attraction;
-        if (j != s) pbPair(P, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, A, [&]() { return velIn[j]; }, F);
-      }
+    for (uint32_t j = lo; j < hi; j++) {
+      const float4 q = prIn[j];
+      // payload factors ride in q.w / att1 (impl.cuh:629-633, 640-649)
+      const float A = PAYLOAD ? P.attraction * q.w * att1 : P.attraction;
+      if (j != s) pbPair(P, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, A, [&]() { return velIn[j]; }, F);
     }
   }
 }
 
-template <bool PAYLOAD, bool FLAT, bool FAST, int L, int NB, class OffT, bool ASUM = true, class PR, class VL>
+// Neighbour sweep of one bot: the 25-cell stencil as 5 grid rows x up to 2 slot ranges (x-wrap), in
+// the reference's order (impl.cuh:617-655).  prIn/velIn are indexed by (global slot - base): the
+// per-step kernel passes the HBM arrays and base 0, the resident kernel its LDS copy and the
+// simulation's first slot.  s is the bot's own index into prIn.
+// L: lanes per bot.  L == 1 is the throughput form (one bot per lane): the lane sweep, or with !FLAT the
+// reference-shaped one.  L > 1 (small batches that cannot fill the chip; the group sweep) gives each bot L
+// adjacent lanes: they evaluate L candidates of the bot's flattened neighbour list at a time, then every lane
+// of the group adds the L terms in list order
+// (ds_swizzle broadcasts inside the group), so the sums -- and their order -- are those of L == 1.
+// The serial chain per bot shrinks ~L/2-fold at ~2x the total VALU work.
+// ASUM: maintain Sum|F_attr| (F.fa).  false (branch-free forms; the caller guarantees that no
+// simulation of the batch has constrained_contraction set, see pbPairEvalXY): F.fa is left alone.
+// CACHED / cache: the group sweep's list cache (resident kernel); a per-step caller passes false and a dummy.
+// OffT: the lane sweep's byte offsets, 32-bit (batches below 2^28 bots) or 64-bit.
+template <bool PAYLOAD, bool FLAT, bool FAST, int L, bool CACHED, class OffT = uint32_t, bool ASUM = true,
+          int REPSTRIDE = TILE, class PR, class VL>
 __device__ __forceinline__ void pbSweep(const PbDevParams &P, PR prIn, VL velIn, const uint32_t *__restrict__ cellS,
                                         uint32_t base, uint32_t s, uint32_t sub, const float4 &me, const float2 &v,
-                                        float att1, PbForce &F, float *repCol = nullptr) {
-  PbSegCache none;
-  pbSweepC<PAYLOAD, FLAT, FAST, L, NB, false, PR, VL, OffT, ASUM>(P, prIn, velIn, cellS, base, s, sub, me, v, att1, F,
-                                                                  none, repCol);
+                                        float att1, PbForce &F, PbSegCache &cache, float *repCol = nullptr) {
+  if constexpr (L > 1)
+    pbSweepGroup<PAYLOAD, FAST, L, CACHED, ASUM>(P, prIn, velIn, cellS, base, s, sub, me, v, att1, F, cache);
+  else if constexpr (FLAT)
+    pbSweepLane<PAYLOAD, FAST, OffT, ASUM, REPSTRIDE>(P, prIn, velIn, cellS, base, s, me, v, att1, F, repCol);
+  else
+    pbSweepRef<PAYLOAD>(P, prIn, velIn, cellS, base, s, me, v, att1, F);
 }
