@@ -168,6 +168,12 @@ class Particlebot {
   /* frames rendered on the device so far and the device time of the last one's launches in milliseconds
    * (pbSimGetRenderStats); false unless the engine is the fused one */
   bool renderStats(unsigned long long &frames, float &lastDeviceMs);
+  /* Cluster analysis of the resident state on the device (pbSimClusterStats / pbSimClusterLabelsOf,
+   * include/particlebot_hip.h has the definition of a link, a cluster and a label): the stats row, or every bot's label
+   * and degree in ORIGINAL order.  Fused engine only: Legacy and HostOnly instances return false with a message on
+   * stderr.  Also false on a negative or non-finite linkGap. */
+  bool clusterStats(float linkGap, pbClusterStats &out);
+  bool clusterLabels(float linkGap, std::vector<unsigned> &labels, std::vector<unsigned> &degree);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -353,6 +353,45 @@ typedef struct pbRenderView {
 int pbSimRenderOf(pbSim *sim, unsigned member, const pbRenderView *view, unsigned char *rgb);
 int pbSimGetRenderStats(pbSim *sim, unsigned long long *renders, float *last_device_ms);
 
+/* Cluster analysis on the device (csrc/pb_cluster.hip): the connected components of every member's contact graph, from
+ * the resident state.
+ * Nodes: all nCells bots of a member, dead bots and the payload bot of payload mode included.
+ * Bots i != j of the same member are LINKED iff, in fp32 with no contraction,
+ *     rx = xj - xi;  ry = yj - yi;  dist = sqrtf(rx*rx + ry*ry);      (the pair law's dist, correctly rounded)
+ *     (dist - (ri + rj)) < linkGap
+ * The predicate is symmetric.  linkGap = 0 is exactly the pair law's contact test dist < ra + rb; coincident bots are
+ * linked.  A positive linkGap also links bots held by attraction across a gap (0.0019f: the outer edge of the law's
+ * linear band).  A bot with a non-finite position or radius has no links and does not fault.  Results are guaranteed for
+ * finite positions with |x|, |y| <= 2^20; outside that range the call does not fault and may return anything.
+ * A CLUSTER is a connected component of that graph; a bot's LABEL is the smallest ORIGINAL index in its component, so
+ * labels are canonical and every output is an integer that can be compared exactly.
+ * pbSimClusterStats: one row per member (nsims entries).  pbSimClusterLabelsOf: one member's labels and degrees, n each,
+ * ORIGINAL order; a NULL pointer is skipped.  Each call analyses the state as it is now.  pbSimGetClusterTimes: analyses
+ * run so far, and the time in milliseconds that the last one took on the batch's stream, from its first launch to its
+ * last (HIP events): the kernels plus the gaps in which the host reads 4 bytes back (the largest radius, and the
+ * "nothing changed" flag once per compress round) -- what one analysis costs the device's queue, not the sum of the
+ * kernels' own times.  Either pointer may be NULL.
+ * PB_ERR_ARG, before the device is touched: NULL handle; NULL stats; member out of range; labels and degree both NULL;
+ * linkGap negative, NaN or infinite; a batch of 2^28 bots or more, or of more than 65535 members.
+ * The analysis only reads the simulation: not the slot layout, keys or cell lists (which are stale between re-sorts and
+ * are not used to find links: the bots are filed afresh), not the counters of pbSimStats, not the time, the RNG or the
+ * render buffers.  Its scratch -- 44 bytes per bot of the batch, 4 bytes per cell of its grid (max(16, nCells rounded
+ * up to a power of two) cells per member), 4 bytes per bot of one member, the sort's histogram and 64 bytes per
+ * member -- is allocated by the first call, kept, and freed by pbSimDestroy. */
+typedef struct pbClusterStats {        /* 32 bytes */
+  unsigned clusters;       /* components, single bots included */
+  unsigned largest;        /* bots in the largest component */
+  unsigned largest_label;  /* its label; the smallest label among ties */
+  unsigned isolated;       /* bots of degree 0 */
+  unsigned long long links;/* undirected links */
+  unsigned max_degree;
+  unsigned rounds;         /* hook/compress rounds the device ran (diagnostic) */
+} pbClusterStats;
+int pbSimClusterStats(pbSim *sim, float linkGap, pbClusterStats *stats /* nsims entries */);
+int pbSimClusterLabelsOf(pbSim *sim, unsigned member, float linkGap,
+                         unsigned *labels, unsigned *degree /* n each, ORIGINAL order; NULL skipped */);
+int pbSimGetClusterTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

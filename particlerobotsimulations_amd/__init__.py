@@ -406,6 +406,28 @@ class Sim:
         return int(n.value), float(ms.value)
 
 
+    def clusters(self, gap=0.0):
+        """Cluster analysis of every member's state as it is now, on the device (pbSimClusterStats): a list of dicts
+        (clusters, largest, largest_label, isolated, links, max_degree, rounds), one per member."""
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbClusterStats * nsims)()
+        _capi.check(_capi.lib().pbSimClusterStats(self._h, float(gap), rows), "pbSimClusterStats")
+        return [{name: int(getattr(r, name)) for name, _ in _capi.pbClusterStats._fields_} for r in rows]
+
+    def cluster_labels(self, gap=0.0, member=0):
+        """(labels, degree) of one member: uint32 arrays in original bot order (pbSimClusterLabelsOf)."""
+        labels, degree = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
+        _capi.check(_capi.lib().pbSimClusterLabelsOf(self._h, int(member), float(gap), _capi.np_ptr(labels),
+                                                     _capi.np_ptr(degree)), "pbSimClusterLabelsOf")
+        return labels, degree
+
+    def cluster_times(self):
+        """(analyses run so far, device milliseconds of the last one)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetClusterTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetClusterTimes")
+        return int(n.value), float(ms.value)
+
+
 class Ensemble(Sim):
     """A batch of independent simulations of equal size stepped by the same launches
     (pbSimCreateBatch): seeds of a Monte-Carlo run, points of a parameter sweep."""

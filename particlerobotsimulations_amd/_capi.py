@@ -83,6 +83,11 @@ class pbRenderView(C.Structure):
                 ("halfExtent", C.c_float), ("lightRadius", C.c_float), ("style", C.c_int)]
 
 
+class pbClusterStats(C.Structure):
+    _fields_ = [("clusters", C.c_uint), ("largest", C.c_uint), ("largest_label", C.c_uint), ("isolated", C.c_uint),
+                ("links", C.c_ulonglong), ("max_degree", C.c_uint), ("rounds", C.c_uint)]
+
+
 class pbForceForm(C.Structure):
     _fields_ = [("flat", C.c_int), ("lanes_per_bot", C.c_int), ("attraction_sums", C.c_int), ("offsets64", C.c_int)]
 
@@ -138,6 +143,9 @@ SYMBOLS = {
     "pbSimGetCentroidTrailOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_U)]),
     "pbSimRenderOf": (_I, [_VP, _U, C.POINTER(pbRenderView), _VP]),
     "pbSimGetRenderStats": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimClusterStats": (_I, [_VP, _F, C.POINTER(pbClusterStats)]),
+    "pbSimClusterLabelsOf": (_I, [_VP, _U, _F, _VP, _VP]),
+    "pbSimGetClusterTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1368,6 +1368,32 @@ bool Particlebot::renderStats(unsigned long long &frames, float &lastDeviceMs) {
   return engineKind == Engine::Fused && pbSimGetRenderStats(sim, &frames, &lastDeviceMs) == PB_OK;
 }
 
+bool Particlebot::clusterStats(float linkGap, pbClusterStats &out) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::clusterStats: the cluster analysis needs the fused engine\n");
+    return false;
+  }
+  if (pbSimClusterStats(sim, linkGap, &out) != PB_OK) {
+    fprintf(stderr, "Particlebot::clusterStats: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::clusterLabels(float linkGap, std::vector<unsigned> &labels, std::vector<unsigned> &degree) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::clusterLabels: the cluster analysis needs the fused engine\n");
+    return false;
+  }
+  labels.resize(params.nCells);
+  degree.resize(params.nCells);
+  if (pbSimClusterLabelsOf(sim, 0, linkGap, labels.data(), degree.data()) != PB_OK) {
+    fprintf(stderr, "Particlebot::clusterLabels: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

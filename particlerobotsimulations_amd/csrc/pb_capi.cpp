@@ -303,6 +303,20 @@ int pbHostRenderStats(void *hv, unsigned long long *frames, float *last_device_m
   return 0;
 }
 
+// cluster analysis of the resident state (Particlebot::clusterStats / clusterLabels; fused engine only): the 32-byte
+// pbClusterStats row, or labels and degrees (nCells unsigned each, original order).  -1 on the other engines or a bad gap.
+int pbHostClusterStats(void *hv, float gap, pbClusterStats *out) {
+  return out && ((HostSim *)hv)->bot->clusterStats(gap, *out) ? 0 : -1;
+}
+
+int pbHostClusterLabels(void *hv, float gap, unsigned *labels, unsigned *degree) {
+  std::vector<unsigned> l, d;
+  if (!((HostSim *)hv)->bot->clusterLabels(gap, l, d)) return -1;
+  if (labels) memcpy(labels, l.data(), l.size() * sizeof(unsigned));
+  if (degree) memcpy(degree, d.data(), d.size() * sizeof(unsigned));
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -1,0 +1,568 @@
+// pb_cluster.hip -- cluster analysis on gfx950: the connected components of every member's contact graph, from the
+// engine's resident state (pbSimClusterStats / pbSimClusterLabelsOf, include/particlebot_hip.h has the definition).
+//
+// The engine's own cell lists are stale between re-sorts, so the analysis files the bots afresh, in scratch of its
+// own, and leaves the simulation untouched.  For the whole batch at once:
+//   k_cluster_rmax      the largest finite radius (bit-pattern max, one atomic per workgroup), 4 bytes read back
+//   k_cluster_hash      key = member * cells + cell of a wrapped power-of-two grid whose edge is a little more than
+//                       2 rmax + linkGap; the cell index is floor(x / edge) in fp64, whose rounding (2^-24 of a cell for
+//                       |x| <= 2^20 and the smallest edge) is far inside the edge's 2^-10 margin: a linked pair is
+//                       never further apart than one cell.  Wrapping only folds distant bots into one list.
+//   pbRadixSortPairs    (pb_sort.hip) slots by key
+//   k_cluster_gather    posrad in sorted order with the GLOBAL original index in .w; a bot with a non-finite position
+//                       or radius becomes a NaN position, which no comparison links; parent[o] = o, size[o] = 0
+//   k_cluster_starts    dense cell starts: a lower bound in the sorted keys per cell (as k_cell_scan)
+//   k_cluster_links     the hot path: one bot per lane over the nine cells (three slot ranges away from the x-wrap),
+//                       the next neighbour's posrad in flight; evaluates the predicate, counts the degree and hooks
+//                       every link once (from its larger index) into a union-find forest over original indices:
+//                       find with path halving, hook the larger root under the smaller with atomicCAS.  Roots only
+//                       ever get smaller, so a component's root is its smallest original index: the label.
+//   k_cluster_compress  every bot follows its chain to the root and points at it; repeated until a device flag says
+//                       nothing changed (4 bytes read back per round; the forest is shallow after path halving).  A
+//                       pass chases all the way to the root, so the second pass normally finds nothing to do and
+//                       pbClusterStats.rounds is 3: the hook round, one pass that moves pointers, one that confirms
+//   k_cluster_sizes     size[root] += 1, lanes of a wave that share a root combined into one atomic
+//   k_cluster_reduce    per member: roots, the largest (size, smallest label) as one 64-bit max, isolated bots, the
+//                       degree sum and maximum; wave shuffles, LDS, one set of atomics per workgroup
+//   k_cluster_rows      one 32-byte pbClusterStats row per member
+//   k_cluster_labels    one member's labels, local indices (pbSimClusterLabelsOf)
+// The predicate is the pair law's geometry in fp32 without contraction: dist = sqrtf(rx*rx + ry*ry), correctly rounded.
+// No LDS beyond the reduction's few words, no scratch memory.
+#include <string.h>
+
+#include "pb_engine.hpp"
+
+struct PbClusterScratch {
+  uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr;
+  float4 *cpr = nullptr;        // total + 2: sorted posrad, .w = global original index
+  uint32_t *start = nullptr;    // nsims * cells + 1
+  uint32_t *parent = nullptr, *degree = nullptr, *size = nullptr;  // total each, ORIGINAL order
+  uint32_t *labels = nullptr;   // n: one member's labels
+  unsigned long long *acc = nullptr;  // 4 words per member
+  pbClusterStats *rows = nullptr;     // nsims
+  uint32_t *flag = nullptr;           // [0] changed, [1] rmax bits
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  uint32_t gxLog2 = 2, gyLog2 = 2;
+  unsigned long long analyses = 0;
+  float lastMs = 0.0f;
+  unsigned rounds = 0;
+};
+
+namespace {
+
+constexpr int CT = 256;
+constexpr unsigned MAX_ROUNDS = 1024;
+
+struct ClusterGrid {
+  double invCell;
+  uint32_t gxLog2, gyLog2;
+};
+
+PB_DEV bool finitePosRad(const float4 &q) {
+  const float inf = __builtin_inff();
+  return fabsf(q.x) < inf && fabsf(q.y) < inf && fabsf(q.z) < inf;
+}
+
+// floor(v) as an int, clamped so that positions outside the guaranteed range convert without overflow
+PB_DEV int cellCoord(double v) {
+  const double f = floor(v);
+  return (int)fmin(fmax(f, -1073741824.0), 1073741824.0);
+}
+
+PB_DEV uint32_t cellX(const ClusterGrid &G, float x) {
+  return (uint32_t)cellCoord((double)x * G.invCell) & ((1u << G.gxLog2) - 1u);
+}
+PB_DEV uint32_t cellY(const ClusterGrid &G, float y) {
+  return (uint32_t)cellCoord((double)y * G.invCell) & ((1u << G.gyLog2) - 1u);
+}
+
+PB_DEV uint32_t waveMaxU32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)v, m);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+PB_DEV uint32_t waveSumU32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
+  return v;
+}
+PB_DEV unsigned long long shflXor64(unsigned long long v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
+  return ((unsigned long long)hi << 32) | lo;
+}
+PB_DEV unsigned long long waveMaxU64(unsigned long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = shflXor64(v, m);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+PB_DEV unsigned long long waveSumU64(unsigned long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += shflXor64(v, m);
+  return v;
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_rmax(const float4 *__restrict__ pr, uint32_t total,
+                                                     uint32_t *__restrict__ out) {
+  __shared__ uint32_t part[CT / 64];
+  uint32_t best = 0u;  // bit pattern of the largest finite positive radius: such floats order like their bits
+  for (uint32_t s = blockIdx.x * CT + threadIdx.x; s < total; s += gridDim.x * CT) {
+    const float r = pr[s].z;
+    if (r > 0.0f && r < __builtin_inff()) {
+      const uint32_t b = __float_as_uint(r);
+      best = b > best ? b : best;
+    }
+  }
+  best = waveMaxU32(best);
+  if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = best;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < CT / 64; w++) best = part[w] > best ? part[w] : best;
+    if (best) atomicMax(out, best);
+  }
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_hash(const float4 *__restrict__ pr, uint32_t n, ClusterGrid G,
+                                                     uint32_t *__restrict__ keys, uint32_t *__restrict__ vals) {
+  const uint32_t l = blockIdx.x * CT + threadIdx.x;
+  if (l >= n) return;
+  const uint32_t s = blockIdx.y * n + l;
+  const float4 q = pr[s];
+  uint32_t cell = 0u;
+  if (finitePosRad(q)) cell = (cellY(G, q.y) << G.gxLog2) | cellX(G, q.x);
+  keys[s] = (blockIdx.y << (G.gxLog2 + G.gyLog2)) + cell;
+  vals[s] = s;
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_gather(const float4 *__restrict__ pr, const uint32_t *__restrict__ orig,
+                                                       const uint32_t *__restrict__ sortedSlots, uint32_t n,
+                                                       float4 *__restrict__ cpr, uint32_t *__restrict__ parent,
+                                                       uint32_t *__restrict__ size) {
+  const uint32_t l = blockIdx.x * CT + threadIdx.x;
+  if (l >= n) return;
+  const uint32_t base = blockIdx.y * n, t = base + l;
+  const uint32_t src = sortedSlots[t];  // keys carry the member: src stays inside this member's block
+  float4 q = pr[src];
+  const uint32_t o = base + orig[src];
+  if (!finitePosRad(q)) q.x = q.y = __builtin_nanf("");
+  q.w = __uint_as_float(o);
+  cpr[t] = q;
+  parent[o] = o;
+  size[o] = 0u;
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_starts(const uint32_t *__restrict__ sortedKeys, uint32_t total,
+                                                       uint32_t numKeys, uint32_t *__restrict__ start) {
+  const uint32_t c = blockIdx.x * CT + threadIdx.x;
+  if (c > numKeys) return;
+  uint32_t lo = 0, hi = total;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (sortedKeys[mid] < c) lo = mid + 1;
+    else hi = mid;
+  }
+  start[c] = lo;
+}
+
+// The forest is read and written by many lanes at once: relaxed atomic accesses (plain vector loads and stores that the
+// compiler may not cache or tear).  Every value ever stored in parent[v] is an ancestor of v and at most v.
+PB_DEV uint32_t ldRelaxed(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+PB_DEV void stRelaxed(uint32_t *p, uint32_t v) { __atomic_store_n(p, v, __ATOMIC_RELAXED); }
+
+// the root of x, halving the path on the way (a root is never written here: only the hook's atomicCAS changes one)
+PB_DEV uint32_t findRoot(uint32_t *__restrict__ parent, uint32_t x) {
+  uint32_t curr = ldRelaxed(parent + x);
+  if (curr != x) {
+    uint32_t prev = x, next;
+    while (curr > (next = ldRelaxed(parent + curr))) {
+      stRelaxed(parent + prev, next);
+      prev = curr;
+      curr = next;
+    }
+  }
+  return curr;
+}
+
+PB_DEV void hook(uint32_t *__restrict__ parent, uint32_t a, uint32_t b) {
+  a = findRoot(parent, a);
+  b = findRoot(parent, b);
+  while (a != b) {
+    if (a < b) {
+      const uint32_t t = a;
+      a = b;
+      b = t;
+    }
+    const uint32_t old = atomicCAS(parent + a, a, b);  // a > b: the larger root goes under the smaller
+    if (old == a) break;
+    a = old;  // a was no root any more: climb from what it points at
+  }
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_links(const float4 *__restrict__ cpr, const uint32_t *__restrict__ start,
+                                                      uint32_t n, ClusterGrid G, float gap,
+                                                      uint32_t *__restrict__ parent, uint32_t *__restrict__ degree) {
+  const uint32_t l = blockIdx.x * CT + threadIdx.x;
+  if (l >= n) return;
+  const uint32_t t = blockIdx.y * n + l;
+  const float4 me = cpr[t];
+  const uint32_t o = __float_as_uint(me.w);
+  uint32_t deg = 0u;
+  if (me.x == me.x) {  // a bot with a non-finite position or radius has no links
+    const uint32_t GX = 1u << G.gxLog2;
+    const uint32_t cx = cellX(G, me.x), cy = cellY(G, me.y);
+    const uint32_t *__restrict__ cells = start + ((size_t)blockIdx.y << (G.gxLog2 + G.gyLog2));
+    // three ranges of three cells; at the x-wrap nine ranges of one (wrapped dimensions >= 4: nine distinct cells)
+    const bool wrap = cx == 0u || cx == GX - 1u;
+    const uint32_t step = wrap ? 1u : 3u;
+    auto bounds = [&](uint32_t si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
+      lo = hi = t;
+      if (si < 9u) {
+        const uint32_t rowI = si / 3u, col = si - 3u * rowI;
+        const uint32_t row = ((cy + rowI - 1u) & ((1u << G.gyLog2) - 1u)) << G.gxLog2;
+        const uint32_t c0 = (cx + col - 1u) & (GX - 1u);
+        lo = cells[row + c0];
+        hi = cells[row + c0 + step];
+      }
+    };
+    // Cheap rejection in front of the correctly rounded root.  A linked pair has fl(dist - R) < gap with R = ri + rj,
+    // hence dist - R <= gap exactly (rounding is monotone), dist <= fl(R + gap) (1 + 2^-23) and
+    // fl(rx*rx + ry*ry) <= fl(R + gap)^2 (1 + 2^-20): the bound below (1e-4 relative, 1e-30 absolute for the
+    // subnormal cases) admits every such pair; whatever else it admits the exact predicate decides.
+    uint32_t loA, hiA, loB, hiB;
+    bounds(0u, loA, hiA);
+    bounds(step, loB, hiB);
+    float4 qA = cpr[loA];
+#pragma unroll 1
+    for (uint32_t si = 0u; si < 9u; si += step) {
+      const uint32_t lo = loA, hi = hiA;
+      float4 q = qA;
+      loA = loB, hiA = hiB;
+      qA = cpr[loA];                      // first posrad of the next range
+      bounds(si + 2u * step, loB, hiB);   // bounds of the range after the next
+      for (uint32_t j = lo; j < hi; j++) {
+        const float4 qn = cpr[j + 1u];  // one slot past a range is inside the array (spare elements)
+        const float rx = q.x - me.x, ry = q.y - me.y;
+        const float d2 = rx * rx + ry * ry;
+        const float R = me.z + q.z;
+        const float s = R + gap;
+        if (j != t && d2 <= s * s * 1.0001f + 1e-30f) {
+          const float dist = sqrtf(d2);
+          if ((dist - R) < gap) {
+            deg++;
+            const uint32_t oj = __float_as_uint(q.w);
+            if (oj < o) hook(parent, o, oj);
+          }
+        }
+        q = qn;
+      }
+    }
+  }
+  degree[o] = deg;
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_compress(uint32_t *__restrict__ parent, uint32_t total,
+                                                         uint32_t *__restrict__ flag) {
+  const uint32_t i = blockIdx.x * CT + threadIdx.x;
+  bool changed = false;
+  if (i < total) {
+    const uint32_t p = ldRelaxed(parent + i);
+    uint32_t r = p, g;
+    while ((g = ldRelaxed(parent + r)) != r) r = g;
+    if (r != p) {
+      stRelaxed(parent + i, r);
+      changed = true;
+    }
+  }
+  if (__any(changed) && (threadIdx.x & 63u) == 0u) stRelaxed(flag, 1u);
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_sizes(const uint32_t *__restrict__ parent, uint32_t total,
+                                                      uint32_t *__restrict__ size) {
+  const uint32_t i = blockIdx.x * CT + threadIdx.x;
+  bool todo = i < total;
+  const uint32_t r = todo ? parent[i] : 0u;
+  // neighbours in original order mostly share a root: the lanes that share the first pending lane's root add once
+#pragma unroll 1
+  for (int turn = 0; turn < 4; turn++) {
+    const unsigned long long pending = __ballot(todo);
+    if (!pending) return;
+    const int lead = __ffsll((long long)pending) - 1;
+    const uint32_t r0 = (uint32_t)__shfl((int)r, lead);
+    const bool mine = todo && r == r0;
+    const unsigned long long group = __ballot(mine);
+    if (mine) {
+      if ((int)(threadIdx.x & 63u) == lead) atomicAdd(size + r0, (uint32_t)__popcll(group));
+      todo = false;
+    }
+  }
+  if (todo) atomicAdd(size + r, 1u);
+}
+
+// acc[4 m + 0] (size << 32 | ~label) of the best root, [1] degree sum, [2] roots | isolated << 32, [3] max degree
+__global__ __launch_bounds__(CT) void k_cluster_reduce(const uint32_t *__restrict__ parent,
+                                                       const uint32_t *__restrict__ size,
+                                                       const uint32_t *__restrict__ degree, uint32_t n,
+                                                       unsigned long long *__restrict__ acc) {
+  __shared__ unsigned long long sBest[CT / 64], sDeg[CT / 64];
+  __shared__ uint32_t sRoots[CT / 64], sIso[CT / 64], sMax[CT / 64];
+  const uint32_t l = blockIdx.x * CT + threadIdx.x;
+  const uint32_t i = blockIdx.y * n + l;
+  unsigned long long best = 0ull, degSum = 0ull;
+  uint32_t roots = 0u, iso = 0u, maxDeg = 0u;
+  if (l < n) {
+    if (parent[i] == i) {
+      roots = 1u;
+      best = ((unsigned long long)size[i] << 32) | (unsigned long long)(0xFFFFFFFFu - l);
+    }
+    const uint32_t d = degree[i];
+    degSum = d;
+    maxDeg = d;
+    iso = d == 0u ? 1u : 0u;
+  }
+  best = waveMaxU64(best);
+  degSum = waveSumU64(degSum);
+  roots = waveSumU32(roots);
+  iso = waveSumU32(iso);
+  maxDeg = waveMaxU32(maxDeg);
+  const uint32_t w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0u) sBest[w] = best, sDeg[w] = degSum, sRoots[w] = roots, sIso[w] = iso, sMax[w] = maxDeg;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int k = 1; k < CT / 64; k++) {
+      best = sBest[k] > best ? sBest[k] : best;
+      degSum += sDeg[k];
+      roots += sRoots[k];
+      iso += sIso[k];
+      maxDeg = sMax[k] > maxDeg ? sMax[k] : maxDeg;
+    }
+    unsigned long long *a = acc + 4u * (size_t)blockIdx.y;
+    if (best) atomicMax(a + 0, best);
+    if (degSum) atomicAdd(a + 1, degSum);
+    if (roots | iso) atomicAdd(a + 2, (unsigned long long)roots | ((unsigned long long)iso << 32));
+    if (maxDeg) atomicMax(a + 3, (unsigned long long)maxDeg);
+  }
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_rows(const unsigned long long *__restrict__ acc, uint32_t nsims,
+                                                     unsigned rounds, pbClusterStats *__restrict__ rows) {
+  const uint32_t m = blockIdx.x * CT + threadIdx.x;
+  if (m >= nsims) return;
+  const unsigned long long *a = acc + 4u * (size_t)m;
+  pbClusterStats r;
+  r.clusters = (unsigned)a[2];
+  r.largest = (unsigned)(a[0] >> 32);
+  r.largest_label = 0xFFFFFFFFu - (unsigned)a[0];
+  r.isolated = (unsigned)(a[2] >> 32);
+  r.links = a[1] >> 1;
+  r.max_degree = (unsigned)a[3];
+  r.rounds = rounds;
+  rows[m] = r;
+}
+
+__global__ __launch_bounds__(CT) void k_cluster_labels(const uint32_t *__restrict__ parent, uint32_t base, uint32_t n,
+                                                       uint32_t *__restrict__ labels) {
+  const uint32_t l = blockIdx.x * CT + threadIdx.x;
+  if (l < n) labels[l] = parent[base + l] - base;
+}
+
+int ensureScratch(pbSim *S, uint32_t numKeys) {
+  if (S->cluster) return PB_OK;
+  PbClusterScratch *C = new PbClusterScratch();
+  S->cluster = C;  // pbSimDestroy frees whatever a failed allocation below leaves behind
+  const size_t total = S->total;
+  for (int k = 0; k < 2; k++) {
+    PB_TRY(hipMalloc((void **)&C->keys[k], sizeof(uint32_t) * total));
+    PB_TRY(hipMalloc((void **)&C->vals[k], sizeof(uint32_t) * total));
+  }
+  PB_TRY(hipMalloc((void **)&C->hist, sizeof(uint32_t) * pbSortHistEntries(S->total)));
+  PB_TRY(hipMalloc((void **)&C->cpr, sizeof(float4) * (total + 2)));
+  PB_TRY(hipMemset(C->cpr, 0, sizeof(float4) * (total + 2)));
+  PB_TRY(hipMalloc((void **)&C->start, sizeof(uint32_t) * ((size_t)numKeys + 1)));
+  PB_TRY(hipMalloc((void **)&C->parent, sizeof(uint32_t) * total));
+  PB_TRY(hipMalloc((void **)&C->degree, sizeof(uint32_t) * total));
+  PB_TRY(hipMalloc((void **)&C->size, sizeof(uint32_t) * total));
+  PB_TRY(hipMalloc((void **)&C->labels, sizeof(uint32_t) * S->n));
+  PB_TRY(hipMalloc((void **)&C->acc, sizeof(unsigned long long) * 4 * S->nsims));
+  PB_TRY(hipMalloc((void **)&C->rows, sizeof(pbClusterStats) * S->nsims));
+  PB_TRY(hipMalloc((void **)&C->flag, sizeof(uint32_t) * 2));
+  PB_TRY(hipEventCreate(&C->ev0));
+  PB_TRY(hipEventCreate(&C->ev1));
+  return PB_OK;
+}
+
+// The whole pipeline; leaves parent (roots), degree and the rows on the device and the stream drained.
+int analyse(pbSim *S, float gap) {
+  useDevice(S);
+  // the grid's shape depends on the batch alone: cells = max(16, n rounded up to a power of two) per member
+  uint32_t bits = 4;
+  while (bits < 31 && (1u << bits) < S->n) bits++;
+  const uint32_t gxLog2 = (bits + 1) / 2, gyLog2 = bits / 2;
+  const uint32_t cells = 1u << bits, numKeys = S->nsims * cells;
+  const int rc = ensureScratch(S, numKeys);
+  if (rc != PB_OK) return rc;
+  PbClusterScratch *C = S->cluster;
+  C->gxLog2 = gxLog2, C->gyLog2 = gyLog2;
+  const uint32_t n = S->n, total = S->total;
+  const int c = S->cur;
+  const dim3 b(CT), gBots(cdiv(n, CT), S->nsims), gAll(cdiv(total, CT));
+  PB_TRY(hipEventRecord(C->ev0, S->stream));
+  PB_TRY(hipMemsetAsync(C->flag, 0, sizeof(uint32_t) * 2, S->stream));
+  PB_TRY(hipMemsetAsync(C->acc, 0, sizeof(unsigned long long) * 4 * S->nsims, S->stream));
+  const uint32_t rmaxBlocks = cdiv(total, CT) < 1024u ? cdiv(total, CT) : 1024u;
+  hipLaunchKernelGGL(k_cluster_rmax, dim3(rmaxBlocks), b, 0, S->stream, S->pr[c], total, C->flag + 1);
+  uint32_t rmaxBits = 0;
+  PB_TRY(hipMemcpyAsync(&rmaxBits, C->flag + 1, sizeof rmaxBits, hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  float rmax;
+  memcpy(&rmax, &rmaxBits, sizeof rmax);
+  // edge >= 2 rmax + gap, rounded up by 2^-10 (fp32 rounding of the predicate and fp64 rounding of the cell index are
+  // below 2^-20 of it); never below 2^-8, so that |x| <= 2^20 gives a cell index below 2^28
+  double edge = (2.0 * (double)rmax + (double)gap) * (1.0 + 1.0 / 1024.0);
+  if (!(edge > 1.0 / 256.0)) edge = 1.0 / 256.0;
+  ClusterGrid G;
+  G.invCell = 1.0 / edge;
+  G.gxLog2 = gxLog2, G.gyLog2 = gyLog2;
+  hipLaunchKernelGGL(k_cluster_hash, gBots, b, 0, S->stream, S->pr[c], n, G, C->keys[0], C->vals[0]);
+  hipError_t e;
+  const int where = pbRadixSortPairs(C->keys[0], C->vals[0], C->keys[1], C->vals[1], C->hist, total,
+                                     pbKeyBits(numKeys), S->stream, &e);
+  if (where < 0) PB_TRY(e);
+  hipLaunchKernelGGL(k_cluster_gather, gBots, b, 0, S->stream, S->pr[c], S->orig[c], C->vals[where], n, C->cpr,
+                     C->parent, C->size);
+  hipLaunchKernelGGL(k_cluster_starts, dim3(cdiv(numKeys + 1u, CT)), b, 0, S->stream, C->keys[where], total, numKeys,
+                     C->start);
+  hipLaunchKernelGGL(k_cluster_links, gBots, b, 0, S->stream, C->cpr, C->start, n, G, gap, C->parent, C->degree);
+  PB_TRY(hipGetLastError());
+  unsigned rounds = 1;  // the hook round
+  for (;;) {
+    uint32_t changed = 0;
+    hipLaunchKernelGGL(k_cluster_compress, gAll, b, 0, S->stream, C->parent, total, C->flag);
+    PB_TRY(hipMemcpyAsync(&changed, C->flag, sizeof changed, hipMemcpyDeviceToHost, S->stream));
+    PB_TRY(hipStreamSynchronize(S->stream));
+    rounds++;
+    if (!changed) break;
+    if (rounds >= MAX_ROUNDS) {
+      pbLastError() = "cluster analysis: the forest did not settle";
+      return PB_ERR_HIP;
+    }
+    PB_TRY(hipMemsetAsync(C->flag, 0, sizeof(uint32_t), S->stream));
+  }
+  hipLaunchKernelGGL(k_cluster_sizes, gAll, b, 0, S->stream, C->parent, total, C->size);
+  hipLaunchKernelGGL(k_cluster_reduce, gBots, b, 0, S->stream, C->parent, C->size, C->degree, n, C->acc);
+  hipLaunchKernelGGL(k_cluster_rows, dim3(cdiv(S->nsims, CT)), b, 0, S->stream, C->acc, S->nsims, rounds, C->rows);
+  PB_TRY(hipGetLastError());
+  PB_TRY(hipEventRecord(C->ev1, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  PB_TRY(hipEventElapsedTime(&C->lastMs, C->ev0, C->ev1));
+  C->rounds = rounds;
+  C->analyses++;
+  return PB_OK;
+}
+
+// the checks both entry points share, after their own pointer checks; nothing here touches the device (checkBatch
+// reads the host-side batch object, so it needs a real handle)
+int checkGap(const char *fn, float gap) {
+  if (!(gap >= 0.0f) || !(gap < __builtin_inff())) {
+    pbLastError() = std::string(fn) + ": linkGap must be finite and >= 0";
+    return PB_ERR_ARG;
+  }
+  return PB_OK;
+}
+int checkBatch(const char *fn, const pbSim *S) {
+  if (S->nsims > 65535u) {  // the member is a launch's grid y
+    pbLastError() = std::string(fn) + ": the batch must hold at most 65535 members";
+    return PB_ERR_ARG;
+  }
+  if (S->total >= (1u << 28)) {
+    pbLastError() = std::string(fn) + ": the batch must hold fewer than 2^28 bots";
+    return PB_ERR_ARG;
+  }
+  return PB_OK;
+}
+
+}  // namespace
+
+void pbClusterFree(pbSim *S) {
+  PbClusterScratch *C = S->cluster;
+  if (!C) return;
+  for (int k = 0; k < 2; k++) {
+    (void)hipFree(C->keys[k]);
+    (void)hipFree(C->vals[k]);
+  }
+  (void)hipFree(C->hist);
+  (void)hipFree(C->cpr);
+  (void)hipFree(C->start);
+  (void)hipFree(C->parent);
+  (void)hipFree(C->degree);
+  (void)hipFree(C->size);
+  (void)hipFree(C->labels);
+  (void)hipFree(C->acc);
+  (void)hipFree(C->rows);
+  (void)hipFree(C->flag);
+  if (C->ev0) (void)hipEventDestroy(C->ev0);
+  if (C->ev1) (void)hipEventDestroy(C->ev1);
+  delete C;
+  S->cluster = nullptr;
+}
+
+int pbSimClusterStats(pbSim *S, float linkGap, pbClusterStats *stats) {
+  if (!S || !stats) {
+    pbLastError() = "pbSimClusterStats: null handle or stats";
+    return PB_ERR_ARG;
+  }
+  int rc = checkGap("pbSimClusterStats", linkGap);  // needs no look at the handle; the batch check reads it
+  if (rc == PB_OK) rc = checkBatch("pbSimClusterStats", S);
+  if (rc != PB_OK) return rc;
+  rc = analyse(S, linkGap);
+  if (rc != PB_OK) return rc;
+  PB_TRY(hipMemcpy(stats, S->cluster->rows, sizeof(pbClusterStats) * S->nsims, hipMemcpyDeviceToHost));
+  return PB_OK;
+}
+
+int pbSimClusterLabelsOf(pbSim *S, unsigned member, float linkGap, unsigned *labels, unsigned *degree) {
+  if (!S) {
+    pbLastError() = "pbSimClusterLabelsOf: null handle";
+    return PB_ERR_ARG;
+  }
+  if (!labels && !degree) {
+    pbLastError() = "pbSimClusterLabelsOf: labels and degree are both null";
+    return PB_ERR_ARG;
+  }
+  int rc = checkGap("pbSimClusterLabelsOf", linkGap);  // needs no look at the handle; the checks below read it
+  if (rc != PB_OK) return rc;
+  if (member >= S->nsims) {
+    pbLastError() = "pbSimClusterLabelsOf: member out of range";
+    return PB_ERR_ARG;
+  }
+  rc = checkBatch("pbSimClusterLabelsOf", S);
+  if (rc != PB_OK) return rc;
+  rc = analyse(S, linkGap);
+  if (rc != PB_OK) return rc;
+  PbClusterScratch *C = S->cluster;
+  const uint32_t n = S->n, base = member * n;
+  if (labels) {
+    hipLaunchKernelGGL(k_cluster_labels, dim3(cdiv(n, CT)), dim3(CT), 0, S->stream, C->parent, base, n, C->labels);
+    PB_TRY(hipGetLastError());
+    PB_TRY(hipMemcpyAsync(labels, C->labels, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, S->stream));
+  }
+  if (degree)
+    PB_TRY(hipMemcpyAsync(degree, C->degree + base, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  return PB_OK;
+}
+
+int pbSimGetClusterTimes(pbSim *S, unsigned long long *analyses, float *last_device_ms) {
+  if (!S) {
+    pbLastError() = "pbSimGetClusterTimes: null handle";
+    return PB_ERR_ARG;
+  }
+  if (analyses) *analyses = S->cluster ? S->cluster->analyses : 0ull;
+  if (last_device_ms) *last_device_ms = S->cluster ? S->cluster->lastMs : 0.0f;
+  return PB_OK;
+}

@@ -743,6 +743,7 @@ void pbSimDestroy(pbSim *S) {
   (void)hipFree(S->colors);
   (void)hipFree(S->trail);
   (void)hipFree(S->trailTmp);
+  pbClusterFree(S);
   (void)hipFree(S->renderIds);
   (void)hipFree(S->renderOut);
   (void)hipFree(S->renderRgb8);

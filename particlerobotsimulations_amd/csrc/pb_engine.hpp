@@ -7,6 +7,7 @@
 //   pb_resident.hip  k_resident: the multi-step one-workgroup-per-simulation kernel
 //   pb_display.hip   the reference's display kernels (colours, centroid trail)
 //   pb_render.hip    the frame rasteriser behind pbSimRenderOf
+//   pb_cluster.hip   cluster analysis: connected components of the contact graph (pbSimClusterStats)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 #pragma once
@@ -37,6 +38,8 @@ std::string &pbLastError();
 constexpr int TILE = PB_TILE;
 
 static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+
+struct PbClusterScratch;  // pb_cluster.hip
 
 struct pbSim {
   std::vector<PbDevParams> hP;  // one parameter block per simulation
@@ -116,6 +119,8 @@ struct pbSim {
   hipEvent_t renderEv0 = nullptr, renderEv1 = nullptr;
   unsigned long long renders = 0;
   float lastRenderMs = 0.0f;
+  // cluster analysis (pb_cluster.hip): scratch of its own, allocated by the first analysis, freed by pbSimDestroy
+  PbClusterScratch *cluster = nullptr;
   pbSimStats stats{};
 };
 
@@ -169,3 +174,5 @@ std::string pbForceStreamName(const pbSim *S);                                  
 // m whole timesteps from time t0 in one launch (simulations of <= 1024 bots)
 bool pbResidentWanted(const pbSim *S);                                                                    // pb_resident.hip
 void pbLaunchResident(pbSim *S, float dt, float t0, int m, int lightWave);
+// frees the cluster analysis' scratch, if any (pbSimDestroy)                                             pb_cluster.hip
+void pbClusterFree(pbSim *S);

@@ -2,7 +2,7 @@
 //
 //   particlebot_run [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet]
 //                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]]
-//                   [--trail FILE]
+//                   [--trail FILE] [--clusters FILE [--cluster-gap G]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -28,6 +28,9 @@
 // the same bytes, no state copy; fused engine only); host (default) is the class's CPU writer.  --trail FILE
 // records the reference's centroid trail (Particlebot::setDisplay) and writes it at the end of the run as
 // `slot,time,x,y` rows (slots holding a record; fp32 time and x to 9 digits), y as the double (stored y) - 2000, without the shader's +2000 (a resumed run starts a fresh trail).
+// --clusters FILE appends, at every dump time (the gate dumpParticlebot uses), one row of the device's cluster analysis
+// (Particlebot::clusterStats): `Time, Clusters, Largest, Isolated, Links, MaxDegree`, the header once at time 0;
+// --cluster-gap G (default 0, finite and >= 0) is the analysis' linkGap.  Without --clusters nothing is analysed.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -84,7 +87,9 @@ int main(int argc, char **argv) {
   std::string framesDir, resumePath, ckptPath, finalCkptPath;
   int frameSize = 800;
   bool referenceFrames = false, deviceFrames = false;
-  std::string trailPath;
+  std::string trailPath, clustersPath;
+  float clusterGap = 0.0f;
+  bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
   for (int i = 1; i < argc; i++) {
@@ -109,6 +114,12 @@ int main(int argc, char **argv) {
       deviceFrames = !strcmp(argv[++i], "device");
     } else if (!strcmp(argv[i], "--trail") && i + 1 < argc) {
       trailPath = argv[++i];
+    } else if (!strcmp(argv[i], "--clusters") && i + 1 < argc) {
+      clustersPath = argv[++i];
+    } else if (!strcmp(argv[i], "--cluster-gap") && i + 1 < argc) {
+      char *end = nullptr;
+      clusterGap = strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(clusterGap >= 0.0f) || std::isinf(clusterGap)) badArg = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -124,13 +135,20 @@ int main(int argc, char **argv) {
     } else if (argv[i][0] != '-') {
       path = argv[i];
     } else {
+      badArg = true;
+    }
+    if (badArg) {
       fprintf(stderr,
               "usage: %s [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet] "
-              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
+              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--clusters FILE [--cluster-gap G]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
               "[--checkpoint-every SECONDS] [--checkpoint-steps N]] [--final-checkpoint FILE]\n",
               argv[0]);
       return 2;
     }
+  }
+  if (!clustersPath.empty() && engine != Particlebot::Engine::Fused) {
+    fprintf(stderr, "--clusters needs the fused engine (the analysis runs on its resident state)\n");
+    return 2;
   }
   if (!cfg.loadFile(path)) fprintf(stderr, "warning: cannot open %s, running on defaults\n", path.c_str());
   for (auto &kv : sets) cfg.setParam(kv.first, kv.second);
@@ -240,6 +258,19 @@ int main(int argc, char **argv) {
     }
     if (stopAfterSteps >= 0 && stepsDone >= stopAfterSteps) _exit(9);  // (no flush, no destructors: a kill)
     sim.dumpParticlebot(0, p.nCells, fp, cfg.dump_interval, p.testing, p.light_x, p.light_y);
+    if (!clustersPath.empty() && sim.dumpDue(cfg.dump_interval)) {
+      pbClusterStats cs;
+      if (!sim.clusterStats(clusterGap, cs)) return 1;
+      FILE *cf = fopen(clustersPath.c_str(), sim.getTime() == 0.0f ? "w" : "a");
+      if (!cf) {
+        fprintf(stderr, "cannot open %s\n", clustersPath.c_str());
+        return 1;
+      }
+      if (sim.getTime() == 0.0f) fprintf(cf, "Time, Clusters, Largest, Isolated, Links, MaxDegree\n");
+      fprintf(cf, "%f, %u, %u, %u, %llu, %u\n", sim.getTime(), cs.clusters, cs.largest, cs.isolated, cs.links,
+              cs.max_degree);
+      if (fclose(cf) != 0) return 1;
+    }
     if (!framesDir.empty() && stepsDone % frameEvery == 0) {
       char name[64];
       snprintf(name, sizeof name, "/frame_%06ld.ppm", frames++);

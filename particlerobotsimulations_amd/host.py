@@ -100,6 +100,10 @@ def lib():
     L.pbHostRenderFrame.restype = C.c_int
     L.pbHostRenderStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)]
     L.pbHostRenderStats.restype = C.c_int
+    L.pbHostClusterStats.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+    L.pbHostClusterStats.restype = C.c_int
+    L.pbHostClusterLabels.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    L.pbHostClusterLabels.restype = C.c_int
     _lib = L
     return L
 
@@ -243,6 +247,24 @@ class HostSim:
         if lib().pbHostRenderStats(self._h, C.byref(n), C.byref(ms)) != 0:
             raise RuntimeError("render_stats: the device rasteriser needs the fused engine")
         return int(n.value), float(ms.value)
+
+    def clusters(self, gap=0.0):
+        """Cluster analysis of the state as it is now, on the device (pbSimClusterStats; fused engine only): a dict with
+        clusters, largest, largest_label, isolated, links, max_degree and rounds.  Bots are linked when
+        dist - (ri + rj) < gap in fp32; a label is the smallest original index of a component."""
+        from . import _capi
+        row = _capi.pbClusterStats()
+        if lib().pbHostClusterStats(self._h, float(gap), C.byref(row)) != 0:
+            raise RuntimeError("clusters: the cluster analysis needs the fused engine and a finite gap >= 0")
+        return {name: int(getattr(row, name)) for name, _ in _capi.pbClusterStats._fields_}
+
+    def cluster_labels(self, gap=0.0):
+        """(labels, degree): two uint32 arrays in original bot order (pbSimClusterLabelsOf; fused engine only)."""
+        labels, degree = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
+        if lib().pbHostClusterLabels(self._h, float(gap), labels.ctypes.data_as(C.c_void_p),
+                                     degree.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("cluster_labels: the cluster analysis needs the fused engine and a finite gap >= 0")
+        return labels, degree
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
