@@ -15,7 +15,9 @@
 #ifndef PARTICLEBOT_H
 #define PARTICLEBOT_H
 
+#include <cmath>
 #include <cstdio>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -41,6 +43,22 @@ class PbLibcRand {
   int r[34];
   int f, b; /* front / rear indices into r[3..33] */
 };
+
+/* The reference's dump-row gate (particlebot.cpp:309): true when a CSV row is due at time t.  THE one definition:
+ * class Particlebot, the ensemble's row schedule and its row count all ask it.  The fp32 expression and its operand
+ * order decide which step writes a row; do not rearrange it. */
+static inline bool pbDumpRowDue(float t, float dump_interval) {
+  return !(t - dump_interval * floorf(t / dump_interval) > 0.01f);
+}
+
+/* One row of the reference's CSV (particlebot.cpp:303-367: "Seed", the header and the time-0 row come together) from
+ * the fp32 coordinate sums of `count` bots: the text dumpParticlebot writes with testing = 0, which the ensemble's
+ * member CSVs repeat byte for byte.  testingColumns(header), when given, writes the testing = 1 columns (their names
+ * with header = true, else their values) where the reference has them.  Shared inside libparticlebot_host.so, not
+ * exported. */
+__attribute__((visibility("hidden"))) void pbWriteCsvRow(FILE *fp, float time, unsigned seed, float sumX, float sumY,
+                                                         unsigned count, float light_x, float light_y,
+                                                         const std::function<void(bool header)> &testingColumns = nullptr);
 
 class Particlebot {
  public:

@@ -74,7 +74,7 @@ void *pbEnsemblePipelineCreate(const char *cfg_path, const char *common_override
                                int nmembers, int sub_batch, int host_threads, int keep_final_states);
 /* The same with CHECKPOINTS under checkpoint_dir (created if missing): whenever a summary row is written, and
  * when a sub-batch ends, every member of the sub-batch on the device is saved exactly (state arrays, stale slot
- * layout, both generators, its rows so far; csrc/pb_capi.cpp "ensemble checkpoints"), two generations alternating
+ * layout, both generators, its rows so far; csrc/pb_ensemble_ckpt.cpp), two generations alternating
  * so that a kill in mid-write loses nothing.  resume != 0: sub-batches with a complete checkpoint in the directory
  * continue from it (finished ones only hand back their rows; their members are not even placed); the others start
  * afresh.  The resumed run's rows (and final states of the sub-batches that still ran) equal the uninterrupted

@@ -617,14 +617,14 @@ void Particlebot::setTime(float t) {
 }
 
 bool Particlebot::dumpDue(float dump_interval) const {
-  return !(time - dump_interval * floorf(time / dump_interval) > 0.01f);  // particlebot.cpp:309
+  return pbDumpRowDue(time, dump_interval);
 }
 
 int Particlebot::stepsUntilHostEvent(float deltaTime, float dump_interval, int maxSteps) const {
   // replay the fp32 clock to find the next step whose start time makes a dump row due
   float t = time + deltaTime;
   int k = 1;
-  while (k < maxSteps && (t - dump_interval * floorf(t / dump_interval) > 0.01f) && !(t > params.max_time)) {
+  while (k < maxSteps && !pbDumpRowDue(t, dump_interval) && !(t > params.max_time)) {
     t = t + deltaTime;
     k++;
   }
@@ -730,37 +730,46 @@ void Particlebot::setArray(ParticlebotArray array, const float *data, int start,
 
 // ---- CSV dump / reload ------------------------------------------------------------------------
 
-void Particlebot::dumpParticlebot(uint start, uint count, FILE *fp, float dump_interval, uint testing,
-                                  float light_x, float light_y) {
+void pbWriteCsvRow(FILE *fp, float time, unsigned seed, float sumX, float sumY, unsigned count, float light_x,
+                   float light_y, const std::function<void(bool header)> &testingColumns) {
   // particlebot.cpp:303-367, same text byte for byte
-  float sumX = 0.0f;
-  float sumY = 0.0f;
-  if (time - dump_interval * floorf(time / dump_interval) > 0.01f) return;
-  pullState(true, true, true);
   if (time == 0) {
-    fprintf(fp, "Seed, %u\n", params.seed);
+    fprintf(fp, "Seed, %u\n", seed);
     fprintf(fp, "Time,");
-    if (testing) {
-      for (uint i = start; i < start + count; i++) fprintf(fp, "Particlebot_%d_xpos, Particlebot_%d_ypos,", i, i);
-      for (uint i = start; i < start + count; i++) fprintf(fp, "Particlebot_%d_xvel, Particlebot_%d_yvel,", i, i);
-      for (uint i = start; i < start + count; i++) fprintf(fp, "Particlebot_%d_rad,", i);
-    }
+    if (testingColumns) testingColumns(true);
     fprintf(fp, "Centroid X, Centroid Y, Distance");
     fprintf(fp, "\n");
   }
   fprintf(fp, "%f,", time);
-  if (testing) {
-    for (uint i = start; i < start + count; i++) fprintf(fp, "%f, %f,", hPos[i * 2 + 0], hPos[i * 2 + 1]);
-    for (uint i = start; i < start + count; i++) fprintf(fp, "%f, %f,", hVel[i * 2 + 0], hVel[i * 2 + 1]);
-    for (uint i = start; i < start + count; i++) fprintf(fp, "%f,", hRad[i]);
-  }
+  if (testingColumns) testingColumns(false);
+  fprintf(fp, "%f, %f, %f,", sumX / (float)count, sumY / (float)count,
+          powf(powf(sumX / (float)count - light_x, 2.0) + powf(sumY / (float)count - light_y, 2.0), 0.5));
+  fprintf(fp, "\n");
+}
+
+void Particlebot::dumpParticlebot(uint start, uint count, FILE *fp, float dump_interval, uint testing,
+                                  float light_x, float light_y) {
+  float sumX = 0.0f;
+  float sumY = 0.0f;
+  if (!pbDumpRowDue(time, dump_interval)) return;
+  pullState(true, true, true);
   for (uint i = start; i < start + count; i++) {
     sumX += hPos[i * 2 + 0];
     sumY += hPos[i * 2 + 1];
   }
-  fprintf(fp, "%f, %f, %f,", sumX / (float)count, sumY / (float)count,
-          powf(powf(sumX / (float)count - light_x, 2.0) + powf(sumY / (float)count - light_y, 2.0), 0.5));
-  fprintf(fp, "\n");
+  auto testingColumns = [&](bool header) {
+    if (header) {
+      for (uint i = start; i < start + count; i++) fprintf(fp, "Particlebot_%d_xpos, Particlebot_%d_ypos,", i, i);
+      for (uint i = start; i < start + count; i++) fprintf(fp, "Particlebot_%d_xvel, Particlebot_%d_yvel,", i, i);
+      for (uint i = start; i < start + count; i++) fprintf(fp, "Particlebot_%d_rad,", i);
+    } else {
+      for (uint i = start; i < start + count; i++) fprintf(fp, "%f, %f,", hPos[i * 2 + 0], hPos[i * 2 + 1]);
+      for (uint i = start; i < start + count; i++) fprintf(fp, "%f, %f,", hVel[i * 2 + 0], hVel[i * 2 + 1]);
+      for (uint i = start; i < start + count; i++) fprintf(fp, "%f,", hRad[i]);
+    }
+  };
+  if (testing) pbWriteCsvRow(fp, time, params.seed, sumX, sumY, count, light_x, light_y, testingColumns);
+  else pbWriteCsvRow(fp, time, params.seed, sumX, sumY, count, light_x, light_y);
   printf("%f %f %f \n", time, sumX / (float)count, sumY / (float)count);
 }
 

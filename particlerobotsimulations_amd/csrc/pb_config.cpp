@@ -229,3 +229,26 @@ void PbRunConfig::derive() {
   params.worldOrigin = make_float2(-half, -half);
   repoint();
 }
+
+void PbRunConfig::applyOverrides(const char *overrides) {
+  if (!overrides) return;
+  std::string s(overrides);
+  size_t pos = 0;
+  while (pos < s.size()) {
+    size_t e1 = s.find('\n', pos);
+    if (e1 == std::string::npos) break;
+    size_t e2 = s.find('\n', e1 + 1);
+    if (e2 == std::string::npos) e2 = s.size();
+    setParam(s.substr(pos, e1 - pos), s.substr(e1 + 1, e2 - e1 - 1));
+    pos = e2 + 1;
+  }
+}
+
+bool PbRunConfig::resolve(const char *cfg_path, const char *common, const char *own) {
+  params.seed = 0;
+  if (cfg_path && !loadFile(cfg_path)) return false;
+  applyOverrides(common);
+  applyOverrides(own);
+  derive();
+  return true;
+}

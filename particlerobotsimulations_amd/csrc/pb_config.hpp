@@ -33,6 +33,13 @@ struct PbRunConfig {
   // main.cpp:932-939 (+ the extensions); call after all setParam/loadFile
   void derive();
   float wallHalf() const { return arena_half > 0.0f ? arena_half : 64.0f; }
+  // The two below are internal to libparticlebot_host.so (hidden: its exported symbols are a fixed list).
+  // overrides: "name\nvalue\nname\nvalue..." (may be NULL) applied through the same setParam as a file's lines
+  __attribute__((visibility("hidden"))) void applyOverrides(const char *overrides);
+  // A member's configuration as main() resolves it: seed 0, the file (cfg_path NULL: defaults only), the common
+  // overrides, its own, derive().  False -- nothing applied or derived -- if the file cannot be read; what that
+  // means is the caller's decision.
+  __attribute__((visibility("hidden"))) bool resolve(const char *cfg_path, const char *common, const char *own);
 
  private:
   void repoint();

@@ -38,7 +38,7 @@ def member_overrides(k, seed0=0, sweep=None, cartesian=False):
 
 class LocalEnsemble:
     """The members this rank runs, as ONE batched pbSim on the current GPU (pbEnsemble* in
-    csrc/pb_capi.cpp): placement and dead-bot draws on the host from each member's own stream, one
+    csrc/pb_ensemble.cpp): placement and dead-bot draws on the host from each member's own stream, one
     kernel launch per timestep for the whole batch, summary rows whenever a dump row is due."""
 
     def __init__(self, cfg_path, overrides_per_member, common=None, max_rows=4096):
@@ -173,7 +173,7 @@ def _pipeline_lib():
 
 class PipelinedEnsemble:
     """The members this rank runs, cut into sub-batches of `sub_batch` members: the host places sub-batch k+1 on
-    `host_threads` producer threads while the device steps sub-batch k (pbEnsemblePipeline* in csrc/pb_capi.cpp).
+    `host_threads` producer threads while the device steps sub-batch k (pbEnsemblePipeline* in csrc/pb_ensemble_pipeline.cpp).
     Placement starts in the constructor.  Rows and final states do not depend on sub_batch or host_threads.
     sub_batch 0: all members in one batch; -1: automatic (pbEnsemblePipelineAutoSubBatch: whole placement
     rounds of the producer pool that bring a sub-batch to ~3e6 bots; for large members)."""

@@ -1,4 +1,4 @@
-"""CPU tests of the ensemble pipeline's host side (csrc/pb_capi.cpp, include/particlebot_ensemble.h): the producer
+"""CPU tests of the ensemble pipeline's host side (csrc/pb_ensemble_pipeline.cpp, include/particlebot_ensemble.h): the producer
 pool builds members in order with a bounded look-ahead, the consumer takes sub-batches in order, and what a member
 looks like does not depend on the sub-batch size or on the number of producer threads (each member draws from its
 own private glibc-compatible stream; placement per /root/reference particlebot.cpp:612-748)."""

@@ -1,4 +1,4 @@
-"""GPU parity of the PIPELINED ensemble (pbEnsemblePipeline*, csrc/pb_capi.cpp): host
+"""GPU parity of the PIPELINED ensemble (pbEnsemblePipeline*, csrc/pb_ensemble_pipeline.cpp): host
 placement of sub-batch k+1 overlapped with device stepping of sub-batch k.  The summary rows and the final states
 must not depend on the sub-batch size or on the number of producer threads, and every member must equal its own
 stand-alone CPU-oracle run (rows within the centroid's double-vs-float64-mean rounding, states bit for bit).

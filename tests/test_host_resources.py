@@ -1,4 +1,4 @@
-"""The ensemble layer's view of the host (pbHostGetResources, csrc/pb_capi.cpp): a rank's producer pool is sized
+"""The ensemble layer's view of the host (pbHostGetResources, csrc/pb_host_resources.cpp): a rank's producer pool is sized
 from what the process may really use -- hardware threads, scheduler affinity, the cgroup CPU quota -- divided by
 the ranks of the node, and is pinned to the cores next to its GPU when sysfs names them.  (the
 driver's box grants 16 CPUs by quota on a 128-thread host; 127 producer threads were started.)

@@ -136,6 +136,30 @@ int main(int argc, char **argv) {
              memcmp(first, sums, sizeof sums) == 0 ? "equal" : "DIFFER");
       pbEnsemblePipelineDestroy(p);
     }
+    // the grouping's other two answers, through the take path Run shares: sharing switched off (twelve placements, the
+    // same members), and a configuration that cannot be read (no member gets a key, each fails where it is built, the
+    // consumer returns a clean -1)
+    {
+      unsigned long long sums[12];
+      int ahead = 0, run = 0, shared = 0;
+      setenv("PB_SHARE_PLACEMENTS", "0", 1);
+      void *q = pbEnsemblePipelineCreate(path, "nCells\n300\nmax_time\n1", sweep, 12, 5, 3, 0);
+      const int rc = q ? pbEnsemblePipelineDryRun(q, 0, sums, &ahead) : -1;
+      if (q) pbEnsemblePipelinePlacementCounts(q, &run, &shared);
+      pbEnsemblePipelineDestroy(q);
+      unsetenv("PB_SHARE_PLACEMENTS");
+      if (rc != 0 || run != 12 || shared != 0 || memcmp(first, sums, sizeof sums) != 0) {
+        printf("unshared sweep: rc %d, %d placed, %d copied, members %s\n", rc, run, shared,
+               memcmp(first, sums, sizeof sums) == 0 ? "equal" : "DIFFER");
+        return 1;
+      }
+      char missing[512];
+      snprintf(missing, sizeof missing, "%s/examples/no_such_file.cfg", root);
+      q = pbEnsemblePipelineCreate(missing, "nCells\n300\nmax_time\n1", sweep, 12, 5, 3, 0);
+      const int bad = q ? pbEnsemblePipelineDryRun(q, 0, sums, &ahead) : 0;
+      pbEnsemblePipelineDestroy(q);
+      if (bad != -1) { printf("unreadable configuration: dry run returned %d\n", bad); return 1; }
+    }
     void *p = pbEnsemblePipelineCreate(path, "nCells\n2000\nmax_time\n1", sweep, 12, 2, 4, 0);
     pbEnsemblePipelineDestroy(p);   // (nothing consumed: the producers are stopped where they are)
   }

@@ -14,6 +14,7 @@ SAN=address,undefined
 g++ -std=c++17 -O1 -g -fsanitize=$SAN -fno-omit-frame-pointer -ffp-contract=off -pthread \
     -I"$ROOT/include" -I"$SRC" -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
     "$ROOT/tools/sanitize/host_driver.cpp" "$SRC/particlebot.cpp" "$SRC/pb_config.cpp" "$SRC/pb_capi.cpp" \
+    "$SRC/pb_host_resources.cpp" "$SRC/pb_ensemble.cpp" "$SRC/pb_ensemble_ckpt.cpp" "$SRC/pb_ensemble_pipeline.cpp" \
     -o "$OUT/drv" -L"$ROOT/particlerobotsimulations_amd/lib" -lparticlebot_hip \
     -Wl,-rpath,"$ROOT/particlerobotsimulations_amd/lib"
 cd "$OUT"
