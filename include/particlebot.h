@@ -192,6 +192,13 @@ class Particlebot {
    * stderr.  Also false on a negative or non-finite linkGap. */
   bool clusterStats(float linkGap, pbClusterStats &out);
   bool clusterLabels(float linkGap, std::vector<unsigned> &labels, std::vector<unsigned> &degree);
+  /* The contact network of the resident state from the device (pbSimContactsOf / pbSimContactVirialOf,
+   * include/particlebot_hip.h has the definition): a CSR adjacency in ORIGINAL order (nCells + 1 offsets, one
+   * pbContactLink per directed entry: other, gap, force on the owning bot), or the per-bot virial (4 nCells doubles).
+   * Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on a negative
+   * or non-finite linkGap. */
+  bool contacts(float linkGap, std::vector<unsigned> &offsets, std::vector<pbContactLink> &links);
+  bool contactVirial(float linkGap, std::vector<double> &virial);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -392,6 +392,52 @@ int pbSimClusterLabelsOf(pbSim *sim, unsigned member, float linkGap,
                          unsigned *labels, unsigned *degree /* n each, ORIGINAL order; NULL skipped */);
 int pbSimGetClusterTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
 
+/* The contact network of one member, from the device (csrc/pb_contacts.hip): who touches whom, how deep, and with what
+ * force.  The front end is the cluster analysis' (fresh grid, sorted posrad, degrees), so everything said above holds:
+ * the link predicate, non-finite bots (no links), the |x|, |y| <= 2^20 guarantee, and what a call leaves untouched
+ * (slot layout, keys, cell lists, pbSimStats, time, RNG, render buffers).  Each call analyses the state as it is now.
+ * LINKS: bots i != j are linked exactly when pbSimClusterLabelsOf counts them in each other's degree for this linkGap.
+ * LAYOUT: a CSR adjacency in ORIGINAL bot order.  offsets[0..n], offsets[0] = 0; bot i owns entries
+ * offsets[i] .. offsets[i+1], strictly ascending in `other`; every undirected link appears twice, once under each end;
+ * offsets[i+1] - offsets[i] is the cluster analysis' degree[i].
+ * ENTRY (16 bytes): other = the neighbour's original index within the member; gap = dist - (ri + rj), the fp32 value
+ * the predicate compared (negative in contact); (fx, fy) = the force ON bot i FROM other: what the reference's
+ * collideSpheres adds into a zeroed accumulator for this ordered pair (A = bot i, B = other), with the velocities of the
+ * state as it is now, the member's own parameters, and in payload mode attraction * attractionFactor for whichever end
+ * is the payload bot (collideCell's expression and order).  It is the force of the pair law for this pair whether or not
+ * the stale 5x5 stencil of the stepping kernels currently sees the pair.  Coincident bots are linked and carry the
+ * reference's own non-finite force (0 / 0).
+ * VIRIAL (pbSimContactVirialOf): per bot four doubles sxx = sum rx fx, sxy = sum rx fy, syx = sum ry fx, syy = sum ry fy
+ * over the bot's entries in CSR order; rx = xj - xi, ry = yj - yi in fp32, widened; fx, fy the entry's fp32 values,
+ * widened; each product formed in double (exact: 24 + 24 bits), acc = acc + product from +0.0.
+ * pbSimContactsOf: *entries = the member's directed entries (2 x undirected links).  offsets (n + 1) and links may each
+ * be NULL.  links != NULL with cap < entries: PB_ERR_ARG, *entries still set, links untouched (call once with links NULL
+ * to size, then again with room).
+ * PB_ERR_ARG, before the device is touched: NULL handle; NULL entries / virial; member out of range; linkGap negative, NaN
+ * or infinite; a batch of 2^28 bots or more, or of more than 65535 members.  After the count pass: a member with 2^31
+ * entries or more (offsets are 32-bit).  PB_ERR_HIP "contact export: count and fill disagree" if the two passes ever
+ * differed (the fill never writes outside a bot's share; a torn list is not returned).
+ * Cost: one cluster analysis of the whole batch, then for the member a prefix sum, a fill and a per-bot insertion sort
+ * of each list in place: about 6 entries at contact gaps; the long lists of a large linkGap stay correct and are slow
+ * (quadratic in the list length, one lane per bot).  Read back besides the results: 8 bytes (the count) between the
+ * passes and the 8-byte disagreement flag.
+ * Scratch on top of the cluster analysis', allocated by the first export, kept, freed by pbSimDestroy: per bot of ONE
+ * member 4 bytes of offsets (n + 1), 8 of velocities, 8 of positions and 32 of virial; 8 bytes per 256 bots for the
+ * scan; 16 bytes per entry of the largest export so far (the link buffer grows when a call needs more).
+ * pbSimGetContactTimes: exports run so far and the span of the last one on the batch's stream in milliseconds, from the
+ * first launch of its front end to its last kernel (HIP events), as pbSimGetClusterTimes.  Either pointer may be NULL. */
+typedef struct pbContactLink {         /* 16 bytes */
+  unsigned other;
+  float gap;
+  float fx, fy;
+} pbContactLink;
+/* entries = directed entries of the member (2 x undirected links).  offsets (n + 1) and links may each be NULL.
+ * links != NULL with cap < entries: PB_ERR_ARG, *entries still set, links untouched (call once with links NULL to size). */
+int pbSimContactsOf(pbSim *sim, unsigned member, float linkGap, unsigned *offsets,
+                    pbContactLink *links, unsigned long long cap, unsigned long long *entries);
+int pbSimContactVirialOf(pbSim *sim, unsigned member, float linkGap, double *virial /* 4 n, ORIGINAL order */);
+int pbSimGetContactTimes(pbSim *sim, unsigned long long *exports, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

@@ -427,6 +427,36 @@ class Sim:
         _capi.check(_capi.lib().pbSimGetClusterTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetClusterTimes")
         return int(n.value), float(ms.value)
 
+    def contacts(self, gap=0.0, member=0):
+        """The contact network of one member's state as it is now, from the device (pbSimContactsOf): a dict with
+        offsets (uint32, n + 1: a CSR adjacency in original bot order, ascending `other` per bot), other (uint32, E),
+        gap (float32, E: dist - (ri + rj), negative in contact) and force (float32, E x 2: the pair law's force ON the
+        owning bot FROM other).  Every undirected link appears twice, once under each end."""
+        L = _capi.lib()
+        count = C.c_ulonglong(0)
+        _capi.check(L.pbSimContactsOf(self._h, int(member), float(gap), None, None, 0, C.byref(count)),
+                    "pbSimContactsOf")
+        offsets = np.empty(self.n + 1, np.uint32)
+        links = np.empty(int(count.value), _capi.CONTACT_LINK_DTYPE)
+        _capi.check(L.pbSimContactsOf(self._h, int(member), float(gap), _capi.np_ptr(offsets), _capi.np_ptr(links),
+                                      links.size, C.byref(count)), "pbSimContactsOf")
+        return {"offsets": offsets, "other": links["other"].copy(), "gap": links["gap"].copy(),
+                "force": np.stack([links["fx"], links["fy"]], axis=1)}
+
+    def contact_virial(self, gap=0.0, member=0):
+        """Per-bot virial of one member's contact network (pbSimContactVirialOf): float64, n x 4, the columns
+        sxx = sum rx fx, sxy = sum rx fy, syx = sum ry fx, syy = sum ry fy over the bot's entries in CSR order."""
+        out = np.empty((self.n, 4), np.float64)
+        _capi.check(_capi.lib().pbSimContactVirialOf(self._h, int(member), float(gap), _capi.np_ptr(out)),
+                    "pbSimContactVirialOf")
+        return out
+
+    def contact_times(self):
+        """(exports run so far, device milliseconds of the last one)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetContactTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetContactTimes")
+        return int(n.value), float(ms.value)
+
 
 class Ensemble(Sim):
     """A batch of independent simulations of equal size stepped by the same launches

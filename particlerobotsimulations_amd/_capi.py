@@ -88,6 +88,14 @@ class pbClusterStats(C.Structure):
                 ("links", C.c_ulonglong), ("max_degree", C.c_uint), ("rounds", C.c_uint)]
 
 
+class pbContactLink(C.Structure):
+    _fields_ = [("other", C.c_uint), ("gap", C.c_float), ("fx", C.c_float), ("fy", C.c_float)]
+
+
+# pbContactLink as a numpy record
+CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
+
+
 class pbForceForm(C.Structure):
     _fields_ = [("flat", C.c_int), ("lanes_per_bot", C.c_int), ("attraction_sums", C.c_int), ("offsets64", C.c_int)]
 
@@ -146,6 +154,9 @@ SYMBOLS = {
     "pbSimClusterStats": (_I, [_VP, _F, C.POINTER(pbClusterStats)]),
     "pbSimClusterLabelsOf": (_I, [_VP, _U, _F, _VP, _VP]),
     "pbSimGetClusterTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimContactsOf": (_I, [_VP, _U, _F, _VP, _VP, C.c_ulonglong, C.POINTER(C.c_ulonglong)]),
+    "pbSimContactVirialOf": (_I, [_VP, _U, _F, _VP]),
+    "pbSimGetContactTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1403,6 +1403,38 @@ bool Particlebot::clusterLabels(float linkGap, std::vector<unsigned> &labels, st
   return true;
 }
 
+bool Particlebot::contacts(float linkGap, std::vector<unsigned> &offsets, std::vector<pbContactLink> &links) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::contacts: the contact export needs the fused engine\n");
+    return false;
+  }
+  offsets.resize((size_t)params.nCells + 1);
+  unsigned long long entries = 0;
+  int rc = pbSimContactsOf(sim, 0, linkGap, nullptr, nullptr, 0, &entries);  // size, then fetch
+  if (rc == PB_OK) {
+    links.resize(entries);
+    rc = pbSimContactsOf(sim, 0, linkGap, offsets.data(), links.data(), links.size(), &entries);
+  }
+  if (rc != PB_OK) {
+    fprintf(stderr, "Particlebot::contacts: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::contactVirial(float linkGap, std::vector<double> &virial) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::contactVirial: the contact export needs the fused engine\n");
+    return false;
+  }
+  virial.resize(4 * (size_t)params.nCells);
+  if (pbSimContactVirialOf(sim, 0, linkGap, virial.data()) != PB_OK) {
+    fprintf(stderr, "Particlebot::contactVirial: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

@@ -287,6 +287,28 @@ int pbHostClusterLabels(void *hv, float gap, unsigned *labels, unsigned *degree)
   return 0;
 }
 
+// the contact network of the resident state (Particlebot::contacts / contactVirial; fused engine only).  *entries is
+// always set on success; offsets (nCells + 1) and links may each be NULL, links is filled only when cap holds every
+// entry (-1 otherwise: call once with links NULL to size).  -1 on the other engines or a bad gap.
+int pbHostContacts(void *hv, float gap, unsigned *offsets, pbContactLink *links, unsigned long long cap,
+                   unsigned long long *entries) {
+  std::vector<unsigned> o;
+  std::vector<pbContactLink> l;
+  if (!entries || !((HostSim *)hv)->bot->contacts(gap, o, l)) return -1;
+  *entries = l.size();
+  if (links && cap < l.size()) return -1;
+  if (offsets) memcpy(offsets, o.data(), o.size() * sizeof(unsigned));
+  if (links && !l.empty()) memcpy(links, l.data(), l.size() * sizeof(pbContactLink));
+  return 0;
+}
+
+int pbHostContactVirial(void *hv, float gap, double *virial) {
+  std::vector<double> v;
+  if (!virial || !((HostSim *)hv)->bot->contactVirial(gap, v)) return -1;
+  memcpy(virial, v.data(), v.size() * sizeof(double));
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -30,51 +30,11 @@
 // No LDS beyond the reduction's few words, no scratch memory.
 #include <string.h>
 
-#include "pb_engine.hpp"
-
-struct PbClusterScratch {
-  uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr;
-  float4 *cpr = nullptr;        // total + 2: sorted posrad, .w = global original index
-  uint32_t *start = nullptr;    // nsims * cells + 1
-  uint32_t *parent = nullptr, *degree = nullptr, *size = nullptr;  // total each, ORIGINAL order
-  uint32_t *labels = nullptr;   // n: one member's labels
-  unsigned long long *acc = nullptr;  // 4 words per member
-  pbClusterStats *rows = nullptr;     // nsims
-  uint32_t *flag = nullptr;           // [0] changed, [1] rmax bits
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  uint32_t gxLog2 = 2, gyLog2 = 2;
-  unsigned long long analyses = 0;
-  float lastMs = 0.0f;
-  unsigned rounds = 0;
-};
+#include "pb_cluster.hpp"
 
 namespace {
 
-constexpr int CT = 256;
 constexpr unsigned MAX_ROUNDS = 1024;
-
-struct ClusterGrid {
-  double invCell;
-  uint32_t gxLog2, gyLog2;
-};
-
-PB_DEV bool finitePosRad(const float4 &q) {
-  const float inf = __builtin_inff();
-  return fabsf(q.x) < inf && fabsf(q.y) < inf && fabsf(q.z) < inf;
-}
-
-// floor(v) as an int, clamped so that positions outside the guaranteed range convert without overflow
-PB_DEV int cellCoord(double v) {
-  const double f = floor(v);
-  return (int)fmin(fmax(f, -1073741824.0), 1073741824.0);
-}
-
-PB_DEV uint32_t cellX(const ClusterGrid &G, float x) {
-  return (uint32_t)cellCoord((double)x * G.invCell) & ((1u << G.gxLog2) - 1u);
-}
-PB_DEV uint32_t cellY(const ClusterGrid &G, float y) {
-  return (uint32_t)cellCoord((double)y * G.invCell) & ((1u << G.gyLog2) - 1u);
-}
 
 PB_DEV uint32_t waveMaxU32(uint32_t v) {
 #pragma unroll
@@ -396,8 +356,10 @@ int ensureScratch(pbSim *S, uint32_t numKeys) {
   return PB_OK;
 }
 
+}  // namespace
+
 // The whole pipeline; leaves parent (roots), degree and the rows on the device and the stream drained.
-int analyse(pbSim *S, float gap) {
+int pbClusterAnalyse(pbSim *S, float gap) {
   useDevice(S);
   // the grid's shape depends on the batch alone: cells = max(16, n rounded up to a power of two) per member
   uint32_t bits = 4;
@@ -428,11 +390,13 @@ int analyse(pbSim *S, float gap) {
   ClusterGrid G;
   G.invCell = 1.0 / edge;
   G.gxLog2 = gxLog2, G.gyLog2 = gyLog2;
+  C->invCell = G.invCell;
   hipLaunchKernelGGL(k_cluster_hash, gBots, b, 0, S->stream, S->pr[c], n, G, C->keys[0], C->vals[0]);
   hipError_t e;
   const int where = pbRadixSortPairs(C->keys[0], C->vals[0], C->keys[1], C->vals[1], C->hist, total,
                                      pbKeyBits(numKeys), S->stream, &e);
   if (where < 0) PB_TRY(e);
+  C->sortedIn = where;
   hipLaunchKernelGGL(k_cluster_gather, gBots, b, 0, S->stream, S->pr[c], S->orig[c], C->vals[where], n, C->cpr,
                      C->parent, C->size);
   hipLaunchKernelGGL(k_cluster_starts, dim3(cdiv(numKeys + 1u, CT)), b, 0, S->stream, C->keys[where], total, numKeys,
@@ -467,14 +431,14 @@ int analyse(pbSim *S, float gap) {
 
 // the checks both entry points share, after their own pointer checks; nothing here touches the device (checkBatch
 // reads the host-side batch object, so it needs a real handle)
-int checkGap(const char *fn, float gap) {
+int pbClusterCheckGap(const char *fn, float gap) {
   if (!(gap >= 0.0f) || !(gap < __builtin_inff())) {
     pbLastError() = std::string(fn) + ": linkGap must be finite and >= 0";
     return PB_ERR_ARG;
   }
   return PB_OK;
 }
-int checkBatch(const char *fn, const pbSim *S) {
+int pbClusterCheckBatch(const char *fn, const pbSim *S) {
   if (S->nsims > 65535u) {  // the member is a launch's grid y
     pbLastError() = std::string(fn) + ": the batch must hold at most 65535 members";
     return PB_ERR_ARG;
@@ -485,8 +449,6 @@ int checkBatch(const char *fn, const pbSim *S) {
   }
   return PB_OK;
 }
-
-}  // namespace
 
 void pbClusterFree(pbSim *S) {
   PbClusterScratch *C = S->cluster;
@@ -507,6 +469,7 @@ void pbClusterFree(pbSim *S) {
   (void)hipFree(C->flag);
   if (C->ev0) (void)hipEventDestroy(C->ev0);
   if (C->ev1) (void)hipEventDestroy(C->ev1);
+  pbContactsFree(C);
   delete C;
   S->cluster = nullptr;
 }
@@ -516,10 +479,10 @@ int pbSimClusterStats(pbSim *S, float linkGap, pbClusterStats *stats) {
     pbLastError() = "pbSimClusterStats: null handle or stats";
     return PB_ERR_ARG;
   }
-  int rc = checkGap("pbSimClusterStats", linkGap);  // needs no look at the handle; the batch check reads it
-  if (rc == PB_OK) rc = checkBatch("pbSimClusterStats", S);
+  int rc = pbClusterCheckGap("pbSimClusterStats", linkGap);  // needs no look at the handle; the batch check reads it
+  if (rc == PB_OK) rc = pbClusterCheckBatch("pbSimClusterStats", S);
   if (rc != PB_OK) return rc;
-  rc = analyse(S, linkGap);
+  rc = pbClusterAnalyse(S, linkGap);
   if (rc != PB_OK) return rc;
   PB_TRY(hipMemcpy(stats, S->cluster->rows, sizeof(pbClusterStats) * S->nsims, hipMemcpyDeviceToHost));
   return PB_OK;
@@ -534,15 +497,15 @@ int pbSimClusterLabelsOf(pbSim *S, unsigned member, float linkGap, unsigned *lab
     pbLastError() = "pbSimClusterLabelsOf: labels and degree are both null";
     return PB_ERR_ARG;
   }
-  int rc = checkGap("pbSimClusterLabelsOf", linkGap);  // needs no look at the handle; the checks below read it
+  int rc = pbClusterCheckGap("pbSimClusterLabelsOf", linkGap);  // needs no look at the handle; the checks below read it
   if (rc != PB_OK) return rc;
   if (member >= S->nsims) {
     pbLastError() = "pbSimClusterLabelsOf: member out of range";
     return PB_ERR_ARG;
   }
-  rc = checkBatch("pbSimClusterLabelsOf", S);
+  rc = pbClusterCheckBatch("pbSimClusterLabelsOf", S);
   if (rc != PB_OK) return rc;
-  rc = analyse(S, linkGap);
+  rc = pbClusterAnalyse(S, linkGap);
   if (rc != PB_OK) return rc;
   PbClusterScratch *C = S->cluster;
   const uint32_t n = S->n, base = member * n;

@@ -8,6 +8,7 @@
 //   pb_display.hip   the reference's display kernels (colours, centroid trail)
 //   pb_render.hip    the frame rasteriser behind pbSimRenderOf
 //   pb_cluster.hip   cluster analysis: connected components of the contact graph (pbSimClusterStats)
+//   pb_contacts.hip  the contact network of one member: links, gaps, pair forces, virial (pbSimContactsOf)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 #pragma once
@@ -39,7 +40,7 @@ constexpr int TILE = PB_TILE;
 
 static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
-struct PbClusterScratch;  // pb_cluster.hip
+struct PbClusterScratch;  // pb_cluster.hpp
 
 struct pbSim {
   std::vector<PbDevParams> hP;  // one parameter block per simulation

@@ -2,7 +2,7 @@
 //
 //   particlebot_run [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet]
 //                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]]
-//                   [--trail FILE] [--clusters FILE [--cluster-gap G]]
+//                   [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -31,6 +31,9 @@
 // --clusters FILE appends, at every dump time (the gate dumpParticlebot uses), one row of the device's cluster analysis
 // (Particlebot::clusterStats): `Time, Clusters, Largest, Isolated, Links, MaxDegree`, the header once at time 0;
 // --cluster-gap G (default 0, finite and >= 0) is the analysis' linkGap.  Without --clusters nothing is analysed.
+// --contacts FILE writes the contact network of the FINAL state once, when the run ends (Particlebot::contacts):
+// the header `I, J, Gap, Fx, Fy`, then one row per directed entry in CSR order (I ascending, J ascending within I),
+// floats as %.9g so that fp32 round-trips; --contact-gap G (default 0, finite and >= 0) is its linkGap.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -87,8 +90,8 @@ int main(int argc, char **argv) {
   std::string framesDir, resumePath, ckptPath, finalCkptPath;
   int frameSize = 800;
   bool referenceFrames = false, deviceFrames = false;
-  std::string trailPath, clustersPath;
-  float clusterGap = 0.0f;
+  std::string trailPath, clustersPath, contactsPath;
+  float clusterGap = 0.0f, contactGap = 0.0f;
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -120,6 +123,12 @@ int main(int argc, char **argv) {
       char *end = nullptr;
       clusterGap = strtof(argv[++i], &end);
       if (end == argv[i] || *end || !(clusterGap >= 0.0f) || std::isinf(clusterGap)) badArg = true;
+    } else if (!strcmp(argv[i], "--contacts") && i + 1 < argc) {
+      contactsPath = argv[++i];
+    } else if (!strcmp(argv[i], "--contact-gap") && i + 1 < argc) {
+      char *end = nullptr;
+      contactGap = strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(contactGap >= 0.0f) || std::isinf(contactGap)) badArg = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -140,7 +149,7 @@ int main(int argc, char **argv) {
     if (badArg) {
       fprintf(stderr,
               "usage: %s [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet] "
-              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--clusters FILE [--cluster-gap G]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
+              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
               "[--checkpoint-every SECONDS] [--checkpoint-steps N]] [--final-checkpoint FILE]\n",
               argv[0]);
       return 2;
@@ -148,6 +157,10 @@ int main(int argc, char **argv) {
   }
   if (!clustersPath.empty() && engine != Particlebot::Engine::Fused) {
     fprintf(stderr, "--clusters needs the fused engine (the analysis runs on its resident state)\n");
+    return 2;
+  }
+  if (!contactsPath.empty() && engine != Particlebot::Engine::Fused) {
+    fprintf(stderr, "--contacts needs the fused engine (the export runs on its resident state)\n");
     return 2;
   }
   if (!cfg.loadFile(path)) fprintf(stderr, "warning: cannot open %s, running on defaults\n", path.c_str());
@@ -317,6 +330,22 @@ int main(int argc, char **argv) {
       if (!std::isnan(times[k]))  // a slot that holds a record
         fprintf(tf, "%zu,%.9g,%.9g,%.17g\n", k, (double)times[k], (double)xy[2 * k], (double)xy[2 * k + 1] - 2000.0);
     if (fclose(tf) != 0) return 1;
+  }
+  if (!contactsPath.empty()) {
+    std::vector<unsigned> offsets;
+    std::vector<pbContactLink> links;
+    if (!sim.contacts(contactGap, offsets, links)) return 1;
+    FILE *cf = fopen(contactsPath.c_str(), "w");
+    if (!cf) {
+      fprintf(stderr, "cannot open %s\n", contactsPath.c_str());
+      return 1;
+    }
+    fprintf(cf, "I, J, Gap, Fx, Fy\n");
+    for (size_t i = 0; i + 1 < offsets.size(); i++)
+      for (unsigned k = offsets[i]; k < offsets[i + 1]; k++)
+        fprintf(cf, "%zu, %u, %.9g, %.9g, %.9g\n", i, links[k].other, (double)links[k].gap, (double)links[k].fx,
+                (double)links[k].fy);
+    if (fclose(cf) != 0) return 1;
   }
   return 0;
 }

@@ -104,6 +104,11 @@ def lib():
     L.pbHostClusterStats.restype = C.c_int
     L.pbHostClusterLabels.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.pbHostClusterLabels.restype = C.c_int
+    L.pbHostContacts.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_ulonglong,
+                                 C.POINTER(C.c_ulonglong)]
+    L.pbHostContacts.restype = C.c_int
+    L.pbHostContactVirial.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+    L.pbHostContactVirial.restype = C.c_int
     _lib = L
     return L
 
@@ -265,6 +270,31 @@ class HostSim:
                                      degree.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError("cluster_labels: the cluster analysis needs the fused engine and a finite gap >= 0")
         return labels, degree
+
+    def contacts(self, gap=0.0):
+        """The contact network of the state as it is now, from the device (pbSimContactsOf; fused engine only): a dict
+        with offsets (uint32, n + 1: CSR in original bot order, ascending `other`), other (uint32, E), gap (float32, E)
+        and force (float32, E x 2: the pair law's force on the owning bot from other)."""
+        from . import _capi
+        count = C.c_ulonglong(0)
+        bad = "contacts: the contact export needs the fused engine and a finite gap >= 0"
+        if lib().pbHostContacts(self._h, float(gap), None, None, 0, C.byref(count)) != 0:
+            raise RuntimeError(bad)
+        offsets = np.empty(self.n + 1, np.uint32)
+        links = np.empty(int(count.value), _capi.CONTACT_LINK_DTYPE)
+        if lib().pbHostContacts(self._h, float(gap), offsets.ctypes.data_as(C.c_void_p),
+                                links.ctypes.data_as(C.c_void_p), links.size, C.byref(count)) != 0:
+            raise RuntimeError(bad)
+        return {"offsets": offsets, "other": links["other"].copy(), "gap": links["gap"].copy(),
+                "force": np.stack([links["fx"], links["fy"]], axis=1)}
+
+    def contact_virial(self, gap=0.0):
+        """Per-bot virial of the contact network (pbSimContactVirialOf; fused engine only): float64, n x 4, the columns
+        sxx, sxy, syx, syy summed over each bot's entries in CSR order."""
+        out = np.empty((self.n, 4), np.float64)
+        if lib().pbHostContactVirial(self._h, float(gap), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("contact_virial: the contact export needs the fused engine and a finite gap >= 0")
+        return out
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
