@@ -528,6 +528,10 @@ int pbSelfTestHoldThreshold(float c, unsigned long long *checked, unsigned long 
 /* The root of the both-sums throughput form's attraction magnitude (one v_rsq_f32, one Newton step, no clamp) against
  * sqrtf for every float of [2^-96, FLT_MAX) -- a superset of what that form can hand it: 1 879 048 191 values. */
 int pbSelfTestMagnitudeRoot(unsigned long long *checked, unsigned long long *mismatches);
+/* The root the both-sums throughput form takes of every pair term's squared magnitude, contact terms included: for
+ * every one of the 2^32 float bit patterns, either the form's wave-uniform guard sends it to sqrtf, or the clamped
+ * one-Newton-step root equals sqrtf bit for bit (two NaNs count as equal).  `checked` is 2^32. */
+int pbSelfTestTermRoot(unsigned long long *checked, unsigned long long *mismatches);
 int pbSelfTestPairGeometry(unsigned first_slice, unsigned slices, unsigned long long *checked,
                            unsigned long long *mismatches);
 /* The same for pbDiv2Fast (the division of the attraction term by gap^2): every denominator mantissa of

@@ -40,6 +40,14 @@ def self_test_magnitude_root():
     return {"checked": int(checked.value), "mismatches": int(bad.value)}
 
 
+def self_test_term_root():
+    """pbSelfTestTermRoot: the both-sums form's in-trip root of a pair term's squared magnitude (contact terms
+    included) on the GPU for all 2^32 bit patterns: guarded to sqrtf, or bit-equal to sqrtf."""
+    checked, bad = C.c_ulonglong(), C.c_ulonglong()
+    _capi.check(_capi.lib().pbSelfTestTermRoot(C.byref(checked), C.byref(bad)), "pbSelfTestTermRoot")
+    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+
+
 def self_test_pair_geometry(first_slice=0, slices=64):
     """pbSelfTestPairGeometry: pbDistUnitFast against sqrtf and IEEE division on EVERY (d2, numerator)
     mantissa pair of `slices` of the 64 slices of d2 in [1, 4) (all 64: 2^47 pairs, ~90 s of one MI355X)."""

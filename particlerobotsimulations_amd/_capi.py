@@ -200,6 +200,7 @@ SYMBOLS = {
     "pbSelfTest": (_I, [C.c_ulonglong] + [C.POINTER(C.c_ulonglong)] * 4),
     "pbSelfTestHoldThreshold": (_I, [C.c_float, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "pbSelfTestMagnitudeRoot": (_I, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
+    "pbSelfTestTermRoot": (_I, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "pbSelfTestPairGeometry": (_I, [_U, _U, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "pbSelfTestDivision": (_I, [_U, _U, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
 }

@@ -414,6 +414,27 @@ PB_DEV void pbDistUnitFast(float rx, float ry, float d2, float &dist, float &nx,
 // non-negative inputs for which pbSqrtFast may differ from sqrtf
 PB_DEV bool pbTinyNonzero(float x) { return __float_as_uint(x) - 1u < 0x0F800000u - 1u; }
 
+// Root of a pair term's squared magnitude m2 = tx^2 + ty^2 when the term may be a CONTACT (the both-sums lane sweep
+// roots every lane's term in the trip it is evaluated in, pbPairEvalXY<FAST, true, true>).  A contact term is not
+// bounded like an attraction term: m2 is 0 for overlapping bots at rest with no spring, may be denormal, overflows to
+// +inf under a huge damping term and is NaN when a velocity is.  The clamped pbRootNewton equals sqrtf on
+// 0 and [2^-96, FLT_MAX); pbTermRootOutside is true for every other bit pattern (an unsigned range test: negative
+// values and NaNs of either sign land above the range too), and the caller sends a wave with such a contact lane to
+// sqrtf (wave-uniform, balloted over the contact lanes; nothing of it is in a trip without a near lane).  pbSelfTestTermRoot checks the pair on all 2^32 bit patterns.
+PB_DEV bool pbTermRootOutside(float m2) {
+  const uint32_t b = __float_as_uint(m2);
+  return b != 0u && b - 0x0F800000u >= 0x7F7FFFFFu - 0x0F800000u;
+}
+// the same predicate as a wave mask (two ballots and a scalar AND: no bool is materialised in a vector register)
+PB_DEV unsigned long long pbTermRootOutsideMask(float m2) {
+  const uint32_t b = __float_as_uint(m2);
+  return __builtin_amdgcn_ballot_w64(b != 0u) & __builtin_amdgcn_ballot_w64(b - 0x0F800000u >= 0x7F7FFFFFu - 0x0F800000u);
+}
+PB_DEV float pbTermRootInside(float m2) {
+  float s;
+  return pbRootNewton(m2, s);
+}
+
 // A lane may use the fast forms for all its pairs when neither of its coordinates is within 2^-20
 // of zero: then every nonzero coordinate difference is >= 2^-44 (it is a multiple of the ulp of a
 // number >= 2^-20), which keeps every numerator in pbDiv2Fast's domain (see DESIGN.md "Fast exact
@@ -584,10 +605,11 @@ PB_DEV float pbAttractionMagnitude(float tx, float ty) {
   return FAST ? pbRootNewtonPositive(m2) : sqrtf(m2);
 }
 
-template <bool FAST, bool WANT_A = false, class VelFetch, class PushRep>
+template <bool FAST, bool WANT_A = false, bool WANT_R = false, class VelFetch, class PushRep>
 PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay, float avx, float avy, float ra,
                              float bx, float by, float rb, VelFetch velB, float attraction, float slope,
-                             PushRep pushRep, float *fa = nullptr) {
+                             PushRep pushRep, float *fa = nullptr, PbForce *acc = nullptr) {
+  static_assert(WANT_A || !WANT_R, "the in-trip contact root rides on the attraction magnitude's");
   const float near1 = 0.0009f, near2 = 0.0019f, fmin_attr = 2.5f;
   const float rx = bx - ax, ry = by - ay;
   const float d2 = pbDot(rx, ry, rx, ry);
@@ -613,7 +635,8 @@ PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay,
   // gap < 0: for finite floats dist < reach <=> dist - reach < 0, and NaN fails both).  Only a trip in which
   // some live lane passes it works out which lanes are which.
   const unsigned long long mNear = __builtin_amdgcn_ballot_w64(live) & __builtin_amdgcn_ballot_w64(gap < near2);
-  if (mNear != 0ull) {
+  // (WANT_R: the near arm is laid out of line, so that the common trip falls through to its own root below)
+  if (WANT_R ? __builtin_expect(mNear != 0ull, 0) : mNear != 0ull) {
     const bool contact = dist < reach;
     const unsigned long long mContact = __builtin_amdgcn_ballot_w64(contact);
     if ((mNear & ~mContact) != 0ull) {
@@ -634,12 +657,43 @@ PB_DEV PbPairXY pbPairEvalXY(const PbContactK &P, bool live, float ax, float ay,
       cy += P.damping * rvy;
       cx += P.shear * tvx;
       cy += P.shear * tvy;
-      pushRep(contact && live, pbDot(cx, cy, cx, cy));
+      if (!WANT_R) pushRep(contact && live, pbDot(cx, cy, cx, cy));
       tx = contact ? cx : tx;
       ty = contact ? cy : ty;
     }
+    if (WANT_R) {
+      // one root serves all 64 lanes: a contact lane's selected (tx, ty) is (cx, cy), so m2 is the value pushRep
+      // would have parked.  Accumulated by select, never by adding +0: *fr starts as 0.0f * absR[s] and a bot
+      // without contacts must keep exactly that (-0, NaN).
+      const float m2 = pbDot(tx, ty, tx, ty);
+      float mag;
+      if (FAST) {
+        mag = pbTermRootInside(m2);
+        if (__builtin_expect((pbTermRootOutsideMask(m2) & mNear & mContact) != 0ull, 0)) {
+          asm volatile("; rare: a contact magnitude outside the one-step root's domain, full sqrtf" ::: "memory");
+          mag = sqrtf(m2);
+        }
+      } else {
+        mag = sqrtf(m2);
+      }
+      const bool rep = contact && live, att = !contact && live;
+      acc->fa = att ? acc->fa + mag : acc->fa;
+      acc->fr = rep ? acc->fr + mag : acc->fr;
+    }
   }
-  if (WANT_A) {
+  if (WANT_R) {
+    // The arm for a trip with no live lane near, so none in contact: every live lane's term is an attraction term.
+    // Written as a second `if` on a copy of the mask the compiler cannot see through, not as the `else` of the first:
+    // the pair loop's exits are divergent, so the loop is structurized, and an if/else inside it comes out as two
+    // blocks joined by a flow block whose merge copies land in this -- the common -- path.
+    unsigned long long mFar = mNear;
+    asm("" : "+s"(mFar));
+    if (mFar == 0ull) {
+      const float mag = pbAttractionMagnitude<FAST>(tx, ty);
+      if (live) acc->fa += mag;
+    }
+  }
+  if (WANT_A && !WANT_R) {
     const float mag = pbAttractionMagnitude<FAST>(tx, ty);
     if (live && !(dist < reach)) *fa += mag;
   }

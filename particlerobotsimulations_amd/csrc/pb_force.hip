@@ -113,18 +113,24 @@ __global__ __launch_bounds__(TILE, ((L == 1 && FLAT && !BIG && !PAYLOAD) ? PB_TA
   using OffT = typename std::conditional<BIG, uint64_t, uint32_t>::type;
   static_assert(ASUM || FLAT, "the dead-sum form exists for the branch-free sweeps only");
   // (L > 1: magnitudes are rooted inside the contact block; the both-sums throughput form has the list since round 5)
+  // ... until the both-sums form began to root a contact's term in its trip, with the attraction magnitudes: no list
+  constexpr bool TRIPROOT = L == 1 && FLAT && ASUM;
+  // The array keeps its size for both: tests/test_code_objects.py pins the headline forms' LDS footprint at
+  // (PB_REP_CAP + 1) * TILE floats = 9 KB per workgroup (8 workgroups per CU: 72 of 160 KB, no limit on occupancy).  With
+  // TRIPROOT nothing reads or writes it; the empty asm below only keeps it in the code object's allocation.
   constexpr bool REPLIST = L == 1 && FLAT;
   __shared__ float repLds[REPLIST ? (PB_REP_CAP + 1) * TILE : 1];
   float *const repCol = &repLds[REPLIST ? threadIdx.x : 0];
+  if (TRIPROOT) asm volatile("" ::"v"(repCol));
   auto sweep = [&](auto lanes) __attribute__((always_inline)) {
     constexpr int LS = decltype(lanes)::value;
     PbSegCache none;  // (a per-step launch keeps no list)
     if (FLAT && fastOk && __all(pbLaneFastMathOk(me.x, me.y)))
-      pbSweep<PAYLOAD, FLAT, true, LS, false, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, none,
-                                                          repCol);
+      pbSweep<PAYLOAD, FLAT, true, LS, false, OffT, ASUM, TILE, TRIPROOT>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1,
+                                                                          F, none, repCol);
     else
-      pbSweep<PAYLOAD, FLAT, false, LS, false, OffT, ASUM>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1, F, none,
-                                                           repCol);
+      pbSweep<PAYLOAD, FLAT, false, LS, false, OffT, ASUM, TILE, TRIPROOT>(P, prIn, velIn, cellS, 0u, s, sub, me, v, att1,
+                                                                           F, none, repCol);
   };
   if (TAILABLE && tailWg)
     sweep(std::integral_constant<int, TAILABLE ? PB_TAIL_LANES : L>{});

@@ -49,6 +49,23 @@ __global__ __launch_bounds__(256) void k_selftest_magroot(unsigned long long *__
   if (seen) atomicAdd(checked, (unsigned long long)seen);
 }
 
+// the root the both-sums lane sweep takes of EVERY term's squared magnitude, contact terms included (pbTermRootInside +
+// the wave-uniform guard pbTermRootOutside, pb_device.hpp): for every one of the 2^32 bit patterns either the guard sends
+// it to sqrtf or the clamped one-step root equals sqrtf bit for bit (two NaNs count as equal, whatever their payloads)
+__global__ __launch_bounds__(256) void k_selftest_termroot(unsigned long long *__restrict__ mismatches,
+                                                           unsigned long long *__restrict__ checked) {
+  const uint32_t base = (blockIdx.x * 256u + threadIdx.x) * 16u;
+  uint32_t bad = 0;
+  for (uint32_t k = 0; k < 16u; k++) {
+    const float x = __uint_as_float(base + k);
+    if (pbTermRootOutside(x)) continue;
+    const float fast = pbTermRootInside(x), ref = sqrtf(x);
+    if (__float_as_uint(fast) != __float_as_uint(ref) && !(fast != fast && ref != ref)) bad++;
+  }
+  if (bad) atomicAdd(mismatches, (unsigned long long)bad);
+  if (threadIdx.x == 0) atomicAdd(checked, 256ull * 16ull);
+}
+
 // the static-friction hold (pb_device.hpp PbDevParams::holdV2 / holdF2): `sqrtf(x) < c` against `x < T(c)` for EVERY
 // non-negative float bit pattern x (infinities and NaNs included), T computed on the host (pbSqrtThreshold)
 __global__ __launch_bounds__(256) void k_selftest_hold(float c, float T, unsigned long long *__restrict__ mismatches,
@@ -246,6 +263,20 @@ int pbSelfTestMagnitudeRoot(unsigned long long *checked, unsigned long long *mis
   PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_selftest_magroot, dim3(1u << 19), dim3(256), 0, 0, d + 1, d + 0);  // 2^31 bit patterns
+  PB_TRY(hipGetLastError());
+  unsigned long long h[2];
+  PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
+  PB_TRY(hipFree(d));
+  if (checked) *checked = h[0];
+  if (mismatches) *mismatches = h[1];
+  return PB_OK;
+}
+
+int pbSelfTestTermRoot(unsigned long long *checked, unsigned long long *mismatches) {
+  unsigned long long *d = nullptr;
+  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(k_selftest_termroot, dim3(1u << 20), dim3(256), 0, 0, d + 1, d + 0);  // 2^32 bit patterns
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));

@@ -238,7 +238,7 @@ __device__ __forceinline__ void pbSweepGroup(const PbDevParams &P, PR prIn, VL v
 
 // ---- lane sweep: one bot per lane, one neighbour per trip (the throughput form) ----
 // The contact magnitudes go through the lane's LDS column repCol (PbRepList, columns REPSTRIDE floats apart).
-template <bool PAYLOAD, bool FAST, class OffT, bool ASUM, int REPSTRIDE, class PR, class VL>
+template <bool PAYLOAD, bool FAST, class OffT, bool ASUM, int REPSTRIDE, bool TRIPROOT, class PR, class VL>
 __device__ __forceinline__ void pbSweepLane(const PbDevParams &P, PR prIn, VL velIn,
                                             const uint32_t *__restrict__ cellS, uint32_t base, uint32_t s,
                                             const float4 &me, const float2 &v, float att1, PbForce &F, float *repCol) {
@@ -273,9 +273,10 @@ __device__ __forceinline__ void pbSweepLane(const PbDevParams &P, PR prIn, VL ve
   const OffT selfOff = (OffT)s * 16u;
   const OffT selfOff16 = selfOff + 16u;
   auto at = [&](OffT off) __attribute__((always_inline)) { return *(const float4 *)(prBytes + off); };
-  // contact magnitudes wait in the lane's LDS column (both forms since round 5)
+  // contact magnitudes wait in the lane's LDS column; not with TRIPROOT, where the trip roots them itself
+  static_assert(ASUM || !TRIPROOT, "the dead-sum form has no per-trip root to share");
   PbRepList<FAST, PB_REP_CAP, REPSTRIDE> rep;
-  rep.init(repCol);
+  if (!TRIPROOT) rep.init(repCol);
   // (64-bit address arithmetic with a constant displacement: the displacement becomes the load's
   //  immediate offset, so the look-ahead loads need no address instructions of their own)
   auto atI = [&](OffT off, int imm) __attribute__((always_inline)) {
@@ -289,8 +290,12 @@ __device__ __forceinline__ void pbSweepLane(const PbDevParams &P, PR prIn, VL ve
     const float K = PAYLOAD ? pbBandSlope(A) : slope0;
     // the dead-sum trip; with ASUM also the magnitude of the lane's attraction term (Sum|F_attr| in list order, as
     // absforce_a += length(tempforce), impl.cuh:580-592)
-    const PbPairXY t = pbPairEvalXY<FAST, ASUM>(CK, true, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A, K,
-                                                [&](bool mine, float m2) { rep.push(mine, m2, F.fr); }, &F.fa);
+    const PbPairXY t = pbPairEvalXY<FAST, ASUM, TRIPROOT>(
+        CK, true, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, velOf, A, K,
+        [&](bool mine, float m2) {
+          if (!TRIPROOT) rep.push(mine, m2, F.fr);
+        },
+        &F.fa, &F);
     F.fx += t.tx;
     F.fy += t.ty;
   };
@@ -342,7 +347,7 @@ __device__ __forceinline__ void pbSweepLane(const PbDevParams &P, PR prIn, VL ve
       }
     }
   }
-  rep.flush(F.fr);
+  if (!TRIPROOT) rep.flush(F.fr);
 }
 
 // ---- reference-shaped sweep: pbPair (divergent branches, force variant 0) over the ten ranges ----
@@ -390,14 +395,14 @@ __device__ __forceinline__ void pbSweepRef(const PbDevParams &P, PR prIn, VL vel
 // CACHED / cache: the group sweep's list cache (resident kernel); a per-step caller passes false and a dummy.
 // OffT: the lane sweep's byte offsets, 32-bit (batches below 2^28 bots) or 64-bit.
 template <bool PAYLOAD, bool FLAT, bool FAST, int L, bool CACHED, class OffT = uint32_t, bool ASUM = true,
-          int REPSTRIDE = TILE, class PR, class VL>
+          int REPSTRIDE = TILE, bool TRIPROOT = false, class PR, class VL>
 __device__ __forceinline__ void pbSweep(const PbDevParams &P, PR prIn, VL velIn, const uint32_t *__restrict__ cellS,
                                         uint32_t base, uint32_t s, uint32_t sub, const float4 &me, const float2 &v,
                                         float att1, PbForce &F, PbSegCache &cache, float *repCol = nullptr) {
   if constexpr (L > 1)
     pbSweepGroup<PAYLOAD, FAST, L, CACHED, ASUM>(P, prIn, velIn, cellS, base, s, sub, me, v, att1, F, cache);
   else if constexpr (FLAT)
-    pbSweepLane<PAYLOAD, FAST, OffT, ASUM, REPSTRIDE>(P, prIn, velIn, cellS, base, s, me, v, att1, F, repCol);
+    pbSweepLane<PAYLOAD, FAST, OffT, ASUM, REPSTRIDE, TRIPROOT>(P, prIn, velIn, cellS, base, s, me, v, att1, F, repCol);
   else
     pbSweepRef<PAYLOAD>(P, prIn, velIn, cellS, base, s, me, v, att1, F);
 }
