@@ -199,6 +199,14 @@ class Particlebot {
    * or non-finite linkGap. */
   bool contacts(float linkGap, std::vector<unsigned> &offsets, std::vector<pbContactLink> &links);
   bool contactVirial(float linkGap, std::vector<double> &virial);
+  /* Structure analysis of the resident state on the device (pbSimRadialCounts / pbSimStructureStats / pbSimHexaticOf,
+   * include/particlebot_hip.h has the definitions): the radial pair counts (`bins` entries, ordered pairs), the
+   * member's hexatic row, or every bot's psi6 (2 nCells doubles) and neighbour count in ORIGINAL order.  Fused engine
+   * only: Legacy and HostOnly instances return false with a message on stderr.  Also false on a bad rMax, bins or
+   * linkGap. */
+  bool radialCounts(float rMax, unsigned bins, std::vector<unsigned long long> &counts);
+  bool structureStats(float linkGap, pbStructureStats &out);
+  bool hexatic(float linkGap, std::vector<double> &psi6, std::vector<unsigned> &neighbours);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

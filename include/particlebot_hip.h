@@ -438,6 +438,57 @@ int pbSimContactsOf(pbSim *sim, unsigned member, float linkGap, unsigned *offset
 int pbSimContactVirialOf(pbSim *sim, unsigned member, float linkGap, double *virial /* 4 n, ORIGINAL order */);
 int pbSimGetContactTimes(pbSim *sim, unsigned long long *exports, float *last_device_ms);
 
+/* Structure analysis on the device (csrc/pb_structure.hip): radial pair counts (the raw material of g(r)) and the
+ * hexatic bond-orientational order psi6 of every member, from the resident state.  The bots are filed afresh exactly as
+ * for the cluster analysis, so what is said there holds: nodes are all nCells bots of a member (dead bots and the
+ * payload bot included), a bot with a non-finite position or radius takes part in nothing and does not fault, results
+ * are guaranteed for |x|, |y| <= 2^20, and a call only reads the simulation (slot layout, keys, cell lists, pbSimStats,
+ * time, RNG and render buffers stay untouched).  Each call analyses the state as it is now.
+ * All arithmetic is fp32 without FMA contraction, sqrtf and / correctly rounded.  For bots i != j of the same member
+ *     rx = xj - xi;  ry = yj - yi;  dist = sqrtf(rx*rx + ry*ry);
+ * Every number that leaves the device is an integer, or derived from integers by exactly rounded operations: results do
+ * not depend on the order in which the device adds, and can be compared exactly.
+ * RADIAL PAIR COUNTS (pbSimRadialCounts): scale = (float)bins / rMax, one fp32 division on the host.  The ORDERED pair
+ * (i, j) falls into bin b = (int)(dist * scale), truncated, and is counted iff b < bins -- decided as
+ * fl(dist * scale) < (float)bins, the same decision for every finite product; when scale overflows to infinity (rMax
+ * below bins / FLT_MAX) nothing is counted.  Coincident bots land in bin 0.  counts holds nsims * bins entries, one
+ * histogram per member, over ordered pairs: every count is even.  Normalising to g(r) needs a number density, which for
+ * a free blob is the caller's choice and stays out of this interface.
+ * HEXATIC ORDER: bots i and j are BONDED exactly when the cluster analysis links them for the same linkGap,
+ * (dist - (ri + rj)) < linkGap, so a bot's neighbour count equals pbSimClusterLabelsOf's degree.  A bond with dist > 0
+ * contributes
+ *     ux = rx / dist;  uy = ry / dist;
+ *     c2 = ux*ux - uy*uy;   s2 = (ux*uy) + (ux*uy);
+ *     c4 = c2*c2 - s2*s2;   s4 = (c2*s2) + (c2*s2);
+ *     c6 = c4*c2 - s4*s2;   s6 = s4*c2 + c4*s2;                        (every product rounded before the add or subtract)
+ *     qre = (long long)rint(c6 * 1073741824.0f);   qim = (long long)rint(s6 * 1073741824.0f);
+ * (the scaling by 2^30 is exact, the conversion rounds to nearest even); a bond with dist == 0 counts as a neighbour and
+ * contributes 0.  Per bot: Sre = sum qre, Sim = sum qim over its bonds, 64-bit integers in units of 2^-30, and
+ * psi6[2i] = ((double)Sre / 1073741824.0) / (double)neighbours, psi6[2i+1] likewise from Sim; (0, 0) for a bot without
+ * neighbours.  Per member one pbStructureStats row; its sums (and a bot's) are exact while the member has fewer than
+ * 2^32 directed bonds.
+ * pbSimStructureStats: one row per member.  pbSimHexaticOf: one member's psi6 (2 n doubles) and neighbour counts (n), in
+ * ORIGINAL order; either pointer may be NULL, not both.  pbSimGetStructureTimes: analyses run so far (radial and
+ * hexatic calls alike) and the span of the last one on the batch's stream in milliseconds, from the first launch of its
+ * front end to its last kernel (HIP events), as pbSimGetClusterTimes.  Either pointer may be NULL.
+ * PB_ERR_ARG, before the device is touched: NULL handle; NULL counts / rows; psi6 and neighbours both NULL; member out of
+ * range; rMax not finite or not > 0; bins outside 1 ... PB_RADIAL_MAX_BINS; linkGap negative, NaN or infinite; a batch
+ * of 2^28 bots or more, or of more than 65535 members.
+ * Scratch on top of the cluster analysis', allocated on first use, kept, freed by pbSimDestroy: 8 bytes per bin and
+ * member of the largest histogram asked for so far; for the hexatic calls 20 bytes per bot of the batch, 56 per member
+ * and 16 per bot of one member. */
+#define PB_RADIAL_MAX_BINS 4096u
+typedef struct pbStructureStats {      /* 56 bytes */
+  unsigned long long bonds;            /* directed bonds = sum of neighbours */
+  long long psi6_re, psi6_im;          /* sum of qre, qim over all directed bonds, units of 2^-30 */
+  unsigned coordination[8];            /* bots with 0..6 neighbours; [7]: 7 or more */
+} pbStructureStats;
+int pbSimRadialCounts(pbSim *sim, float rMax, unsigned bins, unsigned long long *counts /* nsims * bins */);
+int pbSimStructureStats(pbSim *sim, float linkGap, pbStructureStats *rows /* nsims entries */);
+int pbSimHexaticOf(pbSim *sim, unsigned member, float linkGap, double *psi6 /* 2 n, ORIGINAL order */,
+                   unsigned *neighbours /* n */);
+int pbSimGetStructureTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

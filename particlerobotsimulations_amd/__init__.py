@@ -14,7 +14,20 @@ import numpy as np
 from . import _capi
 from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
-__all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test"]
+__all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
+           "radial_distribution"]
+
+
+def radial_distribution(counts, r_max, density, n):
+    """g(r) from the radial pair counts of radial_counts(r_max, bins) (pure Python, float64): counts[..., b] ordered
+    pairs among n bots fell into the annulus [b, b + 1) * r_max / bins, an ideal gas of number density `density` (the
+    caller's choice: a free blob has no box) would put n * density * annulus area there.  Returns (r, g): the bin
+    centres and counts / (n * density * pi * (r_hi^2 - r_lo^2)), shaped like counts."""
+    counts = np.asarray(counts, np.float64)
+    bins = counts.shape[-1]
+    edges = np.arange(bins + 1, dtype=np.float64) * (float(r_max) / bins)
+    area = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
+    return 0.5 * (edges[1:] + edges[:-1]), counts / (float(n) * float(density) * area)
 
 
 def self_test(div_samples=1 << 32):
@@ -463,6 +476,39 @@ class Sim:
         """(exports run so far, device milliseconds of the last one)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetContactTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetContactTimes")
+        return int(n.value), float(ms.value)
+
+    def radial_counts(self, r_max, bins, member=None):
+        """Radial pair counts of every member's state as it is now, on the device (pbSimRadialCounts): uint64,
+        (nsims, bins), or (bins,) for one member.  The ordered pair (i, j) is in bin int(dist * (float32(bins) / r_max))
+        in fp32; every count is even.  radial_distribution() turns them into g(r)."""
+        nsims = int(getattr(self, "nsims", 1))
+        out = np.zeros((nsims, int(bins)), np.uint64)
+        _capi.check(_capi.lib().pbSimRadialCounts(self._h, float(r_max), int(bins), _capi.np_ptr(out)),
+                    "pbSimRadialCounts")
+        return out if member is None else out[int(member)]
+
+    def structure(self, gap=0.0):
+        """Hexatic order of every member's state as it is now, on the device (pbSimStructureStats): a list of dicts, one
+        per member: bonds (directed), psi6_re / psi6_im (sums in units of 2^-30), coordination (bots with 0..6 and 7 or
+        more neighbours) and psi6, the complex mean over the bonds.  Bonds are the cluster analysis' links for `gap`."""
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbStructureStats * nsims)()
+        _capi.check(_capi.lib().pbSimStructureStats(self._h, float(gap), rows), "pbSimStructureStats")
+        return [_capi.structure_row(r) for r in rows]
+
+    def hexatic(self, gap=0.0, member=0):
+        """(psi6, neighbours) of one member: complex128[n] and uint32[n] in original bot order (pbSimHexaticOf); psi6 of
+        a bot is the mean of e^(6 i theta) over its bonds, 0 without neighbours."""
+        psi, nb = np.empty(self.n, np.complex128), np.empty(self.n, np.uint32)
+        _capi.check(_capi.lib().pbSimHexaticOf(self._h, int(member), float(gap), _capi.np_ptr(psi), _capi.np_ptr(nb)),
+                    "pbSimHexaticOf")
+        return psi, nb
+
+    def structure_times(self):
+        """(structure analyses run so far, device milliseconds of the last one)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetStructureTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetStructureTimes")
         return int(n.value), float(ms.value)
 
 

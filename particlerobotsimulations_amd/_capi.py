@@ -92,6 +92,20 @@ class pbContactLink(C.Structure):
     _fields_ = [("other", C.c_uint), ("gap", C.c_float), ("fx", C.c_float), ("fy", C.c_float)]
 
 
+class pbStructureStats(C.Structure):
+    _fields_ = [("bonds", C.c_ulonglong), ("psi6_re", C.c_longlong), ("psi6_im", C.c_longlong),
+                ("coordination", C.c_uint * 8)]
+
+
+def structure_row(r):
+    """A pbStructureStats row as a dict: the integers as they are, and psi6 = (psi6_re + i psi6_im) / 2^30 / bonds as a
+    Python complex (0 without bonds): the mean of e^(6 i theta) over the member's directed bonds."""
+    bonds, re, im = int(r.bonds), int(r.psi6_re), int(r.psi6_im)
+    psi = complex(re / 1073741824.0, im / 1073741824.0) / bonds if bonds else 0j
+    return {"bonds": bonds, "psi6_re": re, "psi6_im": im, "coordination": [int(c) for c in r.coordination],
+            "psi6": psi}
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -157,6 +171,10 @@ SYMBOLS = {
     "pbSimContactsOf": (_I, [_VP, _U, _F, _VP, _VP, C.c_ulonglong, C.POINTER(C.c_ulonglong)]),
     "pbSimContactVirialOf": (_I, [_VP, _U, _F, _VP]),
     "pbSimGetContactTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimRadialCounts": (_I, [_VP, _F, _U, _VP]),
+    "pbSimStructureStats": (_I, [_VP, _F, C.POINTER(pbStructureStats)]),
+    "pbSimHexaticOf": (_I, [_VP, _U, _F, _VP, _VP]),
+    "pbSimGetStructureTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -293,6 +293,7 @@ struct PlacementGrid {
 // sequence 16807*x mod (2^31-1), then discards 310 outputs; random_r returns (r[f] += r[b]) >> 1.
 void PbLibcRand::reseed(unsigned seed) {
   if (seed == 0) seed = 1;
+  r[0] = r[1] = r[2] = 0;  // glibc's header words, unused here, but part of getState: a checkpoint must not hold garbage
   int *state = r + 3;
   state[0] = (int)seed;
   long word = (int)seed;
@@ -1430,6 +1431,45 @@ bool Particlebot::contactVirial(float linkGap, std::vector<double> &virial) {
   virial.resize(4 * (size_t)params.nCells);
   if (pbSimContactVirialOf(sim, 0, linkGap, virial.data()) != PB_OK) {
     fprintf(stderr, "Particlebot::contactVirial: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::radialCounts(float rMax, unsigned bins, std::vector<unsigned long long> &counts) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::radialCounts: the structure analysis needs the fused engine\n");
+    return false;
+  }
+  counts.assign(bins >= 1 && bins <= PB_RADIAL_MAX_BINS ? bins : 1, 0ull);
+  if (pbSimRadialCounts(sim, rMax, bins, counts.data()) != PB_OK) {
+    fprintf(stderr, "Particlebot::radialCounts: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::structureStats(float linkGap, pbStructureStats &out) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::structureStats: the structure analysis needs the fused engine\n");
+    return false;
+  }
+  if (pbSimStructureStats(sim, linkGap, &out) != PB_OK) {
+    fprintf(stderr, "Particlebot::structureStats: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::hexatic(float linkGap, std::vector<double> &psi6, std::vector<unsigned> &neighbours) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::hexatic: the structure analysis needs the fused engine\n");
+    return false;
+  }
+  psi6.resize(2 * (size_t)params.nCells);
+  neighbours.resize(params.nCells);
+  if (pbSimHexaticOf(sim, 0, linkGap, psi6.data(), neighbours.data()) != PB_OK) {
+    fprintf(stderr, "Particlebot::hexatic: %s\n", pbGetLastErrorString());
     return false;
   }
   return true;

@@ -309,6 +309,29 @@ int pbHostContactVirial(void *hv, float gap, double *virial) {
   return 0;
 }
 
+// structure analysis of the resident state (Particlebot::radialCounts / structureStats / hexatic; fused engine only):
+// `bins` counts, the 56-byte pbStructureStats row, or psi6 (2 nCells doubles) and neighbour counts (nCells), original
+// order, either of which may be NULL.  -1 on the other engines or a bad rMax, bins or gap.
+int pbHostRadialCounts(void *hv, float rMax, unsigned bins, unsigned long long *counts) {
+  std::vector<unsigned long long> c;
+  if (!counts || !((HostSim *)hv)->bot->radialCounts(rMax, bins, c)) return -1;
+  memcpy(counts, c.data(), c.size() * sizeof(unsigned long long));
+  return 0;
+}
+
+int pbHostStructureStats(void *hv, float gap, pbStructureStats *out) {
+  return out && ((HostSim *)hv)->bot->structureStats(gap, *out) ? 0 : -1;
+}
+
+int pbHostHexatic(void *hv, float gap, double *psi6, unsigned *neighbours) {
+  std::vector<double> p;
+  std::vector<unsigned> nb;
+  if (!((HostSim *)hv)->bot->hexatic(gap, p, nb)) return -1;
+  if (psi6) memcpy(psi6, p.data(), p.size() * sizeof(double));
+  if (neighbours) memcpy(neighbours, nb.data(), nb.size() * sizeof(unsigned));
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -2,7 +2,9 @@
 // engine's resident state (pbSimClusterStats / pbSimClusterLabelsOf, include/particlebot_hip.h has the definition).
 //
 // The engine's own cell lists are stale between re-sorts, so the analysis files the bots afresh, in scratch of its
-// own, and leaves the simulation untouched.  For the whole batch at once:
+// own, and leaves the simulation untouched.  The filing front end (pbClusterFile: the first five kernels below) takes
+// the cell edge and also serves the contact export and the structure analysis (pb_contacts.hip, pb_structure.hip).
+// For the whole batch at once:
 //   k_cluster_rmax      the largest finite radius (bit-pattern max, one atomic per workgroup), 4 bytes read back
 //   k_cluster_hash      key = member * cells + cell of a wrapped power-of-two grid whose edge is a little more than
 //                       2 rmax + linkGap; the cell index is floor(x / edge) in fp64, whose rounding (2^-24 of a cell for
@@ -358,8 +360,8 @@ int ensureScratch(pbSim *S, uint32_t numKeys) {
 
 }  // namespace
 
-// The whole pipeline; leaves parent (roots), degree and the rows on the device and the stream drained.
-int pbClusterAnalyse(pbSim *S, float gap) {
+// The filing front end (pb_cluster.hpp): everything up to, but not including, the link pass.
+int pbClusterFile(pbSim *S, double reach, double perRmax) {
   useDevice(S);
   // the grid's shape depends on the batch alone: cells = max(16, n rounded up to a power of two) per member
   uint32_t bits = 4;
@@ -372,20 +374,21 @@ int pbClusterAnalyse(pbSim *S, float gap) {
   C->gxLog2 = gxLog2, C->gyLog2 = gyLog2;
   const uint32_t n = S->n, total = S->total;
   const int c = S->cur;
-  const dim3 b(CT), gBots(cdiv(n, CT), S->nsims), gAll(cdiv(total, CT));
+  const dim3 b(CT), gBots(cdiv(n, CT), S->nsims);
   PB_TRY(hipEventRecord(C->ev0, S->stream));
   PB_TRY(hipMemsetAsync(C->flag, 0, sizeof(uint32_t) * 2, S->stream));
-  PB_TRY(hipMemsetAsync(C->acc, 0, sizeof(unsigned long long) * 4 * S->nsims, S->stream));
-  const uint32_t rmaxBlocks = cdiv(total, CT) < 1024u ? cdiv(total, CT) : 1024u;
-  hipLaunchKernelGGL(k_cluster_rmax, dim3(rmaxBlocks), b, 0, S->stream, S->pr[c], total, C->flag + 1);
-  uint32_t rmaxBits = 0;
-  PB_TRY(hipMemcpyAsync(&rmaxBits, C->flag + 1, sizeof rmaxBits, hipMemcpyDeviceToHost, S->stream));
-  PB_TRY(hipStreamSynchronize(S->stream));
-  float rmax;
-  memcpy(&rmax, &rmaxBits, sizeof rmax);
-  // edge >= 2 rmax + gap, rounded up by 2^-10 (fp32 rounding of the predicate and fp64 rounding of the cell index are
-  // below 2^-20 of it); never below 2^-8, so that |x| <= 2^20 gives a cell index below 2^28
-  double edge = (2.0 * (double)rmax + (double)gap) * (1.0 + 1.0 / 1024.0);
+  float rmax = 0.0f;
+  if (perRmax != 0.0) {
+    const uint32_t rmaxBlocks = cdiv(total, CT) < 1024u ? cdiv(total, CT) : 1024u;
+    hipLaunchKernelGGL(k_cluster_rmax, dim3(rmaxBlocks), b, 0, S->stream, S->pr[c], total, C->flag + 1);
+    uint32_t rmaxBits = 0;
+    PB_TRY(hipMemcpyAsync(&rmaxBits, C->flag + 1, sizeof rmaxBits, hipMemcpyDeviceToHost, S->stream));
+    PB_TRY(hipStreamSynchronize(S->stream));
+    memcpy(&rmax, &rmaxBits, sizeof rmax);
+  }
+  // the cluster analysis' edge >= 2 rmax + gap, rounded up by 2^-10 (fp32 rounding of the predicate and fp64 rounding of
+  // the cell index are below 2^-20 of it); never below 2^-8, so that |x| <= 2^20 gives a cell index below 2^28
+  double edge = (perRmax * (double)rmax + reach) * (1.0 + 1.0 / 1024.0);
   if (!(edge > 1.0 / 256.0)) edge = 1.0 / 256.0;
   ClusterGrid G;
   G.invCell = 1.0 / edge;
@@ -401,6 +404,19 @@ int pbClusterAnalyse(pbSim *S, float gap) {
                      C->parent, C->size);
   hipLaunchKernelGGL(k_cluster_starts, dim3(cdiv(numKeys + 1u, CT)), b, 0, S->stream, C->keys[where], total, numKeys,
                      C->start);
+  PB_TRY(hipGetLastError());
+  return PB_OK;
+}
+
+// The whole pipeline; leaves parent (roots), degree and the rows on the device and the stream drained.
+int pbClusterAnalyse(pbSim *S, float gap) {
+  const int rc = pbClusterFile(S, (double)gap, 2.0);
+  if (rc != PB_OK) return rc;
+  PbClusterScratch *C = S->cluster;
+  const ClusterGrid G = gridOf(C);
+  const uint32_t n = S->n, total = S->total;
+  const dim3 b(CT), gBots(cdiv(n, CT), S->nsims), gAll(cdiv(total, CT));
+  PB_TRY(hipMemsetAsync(C->acc, 0, sizeof(unsigned long long) * 4 * S->nsims, S->stream));
   hipLaunchKernelGGL(k_cluster_links, gBots, b, 0, S->stream, C->cpr, C->start, n, G, gap, C->parent, C->degree);
   PB_TRY(hipGetLastError());
   unsigned rounds = 1;  // the hook round
@@ -470,6 +486,7 @@ void pbClusterFree(pbSim *S) {
   if (C->ev0) (void)hipEventDestroy(C->ev0);
   if (C->ev1) (void)hipEventDestroy(C->ev1);
   pbContactsFree(C);
+  pbStructureFree(C);
   delete C;
   S->cluster = nullptr;
 }

@@ -1,5 +1,5 @@
-// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip: the scratch object, the fresh grid and the front
-// end that files the bots and counts every bot's links (rmax, hash, sort, gather, cell starts, link pass).
+// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip and pb_structure.hip: the scratch object, the fresh
+// grid, the front end that files the bots (rmax, hash, sort, gather, cell starts) and the link pass on top of it.
 #pragma once
 
 #include "pb_engine.hpp"
@@ -32,6 +32,16 @@ struct PbClusterScratch {
   hipEvent_t cEv1 = nullptr;                 // the export's last launch (its first is the front end's ev0)
   unsigned long long exports = 0;
   float lastExportMs = 0.0f;
+  // structure analysis (pb_structure.hip): allocated by the first call that needs each, counts grown with bins
+  unsigned long long *sCounts = nullptr;     // nsims * sCountsBins: the radial histograms
+  unsigned sCountsBins = 0;
+  long long *sRe = nullptr, *sIm = nullptr;  // total each, ORIGINAL order: per-bot sums of qre, qim
+  uint32_t *sNb = nullptr;                   // total, ORIGINAL order: neighbours
+  pbStructureStats *sRows = nullptr;         // nsims
+  double *sPsi = nullptr;                    // 2 n: one member's psi6
+  hipEvent_t sEv1 = nullptr;                 // the analysis' last launch (its first is the front end's ev0)
+  unsigned long long structures = 0;
+  float lastStructureMs = 0.0f;
 };
 
 namespace {
@@ -42,6 +52,14 @@ struct ClusterGrid {
   double invCell;
   uint32_t gxLog2, gyLog2;
 };
+
+// the grid the last pbClusterFile left in the scratch object
+inline ClusterGrid gridOf(const PbClusterScratch *C) {
+  ClusterGrid G;
+  G.invCell = C->invCell;
+  G.gxLog2 = C->gxLog2, G.gyLog2 = C->gyLog2;
+  return G;
+}
 
 PB_DEV bool finitePosRad(const float4 &q) {
   const float inf = __builtin_inff();
@@ -63,8 +81,14 @@ PB_DEV uint32_t cellY(const ClusterGrid &G, float y) {
 
 }  // namespace
 
-// The whole cluster pipeline; leaves cpr, the cell starts, parent (roots), degree and the rows on the device and the
-// stream drained.                                                                                       pb_cluster.hip
+// The filing front end: records ev0, files every bot of the batch on a wrapped power-of-two grid of edge
+// (perRmax * rmax + reach) (1 + 2^-10), never below 2^-8 (rmax: the largest finite radius, reduced on the device and
+// read back only when perRmax != 0), and leaves cpr (sorted posrad, .w = global original index), the cell starts,
+// vals[sortedIn], parent[o] = o and size[o] = 0 on the device, the grid (invCell, gxLog2, gyLog2) in the scratch object.
+// Allocates the scratch on first use.  Launches are queued on the batch's stream, not waited for.       pb_cluster.hip
+int pbClusterFile(pbSim *S, double reach, double perRmax);
+// The whole cluster pipeline (the front end with reach = gap, perRmax = 2); leaves cpr, the cell starts, parent (roots),
+// degree and the rows on the device and the stream drained.                                             pb_cluster.hip
 int pbClusterAnalyse(pbSim *S, float gap);
 // the argument checks the entry points share; nothing here touches the device (the batch check reads the host-side
 // batch object, so it needs a real handle)
@@ -72,3 +96,5 @@ int pbClusterCheckGap(const char *fn, float gap);
 int pbClusterCheckBatch(const char *fn, const pbSim *S);
 // frees the contact export's buffers, if any (pbClusterFree)                                           pb_contacts.hip
 void pbContactsFree(PbClusterScratch *C);
+// frees the structure analysis' buffers, if any (pbClusterFree)                                       pb_structure.hip
+void pbStructureFree(PbClusterScratch *C);

@@ -3,6 +3,7 @@
 //   particlebot_run [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet]
 //                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]]
 //                   [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]]
+//                   [--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -34,6 +35,12 @@
 // --contacts FILE writes the contact network of the FINAL state once, when the run ends (Particlebot::contacts):
 // the header `I, J, Gap, Fx, Fy`, then one row per directed entry in CSR order (I ascending, J ascending within I),
 // floats as %.9g so that fp32 round-trips; --contact-gap G (default 0, finite and >= 0) is its linkGap.
+// --structure FILE appends, at every dump time, one row of the device's hexatic analysis (Particlebot::structureStats):
+// `Time, Bonds, Psi6Re, Psi6Im, C0, C1, C2, C3, C4, C5, C6, C7`, the header once at time 0, the sums as the integers
+// they are (units of 2^-30); --structure-gap G (default 0, finite and >= 0) is its linkGap.
+// --rdf FILE writes the radial pair counts of the FINAL state once, when the run ends (Particlebot::radialCounts): the
+// header `RLo, RHi, Count`, then one row per bin, the edges b * R / B and (b + 1) * R / B in double as %.9g;
+// --rdf-rmax R (default 10 * max_radius, finite and > 0) and --rdf-bins B (default 200, 1 ... 4096).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -92,6 +99,9 @@ int main(int argc, char **argv) {
   bool referenceFrames = false, deviceFrames = false;
   std::string trailPath, clustersPath, contactsPath;
   float clusterGap = 0.0f, contactGap = 0.0f;
+  std::string structurePath, rdfPath;
+  float structureGap = 0.0f, rdfRmax = 0.0f;  // rdfRmax 0: 10 * max_radius, once the configuration is loaded
+  long rdfBins = 200;
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -129,6 +139,22 @@ int main(int argc, char **argv) {
       char *end = nullptr;
       contactGap = strtof(argv[++i], &end);
       if (end == argv[i] || *end || !(contactGap >= 0.0f) || std::isinf(contactGap)) badArg = true;
+    } else if (!strcmp(argv[i], "--structure") && i + 1 < argc) {
+      structurePath = argv[++i];
+    } else if (!strcmp(argv[i], "--structure-gap") && i + 1 < argc) {
+      char *end = nullptr;
+      structureGap = strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(structureGap >= 0.0f) || std::isinf(structureGap)) badArg = true;
+    } else if (!strcmp(argv[i], "--rdf") && i + 1 < argc) {
+      rdfPath = argv[++i];
+    } else if (!strcmp(argv[i], "--rdf-rmax") && i + 1 < argc) {
+      char *end = nullptr;
+      rdfRmax = strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(rdfRmax > 0.0f) || std::isinf(rdfRmax)) badArg = true;
+    } else if (!strcmp(argv[i], "--rdf-bins") && i + 1 < argc) {
+      char *end = nullptr;
+      rdfBins = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || rdfBins < 1 || rdfBins > (long)PB_RADIAL_MAX_BINS) badArg = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -149,7 +175,8 @@ int main(int argc, char **argv) {
     if (badArg) {
       fprintf(stderr,
               "usage: %s [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet] "
-              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
+              "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]] "
+              "[--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
               "[--checkpoint-every SECONDS] [--checkpoint-steps N]] [--final-checkpoint FILE]\n",
               argv[0]);
       return 2;
@@ -161,6 +188,14 @@ int main(int argc, char **argv) {
   }
   if (!contactsPath.empty() && engine != Particlebot::Engine::Fused) {
     fprintf(stderr, "--contacts needs the fused engine (the export runs on its resident state)\n");
+    return 2;
+  }
+  if (!structurePath.empty() && engine != Particlebot::Engine::Fused) {
+    fprintf(stderr, "--structure needs the fused engine (the analysis runs on its resident state)\n");
+    return 2;
+  }
+  if (!rdfPath.empty() && engine != Particlebot::Engine::Fused) {
+    fprintf(stderr, "--rdf needs the fused engine (the analysis runs on its resident state)\n");
     return 2;
   }
   if (!cfg.loadFile(path)) fprintf(stderr, "warning: cannot open %s, running on defaults\n", path.c_str());
@@ -284,6 +319,20 @@ int main(int argc, char **argv) {
               cs.max_degree);
       if (fclose(cf) != 0) return 1;
     }
+    if (!structurePath.empty() && sim.dumpDue(cfg.dump_interval)) {
+      pbStructureStats ss;
+      if (!sim.structureStats(structureGap, ss)) return 1;
+      FILE *sf = fopen(structurePath.c_str(), sim.getTime() == 0.0f ? "w" : "a");
+      if (!sf) {
+        fprintf(stderr, "cannot open %s\n", structurePath.c_str());
+        return 1;
+      }
+      if (sim.getTime() == 0.0f) fprintf(sf, "Time, Bonds, Psi6Re, Psi6Im, C0, C1, C2, C3, C4, C5, C6, C7\n");
+      fprintf(sf, "%f, %llu, %lld, %lld", sim.getTime(), ss.bonds, ss.psi6_re, ss.psi6_im);
+      for (int k = 0; k < 8; k++) fprintf(sf, ", %u", ss.coordination[k]);
+      fprintf(sf, "\n");
+      if (fclose(sf) != 0) return 1;
+    }
     if (!framesDir.empty() && stepsDone % frameEvery == 0) {
       char name[64];
       snprintf(name, sizeof name, "/frame_%06ld.ppm", frames++);
@@ -346,6 +395,21 @@ int main(int argc, char **argv) {
         fprintf(cf, "%zu, %u, %.9g, %.9g, %.9g\n", i, links[k].other, (double)links[k].gap, (double)links[k].fx,
                 (double)links[k].fy);
     if (fclose(cf) != 0) return 1;
+  }
+  if (!rdfPath.empty()) {
+    const float rmax = rdfRmax > 0.0f ? rdfRmax : 10.0f * p.max_radius;
+    std::vector<unsigned long long> counts;
+    if (!sim.radialCounts(rmax, (unsigned)rdfBins, counts)) return 1;
+    FILE *rf = fopen(rdfPath.c_str(), "w");
+    if (!rf) {
+      fprintf(stderr, "cannot open %s\n", rdfPath.c_str());
+      return 1;
+    }
+    fprintf(rf, "RLo, RHi, Count\n");
+    for (size_t b = 0; b < counts.size(); b++)
+      fprintf(rf, "%.9g, %.9g, %llu\n", (double)b * (double)rmax / (double)rdfBins,
+              (double)(b + 1) * (double)rmax / (double)rdfBins, counts[b]);
+    if (fclose(rf) != 0) return 1;
   }
   return 0;
 }

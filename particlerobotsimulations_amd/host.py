@@ -109,6 +109,12 @@ def lib():
     L.pbHostContacts.restype = C.c_int
     L.pbHostContactVirial.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
     L.pbHostContactVirial.restype = C.c_int
+    L.pbHostRadialCounts.argtypes = [C.c_void_p, C.c_float, C.c_uint, C.c_void_p]
+    L.pbHostRadialCounts.restype = C.c_int
+    L.pbHostStructureStats.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
+    L.pbHostStructureStats.restype = C.c_int
+    L.pbHostHexatic.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
+    L.pbHostHexatic.restype = C.c_int
     _lib = L
     return L
 
@@ -295,6 +301,33 @@ class HostSim:
         if lib().pbHostContactVirial(self._h, float(gap), out.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError("contact_virial: the contact export needs the fused engine and a finite gap >= 0")
         return out
+
+    def radial_counts(self, r_max, bins, member=None):
+        """Radial pair counts of the state as it is now, on the device (pbSimRadialCounts; fused engine only): uint64,
+        (1, bins), or (bins,) with member=0.  Ordered pairs, bin int(dist * (float32(bins) / r_max)) in fp32."""
+        out = np.zeros((1, int(bins)), np.uint64)
+        if lib().pbHostRadialCounts(self._h, float(r_max), int(bins), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("radial_counts: the structure analysis needs the fused engine, a finite r_max > 0 and "
+                               "1 ... 4096 bins")
+        return out if member is None else out[int(member)]
+
+    def structure(self, gap=0.0):
+        """Hexatic order of the state as it is now, on the device (pbSimStructureStats; fused engine only): a list with
+        one dict: bonds, psi6_re, psi6_im, coordination and psi6, the complex mean over the directed bonds."""
+        from . import _capi
+        row = _capi.pbStructureStats()
+        if lib().pbHostStructureStats(self._h, float(gap), C.byref(row)) != 0:
+            raise RuntimeError("structure: the structure analysis needs the fused engine and a finite gap >= 0")
+        return [_capi.structure_row(row)]
+
+    def hexatic(self, gap=0.0, member=0):
+        """(psi6, neighbours): complex128[n] and uint32[n] in original bot order (pbSimHexaticOf; fused engine only)."""
+        if int(member) != 0:
+            raise IndexError(member)
+        psi, nb = np.empty(self.n, np.complex128), np.empty(self.n, np.uint32)
+        if lib().pbHostHexatic(self._h, float(gap), psi.ctypes.data_as(C.c_void_p), nb.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("hexatic: the structure analysis needs the fused engine and a finite gap >= 0")
+        return psi, nb
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
