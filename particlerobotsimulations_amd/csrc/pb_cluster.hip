@@ -14,8 +14,9 @@
 //   k_cluster_gather    posrad in sorted order with the GLOBAL original index in .w; a bot with a non-finite position
 //                       or radius becomes a NaN position, which no comparison links; parent[o] = o, size[o] = 0
 //   k_cluster_starts    dense cell starts: a lower bound in the sorted keys per cell (as k_cell_scan)
-//   k_cluster_links     the hot path: one bot per lane over the nine cells (three slot ranges away from the x-wrap),
-//                       the next neighbour's posrad in flight; evaluates the predicate, counts the degree and hooks
+//   k_cluster_links     the hot path: one bot per lane over the nine cells (pbWalkNine, pb_cluster.hpp: three slot
+//                       ranges away from the x-wrap, the next neighbour's posrad in flight); evaluates the link rule
+//                       (pbWhenLinked, pb_cluster.hpp), counts the degree and hooks
 //                       every link once (from its larger index) into a union-find forest over original indices:
 //                       find with path halving, hook the larger root under the smaller with atomicCAS.  Roots only
 //                       ever get smaller, so a component's root is its smallest original index: the label.
@@ -28,7 +29,6 @@
 //                       degree sum and maximum; wave shuffles, LDS, one set of atomics per workgroup
 //   k_cluster_rows      one 32-byte pbClusterStats row per member
 //   k_cluster_labels    one member's labels, local indices (pbSimClusterLabelsOf)
-// The predicate is the pair law's geometry in fp32 without contraction: dist = sqrtf(rx*rx + ry*ry), correctly rounded.
 // No LDS beyond the reduction's few words, no scratch memory.
 #include <string.h>
 
@@ -37,38 +37,6 @@
 namespace {
 
 constexpr unsigned MAX_ROUNDS = 1024;
-
-PB_DEV uint32_t waveMaxU32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-PB_DEV uint32_t waveSumU32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
-  return v;
-}
-PB_DEV unsigned long long shflXor64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-PB_DEV unsigned long long waveMaxU64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = shflXor64(v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-PB_DEV unsigned long long waveSumU64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += shflXor64(v, m);
-  return v;
-}
 
 __global__ __launch_bounds__(CT) void k_cluster_rmax(const float4 *__restrict__ pr, uint32_t total,
                                                      uint32_t *__restrict__ out) {
@@ -176,54 +144,13 @@ __global__ __launch_bounds__(CT) void k_cluster_links(const float4 *__restrict__
   const uint32_t o = __float_as_uint(me.w);
   uint32_t deg = 0u;
   if (me.x == me.x) {  // a bot with a non-finite position or radius has no links
-    const uint32_t GX = 1u << G.gxLog2;
-    const uint32_t cx = cellX(G, me.x), cy = cellY(G, me.y);
-    const uint32_t *__restrict__ cells = start + ((size_t)blockIdx.y << (G.gxLog2 + G.gyLog2));
-    // three ranges of three cells; at the x-wrap nine ranges of one (wrapped dimensions >= 4: nine distinct cells)
-    const bool wrap = cx == 0u || cx == GX - 1u;
-    const uint32_t step = wrap ? 1u : 3u;
-    auto bounds = [&](uint32_t si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
-      lo = hi = t;
-      if (si < 9u) {
-        const uint32_t rowI = si / 3u, col = si - 3u * rowI;
-        const uint32_t row = ((cy + rowI - 1u) & ((1u << G.gyLog2) - 1u)) << G.gxLog2;
-        const uint32_t c0 = (cx + col - 1u) & (GX - 1u);
-        lo = cells[row + c0];
-        hi = cells[row + c0 + step];
-      }
-    };
-    // Cheap rejection in front of the correctly rounded root.  A linked pair has fl(dist - R) < gap with R = ri + rj,
-    // hence dist - R <= gap exactly (rounding is monotone), dist <= fl(R + gap) (1 + 2^-23) and
-    // fl(rx*rx + ry*ry) <= fl(R + gap)^2 (1 + 2^-20): the bound below (1e-4 relative, 1e-30 absolute for the
-    // subnormal cases) admits every such pair; whatever else it admits the exact predicate decides.
-    uint32_t loA, hiA, loB, hiB;
-    bounds(0u, loA, hiA);
-    bounds(step, loB, hiB);
-    float4 qA = cpr[loA];
-#pragma unroll 1
-    for (uint32_t si = 0u; si < 9u; si += step) {
-      const uint32_t lo = loA, hi = hiA;
-      float4 q = qA;
-      loA = loB, hiA = hiB;
-      qA = cpr[loA];                      // first posrad of the next range
-      bounds(si + 2u * step, loB, hiB);   // bounds of the range after the next
-      for (uint32_t j = lo; j < hi; j++) {
-        const float4 qn = cpr[j + 1u];  // one slot past a range is inside the array (spare elements)
-        const float rx = q.x - me.x, ry = q.y - me.y;
-        const float d2 = rx * rx + ry * ry;
-        const float R = me.z + q.z;
-        const float s = R + gap;
-        if (j != t && d2 <= s * s * 1.0001f + 1e-30f) {
-          const float dist = sqrtf(d2);
-          if ((dist - R) < gap) {
-            deg++;
-            const uint32_t oj = __float_as_uint(q.w);
-            if (oj < o) hook(parent, o, oj);
-          }
-        }
-        q = qn;
-      }
-    }
+    pbWalkNine<false>(cpr, start, blockIdx.y, G, t, me, [&](uint32_t j, const float4 &q, float, float, float d2) {
+      pbWhenLinked(t, me, j, q, d2, gap, [&](float, float) {
+        deg++;
+        const uint32_t oj = __float_as_uint(q.w);
+        if (oj < o) hook(parent, o, oj);
+      });
+    });
   }
   degree[o] = deg;
 }
@@ -354,7 +281,6 @@ int ensureScratch(pbSim *S, uint32_t numKeys) {
   PB_TRY(hipMalloc((void **)&C->rows, sizeof(pbClusterStats) * S->nsims));
   PB_TRY(hipMalloc((void **)&C->flag, sizeof(uint32_t) * 2));
   PB_TRY(hipEventCreate(&C->ev0));
-  PB_TRY(hipEventCreate(&C->ev1));
   return PB_OK;
 }
 
@@ -437,33 +363,20 @@ int pbClusterAnalyse(pbSim *S, float gap) {
   hipLaunchKernelGGL(k_cluster_reduce, gBots, b, 0, S->stream, C->parent, C->size, C->degree, n, C->acc);
   hipLaunchKernelGGL(k_cluster_rows, dim3(cdiv(S->nsims, CT)), b, 0, S->stream, C->acc, S->nsims, rounds, C->rows);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(C->ev1, S->stream));
-  PB_TRY(hipStreamSynchronize(S->stream));
-  PB_TRY(hipEventElapsedTime(&C->lastMs, C->ev0, C->ev1));
   C->rounds = rounds;
-  C->analyses++;
-  return PB_OK;
+  return pbClockStop(S, C->clusterClock);
 }
 
-// the checks both entry points share, after their own pointer checks; nothing here touches the device (checkBatch
-// reads the host-side batch object, so it needs a real handle)
-int pbClusterCheckGap(const char *fn, float gap) {
-  if (!(gap >= 0.0f) || !(gap < __builtin_inff())) {
-    pbLastError() = std::string(fn) + ": linkGap must be finite and >= 0";
-    return PB_ERR_ARG;
-  }
-  return PB_OK;
-}
-int pbClusterCheckBatch(const char *fn, const pbSim *S) {
-  if (S->nsims > 65535u) {  // the member is a launch's grid y
-    pbLastError() = std::string(fn) + ": the batch must hold at most 65535 members";
-    return PB_ERR_ARG;
-  }
-  if (S->total >= (1u << 28)) {
-    pbLastError() = std::string(fn) + ": the batch must hold fewer than 2^28 bots";
-    return PB_ERR_ARG;
-  }
-  return PB_OK;
+// The argument checks of the entry points (pb_cluster.hpp).
+int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const unsigned *member) {
+  const char *what = nullptr;
+  if (gap && (!(*gap >= 0.0f) || !(*gap < __builtin_inff()))) what = ": linkGap must be finite and >= 0";
+  else if (member && *member >= S->nsims) what = ": member out of range";
+  else if (S->nsims > 65535u) what = ": the batch must hold at most 65535 members";  // the member is a launch's grid y
+  else if (S->total >= (1u << 28)) what = ": the batch must hold fewer than 2^28 bots";
+  if (!what) return PB_OK;
+  pbLastError() = std::string(fn) + what;
+  return PB_ERR_ARG;
 }
 
 void pbClusterFree(pbSim *S) {
@@ -484,7 +397,7 @@ void pbClusterFree(pbSim *S) {
   (void)hipFree(C->rows);
   (void)hipFree(C->flag);
   if (C->ev0) (void)hipEventDestroy(C->ev0);
-  if (C->ev1) (void)hipEventDestroy(C->ev1);
+  pbClockFree(C->clusterClock);
   pbContactsFree(C);
   pbStructureFree(C);
   delete C;
@@ -496,8 +409,7 @@ int pbSimClusterStats(pbSim *S, float linkGap, pbClusterStats *stats) {
     pbLastError() = "pbSimClusterStats: null handle or stats";
     return PB_ERR_ARG;
   }
-  int rc = pbClusterCheckGap("pbSimClusterStats", linkGap);  // needs no look at the handle; the batch check reads it
-  if (rc == PB_OK) rc = pbClusterCheckBatch("pbSimClusterStats", S);
+  int rc = pbClusterCheckArgs("pbSimClusterStats", S, &linkGap, nullptr);
   if (rc != PB_OK) return rc;
   rc = pbClusterAnalyse(S, linkGap);
   if (rc != PB_OK) return rc;
@@ -514,13 +426,7 @@ int pbSimClusterLabelsOf(pbSim *S, unsigned member, float linkGap, unsigned *lab
     pbLastError() = "pbSimClusterLabelsOf: labels and degree are both null";
     return PB_ERR_ARG;
   }
-  int rc = pbClusterCheckGap("pbSimClusterLabelsOf", linkGap);  // needs no look at the handle; the checks below read it
-  if (rc != PB_OK) return rc;
-  if (member >= S->nsims) {
-    pbLastError() = "pbSimClusterLabelsOf: member out of range";
-    return PB_ERR_ARG;
-  }
-  rc = pbClusterCheckBatch("pbSimClusterLabelsOf", S);
+  int rc = pbClusterCheckArgs("pbSimClusterLabelsOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   rc = pbClusterAnalyse(S, linkGap);
   if (rc != PB_OK) return rc;
@@ -538,11 +444,5 @@ int pbSimClusterLabelsOf(pbSim *S, unsigned member, float linkGap, unsigned *lab
 }
 
 int pbSimGetClusterTimes(pbSim *S, unsigned long long *analyses, float *last_device_ms) {
-  if (!S) {
-    pbLastError() = "pbSimGetClusterTimes: null handle";
-    return PB_ERR_ARG;
-  }
-  if (analyses) *analyses = S->cluster ? S->cluster->analyses : 0ull;
-  if (last_device_ms) *last_device_ms = S->cluster ? S->cluster->lastMs : 0.0f;
-  return PB_OK;
+  return pbClockGet("pbSimGetClusterTimes", S, &PbClusterScratch::clusterClock, analyses, last_device_ms);
 }

@@ -1,8 +1,17 @@
-// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip and pb_structure.hip: the scratch object, the fresh
-// grid, the front end that files the bots (rmax, hash, sort, gather, cell starts) and the link pass on top of it.
+// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip and pb_structure.hip: the scratch object with its
+// three clocks, the fresh grid, the wave helpers, the walk over a bot's nine cells (pbWalkNine) and the link rule
+// (pbWhenLinked) that every neighbour sweep of the analysis layer is built on, the front end that files the bots (rmax,
+// hash, sort, gather, cell starts) and the argument checks of the entry points.
 #pragma once
 
 #include "pb_engine.hpp"
+
+// One analysis' clock: it starts at the front end's ev0 and ends at an event of its own (pbClockStop).
+struct PbAnalysisClock {
+  hipEvent_t end = nullptr;  // behind the analysis' last launch; created by the first stop
+  unsigned long long runs = 0;
+  float lastMs = 0.0f;
+};
 
 struct PbClusterScratch {
   uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr;
@@ -13,10 +22,9 @@ struct PbClusterScratch {
   unsigned long long *acc = nullptr;  // 4 words per member
   pbClusterStats *rows = nullptr;     // nsims
   uint32_t *flag = nullptr;           // [0] changed, [1] rmax bits
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t ev0 = nullptr;           // the front end's first launch: where every clock starts
+  PbAnalysisClock clusterClock, contactClock, structureClock;
   uint32_t gxLog2 = 2, gyLog2 = 2;
-  unsigned long long analyses = 0;
-  float lastMs = 0.0f;
   unsigned rounds = 0;
   // what the last analysis left behind for the contact export (pb_contacts.hip)
   double invCell = 0.0;  // the grid's 1 / edge
@@ -29,9 +37,6 @@ struct PbClusterScratch {
   double *cVirial = nullptr;                 // 4 n, ORIGINAL order
   uint4 *cLinks = nullptr;                   // cLinksCap entries of 16 bytes (pbContactLink)
   unsigned long long cLinksCap = 0;
-  hipEvent_t cEv1 = nullptr;                 // the export's last launch (its first is the front end's ev0)
-  unsigned long long exports = 0;
-  float lastExportMs = 0.0f;
   // structure analysis (pb_structure.hip): allocated by the first call that needs each, counts grown with bins
   unsigned long long *sCounts = nullptr;     // nsims * sCountsBins: the radial histograms
   unsigned sCountsBins = 0;
@@ -39,9 +44,6 @@ struct PbClusterScratch {
   uint32_t *sNb = nullptr;                   // total, ORIGINAL order: neighbours
   pbStructureStats *sRows = nullptr;         // nsims
   double *sPsi = nullptr;                    // 2 n: one member's psi6
-  hipEvent_t sEv1 = nullptr;                 // the analysis' last launch (its first is the front end's ev0)
-  unsigned long long structures = 0;
-  float lastStructureMs = 0.0f;
 };
 
 namespace {
@@ -79,6 +81,153 @@ PB_DEV uint32_t cellY(const ClusterGrid &G, float y) {
   return (uint32_t)cellCoord((double)y * G.invCell) & ((1u << G.gyLog2) - 1u);
 }
 
+// ---- wave helpers (wave64) ---------------------------------------------------------------------------------------------
+PB_DEV uint32_t waveMaxU32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const uint32_t o = (uint32_t)__shfl_xor((int)v, m);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+PB_DEV uint32_t waveSumU32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
+  return v;
+}
+PB_DEV unsigned long long shflXor64(unsigned long long v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
+  return ((unsigned long long)hi << 32) | lo;
+}
+PB_DEV unsigned long long shflUp64(unsigned long long v, int d) {
+  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d);
+  const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
+  return ((unsigned long long)hi << 32) | lo;
+}
+PB_DEV unsigned long long waveMaxU64(unsigned long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    const unsigned long long o = shflXor64(v, m);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+PB_DEV unsigned long long waveSumU64(unsigned long long v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += shflXor64(v, m);
+  return v;
+}
+
+// ---- the walk ------------------------------------------------------------------------------------------------------------
+// The neighbour sweep of one bot (sorted slot t, posrad me with a finite position, member `member` of the batch) over the
+// nine cells around its own: three slot ranges of three cells each, and at the x-wrap (the own cell in the first or last
+// column) nine ranges of one.  The wrapped dimensions are >= 4, so the nine cells are distinct and a pair is met once
+// from each end however the grid folds.  The bounds of the range after the next and the first posrad of the next range
+// are in flight while a range is walked, and so is the next slot's posrad inside a range (one slot past a range is
+// inside the array: cpr has spare elements).  For every slot j of every range, the own one included,
+// body(j, q, rx, ry, d2) gets the slot's posrad and rx = q.x - me.x, ry = q.y - me.y, d2 = rx*rx + ry*ry in fp32 without
+// contraction.  BEHIND: only the slots behind the own one are walked (j > t), for a sweep that counts a pair at one end.
+template <bool BEHIND, typename Body>
+PB_DEV void pbWalkNine(const float4 *__restrict__ cpr, const uint32_t *__restrict__ start, uint32_t member,
+                       const ClusterGrid &G, uint32_t t, const float4 &me, const Body &body) {
+  const uint32_t GX = 1u << G.gxLog2;
+  const uint32_t cx = cellX(G, me.x), cy = cellY(G, me.y);
+  const uint32_t *__restrict__ cells = start + ((size_t)member << (G.gxLog2 + G.gyLog2));
+  const bool wrap = cx == 0u || cx == GX - 1u;
+  const uint32_t step = wrap ? 1u : 3u;
+  auto bounds = [&](uint32_t si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
+    lo = hi = t;
+    if (si < 9u) {
+      const uint32_t rowI = si / 3u, col = si - 3u * rowI;
+      const uint32_t row = ((cy + rowI - 1u) & ((1u << G.gyLog2) - 1u)) << G.gxLog2;
+      const uint32_t c0 = (cx + col - 1u) & (GX - 1u);
+      lo = cells[row + c0];
+      hi = cells[row + c0 + step];
+      if constexpr (BEHIND) {
+        lo = lo > t ? lo : t + 1u;
+        lo = lo < hi ? lo : hi;
+      }
+    }
+  };
+  uint32_t loA, hiA, loB, hiB;
+  bounds(0u, loA, hiA);
+  bounds(step, loB, hiB);
+  float4 qA = cpr[loA];
+#pragma unroll 1
+  for (uint32_t si = 0u; si < 9u; si += step) {
+    const uint32_t lo = loA, hi = hiA;
+    float4 q = qA;
+    loA = loB, hiA = hiB;
+    qA = cpr[loA];                      // first posrad of the next range
+    bounds(si + 2u * step, loB, hiB);   // bounds of the range after the next
+    for (uint32_t j = lo; j < hi; j++) {
+      const float4 qn = cpr[(size_t)j + 1u];  // (widened before the add: the address needs no 32-bit wrap)
+      const float rx = q.x - me.x, ry = q.y - me.y;
+      const float d2 = rx * rx + ry * ry;
+      body(j, q, rx, ry, d2);
+      q = qn;
+    }
+  }
+}
+
+// ---- the link rule -------------------------------------------------------------------------------------------------------
+// then(dist, R) when the bots in sorted slots t (posrad me) and j (posrad q), d2 apart squared as the walk computes it,
+// are linked at `gap`: two different slots with fl(dist - R) < gap, R = ri + rj and dist = sqrtf(d2), the pair law's
+// geometry in fp32 without contraction (the stored gap is dist - R).  A bot is not linked to itself: j != t is part of
+// the rule.  A continuation and not a bool, so that the root stays behind the rejection in the machine code: the
+// compiler folds a returned `near && exact` into one test and takes the root for every pair.
+// The cheap rejection in front of the correctly rounded root: a linked pair has fl(dist - R) < gap, hence
+// dist - R <= gap exactly (rounding is monotone), dist <= fl(R + gap) (1 + 2^-23) and
+// fl(rx*rx + ry*ry) <= fl(R + gap)^2 (1 + 2^-20): the bound below (1e-4 relative, 1e-30 absolute for the subnormal cases)
+// admits every such pair; whatever else it admits the exact predicate decides.  A non-finite partner's position is NaN,
+// which passes neither.
+template <typename Then>
+PB_DEV void pbWhenLinked(uint32_t t, const float4 &me, uint32_t j, const float4 &q, float d2, float gap,
+                         const Then &then) {
+  const float R = me.z + q.z;
+  const float s = R + gap;
+  if (j != t && d2 <= s * s * 1.0001f + 1e-30f) {
+    const float dist = sqrtf(d2);
+    if ((dist - R) < gap) then(dist, R);
+  }
+}
+
+// ---- the clocks ----------------------------------------------------------------------------------------------------------
+// The end of a run of the analysis K times, in two steps for a caller that queues something of its own in between:
+// pbClockMark records K's end event (created here the first time) behind what the stream holds; pbClockRead drains the
+// stream, takes the device time since the front end's ev0 and counts the run.  pbClockStop is both.
+inline int pbClockMark(pbSim *S, PbAnalysisClock &K) {
+  if (!K.end) PB_TRY(hipEventCreate(&K.end));
+  PB_TRY(hipEventRecord(K.end, S->stream));
+  return PB_OK;
+}
+inline int pbClockRead(pbSim *S, PbAnalysisClock &K) {
+  PB_TRY(hipStreamSynchronize(S->stream));
+  PB_TRY(hipEventElapsedTime(&K.lastMs, S->cluster->ev0, K.end));
+  K.runs++;
+  return PB_OK;
+}
+inline int pbClockStop(pbSim *S, PbAnalysisClock &K) {
+  const int rc = pbClockMark(S, K);
+  return rc != PB_OK ? rc : pbClockRead(S, K);
+}
+inline void pbClockFree(PbAnalysisClock &K) {
+  if (K.end) (void)hipEventDestroy(K.end);
+  K = PbAnalysisClock();
+}
+// the body of pbSimGet{Cluster,Contact,Structure}Times; K points into S's scratch object
+inline int pbClockGet(const char *fn, const pbSim *S, PbAnalysisClock PbClusterScratch::*K, unsigned long long *runs,
+                      float *last_device_ms) {
+  if (!S) {
+    pbLastError() = std::string(fn) + ": null handle";
+    return PB_ERR_ARG;
+  }
+  if (runs) *runs = S->cluster ? (S->cluster->*K).runs : 0ull;
+  if (last_device_ms) *last_device_ms = S->cluster ? (S->cluster->*K).lastMs : 0.0f;
+  return PB_OK;
+}
+
 }  // namespace
 
 // The filing front end: records ev0, files every bot of the batch on a wrapped power-of-two grid of edge
@@ -90,10 +239,11 @@ int pbClusterFile(pbSim *S, double reach, double perRmax);
 // The whole cluster pipeline (the front end with reach = gap, perRmax = 2); leaves cpr, the cell starts, parent (roots),
 // degree and the rows on the device and the stream drained.                                             pb_cluster.hip
 int pbClusterAnalyse(pbSim *S, float gap);
-// the argument checks the entry points share; nothing here touches the device (the batch check reads the host-side
-// batch object, so it needs a real handle)
-int pbClusterCheckGap(const char *fn, float gap);
-int pbClusterCheckBatch(const char *fn, const pbSim *S);
+// The argument checks the seven entry points share after their own pointer checks, in this order: linkGap finite and
+// >= 0 (when gap is given), member inside the batch (when member is given), the batch within what a launch can index.
+// Nothing here touches the device; the gap check needs no look at the handle, the other two read the host-side batch
+// object, so they need a real one.                                                                       pb_cluster.hip
+int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const unsigned *member);
 // frees the contact export's buffers, if any (pbClusterFree)                                           pb_contacts.hip
 void pbContactsFree(PbClusterScratch *C);
 // frees the structure analysis' buffers, if any (pbClusterFree)                                       pb_structure.hip

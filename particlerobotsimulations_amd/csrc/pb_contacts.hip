@@ -8,15 +8,16 @@
 //                         block sums, and the offsets themselves.  Sums are 64-bit, so a member with 2^31 entries or more
 //                         is seen as such; the total (8 bytes) goes back to the host, which sizes the link buffer
 //   k_contact_gather_vel  the member's velocities in sorted order next to cpr, its positions in ORIGINAL order
-//   k_contact_fill        k_cluster_links' walk over the nine cells with the same ranges, prefetch and cheap rejection;
-//                         every accepted neighbour goes through pbPair (zeroed accumulator, this bot as A) and becomes one
-//                         16-byte entry at offsets[o] + k.  The store is guarded by offsets[o + 1], and a lane whose count
-//                         differs from its degree raises a flag: the host reports it instead of a torn list
+//   k_contact_fill        the walk over the nine cells and the link rule that counted the degrees (pbWalkNine and
+//                         pbWhenLinked, pb_cluster.hpp); every accepted neighbour goes through pbPair (zeroed accumulator,
+//                         this bot as A) and becomes one 16-byte entry at offsets[o] + k.  The store is guarded by
+//                         offsets[o + 1], and a lane whose count differs from its degree raises a flag: the host reports
+//                         it instead of a torn list
 //   k_contact_order       one lane per bot: insertion sort of its entries by `other`, in place in global memory (lists are
 //                         about 6 long at contact gaps; long lists of a large linkGap stay correct and are slow), then
 //                         the four virial sums over the ordered list when a virial buffer is attached
-// Count and fill agree because both evaluate the same fp32 predicate, compiled without contraction, on the same bytes
-// of cpr over the same ranges.  No scratch memory: a list is never staged in a private array.
+// Count and fill agree because both evaluate the one link rule, compiled without contraction, on the same bytes of cpr
+// over the one walk's ranges.  No scratch memory: a list is never staged in a private array.
 #include <string.h>
 
 #include "pb_cluster.hpp"
@@ -27,12 +28,6 @@ namespace {
 
 // one link entry as the compiler's own 16-byte vector (other, gap, fx, fy as bit patterns): a single dwordx4 access
 typedef uint32_t LinkBits __attribute__((ext_vector_type(4)));
-
-PB_DEV unsigned long long shflUp64(unsigned long long v, int d) {
-  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d);
-  const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 // exclusive prefix of v over the workgroup and the workgroup's total: an inclusive scan inside each wave with
 // shuffles, the four wave totals through LDS.  Every lane of the workgroup must call it.
@@ -124,57 +119,19 @@ __global__ __launch_bounds__(CT) void k_contact_fill(const float4 *__restrict__ 
     const uint32_t payloadIdx = P.nCells - 1u;
     const float att1 = (payloadMode && o == payloadIdx) ? P.attractionFactor : 1.0f;
     const float2 v = cVel[l];
-    const uint32_t GX = 1u << G.gxLog2;
-    const uint32_t cx = cellX(G, me.x), cy = cellY(G, me.y);
-    const uint32_t *__restrict__ cells = start + ((size_t)member << (G.gxLog2 + G.gyLog2));
-    // three ranges of three cells; at the x-wrap nine ranges of one (k_cluster_links)
-    const bool wrap = cx == 0u || cx == GX - 1u;
-    const uint32_t step = wrap ? 1u : 3u;
-    auto bounds = [&](uint32_t si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
-      lo = hi = t;
-      if (si < 9u) {
-        const uint32_t rowI = si / 3u, col = si - 3u * rowI;
-        const uint32_t row = ((cy + rowI - 1u) & ((1u << G.gyLog2) - 1u)) << G.gxLog2;
-        const uint32_t c0 = (cx + col - 1u) & (GX - 1u);
-        lo = cells[row + c0];
-        hi = cells[row + c0 + step];
-      }
-    };
-    uint32_t loA, hiA, loB, hiB;
-    bounds(0u, loA, hiA);
-    bounds(step, loB, hiB);
-    float4 qA = cpr[loA];
-#pragma unroll 1
-    for (uint32_t si = 0u; si < 9u; si += step) {
-      const uint32_t lo = loA, hi = hiA;
-      float4 q = qA;
-      loA = loB, hiA = hiB;
-      qA = cpr[loA];                      // first posrad of the next range
-      bounds(si + 2u * step, loB, hiB);   // bounds of the range after the next
-      for (uint32_t j = lo; j < hi; j++) {
-        const float4 qn = cpr[j + 1u];  // one slot past a range is inside the array (spare elements)
-        const float rx = q.x - me.x, ry = q.y - me.y;
-        const float d2 = rx * rx + ry * ry;
-        const float R = me.z + q.z;
-        const float s = R + gap;
-        // the cheap rejection of k_cluster_links: it admits every linked pair, the exact predicate decides
-        if (j != t && d2 <= s * s * 1.0001f + 1e-30f) {
-          const float dist = sqrtf(d2);
-          const float g = dist - R;
-          if (g < gap) {
-            const uint32_t oj = __float_as_uint(q.w) - base;
-            const float att2 = (payloadMode && oj == payloadIdx) ? P.attractionFactor : 1.0f;
-            PbForce F = {0.0f, 0.0f, 0.0f, 0.0f};
-            pbPair(P, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, P.attraction * att2 * att1,
-                   [&]() { return cVel[j - base]; }, F);
-            if (first + k < end)  // never outside this bot's share of the buffer, whatever the count pass said
-              links[first + k] = LinkBits{oj, __float_as_uint(g), __float_as_uint(F.fx), __float_as_uint(F.fy)};
-            k++;
-          }
-        }
-        q = qn;
-      }
-    }
+    pbWalkNine<false>(cpr, start, member, G, t, me, [&](uint32_t j, const float4 &q, float, float, float d2) {
+      pbWhenLinked(t, me, j, q, d2, gap, [&](float dist, float R) {
+        const float g = dist - R;
+        const uint32_t oj = __float_as_uint(q.w) - base;
+        const float att2 = (payloadMode && oj == payloadIdx) ? P.attractionFactor : 1.0f;
+        PbForce F = {0.0f, 0.0f, 0.0f, 0.0f};
+        pbPair(P, me.x, me.y, v.x, v.y, me.z, q.x, q.y, q.z, P.attraction * att2 * att1,
+               [&]() { return cVel[j - base]; }, F);
+        if (first + k < end)  // never outside this bot's share of the buffer, whatever the count pass said
+          links[first + k] = LinkBits{oj, __float_as_uint(g), __float_as_uint(F.fx), __float_as_uint(F.fy)};
+        k++;
+      });
+    });
   }
   if (k != end - first) __atomic_store_n(flag, 1ull, __ATOMIC_RELAXED);
 }
@@ -222,7 +179,6 @@ int ensureContactScratch(pbSim *S) {
   PB_TRY(hipMalloc((void **)&C->cVel, sizeof(float2) * n));
   PB_TRY(hipMalloc((void **)&C->cPos, sizeof(float2) * n));
   PB_TRY(hipMalloc((void **)&C->cVirial, sizeof(double) * 4 * n));
-  PB_TRY(hipEventCreate(&C->cEv1));
   return PB_OK;
 }
 
@@ -264,9 +220,7 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
       PB_TRY(hipMalloc((void **)&C->cLinks, sizeof(uint4) * want));
       C->cLinksCap = want;
     }
-    ClusterGrid G;
-    G.invCell = C->invCell;
-    G.gxLog2 = C->gxLog2, G.gyLog2 = C->gyLog2;
+    const ClusterGrid G = gridOf(C);
     hipLaunchKernelGGL(k_contact_gather_vel, g, b, 0, S->stream, C->cpr, C->vals[C->sortedIn], S->vel[S->cur], base, n,
                        C->cVel, C->cPos);
     hipLaunchKernelGGL(k_contact_fill, g, b, 0, S->stream, C->cpr, C->start, C->cVel, S->dP, member, n, G, gap,
@@ -274,30 +228,19 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
     hipLaunchKernelGGL(k_contact_order, g, b, 0, S->stream, C->cOffsets, (LinkBits *)C->cLinks, C->cPos, n,
                        wantVirial ? C->cVirial : (double *)nullptr);
     PB_TRY(hipGetLastError());
-    PB_TRY(hipEventRecord(C->cEv1, S->stream));
+    rc = pbClockMark(S, C->contactClock);  // the export ends here: the flag's way back is not part of its device time
+    if (rc != PB_OK) return rc;
     PB_TRY(hipMemcpyAsync(&raised, flag, sizeof raised, hipMemcpyDeviceToHost, S->stream));
+    rc = pbClockRead(S, C->contactClock);  // one drain serves the clock and the flag
   } else {
-    PB_TRY(hipEventRecord(C->cEv1, S->stream));
+    rc = pbClockStop(S, C->contactClock);
   }
-  PB_TRY(hipStreamSynchronize(S->stream));
-  PB_TRY(hipEventElapsedTime(&C->lastExportMs, C->ev0, C->cEv1));  // ev0: the front end's first launch
-  C->exports++;
+  if (rc != PB_OK) return rc;
   if (raised) {
     pbLastError() = "contact export: count and fill disagree";
     return PB_ERR_HIP;
   }
   return PB_OK;
-}
-
-// the checks the two entry points share after their own pointer checks; nothing here touches the device
-int checkContactArgs(const char *fn, const pbSim *S, unsigned member, float gap) {
-  int rc = pbClusterCheckGap(fn, gap);  // needs no look at the handle; the checks below read it
-  if (rc != PB_OK) return rc;
-  if (member >= S->nsims) {
-    pbLastError() = std::string(fn) + ": member out of range";
-    return PB_ERR_ARG;
-  }
-  return pbClusterCheckBatch(fn, S);
 }
 
 }  // namespace
@@ -309,9 +252,9 @@ void pbContactsFree(PbClusterScratch *C) {
   (void)hipFree(C->cPos);
   (void)hipFree(C->cVirial);
   (void)hipFree(C->cLinks);
-  if (C->cEv1) (void)hipEventDestroy(C->cEv1);
+  pbClockFree(C->contactClock);
   C->cOffsets = nullptr, C->cParts = nullptr, C->cVel = nullptr, C->cPos = nullptr, C->cVirial = nullptr;
-  C->cLinks = nullptr, C->cLinksCap = 0, C->cEv1 = nullptr;
+  C->cLinks = nullptr, C->cLinksCap = 0;
 }
 
 int pbSimContactsOf(pbSim *S, unsigned member, float linkGap, unsigned *offsets, pbContactLink *links,
@@ -320,7 +263,7 @@ int pbSimContactsOf(pbSim *S, unsigned member, float linkGap, unsigned *offsets,
     pbLastError() = "pbSimContactsOf: null handle or entries";
     return PB_ERR_ARG;
   }
-  int rc = checkContactArgs("pbSimContactsOf", S, member, linkGap);
+  int rc = pbClusterCheckArgs("pbSimContactsOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   rc = exportContacts("pbSimContactsOf", S, member, linkGap, links != nullptr, cap, false, entries);
   if (rc != PB_OK) return rc;
@@ -338,7 +281,7 @@ int pbSimContactVirialOf(pbSim *S, unsigned member, float linkGap, double *viria
     pbLastError() = "pbSimContactVirialOf: null handle or virial";
     return PB_ERR_ARG;
   }
-  int rc = checkContactArgs("pbSimContactVirialOf", S, member, linkGap);
+  int rc = pbClusterCheckArgs("pbSimContactVirialOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   unsigned long long entries = 0ull;
   rc = exportContacts("pbSimContactVirialOf", S, member, linkGap, false, 0ull, true, &entries);
@@ -348,11 +291,5 @@ int pbSimContactVirialOf(pbSim *S, unsigned member, float linkGap, double *viria
 }
 
 int pbSimGetContactTimes(pbSim *S, unsigned long long *exports, float *last_device_ms) {
-  if (!S) {
-    pbLastError() = "pbSimGetContactTimes: null handle";
-    return PB_ERR_ARG;
-  }
-  if (exports) *exports = S->cluster ? S->cluster->exports : 0ull;
-  if (last_device_ms) *last_device_ms = S->cluster ? S->cluster->lastExportMs : 0.0f;
-  return PB_OK;
+  return pbClockGet("pbSimGetContactTimes", S, &PbClusterScratch::contactClock, exports, last_device_ms);
 }

@@ -6,13 +6,14 @@
 // power-of-two grid, the sorted posrad array, dense cell starts.  Every entry point re-files with the edge it needs.
 // On top of it, for the whole batch at once:
 //   k_struct_rdf      the hot path.  Grid edge rMax (1 + 2^-10): a counted pair is never further apart than one cell.
-//                     One bot per lane over the nine cells with k_cluster_links' walk (three slot ranges away from the
-//                     x-wrap, nine at it, the next posrad in flight).  Every unordered pair is met from both ends; it is
-//                     counted by the end with the smaller sorted slot, as 2, and the walk starts each range behind the
-//                     own slot.  Bins go into the workgroup's LDS histogram (32-bit counters, LDS atomics), which is
-//                     flushed once into the member's 64-bit counters with vector atomics, zeros skipped.  blockIdx.y is
-//                     the member, so a workgroup's histogram belongs to one member.
-//   k_struct_psi6     on the cluster analysis' grid, k_cluster_links' predicate and rejection without the union-find:
+//                     One bot per lane over the nine cells (pbWalkNine, pb_cluster.hpp).  Every unordered pair is met
+//                     from both ends; it is counted by the end with the smaller sorted slot, as 2: the walk is the one
+//                     that starts each range behind the own slot.  Bins go into the workgroup's LDS histogram (32-bit
+//                     counters, LDS atomics), which is flushed once into the member's 64-bit counters with vector
+//                     atomics, zeros skipped.  blockIdx.y is the member, so a workgroup's histogram belongs to one
+//                     member.
+//   k_struct_psi6     on the cluster analysis' grid, the same walk and the link rule (pbWhenLinked) without the
+//                     union-find:
 //                     per bot the neighbour count and the two fixed-point sums in registers, written in ORIGINAL order;
 //                     the member's row reduced with wave shuffles and ballots, LDS, one set of integer atomics per
 //                     workgroup (as k_cluster_reduce)
@@ -35,17 +36,6 @@ namespace {
 // folded into one cell (up to 2^28 - 1 partners per bot) included.
 constexpr uint32_t LDS_ADDS_PER_LANE = 1u << 22;
 
-PB_DEV unsigned long long shflXor64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-PB_DEV unsigned long long waveSumU64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += shflXor64(v, m);
-  return v;
-}
-
 __global__ __launch_bounds__(CT) void k_struct_rdf(const float4 *__restrict__ cpr, const uint32_t *__restrict__ start,
                                                    uint32_t n, ClusterGrid G, float scale, float d2max, uint32_t bins,
                                                    unsigned long long *__restrict__ counts) {
@@ -60,61 +50,26 @@ __global__ __launch_bounds__(CT) void k_struct_rdf(const float4 *__restrict__ cp
   if (me.x == me.x) {  // a bot with a non-finite position or radius is in no pair
     const float fbins = (float)bins;
     uint32_t ldsAdds = 0u;
-    const uint32_t GX = 1u << G.gxLog2;
-    const uint32_t cx = cellX(G, me.x), cy = cellY(G, me.y);
-    const uint32_t *__restrict__ cells = start + ((size_t)blockIdx.y << (G.gxLog2 + G.gyLog2));
-    // three ranges of three cells; at the x-wrap nine ranges of one (wrapped dimensions >= 4: nine distinct cells, so a
-    // pair is met once from each end however the grid folds).  Only the slots behind the own one are walked.
-    const bool wrap = cx == 0u || cx == GX - 1u;
-    const uint32_t step = wrap ? 1u : 3u;
-    auto bounds = [&](uint32_t si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
-      lo = hi = t;
-      if (si < 9u) {
-        const uint32_t rowI = si / 3u, col = si - 3u * rowI;
-        const uint32_t row = ((cy + rowI - 1u) & ((1u << G.gyLog2) - 1u)) << G.gxLog2;
-        const uint32_t c0 = (cx + col - 1u) & (GX - 1u);
-        lo = cells[row + c0];
-        hi = cells[row + c0 + step];
-        lo = lo > t ? lo : t + 1u;
-        lo = lo < hi ? lo : hi;
-      }
-    };
     // Cheap rejection in front of the correctly rounded root.  A counted pair has fl(dist * scale) < bins, hence
     // dist * scale < bins exactly (rounding is monotone, bins is a float), dist < bins / scale <= rMax (1 + 2^-23) for a
     // normal scale = fl(bins / rMax), sqrt(d2) <= dist (1 + 2^-23) and d2 < fl(rMax * rMax) (1 + 2^-20): d2max =
     // rMax * rMax * 1.0001f + 1e-30f (host, fp32) admits every such pair -- the absolute term where rMax * rMax is
     // subnormal, infinity where it overflows or scale is subnormal; with an infinite scale nothing is counted at all.
     // Whatever else it admits the exact rule decides.
-    uint32_t loA, hiA, loB, hiB;
-    bounds(0u, loA, hiA);
-    bounds(step, loB, hiB);
-    float4 qA = cpr[loA];
-#pragma unroll 1
-    for (uint32_t si = 0u; si < 9u; si += step) {
-      const uint32_t lo = loA, hi = hiA;
-      float4 q = qA;
-      loA = loB, hiA = hiB;
-      qA = cpr[loA];                      // first posrad of the next range
-      bounds(si + 2u * step, loB, hiB);   // bounds of the range after the next
-      for (uint32_t j = lo; j < hi; j++) {
-        const float4 qn = cpr[j + 1u];  // one slot past a range is inside the array (spare elements)
-        const float rx = q.x - me.x, ry = q.y - me.y;
-        const float d2 = rx * rx + ry * ry;
-        if (d2 <= d2max) {  // (false for a non-finite partner: its position is NaN)
-          const float fb = sqrtf(d2) * scale;
-          if (fb < fbins) {
-            const uint32_t b = (uint32_t)(int)fb;
-            if (ldsAdds < LDS_ADDS_PER_LANE) {
-              ldsAdds++;
-              __hip_atomic_fetch_add(hist + b, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            } else {
-              __hip_atomic_fetch_add(mine + b, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
+    pbWalkNine<true>(cpr, start, blockIdx.y, G, t, me, [&](uint32_t, const float4 &, float, float, float d2) {
+      if (d2 <= d2max) {  // (false for a non-finite partner: its position is NaN)
+        const float fb = sqrtf(d2) * scale;
+        if (fb < fbins) {
+          const uint32_t b = (uint32_t)(int)fb;
+          if (ldsAdds < LDS_ADDS_PER_LANE) {
+            ldsAdds++;
+            __hip_atomic_fetch_add(hist + b, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          } else {
+            __hip_atomic_fetch_add(mine + b, 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           }
         }
-        q = qn;
       }
-    }
+    });
   }
   __syncthreads();
   for (uint32_t b = threadIdx.x; b < bins; b += CT) {
@@ -140,57 +95,19 @@ __global__ __launch_bounds__(CT) void k_struct_psi6(const float4 *__restrict__ c
   uint32_t deg = 0u;
   long long re = 0ll, im = 0ll;
   if (live && me.x == me.x) {  // a bot with a non-finite position or radius has no bonds
-    const uint32_t GX = 1u << G.gxLog2;
-    const uint32_t cx = cellX(G, me.x), cy = cellY(G, me.y);
-    const uint32_t *__restrict__ cells = start + ((size_t)blockIdx.y << (G.gxLog2 + G.gyLog2));
-    // three ranges of three cells; at the x-wrap nine ranges of one (k_cluster_links)
-    const bool wrap = cx == 0u || cx == GX - 1u;
-    const uint32_t step = wrap ? 1u : 3u;
-    auto bounds = [&](uint32_t si, uint32_t &lo, uint32_t &hi) __attribute__((always_inline)) {
-      lo = hi = t;
-      if (si < 9u) {
-        const uint32_t rowI = si / 3u, col = si - 3u * rowI;
-        const uint32_t row = ((cy + rowI - 1u) & ((1u << G.gyLog2) - 1u)) << G.gxLog2;
-        const uint32_t c0 = (cx + col - 1u) & (GX - 1u);
-        lo = cells[row + c0];
-        hi = cells[row + c0 + step];
-      }
-    };
-    uint32_t loA, hiA, loB, hiB;
-    bounds(0u, loA, hiA);
-    bounds(step, loB, hiB);
-    float4 qA = cpr[loA];
-#pragma unroll 1
-    for (uint32_t si = 0u; si < 9u; si += step) {
-      const uint32_t lo = loA, hi = hiA;
-      float4 q = qA;
-      loA = loB, hiA = hiB;
-      qA = cpr[loA];                      // first posrad of the next range
-      bounds(si + 2u * step, loB, hiB);   // bounds of the range after the next
-      for (uint32_t j = lo; j < hi; j++) {
-        const float4 qn = cpr[j + 1u];  // one slot past a range is inside the array (spare elements)
-        const float rx = q.x - me.x, ry = q.y - me.y;
-        const float d2 = rx * rx + ry * ry;
-        const float R = me.z + q.z;
-        const float s = R + gap;
-        // the cheap rejection of k_cluster_links: it admits every linked pair, the exact predicate decides
-        if (j != t && d2 <= s * s * 1.0001f + 1e-30f) {
-          const float dist = sqrtf(d2);
-          if ((dist - R) < gap) {
-            deg++;
-            if (dist > 0.0f) {
-              const float ux = rx / dist, uy = ry / dist;
-              const float c2 = ux * ux - uy * uy, s2 = (ux * uy) + (ux * uy);
-              const float c4 = c2 * c2 - s2 * s2, s4 = (c2 * s2) + (c2 * s2);
-              const float c6 = c4 * c2 - s4 * s2, s6 = s4 * c2 + c4 * s2;
-              re += fixed30(c6);
-              im += fixed30(s6);
-            }
-          }
+    pbWalkNine<false>(cpr, start, blockIdx.y, G, t, me, [&](uint32_t j, const float4 &q, float rx, float ry, float d2) {
+      pbWhenLinked(t, me, j, q, d2, gap, [&](float dist, float) {
+        deg++;
+        if (dist > 0.0f) {
+          const float ux = rx / dist, uy = ry / dist;
+          const float c2 = ux * ux - uy * uy, s2 = (ux * uy) + (ux * uy);
+          const float c4 = c2 * c2 - s2 * s2, s4 = (c2 * s2) + (c2 * s2);
+          const float c6 = c4 * c2 - s4 * s2, s6 = s4 * c2 + c4 * s2;
+          re += fixed30(c6);
+          im += fixed30(s6);
         }
-        q = qn;
-      }
-    }
+      });
+    });
   }
   if (live) {
     const uint32_t o = __float_as_uint(me.w);
@@ -239,15 +156,7 @@ __global__ __launch_bounds__(CT) void k_struct_hexatic(const long long *__restri
   psi[2u * l + 1u] = im;
 }
 
-int endOfAnalysis(pbSim *S) {
-  PbClusterScratch *C = S->cluster;
-  if (!C->sEv1) PB_TRY(hipEventCreate(&C->sEv1));
-  PB_TRY(hipEventRecord(C->sEv1, S->stream));
-  PB_TRY(hipStreamSynchronize(S->stream));
-  PB_TRY(hipEventElapsedTime(&C->lastStructureMs, C->ev0, C->sEv1));  // ev0: the front end's first launch
-  C->structures++;
-  return PB_OK;
-}
+int endOfAnalysis(pbSim *S) { return pbClockStop(S, S->cluster->structureClock); }
 
 // files the bots on the cluster analysis' grid and leaves every bot's sums and every member's row on the device
 int hexaticSweep(pbSim *S, float gap) {
@@ -277,9 +186,9 @@ void pbStructureFree(PbClusterScratch *C) {
   (void)hipFree(C->sNb);
   (void)hipFree(C->sRows);
   (void)hipFree(C->sPsi);
-  if (C->sEv1) (void)hipEventDestroy(C->sEv1);
+  pbClockFree(C->structureClock);
   C->sCounts = nullptr, C->sCountsBins = 0, C->sRe = nullptr, C->sIm = nullptr, C->sNb = nullptr, C->sRows = nullptr;
-  C->sPsi = nullptr, C->sEv1 = nullptr;
+  C->sPsi = nullptr;
 }
 
 int pbSimRadialCounts(pbSim *S, float rMax, unsigned bins, unsigned long long *counts) {
@@ -295,7 +204,7 @@ int pbSimRadialCounts(pbSim *S, float rMax, unsigned bins, unsigned long long *c
     pbLastError() = "pbSimRadialCounts: bins must be 1 ... 4096";
     return PB_ERR_ARG;
   }
-  int rc = pbClusterCheckBatch("pbSimRadialCounts", S);
+  int rc = pbClusterCheckArgs("pbSimRadialCounts", S, nullptr, nullptr);
   if (rc != PB_OK) return rc;
   rc = pbClusterFile(S, (double)rMax, 0.0);
   if (rc != PB_OK) return rc;
@@ -325,8 +234,7 @@ int pbSimStructureStats(pbSim *S, float linkGap, pbStructureStats *rows) {
     pbLastError() = "pbSimStructureStats: null handle or rows";
     return PB_ERR_ARG;
   }
-  int rc = pbClusterCheckGap("pbSimStructureStats", linkGap);  // needs no look at the handle; the batch check reads it
-  if (rc == PB_OK) rc = pbClusterCheckBatch("pbSimStructureStats", S);
+  int rc = pbClusterCheckArgs("pbSimStructureStats", S, &linkGap, nullptr);
   if (rc != PB_OK) return rc;
   rc = hexaticSweep(S, linkGap);
   if (rc == PB_OK) rc = endOfAnalysis(S);
@@ -344,13 +252,7 @@ int pbSimHexaticOf(pbSim *S, unsigned member, float linkGap, double *psi6, unsig
     pbLastError() = "pbSimHexaticOf: psi6 and neighbours are both null";
     return PB_ERR_ARG;
   }
-  int rc = pbClusterCheckGap("pbSimHexaticOf", linkGap);  // needs no look at the handle; the checks below read it
-  if (rc != PB_OK) return rc;
-  if (member >= S->nsims) {
-    pbLastError() = "pbSimHexaticOf: member out of range";
-    return PB_ERR_ARG;
-  }
-  rc = pbClusterCheckBatch("pbSimHexaticOf", S);
+  int rc = pbClusterCheckArgs("pbSimHexaticOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   rc = hexaticSweep(S, linkGap);
   if (rc != PB_OK) return rc;
@@ -371,11 +273,5 @@ int pbSimHexaticOf(pbSim *S, unsigned member, float linkGap, double *psi6, unsig
 }
 
 int pbSimGetStructureTimes(pbSim *S, unsigned long long *analyses, float *last_device_ms) {
-  if (!S) {
-    pbLastError() = "pbSimGetStructureTimes: null handle";
-    return PB_ERR_ARG;
-  }
-  if (analyses) *analyses = S->cluster ? S->cluster->structures : 0ull;
-  if (last_device_ms) *last_device_ms = S->cluster ? S->cluster->lastStructureMs : 0.0f;
-  return PB_OK;
+  return pbClockGet("pbSimGetStructureTimes", S, &PbClusterScratch::structureClock, analyses, last_device_ms);
 }
