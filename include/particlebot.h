@@ -207,6 +207,18 @@ class Particlebot {
   bool radialCounts(float rMax, unsigned bins, std::vector<unsigned long long> &counts);
   bool structureStats(float linkGap, pbStructureStats &out);
   bool hexatic(float linkGap, std::vector<double> &psi6, std::vector<unsigned> &neighbours);
+  /* Rearrangement analysis of the resident state on the device (pbSimMarkReference / pbSimRearrangementStats /
+   * pbSimRearrangementOf, include/particlebot_hip.h has the definitions): markReference keeps the positions and the
+   * link network at linkGap on the device, clearReference frees them; rearrangementStats gives the row that compares
+   * the state as it is now with the mark (bonds marked, now and kept, displacement sums); rearrangement every bot's
+   * displacement (2 nCells floats: dx, dy) and its marked, present and kept bond counts in ORIGINAL order.  Fused engine
+   * only: Legacy and HostOnly instances return false with a message on stderr.  Also false on a bad linkGap, and for a
+   * compare with no mark held.  The mark is not part of a checkpoint. */
+  bool markReference(float linkGap);
+  bool clearReference();
+  bool rearrangementStats(pbRearrangementStats &out);
+  bool rearrangement(std::vector<float> &disp, std::vector<unsigned> &marked, std::vector<unsigned> &now,
+                     std::vector<unsigned> &kept);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -489,6 +489,73 @@ int pbSimHexaticOf(pbSim *sim, unsigned member, float linkGap, double *psi6 /* 2
                    unsigned *neighbours /* n */);
 int pbSimGetStructureTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
 
+/* Rearrangement analysis on the device (csrc/pb_dynamics.hip): the one analysis that compares two instants.  A MARK keeps
+ * a reference on the device; a COMPARE says, for the state as it is now, which bonds of the reference survive and how
+ * far every bot has moved since.  The bots are filed afresh exactly as for the cluster analysis, so what is said there
+ * holds: nodes are all nCells bots of a member (dead bots and the payload bot included), a bot with a non-finite
+ * position or radius has no links and does not fault, results are guaranteed for |x|, |y| <= 2^20, and a call only
+ * reads the simulation (slot layout, keys, cell lists, pbSimStats, time, RNG and render buffers stay untouched).
+ * LINKS are the cluster analysis': bots i != j of one member are linked at linkGap iff (dist - (ri + rj)) < linkGap,
+ * dist = sqrtf(rx*rx + ry*ry) in fp32 without contraction.
+ * MARK (pbSimMarkReference): for every member of the batch the device keeps the positions as they are now, in ORIGINAL
+ * order, bit for bit; the link network N0 at linkGap as a CSR in ORIGINAL order over the whole batch (32-bit offsets,
+ * one 4-byte entry per directed link: `other`, the member-local original index; a bot's entries strictly ascending);
+ * linkGap itself and the fp32 time.  A new mark replaces the old one.  The mark is addressed by original index:
+ * re-sorts, pbSimSetState* and pbSimSetLayoutOf do not invalidate it.  It is not part of a checkpoint (like the centroid
+ * trail).  pbSimClearReference frees it, pbSimDestroy frees everything.  A mark refused for its arguments changes
+ * nothing; one that fails later leaves no mark held.
+ * pbSimGetReferenceInfo: *marked = 1 with the mark's linkGap, time and directed entries (of the whole batch), or
+ * *marked = 0 and zeros; any pointer may be NULL.
+ * COMPARE, on the state as it is now; N1 is the link network now, at the mark's linkGap.  Per bot i:
+ *     marked[i] = |N0(i)|;   now[i] = |N1(i)|;   kept[i] = |N0(i) n N1(i)|
+ * marked[i] is what pbSimClusterLabelsOf gave as degree at the mark, now[i] the degree it gives now; kept is symmetric
+ * (j counts for i exactly when i counts for j).  A bot that is non-finite now has now = kept = 0: its marked bonds count
+ * as broken at both ends.
+ *     dx = x_now - x_mark;   dy = y_now - y_mark                                                          (fp32)
+ * The bot is MEASURED iff all four coordinates are finite and fabsf(dx) < 2048.0f and fabsf(dy) < 2048.0f.  Then
+ *     qx = (long long)rint(dx * 1048576.0f);   qy likewise;   s = qx*qx + qy*qy
+ * (the scaling by 2^20 is exact, the conversion rounds to nearest even, |qx| < 2^31, s < 2^63).
+ * Per member one pbRearrangementStats row.  Every number is an integer, so results do not depend on the order in which
+ * the device adds and can be compared exactly; with fewer than 2^28 bots |sum q| < 2^59.  The device sums the low and
+ * the high 32 bits of every s in two 64-bit accumulators (each below 2^60); the host composes the 128-bit value
+ * hi_part * 2^32 + lo_part.  No float atomics, no 128-bit atomics.
+ * pbSimRearrangementStats: one row per member.  pbSimRearrangementOf: one member's per-bot results in ORIGINAL order;
+ * disp holds dx, dy verbatim (2 n floats), unmeasured bots included; any of the four pointers may be NULL, not all.
+ * pbSimGetRearrangementTimes: marks and compares run so far, counted alike, and the span of the last one on the batch's
+ * stream in milliseconds, from the first launch of its front end to its last kernel (HIP events), as
+ * pbSimGetClusterTimes.  Either pointer may be NULL.
+ * PB_ERR_ARG, before the device is touched: NULL handle; NULL rows; all four per-bot pointers NULL; member out of range;
+ * linkGap negative, NaN or infinite; a batch of 2^28 bots or more, or of more than 65535 members; a compare with no mark
+ * held ("no reference marked").  After the mark's count pass: a batch with 2^31 directed entries or more (offsets are
+ * 32-bit).  PB_ERR_HIP "reference mark: count and fill disagree" if the mark's two passes ever differed (the fill never
+ * writes outside a bot's share).
+ * Cost: a mark files the batch, counts, scans, fills and orders each bot's list by insertion (about 6 entries at contact
+ * gaps; the long lists of a large linkGap stay correct and are slow to mark).  A compare files the batch and runs one
+ * sweep; a neighbour is looked up in the marked list held in registers (up to 8 entries) or by a binary search in
+ * global memory (longer lists).  Read back besides the results: 8 bytes (the count) between the mark's passes and its
+ * 8-byte disagreement flag.
+ * Scratch on top of the cluster analysis': for the mark 8 + 4 bytes per bot of the batch (positions, offsets), 4 per
+ * directed entry of the largest mark so far and 8 per 256 bots for the scan, freed by pbSimClearReference; for the
+ * compare 16 bytes per bot of the batch (now, kept, dx, dy) and 80 per member (the row, whose sum_q2 fields hold the two
+ * partial sums on the device), allocated by the first compare, kept, freed by pbSimDestroy. */
+typedef struct pbRearrangementStats {  /* 80 bytes */
+  unsigned long long bonds_marked, bonds_now, bonds_kept; /* directed; all even */
+  unsigned bots_unchanged;  /* kept == marked && kept == now: the same neighbour set */
+  unsigned bots_lost;       /* kept < marked */
+  unsigned bots_gained;     /* kept < now */
+  unsigned measured;
+  long long sum_qx, sum_qy;                    /* over measured bots, units of 2^-20 */
+  unsigned long long sum_q2_lo, sum_q2_hi;     /* sum of s as one 128-bit integer, units of 2^-40 */
+  unsigned long long max_q2;                   /* largest s; 0 with no measured bot */
+} pbRearrangementStats;
+int pbSimMarkReference(pbSim *sim, float linkGap);
+int pbSimClearReference(pbSim *sim);
+int pbSimGetReferenceInfo(pbSim *sim, int *marked, float *linkGap, float *time, unsigned long long *entries);
+int pbSimRearrangementStats(pbSim *sim, pbRearrangementStats *rows /* nsims entries */);
+int pbSimRearrangementOf(pbSim *sim, unsigned member, float *disp /* 2 n: dx, dy verbatim, unmeasured bots included */,
+                         unsigned *marked, unsigned *now, unsigned *kept /* n each, ORIGINAL order; NULL skipped */);
+int pbSimGetRearrangementTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

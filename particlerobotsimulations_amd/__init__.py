@@ -15,7 +15,7 @@ from . import _capi
 from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
-           "radial_distribution"]
+           "radial_distribution", "mean_squared_displacement"]
 
 
 def radial_distribution(counts, r_max, density, n):
@@ -28,6 +28,21 @@ def radial_distribution(counts, r_max, density, n):
     edges = np.arange(bins + 1, dtype=np.float64) * (float(r_max) / bins)
     area = np.pi * (edges[1:] ** 2 - edges[:-1] ** 2)
     return 0.5 * (edges[1:] + edges[:-1]), counts / (float(n) * float(density) * area)
+
+
+def mean_squared_displacement(row, subtract_drift=False):
+    """The mean squared displacement since the mark from one row of rearrangement() (pure Python): sum_q2 / 2^40 /
+    measured, and with subtract_drift the squared mean displacement (sum_qx^2 + sum_qy^2) / measured^2 / 2^40 taken
+    off, which leaves the variance about the common drift.  Formed from the integers as one exact fraction and
+    converted to float once; NaN when no bot was measured."""
+    from fractions import Fraction
+    m = int(row["measured"])
+    if m == 0:
+        return float("nan")
+    num = int(row["sum_q2"]) * m
+    if subtract_drift:
+        num -= int(row["sum_qx"]) ** 2 + int(row["sum_qy"]) ** 2
+    return float(Fraction(num, m * m << 40))
 
 
 def self_test(div_samples=1 << 32):
@@ -509,6 +524,53 @@ class Sim:
         """(structure analyses run so far, device milliseconds of the last one)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetStructureTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetStructureTimes")
+        return int(n.value), float(ms.value)
+
+    def mark_reference(self, gap=0.0):
+        """Keep every member's positions and link network at `gap` on the device as the reference that rearrangement()
+        compares against (pbSimMarkReference).  A new mark replaces the old one; re-sorts and set_state do not
+        invalidate it; it is not part of a checkpoint."""
+        _capi.check(_capi.lib().pbSimMarkReference(self._h, float(gap)), "pbSimMarkReference")
+
+    def clear_reference(self):
+        """Free the mark (pbSimClearReference)."""
+        _capi.check(_capi.lib().pbSimClearReference(self._h), "pbSimClearReference")
+
+    def reference_info(self):
+        """The mark held: a dict of marked (bool), gap, time (fp32, when it was taken) and entries (directed links of
+        the whole batch); zeros without one (pbSimGetReferenceInfo)."""
+        held, gap, t, e = C.c_int(0), C.c_float(0.0), C.c_float(0.0), C.c_ulonglong(0)
+        _capi.check(_capi.lib().pbSimGetReferenceInfo(self._h, C.byref(held), C.byref(gap), C.byref(t), C.byref(e)),
+                    "pbSimGetReferenceInfo")
+        return {"marked": bool(held.value), "gap": float(gap.value), "time": float(t.value), "entries": int(e.value)}
+
+    def rearrangement(self):
+        """Every member's state as it is now against the mark, on the device (pbSimRearrangementStats): a list of dicts,
+        one per member: bonds_marked / bonds_now / bonds_kept (directed links at the mark, now, and in both),
+        bots_unchanged / bots_lost / bots_gained, measured, sum_qx / sum_qy (displacement sums, units of 2^-20), sum_q2
+        (the sum of squared displacements as one Python int, units of 2^-40) and max_q2.  mean_squared_displacement()
+        turns a row into the MSD."""
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbRearrangementStats * nsims)()
+        _capi.check(_capi.lib().pbSimRearrangementStats(self._h, rows), "pbSimRearrangementStats")
+        return [_capi.rearrangement_row(r) for r in rows]
+
+    def rearrangement_of(self, member=0):
+        """One member per bot, original order (pbSimRearrangementOf): a dict of disp (float32, n x 2: dx, dy since the
+        mark, verbatim) and marked, now, kept (uint32: the bot's links at the mark, now, and in both)."""
+        n = self.n
+        out = {"disp": np.empty((n, 2), np.float32), "marked": np.empty(n, np.uint32), "now": np.empty(n, np.uint32),
+               "kept": np.empty(n, np.uint32)}
+        _capi.check(_capi.lib().pbSimRearrangementOf(self._h, int(member), *[_capi.np_ptr(out[k]) for k in
+                                                                            ("disp", "marked", "now", "kept")]),
+                    "pbSimRearrangementOf")
+        return out
+
+    def rearrangement_times(self):
+        """(marks and compares run so far, device milliseconds of the last one)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetRearrangementTimes(self._h, C.byref(n), C.byref(ms)),
+                    "pbSimGetRearrangementTimes")
         return int(n.value), float(ms.value)
 
 

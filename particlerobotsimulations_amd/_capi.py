@@ -106,6 +106,22 @@ def structure_row(r):
             "psi6": psi}
 
 
+class pbRearrangementStats(C.Structure):
+    _fields_ = [("bonds_marked", C.c_ulonglong), ("bonds_now", C.c_ulonglong), ("bonds_kept", C.c_ulonglong),
+                ("bots_unchanged", C.c_uint), ("bots_lost", C.c_uint), ("bots_gained", C.c_uint), ("measured", C.c_uint),
+                ("sum_qx", C.c_longlong), ("sum_qy", C.c_longlong),
+                ("sum_q2_lo", C.c_ulonglong), ("sum_q2_hi", C.c_ulonglong), ("max_q2", C.c_ulonglong)]
+
+
+def rearrangement_row(r):
+    """A pbRearrangementStats row as a dict of Python ints; sum_q2 is the 128-bit sum (sum_q2_hi * 2^64 + sum_q2_lo) as
+    one int.  Bond counts are directed; sum_qx / sum_qy are in units of 2^-20, sum_q2 and max_q2 in units of 2^-40."""
+    d = {name: int(getattr(r, name)) for name, _ in pbRearrangementStats._fields_
+         if name not in ("sum_q2_lo", "sum_q2_hi")}
+    d["sum_q2"] = (int(r.sum_q2_hi) << 64) | int(r.sum_q2_lo)
+    return d
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -175,6 +191,12 @@ SYMBOLS = {
     "pbSimStructureStats": (_I, [_VP, _F, C.POINTER(pbStructureStats)]),
     "pbSimHexaticOf": (_I, [_VP, _U, _F, _VP, _VP]),
     "pbSimGetStructureTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimMarkReference": (_I, [_VP, _F]),
+    "pbSimClearReference": (_I, [_VP]),
+    "pbSimGetReferenceInfo": (_I, [_VP, C.POINTER(_I), C.POINTER(_F), C.POINTER(_F), C.POINTER(C.c_ulonglong)]),
+    "pbSimRearrangementStats": (_I, [_VP, C.POINTER(pbRearrangementStats)]),
+    "pbSimRearrangementOf": (_I, [_VP, _U, _VP, _VP, _VP, _VP]),
+    "pbSimGetRearrangementTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

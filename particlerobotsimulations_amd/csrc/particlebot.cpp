@@ -1475,6 +1475,55 @@ bool Particlebot::hexatic(float linkGap, std::vector<double> &psi6, std::vector<
   return true;
 }
 
+bool Particlebot::markReference(float linkGap) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::markReference: the rearrangement analysis needs the fused engine\n");
+    return false;
+  }
+  if (pbSimMarkReference(sim, linkGap) != PB_OK) {
+    fprintf(stderr, "Particlebot::markReference: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::clearReference() {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::clearReference: the rearrangement analysis needs the fused engine\n");
+    return false;
+  }
+  return pbSimClearReference(sim) == PB_OK;
+}
+
+bool Particlebot::rearrangementStats(pbRearrangementStats &out) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::rearrangementStats: the rearrangement analysis needs the fused engine\n");
+    return false;
+  }
+  if (pbSimRearrangementStats(sim, &out) != PB_OK) {
+    fprintf(stderr, "Particlebot::rearrangementStats: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
+bool Particlebot::rearrangement(std::vector<float> &disp, std::vector<unsigned> &marked, std::vector<unsigned> &now,
+                                std::vector<unsigned> &kept) {
+  if (engineKind != Engine::Fused) {
+    fprintf(stderr, "Particlebot::rearrangement: the rearrangement analysis needs the fused engine\n");
+    return false;
+  }
+  disp.resize(2 * (size_t)params.nCells);
+  marked.resize(params.nCells);
+  now.resize(params.nCells);
+  kept.resize(params.nCells);
+  if (pbSimRearrangementOf(sim, 0, disp.data(), marked.data(), now.data(), kept.data()) != PB_OK) {
+    fprintf(stderr, "Particlebot::rearrangement: %s\n", pbGetLastErrorString());
+    return false;
+  }
+  return true;
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

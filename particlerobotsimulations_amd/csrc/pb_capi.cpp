@@ -332,6 +332,27 @@ int pbHostHexatic(void *hv, float gap, double *psi6, unsigned *neighbours) {
   return 0;
 }
 
+// rearrangement analysis of the resident state (Particlebot::markReference / rearrangementStats / rearrangement; fused
+// engine only): the mark at `gap`, the 80-byte pbRearrangementStats row, or the per-bot displacement (2 nCells floats)
+// and marked, present and kept bond counts (nCells each), original order, any of which may be NULL.  -1 on the other
+// engines, a bad gap, or a compare without a mark.
+int pbHostMarkReference(void *hv, float gap) { return ((HostSim *)hv)->bot->markReference(gap) ? 0 : -1; }
+
+int pbHostRearrangementStats(void *hv, pbRearrangementStats *out) {
+  return out && ((HostSim *)hv)->bot->rearrangementStats(*out) ? 0 : -1;
+}
+
+int pbHostRearrangementOf(void *hv, float *disp, unsigned *marked, unsigned *now, unsigned *kept) {
+  std::vector<float> d;
+  std::vector<unsigned> m, w, k;
+  if (!((HostSim *)hv)->bot->rearrangement(d, m, w, k)) return -1;
+  if (disp) memcpy(disp, d.data(), d.size() * sizeof(float));
+  if (marked) memcpy(marked, m.data(), m.size() * sizeof(unsigned));
+  if (now) memcpy(now, w.data(), w.size() * sizeof(unsigned));
+  if (kept) memcpy(kept, k.data(), k.size() * sizeof(unsigned));
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -3,7 +3,8 @@
 //
 // The engine's own cell lists are stale between re-sorts, so the analysis files the bots afresh, in scratch of its
 // own, and leaves the simulation untouched.  The filing front end (pbClusterFile: the first five kernels below) takes
-// the cell edge and also serves the contact export and the structure analysis (pb_contacts.hip, pb_structure.hip).
+// the cell edge and also serves the contact export, the structure analysis and the rearrangement analysis
+// (pb_contacts.hip, pb_structure.hip, pb_dynamics.hip).
 // For the whole batch at once:
 //   k_cluster_rmax      the largest finite radius (bit-pattern max, one atomic per workgroup), 4 bytes read back
 //   k_cluster_hash      key = member * cells + cell of a wrapped power-of-two grid whose edge is a little more than
@@ -400,6 +401,7 @@ void pbClusterFree(pbSim *S) {
   pbClockFree(C->clusterClock);
   pbContactsFree(C);
   pbStructureFree(C);
+  pbDynamicsFree(C);
   delete C;
   S->cluster = nullptr;
 }

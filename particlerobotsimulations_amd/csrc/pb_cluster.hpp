@@ -1,7 +1,7 @@
-// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip and pb_structure.hip: the scratch object with its
-// three clocks, the fresh grid, the wave helpers, the walk over a bot's nine cells (pbWalkNine) and the link rule
-// (pbWhenLinked) that every neighbour sweep of the analysis layer is built on, the front end that files the bots (rmax,
-// hash, sort, gather, cell starts) and the argument checks of the entry points.
+// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip and pb_dynamics.hip: the scratch
+// object with its four clocks, the fresh grid, the wave helpers, the workgroup scan, the walk over a bot's nine cells
+// (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour sweep of the analysis layer is built on, the front
+// end that files the bots (rmax, hash, sort, gather, cell starts) and the argument checks of the entry points.
 #pragma once
 
 #include "pb_engine.hpp"
@@ -23,7 +23,7 @@ struct PbClusterScratch {
   pbClusterStats *rows = nullptr;     // nsims
   uint32_t *flag = nullptr;           // [0] changed, [1] rmax bits
   hipEvent_t ev0 = nullptr;           // the front end's first launch: where every clock starts
-  PbAnalysisClock clusterClock, contactClock, structureClock;
+  PbAnalysisClock clusterClock, contactClock, structureClock, dynamicsClock;
   uint32_t gxLog2 = 2, gyLog2 = 2;
   unsigned rounds = 0;
   // what the last analysis left behind for the contact export (pb_contacts.hip)
@@ -44,6 +44,21 @@ struct PbClusterScratch {
   uint32_t *sNb = nullptr;                   // total, ORIGINAL order: neighbours
   pbStructureStats *sRows = nullptr;         // nsims
   double *sPsi = nullptr;                    // 2 n: one member's psi6
+  // rearrangement analysis (pb_dynamics.hip).  The mark: allocated by the first pbSimMarkReference, entries grown when a
+  // mark needs more, kept until pbSimClearReference
+  bool dMarked = false;                      // a mark is held: everything below describes it
+  float dGap = 0.0f, dTime = 0.0f;           // its linkGap and the batch's fp32 time when it was taken
+  unsigned long long dEntries = 0;           // directed entries of the whole batch
+  float2 *dPos0 = nullptr;                   // total, ORIGINAL order: the marked positions, bit for bit
+  uint32_t *dOffsets = nullptr;              // total + 1, ORIGINAL order: the marked network's CSR over the whole batch
+  uint32_t *dOther = nullptr;                // dOtherCap entries: `other`, member-local original index
+  unsigned long long dOtherCap = 0;
+  unsigned long long *dParts = nullptr;      // ceil(total / 256) + 2: block sums, then the total, then the flag
+  // the compare: allocated by the first one, kept, freed by pbSimDestroy
+  uint32_t *dNow = nullptr, *dKept = nullptr;  // total each, ORIGINAL order
+  float2 *dDisp = nullptr;                   // total, ORIGINAL order: dx, dy
+  pbRearrangementStats *dRows = nullptr;     // nsims; sum_q2_lo / sum_q2_hi hold the two partial sums until the host
+                                             // composes them
 };
 
 namespace {
@@ -117,6 +132,31 @@ PB_DEV unsigned long long waveSumU64(unsigned long long v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v += shflXor64(v, m);
   return v;
+}
+
+// exclusive prefix of v over the workgroup and the workgroup's total: an inclusive scan inside each wave with
+// shuffles, the four wave totals through LDS.  Every lane of the workgroup must call it.
+PB_DEV unsigned long long blockScanExclusive(unsigned long long v, unsigned long long *sWave,
+                                             unsigned long long &blockTotal) {
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  unsigned long long incl = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const unsigned long long up = shflUp64(incl, d);
+    if (lane >= (uint32_t)d) incl += up;
+  }
+  if (lane == 63u) sWave[w] = incl;
+  __syncthreads();
+  unsigned long long before = 0ull, tot = 0ull;
+#pragma unroll
+  for (uint32_t k = 0; k < CT / 64; k++) {
+    const unsigned long long s = sWave[k];
+    before += k < w ? s : 0ull;
+    tot += s;
+  }
+  __syncthreads();  // sWave may be written again
+  blockTotal = tot;
+  return before + incl - v;
 }
 
 // ---- the walk ------------------------------------------------------------------------------------------------------------
@@ -216,7 +256,7 @@ inline void pbClockFree(PbAnalysisClock &K) {
   if (K.end) (void)hipEventDestroy(K.end);
   K = PbAnalysisClock();
 }
-// the body of pbSimGet{Cluster,Contact,Structure}Times; K points into S's scratch object
+// the body of pbSimGet{Cluster,Contact,Structure,Rearrangement}Times; K points into S's scratch object
 inline int pbClockGet(const char *fn, const pbSim *S, PbAnalysisClock PbClusterScratch::*K, unsigned long long *runs,
                       float *last_device_ms) {
   if (!S) {
@@ -239,12 +279,19 @@ int pbClusterFile(pbSim *S, double reach, double perRmax);
 // The whole cluster pipeline (the front end with reach = gap, perRmax = 2); leaves cpr, the cell starts, parent (roots),
 // degree and the rows on the device and the stream drained.                                             pb_cluster.hip
 int pbClusterAnalyse(pbSim *S, float gap);
-// The argument checks the seven entry points share after their own pointer checks, in this order: linkGap finite and
-// >= 0 (when gap is given), member inside the batch (when member is given), the batch within what a launch can index.
+// The argument checks the entry points of the analysis layer share after their own pointer checks, in this order:
+// linkGap finite and >= 0 (when gap is given), member inside the batch (when member is given), the batch within what a
+// launch can index.
 // Nothing here touches the device; the gap check needs no look at the handle, the other two read the host-side batch
 // object, so they need a real one.                                                                       pb_cluster.hip
 int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const unsigned *member);
 // frees the contact export's buffers, if any (pbClusterFree)                                           pb_contacts.hip
 void pbContactsFree(PbClusterScratch *C);
+// k_contact_scan's three launches, queued on the batch's stream: offsets[0 .. n] = the exclusive prefix sum of
+// degree[0 .. n), parts (ceil(n / 256) + 1 words at the least) the scan's block sums with the 64-bit total in
+// parts[ceil(n / 256)].  Offsets are 32-bit: the caller reads the total before it trusts them.         pb_contacts.hip
+int pbContactScan(pbSim *S, const uint32_t *degree, uint32_t n, unsigned long long *parts, uint32_t *offsets);
 // frees the structure analysis' buffers, if any (pbClusterFree)                                       pb_structure.hip
 void pbStructureFree(PbClusterScratch *C);
+// frees the rearrangement analysis' buffers and the mark, if any (pbClusterFree)                       pb_dynamics.hip
+void pbDynamicsFree(PbClusterScratch *C);

@@ -29,31 +29,6 @@ namespace {
 // one link entry as the compiler's own 16-byte vector (other, gap, fx, fy as bit patterns): a single dwordx4 access
 typedef uint32_t LinkBits __attribute__((ext_vector_type(4)));
 
-// exclusive prefix of v over the workgroup and the workgroup's total: an inclusive scan inside each wave with
-// shuffles, the four wave totals through LDS.  Every lane of the workgroup must call it.
-PB_DEV unsigned long long blockScanExclusive(unsigned long long v, unsigned long long *sWave,
-                                             unsigned long long &blockTotal) {
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  unsigned long long incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long up = shflUp64(incl, d);
-    if (lane >= (uint32_t)d) incl += up;
-  }
-  if (lane == 63u) sWave[w] = incl;
-  __syncthreads();
-  unsigned long long before = 0ull, tot = 0ull;
-#pragma unroll
-  for (uint32_t k = 0; k < CT / 64; k++) {
-    const unsigned long long s = sWave[k];
-    before += k < w ? s : 0ull;
-    tot += s;
-  }
-  __syncthreads();  // sWave may be written again
-  blockTotal = tot;
-  return before + incl - v;
-}
-
 // phase 0: parts[b] = sum of workgroup b's degrees.  phase 1 (one workgroup): parts[0 .. blocks) becomes its own
 // exclusive prefix, parts[blocks] the total.  phase 2: offsets[l] = parts[b] + the prefix inside workgroup b, and
 // offsets[n] behind the last bot.
@@ -87,6 +62,20 @@ __global__ __launch_bounds__(CT) void k_contact_scan(int phase, const uint32_t *
     if (l == n - 1u) offsets[n] = (uint32_t)(off + v);
   }
 }
+
+}  // namespace
+
+// The scan's three launches (pb_cluster.hpp).
+int pbContactScan(pbSim *S, const uint32_t *degree, uint32_t n, unsigned long long *parts, uint32_t *offsets) {
+  const uint32_t blocks = cdiv(n, CT);
+  for (int phase = 0; phase < 3; phase++)
+    hipLaunchKernelGGL(k_contact_scan, phase == 1 ? dim3(1) : dim3(blocks), dim3(CT), 0, S->stream, phase, degree, n,
+                       blocks, parts, offsets);
+  PB_TRY(hipGetLastError());
+  return PB_OK;
+}
+
+namespace {
 
 __global__ __launch_bounds__(CT) void k_contact_gather_vel(const float4 *__restrict__ cpr,
                                                            const uint32_t *__restrict__ sortedSlots,
@@ -195,10 +184,8 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
   const dim3 b(CT), g(blocks);
   unsigned long long *total = C->cParts + blocks, *flag = total + 1;
   PB_TRY(hipMemsetAsync(total, 0, sizeof(unsigned long long) * 2, S->stream));
-  for (int phase = 0; phase < 3; phase++)
-    hipLaunchKernelGGL(k_contact_scan, phase == 1 ? dim3(1) : g, b, 0, S->stream, phase, C->degree + base, n, blocks,
-                       C->cParts, C->cOffsets);
-  PB_TRY(hipGetLastError());
+  rc = pbContactScan(S, C->degree + base, n, C->cParts, C->cOffsets);
+  if (rc != PB_OK) return rc;
   unsigned long long count = 0ull;
   PB_TRY(hipMemcpyAsync(&count, total, sizeof count, hipMemcpyDeviceToHost, S->stream));
   PB_TRY(hipStreamSynchronize(S->stream));

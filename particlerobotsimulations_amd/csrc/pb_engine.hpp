@@ -10,6 +10,7 @@
 //   pb_cluster.hip   cluster analysis: connected components of the contact graph (pbSimClusterStats)
 //   pb_contacts.hip  the contact network of one member: links, gaps, pair forces, virial (pbSimContactsOf)
 //   pb_structure.hip structure analysis: radial pair counts and the hexatic order (pbSimRadialCounts, pbSimStructureStats)
+//   pb_dynamics.hip  rearrangement analysis: a marked reference, bond survival and displacements (pbSimMarkReference)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 #pragma once

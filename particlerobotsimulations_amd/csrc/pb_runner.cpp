@@ -4,6 +4,7 @@
 //                   [--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]]
 //                   [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]]
 //                   [--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]]
+//                   [--rearrange FILE [--rearrange-gap G] [--rearrange-window]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -41,6 +42,13 @@
 // --rdf FILE writes the radial pair counts of the FINAL state once, when the run ends (Particlebot::radialCounts): the
 // header `RLo, RHi, Count`, then one row per bin, the edges b * R / B and (b + 1) * R / B in double as %.9g;
 // --rdf-rmax R (default 10 * max_radius, finite and > 0) and --rdf-bins B (default 200, 1 ... 4096).
+// --rearrange FILE marks a reference on the device at the run's first dump time (Particlebot::markReference; time 0, or
+// the time a resumed run starts at: the mark is not part of a checkpoint) and appends, at every dump time, the first
+// included, one row that compares the state with it (Particlebot::rearrangementStats): `Time, MarkTime, BondsMarked,
+// BondsNow, BondsKept, Unchanged, Lost, Gained, Measured, SumQx, SumQy, SumQ2, MaxQ2`, the header once, every number
+// the integer it is (bonds directed, SumQx / SumQy in units of 2^-20, SumQ2 / MaxQ2 of 2^-40; SumQ2 in decimal from its
+// 128 bits); --rearrange-gap G (default 0, finite and >= 0) is the mark's linkGap; --rearrange-window marks again after
+// each row, so that every row describes one dump interval.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -86,6 +94,17 @@ bool readTrailer(const std::string &path, RunTrailer &t) {
   return ok;
 }
 
+// a 128-bit unsigned integer in decimal
+std::string decimal128(unsigned long long hi, unsigned long long lo) {
+  unsigned __int128 v = ((unsigned __int128)hi << 64) | lo;
+  std::string s;
+  do {
+    s.insert(s.begin(), (char)('0' + (int)(v % 10)));
+    v /= 10;
+  } while (v != 0);
+  return s;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -102,6 +121,9 @@ int main(int argc, char **argv) {
   std::string structurePath, rdfPath;
   float structureGap = 0.0f, rdfRmax = 0.0f;  // rdfRmax 0: 10 * max_radius, once the configuration is loaded
   long rdfBins = 200;
+  std::string rearrangePath;
+  float rearrangeGap = 0.0f;
+  bool rearrangeWindow = false;
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -155,6 +177,14 @@ int main(int argc, char **argv) {
       char *end = nullptr;
       rdfBins = strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end || rdfBins < 1 || rdfBins > (long)PB_RADIAL_MAX_BINS) badArg = true;
+    } else if (!strcmp(argv[i], "--rearrange") && i + 1 < argc) {
+      rearrangePath = argv[++i];
+    } else if (!strcmp(argv[i], "--rearrange-gap") && i + 1 < argc) {
+      char *end = nullptr;
+      rearrangeGap = strtof(argv[++i], &end);
+      if (end == argv[i] || *end || !(rearrangeGap >= 0.0f) || std::isinf(rearrangeGap)) badArg = true;
+    } else if (!strcmp(argv[i], "--rearrange-window")) {
+      rearrangeWindow = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -176,7 +206,7 @@ int main(int argc, char **argv) {
       fprintf(stderr,
               "usage: %s [config.cfg] [--set NAME VALUE]... [--engine fused|legacy] [--quiet] "
               "[--frames DIR [--frame-size PIXELS] [--frame-style plain|reference] [--frame-render host|device]] [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]] "
-              "[--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
+              "[--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]] [--rearrange FILE [--rearrange-gap G] [--rearrange-window]] [--resume FILE [--overwrite-csv]] [--checkpoint FILE "
               "[--checkpoint-every SECONDS] [--checkpoint-steps N]] [--final-checkpoint FILE]\n",
               argv[0]);
       return 2;
@@ -196,6 +226,10 @@ int main(int argc, char **argv) {
   }
   if (!rdfPath.empty() && engine != Particlebot::Engine::Fused) {
     fprintf(stderr, "--rdf needs the fused engine (the analysis runs on its resident state)\n");
+    return 2;
+  }
+  if (!rearrangePath.empty() && engine != Particlebot::Engine::Fused) {
+    fprintf(stderr, "--rearrange needs the fused engine (the analysis runs on its resident state)\n");
     return 2;
   }
   if (!cfg.loadFile(path)) fprintf(stderr, "warning: cannot open %s, running on defaults\n", path.c_str());
@@ -293,6 +327,8 @@ int main(int argc, char **argv) {
   };
   auto lastCkptWall = std::chrono::steady_clock::now();
   long lastCkptStep = stepsDone;
+  bool referenceMarked = false;
+  float markTime = 0.0f;
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!ckptPath.empty() && stepsDone > lastCkptStep) {
@@ -332,6 +368,31 @@ int main(int argc, char **argv) {
       for (int k = 0; k < 8; k++) fprintf(sf, ", %u", ss.coordination[k]);
       fprintf(sf, "\n");
       if (fclose(sf) != 0) return 1;
+    }
+    if (!rearrangePath.empty() && sim.dumpDue(cfg.dump_interval)) {
+      if (!referenceMarked) {  // the run's first dump time
+        if (!sim.markReference(rearrangeGap)) return 1;
+        referenceMarked = true;
+        markTime = sim.getTime();
+      }
+      pbRearrangementStats rs;
+      if (!sim.rearrangementStats(rs)) return 1;
+      FILE *af = fopen(rearrangePath.c_str(), sim.getTime() == 0.0f ? "w" : "a");
+      if (!af) {
+        fprintf(stderr, "cannot open %s\n", rearrangePath.c_str());
+        return 1;
+      }
+      if (fseek(af, 0, SEEK_END) == 0 && ftell(af) == 0)  // a fresh file, or a resumed run that appends to none
+        fprintf(af, "Time, MarkTime, BondsMarked, BondsNow, BondsKept, Unchanged, Lost, Gained, Measured, SumQx, SumQy, "
+                    "SumQ2, MaxQ2\n");
+      fprintf(af, "%f, %f, %llu, %llu, %llu, %u, %u, %u, %u, %lld, %lld, %s, %llu\n", sim.getTime(), markTime,
+              rs.bonds_marked, rs.bonds_now, rs.bonds_kept, rs.bots_unchanged, rs.bots_lost, rs.bots_gained, rs.measured,
+              rs.sum_qx, rs.sum_qy, decimal128(rs.sum_q2_hi, rs.sum_q2_lo).c_str(), rs.max_q2);
+      if (fclose(af) != 0) return 1;
+      if (rearrangeWindow) {  // the next row describes the interval that starts here
+        if (!sim.markReference(rearrangeGap)) return 1;
+        markTime = sim.getTime();
+      }
     }
     if (!framesDir.empty() && stepsDone % frameEvery == 0) {
       char name[64];

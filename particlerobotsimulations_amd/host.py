@@ -115,6 +115,12 @@ def lib():
     L.pbHostStructureStats.restype = C.c_int
     L.pbHostHexatic.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
     L.pbHostHexatic.restype = C.c_int
+    L.pbHostMarkReference.argtypes = [C.c_void_p, C.c_float]
+    L.pbHostMarkReference.restype = C.c_int
+    L.pbHostRearrangementStats.argtypes = [C.c_void_p, C.c_void_p]
+    L.pbHostRearrangementStats.restype = C.c_int
+    L.pbHostRearrangementOf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.pbHostRearrangementOf.restype = C.c_int
     _lib = L
     return L
 
@@ -328,6 +334,35 @@ class HostSim:
         if lib().pbHostHexatic(self._h, float(gap), psi.ctypes.data_as(C.c_void_p), nb.ctypes.data_as(C.c_void_p)) != 0:
             raise RuntimeError("hexatic: the structure analysis needs the fused engine and a finite gap >= 0")
         return psi, nb
+
+    def mark_reference(self, gap=0.0):
+        """Keep the positions and the link network at `gap` on the device as the reference of rearrangement()
+        (pbSimMarkReference; fused engine only).  A new mark replaces the old one."""
+        if lib().pbHostMarkReference(self._h, float(gap)) != 0:
+            raise RuntimeError("mark_reference: the rearrangement analysis needs the fused engine and a finite gap >= 0")
+
+    def rearrangement(self):
+        """The state as it is now against the mark, on the device (pbSimRearrangementStats; fused engine only): a list
+        with one dict: bonds_marked / bonds_now / bonds_kept (directed), bots_unchanged / bots_lost / bots_gained,
+        measured, sum_qx / sum_qy (units of 2^-20), sum_q2 (a Python int, units of 2^-40) and max_q2."""
+        from . import _capi
+        row = _capi.pbRearrangementStats()
+        if lib().pbHostRearrangementStats(self._h, C.byref(row)) != 0:
+            raise RuntimeError("rearrangement: the rearrangement analysis needs the fused engine and a marked reference")
+        return [_capi.rearrangement_row(row)]
+
+    def rearrangement_of(self, member=0):
+        """Per bot, original order (pbSimRearrangementOf; fused engine only): a dict of disp (float32, n x 2: dx, dy since
+        the mark) and marked, now, kept (uint32: bonds at the mark, now, and in both)."""
+        if int(member) != 0:
+            raise IndexError(member)
+        n = self.n
+        out = {"disp": np.empty((n, 2), np.float32), "marked": np.empty(n, np.uint32), "now": np.empty(n, np.uint32),
+               "kept": np.empty(n, np.uint32)}
+        if lib().pbHostRearrangementOf(self._h, *[out[k].ctypes.data_as(C.c_void_p)
+                                                  for k in ("disp", "marked", "now", "kept")]) != 0:
+            raise RuntimeError("rearrangement_of: the rearrangement analysis needs the fused engine and a marked reference")
+        return out
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
