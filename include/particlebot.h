@@ -270,6 +270,10 @@ class Particlebot {
   bool writeFrame(const char *path, int width, int height, float centerX, float centerY, float halfExtent,
                   float lightRadius, bool referenceStyle);
   void resetDisplayRing();
+  /* the analyses above: refuse (with a line on stderr) unless the engine is the fused one, then run `call` and report
+   * what the engine says when it fails (particlebot.cpp) */
+  template <class Call>
+  bool onFusedEngine(const char *method, const char *family, Call call, bool reportFailure = true);
 
   /* host mirrors (original bot order) */
   std::vector<float> hPosV, hVelV, hRadV, hPhaseV, hFreqV;

@@ -1374,154 +1374,98 @@ bool Particlebot::renderFrame(std::vector<unsigned char> &rgb, int width, int he
   return true;
 }
 
+// The analyses' common shell.  Only the fused engine has them (sim is null on the others), so the engine is looked at
+// before `call` runs; `call` sizes the outputs, makes the pbSim* call(s) and returns the engine's code.  The refusal
+// (unless family is null) and the engine's last error (unless reportFailure is off) go to stderr under `method`.
+template <class Call>
+bool Particlebot::onFusedEngine(const char *method, const char *family, Call call, bool reportFailure) {
+  if (engineKind != Engine::Fused) {
+    if (family) fprintf(stderr, "Particlebot::%s: the %s needs the fused engine\n", method, family);
+    return false;
+  }
+  if (call() == PB_OK) return true;
+  if (reportFailure) fprintf(stderr, "Particlebot::%s: %s\n", method, pbGetLastErrorString());
+  return false;
+}
+
 bool Particlebot::renderStats(unsigned long long &frames, float &lastDeviceMs) {
-  return engineKind == Engine::Fused && pbSimGetRenderStats(sim, &frames, &lastDeviceMs) == PB_OK;
+  auto call = [&] { return pbSimGetRenderStats(sim, &frames, &lastDeviceMs); };
+  return onFusedEngine("renderStats", nullptr, call, false);  // (says nothing either way)
 }
 
 bool Particlebot::clusterStats(float linkGap, pbClusterStats &out) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::clusterStats: the cluster analysis needs the fused engine\n");
-    return false;
-  }
-  if (pbSimClusterStats(sim, linkGap, &out) != PB_OK) {
-    fprintf(stderr, "Particlebot::clusterStats: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("clusterStats", "cluster analysis", [&] { return pbSimClusterStats(sim, linkGap, &out); });
 }
 
 bool Particlebot::clusterLabels(float linkGap, std::vector<unsigned> &labels, std::vector<unsigned> &degree) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::clusterLabels: the cluster analysis needs the fused engine\n");
-    return false;
-  }
-  labels.resize(params.nCells);
-  degree.resize(params.nCells);
-  if (pbSimClusterLabelsOf(sim, 0, linkGap, labels.data(), degree.data()) != PB_OK) {
-    fprintf(stderr, "Particlebot::clusterLabels: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("clusterLabels", "cluster analysis", [&] {
+    labels.resize(params.nCells);
+    degree.resize(params.nCells);
+    return pbSimClusterLabelsOf(sim, 0, linkGap, labels.data(), degree.data());
+  });
 }
 
 bool Particlebot::contacts(float linkGap, std::vector<unsigned> &offsets, std::vector<pbContactLink> &links) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::contacts: the contact export needs the fused engine\n");
-    return false;
-  }
-  offsets.resize((size_t)params.nCells + 1);
-  unsigned long long entries = 0;
-  int rc = pbSimContactsOf(sim, 0, linkGap, nullptr, nullptr, 0, &entries);  // size, then fetch
-  if (rc == PB_OK) {
-    links.resize(entries);
-    rc = pbSimContactsOf(sim, 0, linkGap, offsets.data(), links.data(), links.size(), &entries);
-  }
-  if (rc != PB_OK) {
-    fprintf(stderr, "Particlebot::contacts: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("contacts", "contact export", [&] {
+    offsets.resize((size_t)params.nCells + 1);
+    unsigned long long entries = 0;
+    int rc = pbSimContactsOf(sim, 0, linkGap, nullptr, nullptr, 0, &entries);  // size, then fetch
+    if (rc == PB_OK) {
+      links.resize(entries);
+      rc = pbSimContactsOf(sim, 0, linkGap, offsets.data(), links.data(), links.size(), &entries);
+    }
+    return rc;
+  });
 }
 
 bool Particlebot::contactVirial(float linkGap, std::vector<double> &virial) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::contactVirial: the contact export needs the fused engine\n");
-    return false;
-  }
-  virial.resize(4 * (size_t)params.nCells);
-  if (pbSimContactVirialOf(sim, 0, linkGap, virial.data()) != PB_OK) {
-    fprintf(stderr, "Particlebot::contactVirial: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("contactVirial", "contact export", [&] {
+    virial.resize(4 * (size_t)params.nCells);
+    return pbSimContactVirialOf(sim, 0, linkGap, virial.data());
+  });
 }
 
 bool Particlebot::radialCounts(float rMax, unsigned bins, std::vector<unsigned long long> &counts) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::radialCounts: the structure analysis needs the fused engine\n");
-    return false;
-  }
-  counts.assign(bins >= 1 && bins <= PB_RADIAL_MAX_BINS ? bins : 1, 0ull);
-  if (pbSimRadialCounts(sim, rMax, bins, counts.data()) != PB_OK) {
-    fprintf(stderr, "Particlebot::radialCounts: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("radialCounts", "structure analysis", [&] {
+    counts.assign(bins >= 1 && bins <= PB_RADIAL_MAX_BINS ? bins : 1, 0ull);
+    return pbSimRadialCounts(sim, rMax, bins, counts.data());
+  });
 }
 
 bool Particlebot::structureStats(float linkGap, pbStructureStats &out) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::structureStats: the structure analysis needs the fused engine\n");
-    return false;
-  }
-  if (pbSimStructureStats(sim, linkGap, &out) != PB_OK) {
-    fprintf(stderr, "Particlebot::structureStats: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("structureStats", "structure analysis", [&] { return pbSimStructureStats(sim, linkGap, &out); });
 }
 
 bool Particlebot::hexatic(float linkGap, std::vector<double> &psi6, std::vector<unsigned> &neighbours) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::hexatic: the structure analysis needs the fused engine\n");
-    return false;
-  }
-  psi6.resize(2 * (size_t)params.nCells);
-  neighbours.resize(params.nCells);
-  if (pbSimHexaticOf(sim, 0, linkGap, psi6.data(), neighbours.data()) != PB_OK) {
-    fprintf(stderr, "Particlebot::hexatic: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("hexatic", "structure analysis", [&] {
+    psi6.resize(2 * (size_t)params.nCells);
+    neighbours.resize(params.nCells);
+    return pbSimHexaticOf(sim, 0, linkGap, psi6.data(), neighbours.data());
+  });
 }
 
 bool Particlebot::markReference(float linkGap) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::markReference: the rearrangement analysis needs the fused engine\n");
-    return false;
-  }
-  if (pbSimMarkReference(sim, linkGap) != PB_OK) {
-    fprintf(stderr, "Particlebot::markReference: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("markReference", "rearrangement analysis", [&] { return pbSimMarkReference(sim, linkGap); });
 }
 
-bool Particlebot::clearReference() {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::clearReference: the rearrangement analysis needs the fused engine\n");
-    return false;
-  }
-  return pbSimClearReference(sim) == PB_OK;
+bool Particlebot::clearReference() {  // (a clear that fails says nothing)
+  return onFusedEngine("clearReference", "rearrangement analysis", [&] { return pbSimClearReference(sim); }, false);
 }
 
 bool Particlebot::rearrangementStats(pbRearrangementStats &out) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::rearrangementStats: the rearrangement analysis needs the fused engine\n");
-    return false;
-  }
-  if (pbSimRearrangementStats(sim, &out) != PB_OK) {
-    fprintf(stderr, "Particlebot::rearrangementStats: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  auto call = [&] { return pbSimRearrangementStats(sim, &out); };
+  return onFusedEngine("rearrangementStats", "rearrangement analysis", call);
 }
 
 bool Particlebot::rearrangement(std::vector<float> &disp, std::vector<unsigned> &marked, std::vector<unsigned> &now,
                                 std::vector<unsigned> &kept) {
-  if (engineKind != Engine::Fused) {
-    fprintf(stderr, "Particlebot::rearrangement: the rearrangement analysis needs the fused engine\n");
-    return false;
-  }
-  disp.resize(2 * (size_t)params.nCells);
-  marked.resize(params.nCells);
-  now.resize(params.nCells);
-  kept.resize(params.nCells);
-  if (pbSimRearrangementOf(sim, 0, disp.data(), marked.data(), now.data(), kept.data()) != PB_OK) {
-    fprintf(stderr, "Particlebot::rearrangement: %s\n", pbGetLastErrorString());
-    return false;
-  }
-  return true;
+  return onFusedEngine("rearrangement", "rearrangement analysis", [&] {
+    disp.resize(2 * (size_t)params.nCells);
+    marked.resize(params.nCells);
+    now.resize(params.nCells);
+    kept.resize(params.nCells);
+    return pbSimRearrangementOf(sim, 0, disp.data(), marked.data(), now.data(), kept.data());
+  });
 }
 
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,

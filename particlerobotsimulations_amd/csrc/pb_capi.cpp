@@ -137,6 +137,12 @@ struct HostSim {
   Particlebot *bot = nullptr;
 };
 
+// a result to the caller's array, which may be NULL (not wanted)
+template <class T>
+void copyOut(T *dst, const std::vector<T> &src) {
+  if (dst && !src.empty()) memcpy(dst, src.data(), src.size() * sizeof(T));
+}
+
 }  // namespace
 
 extern "C" {
@@ -282,8 +288,8 @@ int pbHostClusterStats(void *hv, float gap, pbClusterStats *out) {
 int pbHostClusterLabels(void *hv, float gap, unsigned *labels, unsigned *degree) {
   std::vector<unsigned> l, d;
   if (!((HostSim *)hv)->bot->clusterLabels(gap, l, d)) return -1;
-  if (labels) memcpy(labels, l.data(), l.size() * sizeof(unsigned));
-  if (degree) memcpy(degree, d.data(), d.size() * sizeof(unsigned));
+  copyOut(labels, l);
+  copyOut(degree, d);
   return 0;
 }
 
@@ -297,15 +303,15 @@ int pbHostContacts(void *hv, float gap, unsigned *offsets, pbContactLink *links,
   if (!entries || !((HostSim *)hv)->bot->contacts(gap, o, l)) return -1;
   *entries = l.size();
   if (links && cap < l.size()) return -1;
-  if (offsets) memcpy(offsets, o.data(), o.size() * sizeof(unsigned));
-  if (links && !l.empty()) memcpy(links, l.data(), l.size() * sizeof(pbContactLink));
+  copyOut(offsets, o);
+  copyOut(links, l);
   return 0;
 }
 
 int pbHostContactVirial(void *hv, float gap, double *virial) {
   std::vector<double> v;
   if (!virial || !((HostSim *)hv)->bot->contactVirial(gap, v)) return -1;
-  memcpy(virial, v.data(), v.size() * sizeof(double));
+  copyOut(virial, v);
   return 0;
 }
 
@@ -315,7 +321,7 @@ int pbHostContactVirial(void *hv, float gap, double *virial) {
 int pbHostRadialCounts(void *hv, float rMax, unsigned bins, unsigned long long *counts) {
   std::vector<unsigned long long> c;
   if (!counts || !((HostSim *)hv)->bot->radialCounts(rMax, bins, c)) return -1;
-  memcpy(counts, c.data(), c.size() * sizeof(unsigned long long));
+  copyOut(counts, c);
   return 0;
 }
 
@@ -327,8 +333,8 @@ int pbHostHexatic(void *hv, float gap, double *psi6, unsigned *neighbours) {
   std::vector<double> p;
   std::vector<unsigned> nb;
   if (!((HostSim *)hv)->bot->hexatic(gap, p, nb)) return -1;
-  if (psi6) memcpy(psi6, p.data(), p.size() * sizeof(double));
-  if (neighbours) memcpy(neighbours, nb.data(), nb.size() * sizeof(unsigned));
+  copyOut(psi6, p);
+  copyOut(neighbours, nb);
   return 0;
 }
 
@@ -346,10 +352,10 @@ int pbHostRearrangementOf(void *hv, float *disp, unsigned *marked, unsigned *now
   std::vector<float> d;
   std::vector<unsigned> m, w, k;
   if (!((HostSim *)hv)->bot->rearrangement(d, m, w, k)) return -1;
-  if (disp) memcpy(disp, d.data(), d.size() * sizeof(float));
-  if (marked) memcpy(marked, m.data(), m.size() * sizeof(unsigned));
-  if (now) memcpy(now, w.data(), w.size() * sizeof(unsigned));
-  if (kept) memcpy(kept, k.data(), k.size() * sizeof(unsigned));
+  copyOut(disp, d);
+  copyOut(marked, m);
+  copyOut(now, w);
+  copyOut(kept, k);
   return 0;
 }
 
@@ -360,8 +366,8 @@ int pbHostCentroidTrail(void *hv, float *xy, float *times, unsigned *records) {
   std::vector<float> a, b;
   unsigned r = 0;
   if (!((HostSim *)hv)->bot->getCentroidTrail(a, b, r)) return -1;
-  if (xy) memcpy(xy, a.data(), sizeof(float) * a.size());
-  if (times) memcpy(times, b.data(), sizeof(float) * b.size());
+  copyOut(xy, a);
+  copyOut(times, b);
   if (records) *records = r;
   return 0;
 }

@@ -105,6 +105,20 @@ std::string decimal128(unsigned long long hi, unsigned long long lo) {
   return s;
 }
 
+// a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
+bool parseFloat(const char *text, float lowest, bool above, float &value) {
+  char *end = nullptr;
+  value = strtof(text, &end);
+  return end != text && !*end && (above ? value > lowest : value >= lowest) && !std::isinf(value);
+}
+
+// an analysis output; NULL after saying so
+FILE *openOutput(const std::string &path, const char *mode) {
+  FILE *f = fopen(path.c_str(), mode);
+  if (!f) fprintf(stderr, "cannot open %s\n", path.c_str());
+  return f;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
@@ -152,27 +166,19 @@ int main(int argc, char **argv) {
     } else if (!strcmp(argv[i], "--clusters") && i + 1 < argc) {
       clustersPath = argv[++i];
     } else if (!strcmp(argv[i], "--cluster-gap") && i + 1 < argc) {
-      char *end = nullptr;
-      clusterGap = strtof(argv[++i], &end);
-      if (end == argv[i] || *end || !(clusterGap >= 0.0f) || std::isinf(clusterGap)) badArg = true;
+      badArg = !parseFloat(argv[++i], 0.0f, false, clusterGap);
     } else if (!strcmp(argv[i], "--contacts") && i + 1 < argc) {
       contactsPath = argv[++i];
     } else if (!strcmp(argv[i], "--contact-gap") && i + 1 < argc) {
-      char *end = nullptr;
-      contactGap = strtof(argv[++i], &end);
-      if (end == argv[i] || *end || !(contactGap >= 0.0f) || std::isinf(contactGap)) badArg = true;
+      badArg = !parseFloat(argv[++i], 0.0f, false, contactGap);
     } else if (!strcmp(argv[i], "--structure") && i + 1 < argc) {
       structurePath = argv[++i];
     } else if (!strcmp(argv[i], "--structure-gap") && i + 1 < argc) {
-      char *end = nullptr;
-      structureGap = strtof(argv[++i], &end);
-      if (end == argv[i] || *end || !(structureGap >= 0.0f) || std::isinf(structureGap)) badArg = true;
+      badArg = !parseFloat(argv[++i], 0.0f, false, structureGap);
     } else if (!strcmp(argv[i], "--rdf") && i + 1 < argc) {
       rdfPath = argv[++i];
     } else if (!strcmp(argv[i], "--rdf-rmax") && i + 1 < argc) {
-      char *end = nullptr;
-      rdfRmax = strtof(argv[++i], &end);
-      if (end == argv[i] || *end || !(rdfRmax > 0.0f) || std::isinf(rdfRmax)) badArg = true;
+      badArg = !parseFloat(argv[++i], 0.0f, true, rdfRmax);
     } else if (!strcmp(argv[i], "--rdf-bins") && i + 1 < argc) {
       char *end = nullptr;
       rdfBins = strtol(argv[++i], &end, 10);
@@ -180,9 +186,7 @@ int main(int argc, char **argv) {
     } else if (!strcmp(argv[i], "--rearrange") && i + 1 < argc) {
       rearrangePath = argv[++i];
     } else if (!strcmp(argv[i], "--rearrange-gap") && i + 1 < argc) {
-      char *end = nullptr;
-      rearrangeGap = strtof(argv[++i], &end);
-      if (end == argv[i] || *end || !(rearrangeGap >= 0.0f) || std::isinf(rearrangeGap)) badArg = true;
+      badArg = !parseFloat(argv[++i], 0.0f, false, rearrangeGap);
     } else if (!strcmp(argv[i], "--rearrange-window")) {
       rearrangeWindow = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
@@ -212,26 +216,15 @@ int main(int argc, char **argv) {
       return 2;
     }
   }
-  if (!clustersPath.empty() && engine != Particlebot::Engine::Fused) {
-    fprintf(stderr, "--clusters needs the fused engine (the analysis runs on its resident state)\n");
-    return 2;
-  }
-  if (!contactsPath.empty() && engine != Particlebot::Engine::Fused) {
-    fprintf(stderr, "--contacts needs the fused engine (the export runs on its resident state)\n");
-    return 2;
-  }
-  if (!structurePath.empty() && engine != Particlebot::Engine::Fused) {
-    fprintf(stderr, "--structure needs the fused engine (the analysis runs on its resident state)\n");
-    return 2;
-  }
-  if (!rdfPath.empty() && engine != Particlebot::Engine::Fused) {
-    fprintf(stderr, "--rdf needs the fused engine (the analysis runs on its resident state)\n");
-    return 2;
-  }
-  if (!rearrangePath.empty() && engine != Particlebot::Engine::Fused) {
-    fprintf(stderr, "--rearrange needs the fused engine (the analysis runs on its resident state)\n");
-    return 2;
-  }
+  const struct { const char *flag; const std::string &path; const char *noun; } fusedOnly[] = {
+      {"--clusters", clustersPath, "analysis"},   {"--contacts", contactsPath, "export"},
+      {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
+      {"--rearrange", rearrangePath, "analysis"}};
+  for (const auto &f : fusedOnly)
+    if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
+      fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
+      return 2;
+    }
   if (!cfg.loadFile(path)) fprintf(stderr, "warning: cannot open %s, running on defaults\n", path.c_str());
   for (auto &kv : sets) cfg.setParam(kv.first, kv.second);
   srand(cfg.params.seed);  // main.cpp:929 (the class itself draws from a private, identical stream)
@@ -345,11 +338,8 @@ int main(int argc, char **argv) {
     if (!clustersPath.empty() && sim.dumpDue(cfg.dump_interval)) {
       pbClusterStats cs;
       if (!sim.clusterStats(clusterGap, cs)) return 1;
-      FILE *cf = fopen(clustersPath.c_str(), sim.getTime() == 0.0f ? "w" : "a");
-      if (!cf) {
-        fprintf(stderr, "cannot open %s\n", clustersPath.c_str());
-        return 1;
-      }
+      FILE *cf = openOutput(clustersPath, sim.getTime() == 0.0f ? "w" : "a");
+      if (!cf) return 1;
       if (sim.getTime() == 0.0f) fprintf(cf, "Time, Clusters, Largest, Isolated, Links, MaxDegree\n");
       fprintf(cf, "%f, %u, %u, %u, %llu, %u\n", sim.getTime(), cs.clusters, cs.largest, cs.isolated, cs.links,
               cs.max_degree);
@@ -358,11 +348,8 @@ int main(int argc, char **argv) {
     if (!structurePath.empty() && sim.dumpDue(cfg.dump_interval)) {
       pbStructureStats ss;
       if (!sim.structureStats(structureGap, ss)) return 1;
-      FILE *sf = fopen(structurePath.c_str(), sim.getTime() == 0.0f ? "w" : "a");
-      if (!sf) {
-        fprintf(stderr, "cannot open %s\n", structurePath.c_str());
-        return 1;
-      }
+      FILE *sf = openOutput(structurePath, sim.getTime() == 0.0f ? "w" : "a");
+      if (!sf) return 1;
       if (sim.getTime() == 0.0f) fprintf(sf, "Time, Bonds, Psi6Re, Psi6Im, C0, C1, C2, C3, C4, C5, C6, C7\n");
       fprintf(sf, "%f, %llu, %lld, %lld", sim.getTime(), ss.bonds, ss.psi6_re, ss.psi6_im);
       for (int k = 0; k < 8; k++) fprintf(sf, ", %u", ss.coordination[k]);
@@ -377,11 +364,8 @@ int main(int argc, char **argv) {
       }
       pbRearrangementStats rs;
       if (!sim.rearrangementStats(rs)) return 1;
-      FILE *af = fopen(rearrangePath.c_str(), sim.getTime() == 0.0f ? "w" : "a");
-      if (!af) {
-        fprintf(stderr, "cannot open %s\n", rearrangePath.c_str());
-        return 1;
-      }
+      FILE *af = openOutput(rearrangePath, sim.getTime() == 0.0f ? "w" : "a");
+      if (!af) return 1;
       if (fseek(af, 0, SEEK_END) == 0 && ftell(af) == 0)  // a fresh file, or a resumed run that appends to none
         fprintf(af, "Time, MarkTime, BondsMarked, BondsNow, BondsKept, Unchanged, Lost, Gained, Measured, SumQx, SumQy, "
                     "SumQ2, MaxQ2\n");
@@ -445,11 +429,8 @@ int main(int argc, char **argv) {
     std::vector<unsigned> offsets;
     std::vector<pbContactLink> links;
     if (!sim.contacts(contactGap, offsets, links)) return 1;
-    FILE *cf = fopen(contactsPath.c_str(), "w");
-    if (!cf) {
-      fprintf(stderr, "cannot open %s\n", contactsPath.c_str());
-      return 1;
-    }
+    FILE *cf = openOutput(contactsPath, "w");
+    if (!cf) return 1;
     fprintf(cf, "I, J, Gap, Fx, Fy\n");
     for (size_t i = 0; i + 1 < offsets.size(); i++)
       for (unsigned k = offsets[i]; k < offsets[i + 1]; k++)
@@ -461,11 +442,8 @@ int main(int argc, char **argv) {
     const float rmax = rdfRmax > 0.0f ? rdfRmax : 10.0f * p.max_radius;
     std::vector<unsigned long long> counts;
     if (!sim.radialCounts(rmax, (unsigned)rdfBins, counts)) return 1;
-    FILE *rf = fopen(rdfPath.c_str(), "w");
-    if (!rf) {
-      fprintf(stderr, "cannot open %s\n", rdfPath.c_str());
-      return 1;
-    }
+    FILE *rf = openOutput(rdfPath, "w");
+    if (!rf) return 1;
     fprintf(rf, "RLo, RHi, Count\n");
     for (size_t b = 0; b < counts.size(); b++)
       fprintf(rf, "%.9g, %.9g, %llu\n", (double)b * (double)rmax / (double)rdfBins,

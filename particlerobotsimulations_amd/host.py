@@ -46,6 +46,15 @@ class FlatConfig(C.Structure):
 
 
 _lib = None
+_ptr = _capi.np_ptr  # an array's address, for a void * argument
+_P, _F = C.c_void_p, C.c_float
+# the analysis wrappers of csrc/pb_capi.cpp: what each takes after the handle (all return 0 or -1)
+_ANALYSES = {
+    "pbHostClusterStats": [_F, _P], "pbHostClusterLabels": [_F, _P, _P],
+    "pbHostContacts": [_F, _P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)], "pbHostContactVirial": [_F, _P],
+    "pbHostRadialCounts": [_F, C.c_uint, _P], "pbHostStructureStats": [_F, _P], "pbHostHexatic": [_F, _P, _P],
+    "pbHostMarkReference": [_F], "pbHostRearrangementStats": [_P], "pbHostRearrangementOf": [_P, _P, _P, _P],
+}
 
 
 def lib():
@@ -100,27 +109,9 @@ def lib():
     L.pbHostRenderFrame.restype = C.c_int
     L.pbHostRenderStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)]
     L.pbHostRenderStats.restype = C.c_int
-    L.pbHostClusterStats.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
-    L.pbHostClusterStats.restype = C.c_int
-    L.pbHostClusterLabels.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
-    L.pbHostClusterLabels.restype = C.c_int
-    L.pbHostContacts.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_ulonglong,
-                                 C.POINTER(C.c_ulonglong)]
-    L.pbHostContacts.restype = C.c_int
-    L.pbHostContactVirial.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
-    L.pbHostContactVirial.restype = C.c_int
-    L.pbHostRadialCounts.argtypes = [C.c_void_p, C.c_float, C.c_uint, C.c_void_p]
-    L.pbHostRadialCounts.restype = C.c_int
-    L.pbHostStructureStats.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
-    L.pbHostStructureStats.restype = C.c_int
-    L.pbHostHexatic.argtypes = [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
-    L.pbHostHexatic.restype = C.c_int
-    L.pbHostMarkReference.argtypes = [C.c_void_p, C.c_float]
-    L.pbHostMarkReference.restype = C.c_int
-    L.pbHostRearrangementStats.argtypes = [C.c_void_p, C.c_void_p]
-    L.pbHostRearrangementStats.restype = C.c_int
-    L.pbHostRearrangementOf.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.pbHostRearrangementOf.restype = C.c_int
+    for name, args in _ANALYSES.items():
+        fn = getattr(L, name)
+        fn.argtypes, fn.restype = [C.c_void_p] + args, C.c_int
     _lib = L
     return L
 
@@ -128,7 +119,7 @@ def lib():
 def libc_rand_draws(seed, n):
     """n outputs of the class's private glibc-compatible generator after seeding with `seed`."""
     out = np.empty(n, np.int32)
-    lib().pbHostLibcRandDraws(int(seed), int(n), out.ctypes.data_as(C.c_void_p))
+    lib().pbHostLibcRandDraws(int(seed), int(n), _ptr(out))
     return out
 
 
@@ -197,7 +188,7 @@ class HostSim:
 
     def draw_dead(self):
         out = np.empty(self.n, np.int32)
-        lib().pbHostDrawDead(self._h, out.ctypes.data_as(C.c_void_p))
+        lib().pbHostDrawDead(self._h, _ptr(out))
         return out
 
     def reset(self):
@@ -215,8 +206,7 @@ class HostSim:
         xy = np.empty((steps, 2), np.float32)
         times = np.empty(steps, np.float32)
         rec = C.c_uint(0)
-        if lib().pbHostCentroidTrail(self._h, xy.ctypes.data_as(C.c_void_p), times.ctypes.data_as(C.c_void_p),
-                                     C.byref(rec)) != 0:
+        if lib().pbHostCentroidTrail(self._h, _ptr(xy), _ptr(times), C.byref(rec)) != 0:
             raise RuntimeError("centroid_trail: set_display(True) first")
         return xy, times, int(rec.value)
 
@@ -253,8 +243,8 @@ class HostSim:
         if style not in ("plain", "reference"):
             raise ValueError(style)
         out = np.empty((int(height), int(width), 3), np.uint8)
-        if lib().pbHostRenderFrame(self._h, None, out.ctypes.data_as(C.c_void_p), int(width), int(height), center[0],
-                                   center[1], half_extent, 1 if style == "reference" else 0) != 0:
+        if lib().pbHostRenderFrame(self._h, None, _ptr(out), int(width), int(height), center[0], center[1],
+                                   half_extent, 1 if style == "reference" else 0) != 0:
             raise RuntimeError("renderFrame failed (the device rasteriser needs the fused engine and a valid view)")
         return out
 
@@ -269,7 +259,6 @@ class HostSim:
         """Cluster analysis of the state as it is now, on the device (pbSimClusterStats; fused engine only): a dict with
         clusters, largest, largest_label, isolated, links, max_degree and rounds.  Bots are linked when
         dist - (ri + rj) < gap in fp32; a label is the smallest original index of a component."""
-        from . import _capi
         row = _capi.pbClusterStats()
         if lib().pbHostClusterStats(self._h, float(gap), C.byref(row)) != 0:
             raise RuntimeError("clusters: the cluster analysis needs the fused engine and a finite gap >= 0")
@@ -278,8 +267,7 @@ class HostSim:
     def cluster_labels(self, gap=0.0):
         """(labels, degree): two uint32 arrays in original bot order (pbSimClusterLabelsOf; fused engine only)."""
         labels, degree = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
-        if lib().pbHostClusterLabels(self._h, float(gap), labels.ctypes.data_as(C.c_void_p),
-                                     degree.ctypes.data_as(C.c_void_p)) != 0:
+        if lib().pbHostClusterLabels(self._h, float(gap), _ptr(labels), _ptr(degree)) != 0:
             raise RuntimeError("cluster_labels: the cluster analysis needs the fused engine and a finite gap >= 0")
         return labels, degree
 
@@ -287,15 +275,13 @@ class HostSim:
         """The contact network of the state as it is now, from the device (pbSimContactsOf; fused engine only): a dict
         with offsets (uint32, n + 1: CSR in original bot order, ascending `other`), other (uint32, E), gap (float32, E)
         and force (float32, E x 2: the pair law's force on the owning bot from other)."""
-        from . import _capi
         count = C.c_ulonglong(0)
         bad = "contacts: the contact export needs the fused engine and a finite gap >= 0"
         if lib().pbHostContacts(self._h, float(gap), None, None, 0, C.byref(count)) != 0:
             raise RuntimeError(bad)
         offsets = np.empty(self.n + 1, np.uint32)
         links = np.empty(int(count.value), _capi.CONTACT_LINK_DTYPE)
-        if lib().pbHostContacts(self._h, float(gap), offsets.ctypes.data_as(C.c_void_p),
-                                links.ctypes.data_as(C.c_void_p), links.size, C.byref(count)) != 0:
+        if lib().pbHostContacts(self._h, float(gap), _ptr(offsets), _ptr(links), links.size, C.byref(count)) != 0:
             raise RuntimeError(bad)
         return {"offsets": offsets, "other": links["other"].copy(), "gap": links["gap"].copy(),
                 "force": np.stack([links["fx"], links["fy"]], axis=1)}
@@ -304,7 +290,7 @@ class HostSim:
         """Per-bot virial of the contact network (pbSimContactVirialOf; fused engine only): float64, n x 4, the columns
         sxx, sxy, syx, syy summed over each bot's entries in CSR order."""
         out = np.empty((self.n, 4), np.float64)
-        if lib().pbHostContactVirial(self._h, float(gap), out.ctypes.data_as(C.c_void_p)) != 0:
+        if lib().pbHostContactVirial(self._h, float(gap), _ptr(out)) != 0:
             raise RuntimeError("contact_virial: the contact export needs the fused engine and a finite gap >= 0")
         return out
 
@@ -312,7 +298,7 @@ class HostSim:
         """Radial pair counts of the state as it is now, on the device (pbSimRadialCounts; fused engine only): uint64,
         (1, bins), or (bins,) with member=0.  Ordered pairs, bin int(dist * (float32(bins) / r_max)) in fp32."""
         out = np.zeros((1, int(bins)), np.uint64)
-        if lib().pbHostRadialCounts(self._h, float(r_max), int(bins), out.ctypes.data_as(C.c_void_p)) != 0:
+        if lib().pbHostRadialCounts(self._h, float(r_max), int(bins), _ptr(out)) != 0:
             raise RuntimeError("radial_counts: the structure analysis needs the fused engine, a finite r_max > 0 and "
                                "1 ... 4096 bins")
         return out if member is None else out[int(member)]
@@ -320,7 +306,6 @@ class HostSim:
     def structure(self, gap=0.0):
         """Hexatic order of the state as it is now, on the device (pbSimStructureStats; fused engine only): a list with
         one dict: bonds, psi6_re, psi6_im, coordination and psi6, the complex mean over the directed bonds."""
-        from . import _capi
         row = _capi.pbStructureStats()
         if lib().pbHostStructureStats(self._h, float(gap), C.byref(row)) != 0:
             raise RuntimeError("structure: the structure analysis needs the fused engine and a finite gap >= 0")
@@ -331,7 +316,7 @@ class HostSim:
         if int(member) != 0:
             raise IndexError(member)
         psi, nb = np.empty(self.n, np.complex128), np.empty(self.n, np.uint32)
-        if lib().pbHostHexatic(self._h, float(gap), psi.ctypes.data_as(C.c_void_p), nb.ctypes.data_as(C.c_void_p)) != 0:
+        if lib().pbHostHexatic(self._h, float(gap), _ptr(psi), _ptr(nb)) != 0:
             raise RuntimeError("hexatic: the structure analysis needs the fused engine and a finite gap >= 0")
         return psi, nb
 
@@ -345,7 +330,6 @@ class HostSim:
         """The state as it is now against the mark, on the device (pbSimRearrangementStats; fused engine only): a list
         with one dict: bonds_marked / bonds_now / bonds_kept (directed), bots_unchanged / bots_lost / bots_gained,
         measured, sum_qx / sum_qy (units of 2^-20), sum_q2 (a Python int, units of 2^-40) and max_q2."""
-        from . import _capi
         row = _capi.pbRearrangementStats()
         if lib().pbHostRearrangementStats(self._h, C.byref(row)) != 0:
             raise RuntimeError("rearrangement: the rearrangement analysis needs the fused engine and a marked reference")
@@ -359,8 +343,7 @@ class HostSim:
         n = self.n
         out = {"disp": np.empty((n, 2), np.float32), "marked": np.empty(n, np.uint32), "now": np.empty(n, np.uint32),
                "kept": np.empty(n, np.uint32)}
-        if lib().pbHostRearrangementOf(self._h, *[out[k].ctypes.data_as(C.c_void_p)
-                                                  for k in ("disp", "marked", "now", "kept")]) != 0:
+        if lib().pbHostRearrangementOf(self._h, *[_ptr(out[k]) for k in ("disp", "marked", "now", "kept")]) != 0:
             raise RuntimeError("rearrangement_of: the rearrangement analysis needs the fused engine and a marked reference")
         return out
 
@@ -378,11 +361,11 @@ class HostSim:
         which, dt, w = {"pos": (0, np.float32, 2), "vel": (1, np.float32, 2), "rad": (2, np.float32, 1),
                         "phase": (3, np.float32, 1), "dead": (5, np.int32, 1), "col": (6, np.float32, 4)}[name]
         out = np.empty((self.n, w) if w > 1 else self.n, dtype=dt)
-        assert lib().pbHostGetArray(self._h, which, out.ctypes.data_as(C.c_void_p)) == 0
+        assert lib().pbHostGetArray(self._h, which, _ptr(out)) == 0
         return out
 
     def set(self, name, data, start=0):
         which = {"pos": 0, "vel": 1, "rad": 2, "phase": 3}[name]
         data = np.ascontiguousarray(data, np.float32)
         count = data.shape[0]
-        assert lib().pbHostSetArray(self._h, which, data.ctypes.data_as(C.c_void_p), int(start), int(count)) == 0
+        assert lib().pbHostSetArray(self._h, which, _ptr(data), int(start), int(count)) == 0
