@@ -219,6 +219,18 @@ class Particlebot {
   bool rearrangementStats(pbRearrangementStats &out);
   bool rearrangement(std::vector<float> &disp, std::vector<unsigned> &marked, std::vector<unsigned> &now,
                      std::vector<unsigned> &kept);
+  /* Time series of the resident state on the device (pbSimMoments / pbSimSetSeries / pbSimGetSeriesOf,
+   * include/particlebot_hip.h has the definitions): moments gives the row of integer moments of the state as it is now;
+   * setSeries(interval, capacity) starts a device ring that takes such a row in front of every step whose start time
+   * passes the schedule's gate at `interval` (0: every step) while update() runs, capacity 0 switches it off; seriesInfo
+   * gives the interval, the capacity and the records taken so far; seriesRows the records from number `first` up to the
+   * last one taken, in order.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.
+   * Also false on a bad interval or capacity, and for a read outside the ring's window or with the series off.  The
+   * series is not part of a checkpoint. */
+  bool moments(pbMomentsRow &out);
+  bool setSeries(float interval, unsigned capacity);
+  bool seriesInfo(float &interval, unsigned &capacity, unsigned long long &records);
+  bool seriesRows(unsigned long long first, std::vector<pbMomentsRow> &rows);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

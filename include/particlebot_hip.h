@@ -556,6 +556,81 @@ int pbSimRearrangementOf(pbSim *sim, unsigned member, float *disp /* 2 n: dx, dy
                          unsigned *marked, unsigned *now, unsigned *kept /* n each, ORIGINAL order; NULL skipped */);
 int pbSimGetRearrangementTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
 
+/* Time series on the device (csrc/pb_moments.hip): one row of integer moments of positions, velocities and radii per
+ * member, taken now on request (pbSimMoments) or recorded into a device ring at a chosen interval while pbSimStep runs
+ * (pbSimSetSeries) and read back afterwards (pbSimGetSeriesOf).  Off by default; a run that does not ask for it is
+ * unchanged.
+ * THE ROW.  Nodes are all nCells bots of a member, dead bots and the payload bot included.  A bot is MEASURED iff x, y,
+ * vx, vy, rad are all finite and each has fabsf(.) < 2048.0f (the rearrangement analysis' bound and scale).  For a
+ * measured bot, in fp32 scaling and with round-to-nearest-even conversion,
+ *     qx = (long long)rint(x * 1048576.0f);   qy, wx (from vx), wy (from vy), qr (from rad) likewise
+ * (the scaling is exact, |q| < 2^31, every product of two q is below 2^62 in magnitude).  Unmeasured bots take part in
+ * nothing.  Per member:
+ *     time      fp32, the start time of the step in front of which the row was taken
+ *     step      pbSimStats.steps at that moment
+ *     measured
+ *     sum_qx, sum_qy, sum_qr, sum_wx, sum_wy     signed 64-bit; with fewer than 2^28 bots they stay below 2^59
+ *     min_qx, max_qx, min_qy, max_qy             32-bit signed, the bounding box; all four 0 when measured == 0
+ *     xx = sum qx*qx,  yy = sum qy*qy,  xy = sum qx*qy (signed),  rr = sum qr*qr,  vv = sum (wx*wx + wy*wy)
+ * the last five 128-bit sums, each as a pair {unsigned long long lo; long long hi} with value hi * 2^32 + lo: per bot
+ * the 64-bit product p is split as lo += (unsigned)p and hi += p >> 32 with an arithmetic shift (the two's-complement
+ * split, so the signed product needs no special case); the two device accumulators stay below 2^60 in magnitude.
+ * No float atomics and no 128-bit atomics.  Every number is an integer: results do not depend on slot order, on the
+ * kernel form that stepped, or on the order in which the device adds, and can be compared exactly.
+ * pbSimMoments returns the state as it is now, one row per member (time = the batch's time, the start time of the next
+ * step).  It reads only: the slot layout, keys, cell lists, pbSimStats, time, RNG, render buffers and every other
+ * analysis' scratch stay untouched.
+ * pbSimSetSeries with capacity > 0 allocates a device ring of `capacity` rows per member (152 bytes each) and resets
+ * the record counter to 0; calling it again restarts the series.  capacity == 0 frees the ring: no allocation and no
+ * launch (the default).  interval > 0 records in front of every executed step whose fp32 start time t passes the
+ * schedule's own gate t - interval floorf(t / interval) < dt, the test the dump, phase-update and trail gates use, so a
+ * series at dump_interval lines up with the CSV.  interval == 0 records in front of every executed step (the gate with
+ * interval == dt need not be that: fp32 rounding can drop steps).
+ * A RECORD is the row pbSimMoments would return had the caller stopped pbSimStep just before that step: positions and
+ * radii from the previous step's update, velocities from the previous step's kick.  This holds on all three stepping
+ * paths: with separate state launches the record is taken before the state kernel; no launch is fused across a series
+ * gate, because the state in front of a gate step never exists on the device once the previous launch has run ahead;
+ * a resident stretch ends in front of a series gate, exactly as it ends in front of a trail gate.  Recording changes no
+ * state bit.  It only changes which launches carry the steps, so the launch counters of pbSimStats differ from a run
+ * without the series (as with the centroid trail, which ends resident stretches too), and interval == 0 costs the fusion
+ * of every step.
+ * THE RING.  Record number r, counted from 0, goes to slot r % capacity.  The host keeps time and step per slot; the
+ * sums stay on the device until asked for; recording never waits for the device.  No record is taken for a step that
+ * does not run because t > max_time.  pbSimGetSeriesInfo: the interval, the capacity (0: off) and the records taken so
+ * far; any pointer may be NULL, not all.  pbSimGetSeriesOf copies records first .. first + count of one member, in the
+ * order taken; PB_ERR_ARG unless that range lies inside [records - min(records, capacity), records); count == 0 is
+ * allowed.  pbSimGetSeriesTimes: records so far and the span of the last row's launches (a record's, or pbSimMoments')
+ * on the batch's stream in milliseconds (HIP events), as pbSimGetClusterTimes; either pointer may be NULL.
+ * The series is not part of a checkpoint, like the trail: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it
+ * alone; pbSimDestroy frees it.
+ * PB_ERR_ARG, before the device is touched: NULL handle or NULL rows; member out of range; interval negative, NaN or
+ * infinite; capacity x nsims x 152 above 2^31 bytes; a batch of 2^28 bots or more; the pointers of pbSimGetSeriesInfo
+ * all NULL; a read with the series off.
+ * Cost: one pass over posrad and velocities of the whole batch in slot order (24 bytes per bot, coalesced; the original
+ * indices are never read), at most PB_MOMENTS_BLOCKS workgroups of 256 lanes per member, each adding its sums into the
+ * member's row with one set of integer atomics.
+ * Out of scope: recording inside the resident kernel without ending the stretch; phase moments (they need a
+ * transcendental and would not be exact); neighbour-based quantities per record such as bonds or psi6 (they need the
+ * fresh filing); the ensemble layer's summary rows and its RCCL gather; the legacy engine. */
+#define PB_MOMENTS_BLOCKS 512u /* workgroups per member: one pass of the launch covers 131072 bots of a member */
+typedef struct pbMoment128 {           /* 16 bytes: the value is hi * 2^32 + lo */
+  unsigned long long lo;
+  long long hi;
+} pbMoment128;
+typedef struct pbMomentsRow {          /* 152 bytes */
+  unsigned long long step;
+  float time;
+  unsigned measured;
+  long long sum_qx, sum_qy, sum_qr, sum_wx, sum_wy;  /* over measured bots, units of 2^-20 */
+  int min_qx, max_qx, min_qy, max_qy;
+  pbMoment128 xx, yy, xy, rr, vv;                    /* units of 2^-40 */
+} pbMomentsRow;
+int pbSimMoments(pbSim *sim, pbMomentsRow *rows /* nsims entries */);
+int pbSimSetSeries(pbSim *sim, float interval, unsigned capacity);
+int pbSimGetSeriesInfo(pbSim *sim, float *interval, unsigned *capacity, unsigned long long *records);
+int pbSimGetSeriesOf(pbSim *sim, unsigned member, unsigned long long first, unsigned count, pbMomentsRow *rows);
+int pbSimGetSeriesTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

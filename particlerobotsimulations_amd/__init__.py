@@ -15,7 +15,7 @@ from . import _capi
 from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
-           "radial_distribution", "mean_squared_displacement"]
+           "radial_distribution", "mean_squared_displacement", "moments_summary"]
 
 
 def radial_distribution(counts, r_max, density, n):
@@ -43,6 +43,39 @@ def mean_squared_displacement(row, subtract_drift=False):
     if subtract_drift:
         num -= int(row["sum_qx"]) ** 2 + int(row["sum_qy"]) ** 2
     return float(Fraction(num, m * m << 40))
+
+
+def moments_summary(row):
+    """What one row of moments() / series_of() says about the member, in float64 from the integers (pure Python; every
+    quotient is formed as one exact fraction and converted once).  Lengths in world units, from the units of 2^-20:
+      centroid (x, y); gyration (gxx, gyy, gxy): the second moments of the positions about the centroid;
+      gyration_eigenvalues (larger, smaller) of that tensor; major_axis_angle of the larger one's axis, in (-pi/2, pi/2];
+      mean_radius, radius_variance; covered_area = pi * sum r^2;
+      centroid_velocity (vx, vy); velocity_variance = mean |v|^2 - |mean v|^2.
+    Every value is None when no bot was measured."""
+    import math
+    from fractions import Fraction
+    keys = ("centroid", "gyration", "gyration_eigenvalues", "major_axis_angle", "mean_radius", "radius_variance",
+            "covered_area", "centroid_velocity", "velocity_variance")
+    m = int(row["measured"])
+    if m == 0:
+        return dict.fromkeys(keys)
+    one, two = 1 << 20, 1 << 40
+    sx, sy, sr, swx, swy = (int(row[k]) for k in ("sum_qx", "sum_qy", "sum_qr", "sum_wx", "sum_wy"))
+    xx, yy, xy, rr, vv = (int(row[k]) for k in ("xx", "yy", "xy", "rr", "vv"))
+    central = lambda s2, a, b: Fraction(s2 * m - a * b, m * m * two)  # mean of the product minus the product of the means
+    gxx, gyy, gxy = central(xx, sx, sx), central(yy, sy, sy), central(xy, sx, sy)
+    fxx, fyy, fxy = float(gxx), float(gyy), float(gxy)
+    half, root = 0.5 * float(gxx + gyy), math.hypot(0.5 * float(gxx - gyy), fxy)
+    return {"centroid": (float(Fraction(sx, m * one)), float(Fraction(sy, m * one))),
+            "gyration": (fxx, fyy, fxy),
+            "gyration_eigenvalues": (half + root, half - root),
+            "major_axis_angle": 0.5 * math.atan2(2.0 * fxy, float(gxx - gyy)),
+            "mean_radius": float(Fraction(sr, m * one)),
+            "radius_variance": float(central(rr, sr, sr)),
+            "covered_area": math.pi * float(Fraction(rr, two)),
+            "centroid_velocity": (float(Fraction(swx, m * one)), float(Fraction(swy, m * one))),
+            "velocity_variance": float(Fraction(vv * m - swx * swx - swy * swy, m * m * two))}
 
 
 def self_test(div_samples=1 << 32):
@@ -571,6 +604,46 @@ class Sim:
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetRearrangementTimes(self._h, C.byref(n), C.byref(ms)),
                     "pbSimGetRearrangementTimes")
+        return int(n.value), float(ms.value)
+
+
+    def moments(self):
+        """Every member's row of integer moments of the state as it is now, from the device (pbSimMoments): a list of
+        dicts of Python ints, one per member: time, step, measured, sum_qx / sum_qy / sum_qr / sum_wx / sum_wy (units of
+        2^-20), the box min_qx / max_qx / min_qy / max_qy, and xx, yy, xy, rr, vv (the 128-bit sums composed, units of
+        2^-40).  moments_summary() turns a row into centroid, gyration tensor, radii and velocities."""
+        rows = (_capi.pbMomentsRow * int(getattr(self, "nsims", 1)))()
+        _capi.check(_capi.lib().pbSimMoments(self._h, rows), "pbSimMoments")
+        return [_capi.moments_row(r) for r in rows]
+
+    def set_series(self, interval, capacity):
+        """Record such a row per member into a device ring of `capacity` rows in front of every step whose start time
+        passes the schedule's gate at `interval` (0: every step) while step() runs (pbSimSetSeries).  Restarts the
+        series at record 0; capacity 0 switches it off.  Recording changes no state bit."""
+        _capi.check(_capi.lib().pbSimSetSeries(self._h, float(interval), int(capacity)), "pbSimSetSeries")
+
+    def series_info(self):
+        """A dict of interval, capacity (0: off) and records taken so far (pbSimGetSeriesInfo)."""
+        i, c, r = C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
+        _capi.check(_capi.lib().pbSimGetSeriesInfo(self._h, C.byref(i), C.byref(c), C.byref(r)), "pbSimGetSeriesInfo")
+        return {"interval": float(i.value), "capacity": int(c.value), "records": int(r.value)}
+
+    def series_of(self, member=0, first=None, count=None):
+        """Records first .. first + count of one member in the order taken, as moments() gives rows (pbSimGetSeriesOf).
+        first defaults to the oldest record the ring still holds, count to everything from `first` on."""
+        info = self.series_info()
+        if first is None:
+            first = info["records"] - min(info["records"], info["capacity"])
+        if count is None:
+            count = max(info["records"] - int(first), 0)
+        rows = (_capi.pbMomentsRow * max(int(count), 1))()
+        _capi.check(_capi.lib().pbSimGetSeriesOf(self._h, int(member), int(first), int(count), rows), "pbSimGetSeriesOf")
+        return [_capi.moments_row(r) for r in rows[:int(count)]]
+
+    def series_times(self):
+        """(records taken so far, device milliseconds of the last row's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetSeriesTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetSeriesTimes")
         return int(n.value), float(ms.value)
 
 

@@ -122,6 +122,28 @@ def rearrangement_row(r):
     return d
 
 
+class pbMoment128(C.Structure):
+    _fields_ = [("lo", C.c_ulonglong), ("hi", C.c_longlong)]
+
+
+class pbMomentsRow(C.Structure):
+    _fields_ = [("step", C.c_ulonglong), ("time", C.c_float), ("measured", C.c_uint),
+                ("sum_qx", C.c_longlong), ("sum_qy", C.c_longlong), ("sum_qr", C.c_longlong),
+                ("sum_wx", C.c_longlong), ("sum_wy", C.c_longlong),
+                ("min_qx", C.c_int), ("max_qx", C.c_int), ("min_qy", C.c_int), ("max_qy", C.c_int),
+                ("xx", pbMoment128), ("yy", pbMoment128), ("xy", pbMoment128), ("rr", pbMoment128), ("vv", pbMoment128)]
+
+
+def moments_row(r):
+    """A pbMomentsRow as a dict of Python ints (time: the fp32 value as a float); each of xx, yy, xy, rr, vv is the
+    128-bit sum hi * 2^32 + lo as one int.  Sums of q are in units of 2^-20, sums of products in units of 2^-40."""
+    d = {}
+    for name, kind in pbMomentsRow._fields_:
+        v = getattr(r, name)
+        d[name] = (int(v.hi) << 32) + int(v.lo) if kind is pbMoment128 else float(v) if name == "time" else int(v)
+    return d
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -197,6 +219,11 @@ SYMBOLS = {
     "pbSimRearrangementStats": (_I, [_VP, C.POINTER(pbRearrangementStats)]),
     "pbSimRearrangementOf": (_I, [_VP, _U, _VP, _VP, _VP, _VP]),
     "pbSimGetRearrangementTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimMoments": (_I, [_VP, C.POINTER(pbMomentsRow)]),
+    "pbSimSetSeries": (_I, [_VP, _F, _U]),
+    "pbSimGetSeriesInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(C.c_ulonglong)]),
+    "pbSimGetSeriesOf": (_I, [_VP, _U, C.c_ulonglong, _U, C.POINTER(pbMomentsRow)]),
+    "pbSimGetSeriesTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1468,6 +1468,32 @@ bool Particlebot::rearrangement(std::vector<float> &disp, std::vector<unsigned> 
   });
 }
 
+bool Particlebot::moments(pbMomentsRow &out) {
+  return onFusedEngine("moments", "time series", [&] { return pbSimMoments(sim, &out); });
+}
+
+bool Particlebot::setSeries(float interval, unsigned capacity) {
+  return onFusedEngine("setSeries", "time series", [&] { return pbSimSetSeries(sim, interval, capacity); });
+}
+
+bool Particlebot::seriesInfo(float &interval, unsigned &capacity, unsigned long long &records) {
+  auto call = [&] { return pbSimGetSeriesInfo(sim, &interval, &capacity, &records); };
+  return onFusedEngine("seriesInfo", "time series", call);
+}
+
+bool Particlebot::seriesRows(unsigned long long first, std::vector<pbMomentsRow> &rows) {
+  return onFusedEngine("seriesRows", "time series", [&] {
+    unsigned long long records = 0;
+    const int rc = pbSimGetSeriesInfo(sim, nullptr, nullptr, &records);
+    if (rc != PB_OK) return rc;
+    const unsigned long long count = records > first ? records - first : 0ull;
+    rows.resize(count ? (size_t)count : 1);  // (the engine takes no NULL, and refuses a count beyond its window)
+    const int got = pbSimGetSeriesOf(sim, 0, first, (unsigned)(count < 0xFFFFFFFFull ? count : 0xFFFFFFFFull), rows.data());
+    if (got == PB_OK) rows.resize((size_t)count);
+    return got;
+  });
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

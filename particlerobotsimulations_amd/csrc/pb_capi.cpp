@@ -359,6 +359,37 @@ int pbHostRearrangementOf(void *hv, float *disp, unsigned *marked, unsigned *now
   return 0;
 }
 
+// time series of the resident state (Particlebot::moments / setSeries / seriesInfo / seriesRows; fused engine only): the
+// 152-byte pbMomentsRow of the state as it is, the recorder's switch, what it holds, and the records from `first` on
+// (cap entries of room; *count = how many there are).  -1 on the other engines, a bad interval or capacity, a read
+// outside the ring's window or with the series off, or too little room.
+int pbHostMoments(void *hv, pbMomentsRow *out) { return out && ((HostSim *)hv)->bot->moments(*out) ? 0 : -1; }
+
+int pbHostSetSeries(void *hv, float interval, unsigned capacity) {
+  return ((HostSim *)hv)->bot->setSeries(interval, capacity) ? 0 : -1;
+}
+
+int pbHostSeriesInfo(void *hv, float *interval, unsigned *capacity, unsigned long long *records) {
+  float i = 0.0f;
+  unsigned c = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->seriesInfo(i, c, r)) return -1;
+  if (interval) *interval = i;
+  if (capacity) *capacity = c;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostSeriesRows(void *hv, unsigned long long first, pbMomentsRow *rows, unsigned long long cap,
+                     unsigned long long *count) {
+  std::vector<pbMomentsRow> v;
+  if (!count || !((HostSim *)hv)->bot->seriesRows(first, v)) return -1;
+  *count = v.size();
+  if (rows && cap < v.size()) return -1;
+  copyOut(rows, v);
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

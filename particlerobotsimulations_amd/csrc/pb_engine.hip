@@ -620,11 +620,21 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const bool resident = pbResidentWanted(S);
   const bool trail = S->trail != nullptr;
   const float ci = S->trailInt;
+  // the time series (pb_moments.hip): a record in front of every step whose start time passes the gate, or of every
+  // step at interval 0.  A record reads the state in front of its step, which a launch that runs ahead never leaves on
+  // the device: no launch is fused across a series gate, and a resident stretch ends in front of one.
+  const bool series = S->series != nullptr;
+  const float si = S->seriesInt;
+  auto seriesGate = [&](float at) { return series && (si == 0.0f || gate(at, si, dt)); };
   int k = 0;
   for (; k < nsteps; k++) {
     const float t = S->time;
     if (t > S->host.max_time) break;  // particlebot.cpp:174-176 (the reference exits the process)
     if (!ahead) {
+      if (seriesGate(t)) {
+        const int rc = pbSeriesRecord(S, t);
+        if (rc) return rc;
+      }
       if (trail && gate(t, ci, dt)) {
         const int rc = trailRecord(S, t);
         if (rc) return rc;
@@ -639,7 +649,7 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
         int m = 1;
         float tt = t + dt;
         while (k + m < nsteps && !(tt > S->host.max_time) && !(lightWave && gate(tt, pui, dt)) &&
-               !(trail && gate(tt, ci, dt)) && !gate(tt, sortInterval, dt)) {
+               !(trail && gate(tt, ci, dt)) && !seriesGate(tt) && !gate(tt, sortInterval, dt)) {
           m++;
           tt += dt;
         }
@@ -664,7 +674,7 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     // next step will not run.  A phase update due at the start of the next step only needs the
     // positions of THIS step's integration, which are final now, so it runs before the launch.
     // (resident form: never run ahead, so that the next step can start a resident stretch)
-    const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time);
+    const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time) && !seriesGate(tNext);
     if (fuse && trail && gate(tNext, ci, dt)) {
       const int rc = trailRecord(S, tNext);
       if (rc) return rc;
@@ -743,6 +753,7 @@ void pbSimDestroy(pbSim *S) {
   (void)hipFree(S->colors);
   (void)hipFree(S->trail);
   (void)hipFree(S->trailTmp);
+  pbMomentsFree(S);
   pbClusterFree(S);
   (void)hipFree(S->renderIds);
   (void)hipFree(S->renderOut);

@@ -11,6 +11,7 @@
 //   pb_contacts.hip  the contact network of one member: links, gaps, pair forces, virial (pbSimContactsOf)
 //   pb_structure.hip structure analysis: radial pair counts and the hexatic order (pbSimRadialCounts, pbSimStructureStats)
 //   pb_dynamics.hip  rearrangement analysis: a marked reference, bond survival and displacements (pbSimMarkReference)
+//   pb_moments.hip   time series: integer moment rows per member, now or recorded while stepping (pbSimSetSeries)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 #pragma once
@@ -124,6 +125,16 @@ struct pbSim {
   float lastRenderMs = 0.0f;
   // cluster analysis (pb_cluster.hip): scratch of its own, allocated by the first analysis, freed by pbSimDestroy
   PbClusterScratch *cluster = nullptr;
+  // time series (pb_moments.hip): the ring when on (pbSimSetSeries), the one-shot rows of pbSimMoments, the record's events
+  pbMomentsRow *series = nullptr;   // nsims x seriesCap, member-major: record r of member m at [m * seriesCap + r % seriesCap]
+  pbMomentsRow *momRows = nullptr;  // nsims, allocated by the first pbSimMoments
+  float seriesInt = 0.0f;           // 0: in front of every step
+  unsigned seriesCap = 0;
+  unsigned long long seriesRecords = 0;
+  std::vector<float> seriesTimes;   // per slot: start time of the step the record was taken in front of
+  std::vector<unsigned long long> seriesSteps;  // per slot: stats.steps at that moment
+  hipEvent_t momEv0 = nullptr, momEv1 = nullptr;  // around the last pass' launches
+  bool momTimed = false;
   pbSimStats stats{};
 };
 
@@ -179,3 +190,7 @@ bool pbResidentWanted(const pbSim *S);                                          
 void pbLaunchResident(pbSim *S, float dt, float t0, int m, int lightWave);
 // frees the cluster analysis' scratch, if any (pbSimDestroy)                                             pb_cluster.hip
 void pbClusterFree(pbSim *S);
+// one record of every member into the ring's next slot, in front of the step that starts at t (stepMany)   pb_moments.hip
+int pbSeriesRecord(pbSim *S, float t);
+// frees the ring, the one-shot rows and the events (pbSimDestroy)
+void pbMomentsFree(pbSim *S);

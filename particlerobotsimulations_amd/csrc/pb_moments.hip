@@ -1,0 +1,298 @@
+// pb_moments.hip -- time series on gfx950: one row of integer moments of positions, velocities and radii per member
+// (pbMomentsRow), taken now (pbSimMoments) or recorded into a device ring in front of chosen steps while pbSimStep runs
+// (pbSimSetSeries / pbSimGetSeriesOf; include/particlebot_hip.h has the definitions).
+//
+//   k_mom_init        the target row of every member: zeros, the box at its identities (INT_MAX / INT_MIN)
+//   k_mom_accumulate  one pass over pr[cur] and vel[cur] of the whole batch in SLOT order (16 + 8 bytes per bot, coalesced;
+//                     orig is never read).  Up to PB_MOMENTS_BLOCKS workgroups per member, each lane a grid-stride loop
+//                     over its member's slots with twenty accumulators in registers; then shuffles inside the wave, the
+//                     four waves through 640 bytes of LDS, and one set of 64-bit integer atomics (32-bit min / max for
+//                     the box) per workgroup into the member's row.
+// Everything that is added is an integer, so nothing depends on the slot order, on the kernel form that stepped or on the
+// order of the adds.  No float atomics, no 128-bit atomics, no scratch memory.  A record is two launches on the batch's
+// stream between two events; the host never waits for them.
+#include <limits.h>
+#include <math.h>
+
+#include "pb_engine.hpp"
+
+static_assert(sizeof(pbMoment128) == 16, "a 128-bit sum is two 64-bit accumulators");
+static_assert(sizeof(pbMomentsRow) == 152, "a member's row is 152 bytes");
+
+namespace {
+
+constexpr int MT = 256;
+// the columns of the row reduction: sixteen sums, then the box
+enum {
+  M_MEASURED, M_QX, M_QY, M_QR, M_WX, M_WY,
+  M_XX_LO, M_XX_HI, M_YY_LO, M_YY_HI, M_XY_LO, M_XY_HI, M_RR_LO, M_RR_HI, M_VV_LO, M_VV_HI,
+  M_SUMS,
+  M_MIN_X = M_SUMS, M_MAX_X, M_MIN_Y, M_MAX_Y,
+  M_COLS
+};
+
+__global__ __launch_bounds__(MT) void k_mom_init(pbMomentsRow *__restrict__ rows, uint32_t stride, uint32_t nsims) {
+  const uint32_t m = blockIdx.x * MT + threadIdx.x;
+  if (m >= nsims) return;
+  pbMomentsRow *r = rows + (size_t)m * stride;
+  r->step = 0ull, r->time = 0.0f, r->measured = 0u;
+  r->sum_qx = r->sum_qy = r->sum_qr = r->sum_wx = r->sum_wy = 0ll;
+  r->min_qx = r->min_qy = INT_MAX;
+  r->max_qx = r->max_qy = INT_MIN;
+  r->xx.lo = r->yy.lo = r->xy.lo = r->rr.lo = r->vv.lo = 0ull;
+  r->xx.hi = r->yy.hi = r->xy.hi = r->rr.hi = r->vv.hi = 0ll;
+}
+
+__device__ __forceinline__ unsigned long long momShflXor64(unsigned long long v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// (long long)rint(v * 2^20) of a value with |v| < 2048: the scaling is exact, v_rndne_f32 rounds to nearest even,
+// |.| <= 2^31 - 128
+__device__ __forceinline__ long long momQuantise(float v) { return (long long)(int)__builtin_rintf(v * 1048576.0f); }
+
+// the 64-bit product p into its two accumulators: the two's-complement split, so a signed p needs no special case
+__device__ __forceinline__ void momSplit(long long p, unsigned long long &lo, unsigned long long &hi) {
+  lo += (unsigned long long)(uint32_t)p;
+  hi += (unsigned long long)(p >> 32);  // arithmetic shift; the accumulator wraps like the signed sum it stands for
+}
+
+__global__ __launch_bounds__(MT) void k_mom_accumulate(const float4 *__restrict__ pr, const float2 *__restrict__ vel,
+                                                       uint32_t n, uint32_t blocksPerMember,
+                                                       pbMomentsRow *__restrict__ rows, uint32_t stride) {
+  __shared__ unsigned long long sRed[MT / 64][M_COLS];
+  const uint32_t member = blockIdx.x / blocksPerMember, b = blockIdx.x - member * blocksPerMember;
+  const uint32_t base = member * n;  // a member's slots are its own block of the arrays; the batch is below 2^28 bots
+  unsigned long long a[M_SUMS];
+#pragma unroll
+  for (int c = 0; c < M_SUMS; c++) a[c] = 0ull;
+  int minX = INT_MAX, maxX = INT_MIN, minY = INT_MAX, maxY = INT_MIN;
+#pragma unroll 1
+  for (uint32_t i = b * MT + threadIdx.x; i < n; i += blocksPerMember * MT) {
+    const float4 q = pr[base + i];
+    const float2 v = vel[base + i];
+    // (a NaN or an infinity fails its comparison)
+    if (fabsf(q.x) < 2048.0f && fabsf(q.y) < 2048.0f && fabsf(v.x) < 2048.0f && fabsf(v.y) < 2048.0f &&
+        fabsf(q.z) < 2048.0f) {
+      const long long qx = momQuantise(q.x), qy = momQuantise(q.y), qr = momQuantise(q.z);
+      const long long wx = momQuantise(v.x), wy = momQuantise(v.y);
+      a[M_MEASURED] += 1ull;
+      a[M_QX] += (unsigned long long)qx, a[M_QY] += (unsigned long long)qy, a[M_QR] += (unsigned long long)qr;
+      a[M_WX] += (unsigned long long)wx, a[M_WY] += (unsigned long long)wy;
+      momSplit(qx * qx, a[M_XX_LO], a[M_XX_HI]);
+      momSplit(qy * qy, a[M_YY_LO], a[M_YY_HI]);
+      momSplit(qx * qy, a[M_XY_LO], a[M_XY_HI]);
+      momSplit(qr * qr, a[M_RR_LO], a[M_RR_HI]);
+      momSplit(wx * wx + wy * wy, a[M_VV_LO], a[M_VV_HI]);  // below 2^63
+      minX = min(minX, (int)qx), maxX = max(maxX, (int)qx);
+      minY = min(minY, (int)qy), maxY = max(maxY, (int)qy);
+    }
+  }
+  // the wave's sums with shuffles, the four waves through LDS, one set of atomics
+  // (one butterfly stage in the code, run six times: unrolled, the stages' temporaries cost registers that the pass
+  //  once per workgroup does not earn back)
+#pragma unroll 1
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int c = 0; c < M_SUMS; c++) a[c] += momShflXor64(a[c], m);
+    minX = min(minX, __shfl_xor(minX, m)), maxX = max(maxX, __shfl_xor(maxX, m));
+    minY = min(minY, __shfl_xor(minY, m)), maxY = max(maxY, __shfl_xor(maxY, m));
+  }
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  if (lane == 0u) {
+#pragma unroll
+    for (int c = 0; c < M_SUMS; c++) sRed[w][c] = a[c];
+    // the box as sign-extended 64-bit values, so that one signed compare serves all four columns
+    sRed[w][M_MIN_X] = (unsigned long long)(long long)minX, sRed[w][M_MAX_X] = (unsigned long long)(long long)maxX;
+    sRed[w][M_MIN_Y] = (unsigned long long)(long long)minY, sRed[w][M_MAX_Y] = (unsigned long long)(long long)maxY;
+  }
+  __syncthreads();
+  if (threadIdx.x >= (uint32_t)M_COLS) return;
+  const uint32_t c = threadIdx.x;
+  const bool isMin = c == (uint32_t)M_MIN_X || c == (uint32_t)M_MIN_Y;
+  unsigned long long s = sRed[0][c];
+  for (int k = 1; k < MT / 64; k++) {
+    const unsigned long long u = sRed[k][c];
+    if (c < (uint32_t)M_SUMS) s += u;
+    else if (isMin) s = (long long)u < (long long)s ? u : s;
+    else s = (long long)u > (long long)s ? u : s;
+  }
+  pbMomentsRow *row = rows + (size_t)member * stride;
+  if (c >= (uint32_t)M_SUMS) {  // (a workgroup without a measured bot holds the identities: they change nothing)
+    int *f = c == (uint32_t)M_MIN_X ? &row->min_qx : c == (uint32_t)M_MAX_X ? &row->max_qx
+             : c == (uint32_t)M_MIN_Y ? &row->min_qy : &row->max_qy;
+    if (isMin) atomicMin(f, (int)(long long)s);
+    else atomicMax(f, (int)(long long)s);
+    return;
+  }
+  if (!s) return;  // (a signed sum that is zero adds nothing either)
+  if (c == (uint32_t)M_MEASURED) {
+    atomicAdd(&row->measured, (unsigned)s);
+    return;
+  }
+  unsigned long long *f;  // two's complement: a signed field takes its sum modulo 2^64
+  switch (c) {
+    case M_QX: f = (unsigned long long *)&row->sum_qx; break;
+    case M_QY: f = (unsigned long long *)&row->sum_qy; break;
+    case M_QR: f = (unsigned long long *)&row->sum_qr; break;
+    case M_WX: f = (unsigned long long *)&row->sum_wx; break;
+    case M_WY: f = (unsigned long long *)&row->sum_wy; break;
+    case M_XX_LO: f = &row->xx.lo; break;
+    case M_XX_HI: f = (unsigned long long *)&row->xx.hi; break;
+    case M_YY_LO: f = &row->yy.lo; break;
+    case M_YY_HI: f = (unsigned long long *)&row->yy.hi; break;
+    case M_XY_LO: f = &row->xy.lo; break;
+    case M_XY_HI: f = (unsigned long long *)&row->xy.hi; break;
+    case M_RR_LO: f = &row->rr.lo; break;
+    case M_RR_HI: f = (unsigned long long *)&row->rr.hi; break;
+    case M_VV_LO: f = &row->vv.lo; break;
+    default: f = (unsigned long long *)&row->vv.hi; break;
+  }
+  atomicAdd(f, s);
+}
+
+int fail(const char *fn, const char *what) {
+  pbLastError() = std::string(fn) + what;
+  return PB_ERR_ARG;
+}
+
+int checkBatch(const char *fn, const pbSim *S) {
+  return S->total >= (1u << 28) ? fail(fn, ": the batch must hold fewer than 2^28 bots") : PB_OK;
+}
+
+// the rows of every member, rows[m * stride], from the state as it is: queued on the batch's stream, not waited for
+int momentsPass(pbSim *S, pbMomentsRow *rows, uint32_t stride) {
+  if (!S->momEv0) PB_TRY(hipEventCreate(&S->momEv0));
+  if (!S->momEv1) PB_TRY(hipEventCreate(&S->momEv1));
+  const uint32_t perMember = cdiv(S->n, MT);
+  const uint32_t bpm = perMember < PB_MOMENTS_BLOCKS ? perMember : PB_MOMENTS_BLOCKS;
+  PB_TRY(hipEventRecord(S->momEv0, S->stream));
+  hipLaunchKernelGGL(k_mom_init, dim3(cdiv(S->nsims, MT)), dim3(MT), 0, S->stream, rows, stride, S->nsims);
+  hipLaunchKernelGGL(k_mom_accumulate, dim3(S->nsims * bpm), dim3(MT), 0, S->stream, S->pr[S->cur], S->vel[S->cur],
+                     S->n, bpm, rows, stride);
+  PB_TRY(hipGetLastError());
+  PB_TRY(hipEventRecord(S->momEv1, S->stream));
+  S->momTimed = true;
+  return PB_OK;
+}
+
+// what the device leaves to the host: the clock, and a box of zeros for a row without a measured bot
+void finishRow(pbMomentsRow &r, float time, unsigned long long step) {
+  r.time = time, r.step = step;
+  if (!r.measured) r.min_qx = r.max_qx = r.min_qy = r.max_qy = 0;
+}
+
+void freeSeries(pbSim *S) {
+  (void)hipFree(S->series);
+  S->series = nullptr;
+  S->seriesInt = 0.0f, S->seriesCap = 0u, S->seriesRecords = 0ull;
+  S->seriesTimes.clear(), S->seriesSteps.clear();
+}
+
+}  // namespace
+
+void pbMomentsFree(pbSim *S) {
+  freeSeries(S);
+  (void)hipFree(S->momRows);
+  S->momRows = nullptr;
+  if (S->momEv0) (void)hipEventDestroy(S->momEv0);
+  if (S->momEv1) (void)hipEventDestroy(S->momEv1);
+  S->momEv0 = S->momEv1 = nullptr;
+  S->momTimed = false;
+}
+
+int pbSeriesRecord(pbSim *S, float t) {
+  const uint32_t slot = (uint32_t)(S->seriesRecords % S->seriesCap);
+  const int rc = momentsPass(S, S->series + slot, S->seriesCap);
+  if (rc != PB_OK) return rc;
+  S->seriesTimes[slot] = t, S->seriesSteps[slot] = S->stats.steps;
+  S->seriesRecords++;
+  return PB_OK;
+}
+
+extern "C" {
+
+int pbSimMoments(pbSim *S, pbMomentsRow *rows) {
+  if (!S || !rows) return fail("pbSimMoments", ": null handle or rows");
+  int rc = checkBatch("pbSimMoments", S);
+  if (rc != PB_OK) return rc;
+  useDevice(S);
+  if (!S->momRows) PB_TRY(hipMalloc((void **)&S->momRows, sizeof(pbMomentsRow) * S->nsims));
+  rc = momentsPass(S, S->momRows, 1u);
+  if (rc != PB_OK) return rc;
+  PB_TRY(hipMemcpyAsync(rows, S->momRows, sizeof(pbMomentsRow) * S->nsims, hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  for (uint32_t m = 0; m < S->nsims; m++) finishRow(rows[m], S->time, S->stats.steps);
+  return PB_OK;
+}
+
+int pbSimSetSeries(pbSim *S, float interval, unsigned capacity) {
+  if (!S) return fail("pbSimSetSeries", ": null handle");
+  if (!(interval >= 0.0f) || !(interval < __builtin_inff()))
+    return fail("pbSimSetSeries", ": interval must be finite and >= 0");
+  if ((unsigned long long)capacity * S->nsims * sizeof(pbMomentsRow) > (1ull << 31))
+    return fail("pbSimSetSeries", ": capacity x members x 152 bytes must not exceed 2^31 bytes");
+  const int rc = checkBatch("pbSimSetSeries", S);
+  if (rc != PB_OK) return rc;
+  useDevice(S);
+  PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
+  freeSeries(S);
+  if (!capacity) return PB_OK;
+  PB_TRY(hipMalloc((void **)&S->series, sizeof(pbMomentsRow) * (size_t)capacity * S->nsims));
+  S->seriesInt = interval, S->seriesCap = capacity;
+  S->seriesTimes.assign(capacity, 0.0f);
+  S->seriesSteps.assign(capacity, 0ull);
+  return PB_OK;
+}
+
+int pbSimGetSeriesInfo(pbSim *S, float *interval, unsigned *capacity, unsigned long long *records) {
+  if (!S) return fail("pbSimGetSeriesInfo", ": null handle");
+  if (!interval && !capacity && !records) return fail("pbSimGetSeriesInfo", ": interval, capacity and records are all null");
+  if (interval) *interval = S->seriesInt;
+  if (capacity) *capacity = S->seriesCap;
+  if (records) *records = S->seriesRecords;
+  return PB_OK;
+}
+
+int pbSimGetSeriesOf(pbSim *S, unsigned member, unsigned long long first, unsigned count, pbMomentsRow *rows) {
+  if (!S || !rows) return fail("pbSimGetSeriesOf", ": null handle or rows");
+  if (member >= S->nsims) return fail("pbSimGetSeriesOf", ": member out of range");
+  if (!S->series) return fail("pbSimGetSeriesOf", ": the series is off");
+  const unsigned long long have = S->seriesRecords, cap = S->seriesCap;
+  const unsigned long long oldest = have - (have < cap ? have : cap);
+  if (first < oldest || first > have || count > have - first)
+    return fail("pbSimGetSeriesOf", ": records outside the ring's window");
+  if (!count) return PB_OK;
+  useDevice(S);
+  // the ring wraps at most once inside the range
+  const pbMomentsRow *ring = S->series + (size_t)member * cap;
+  const unsigned long long s0 = first % cap;
+  const unsigned long long head = count < cap - s0 ? count : cap - s0;
+  PB_TRY(hipMemcpyAsync(rows, ring + s0, sizeof(pbMomentsRow) * head, hipMemcpyDeviceToHost, S->stream));
+  if (head < count)
+    PB_TRY(hipMemcpyAsync(rows + head, ring, sizeof(pbMomentsRow) * (count - head), hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  for (unsigned k = 0; k < count; k++) {
+    const size_t slot = (size_t)((first + k) % cap);
+    finishRow(rows[k], S->seriesTimes[slot], S->seriesSteps[slot]);
+  }
+  return PB_OK;
+}
+
+int pbSimGetSeriesTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
+  if (!S) return fail("pbSimGetSeriesTimes", ": null handle");
+  if (records) *records = S->seriesRecords;
+  if (last_device_ms) {
+    *last_device_ms = 0.0f;
+    if (S->momTimed) {
+      useDevice(S);
+      PB_TRY(hipEventSynchronize(S->momEv1));
+      PB_TRY(hipEventElapsedTime(last_device_ms, S->momEv0, S->momEv1));
+    }
+  }
+  return PB_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 //                   [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]]
 //                   [--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]]
 //                   [--rearrange FILE [--rearrange-gap G] [--rearrange-window]]
+//                   [--series FILE [--series-interval T] [--series-capacity N]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -49,6 +50,16 @@
 // the integer it is (bonds directed, SumQx / SumQy in units of 2^-20, SumQ2 / MaxQ2 of 2^-40; SumQ2 in decimal from its
 // 128 bits); --rearrange-gap G (default 0, finite and >= 0) is the mark's linkGap; --rearrange-window marks again after
 // each row, so that every row describes one dump interval.
+// --series FILE switches the device's time-series recorder on (Particlebot::setSeries): while the engine steps, one row
+// of integer moments of positions, velocities and radii (pbMomentsRow, include/particlebot_hip.h) is taken in front of
+// every step whose start time passes the schedule's gate at --series-interval T (default dump_interval, so that the
+// rows line up with the CSV; 0: every step; finite and >= 0) into a device ring of --series-capacity N rows (default
+// 4096, 1 ... 1048576).  The runner drains the new records at every host stop of its loop and once after it, and never
+// hands the engine more than N steps in one batch, so no record is overwritten unread.  FILE gets the header `Time,
+// Step, Measured, SumQx, SumQy, MinQx, MaxQx, MinQy, MaxQy, SumXX, SumYY, SumXY, SumQr, SumRR, SumWx, SumWy, SumVV`
+// once, then one line per record: Time as %.9g, every other number the integer it is (sums of q in units of 2^-20, sums
+// of products of 2^-40, in decimal from their 128 bits, SumXY signed).  A resumed run appends from the resume point (the
+// series is not part of a checkpoint).  (The usage line printed on a bad command line does not list these three.)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -105,6 +116,13 @@ std::string decimal128(unsigned long long hi, unsigned long long lo) {
   return s;
 }
 
+// hi * 2^32 + lo, the two accumulators of a pbMoment128: a signed 128-bit integer in decimal
+std::string decimal128(const pbMoment128 &m) {
+  const __int128 v = (__int128)m.hi * ((__int128)1 << 32) + (__int128)m.lo;
+  const unsigned __int128 mag = v < 0 ? -(unsigned __int128)v : (unsigned __int128)v;
+  return (v < 0 ? "-" : "") + decimal128((unsigned long long)(mag >> 64), (unsigned long long)mag);
+}
+
 // a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
 bool parseFloat(const char *text, float lowest, bool above, float &value) {
   char *end = nullptr;
@@ -138,6 +156,9 @@ int main(int argc, char **argv) {
   std::string rearrangePath;
   float rearrangeGap = 0.0f;
   bool rearrangeWindow = false;
+  std::string seriesPath;
+  float seriesInterval = -1.0f;  // below 0: dump_interval, once the configuration is loaded
+  long seriesCapacity = 4096;
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -189,6 +210,14 @@ int main(int argc, char **argv) {
       badArg = !parseFloat(argv[++i], 0.0f, false, rearrangeGap);
     } else if (!strcmp(argv[i], "--rearrange-window")) {
       rearrangeWindow = true;
+    } else if (!strcmp(argv[i], "--series") && i + 1 < argc) {
+      seriesPath = argv[++i];
+    } else if (!strcmp(argv[i], "--series-interval") && i + 1 < argc) {
+      badArg = !parseFloat(argv[++i], 0.0f, false, seriesInterval);
+    } else if (!strcmp(argv[i], "--series-capacity") && i + 1 < argc) {
+      char *end = nullptr;
+      seriesCapacity = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || seriesCapacity < 1 || seriesCapacity > (1l << 20)) badArg = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -219,7 +248,7 @@ int main(int argc, char **argv) {
   const struct { const char *flag; const std::string &path; const char *noun; } fusedOnly[] = {
       {"--clusters", clustersPath, "analysis"},   {"--contacts", contactsPath, "export"},
       {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
-      {"--rearrange", rearrangePath, "analysis"}};
+      {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"}};
   for (const auto &f : fusedOnly)
     if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
       fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
@@ -322,6 +351,33 @@ int main(int argc, char **argv) {
   long lastCkptStep = stepsDone;
   bool referenceMarked = false;
   float markTime = 0.0f;
+  // the time series: switched on here, behind a resume, so that the records start at the run's first step; drained at
+  // every host stop below
+  unsigned long long seriesWritten = 0;
+  if (!seriesPath.empty()) {
+    if (!sim.setSeries(seriesInterval < 0.0f ? cfg.dump_interval : seriesInterval, (unsigned)seriesCapacity)) return 1;
+    FILE *sf = openOutput(seriesPath, resumePath.empty() ? "w" : "a");
+    if (!sf) return 1;
+    if (fseek(sf, 0, SEEK_END) == 0 && ftell(sf) == 0)  // a fresh file, or a resumed run that appends to none
+      fprintf(sf, "Time, Step, Measured, SumQx, SumQy, MinQx, MaxQx, MinQy, MaxQy, SumXX, SumYY, SumXY, SumQr, SumRR, "
+                  "SumWx, SumWy, SumVV\n");
+    if (fclose(sf) != 0) return 1;
+  }
+  auto drainSeries = [&]() {
+    if (seriesPath.empty()) return true;
+    std::vector<pbMomentsRow> rows;
+    if (!sim.seriesRows(seriesWritten, rows)) return false;
+    if (rows.empty()) return true;
+    FILE *sf = openOutput(seriesPath, "a");
+    if (!sf) return false;
+    for (const pbMomentsRow &r : rows)
+      fprintf(sf, "%.9g, %llu, %u, %lld, %lld, %d, %d, %d, %d, %s, %s, %s, %lld, %s, %lld, %lld, %s\n", (double)r.time,
+              r.step, r.measured, r.sum_qx, r.sum_qy, r.min_qx, r.max_qx, r.min_qy, r.max_qy, decimal128(r.xx).c_str(),
+              decimal128(r.yy).c_str(), decimal128(r.xy).c_str(), r.sum_qr, decimal128(r.rr).c_str(), r.sum_wx, r.sum_wy,
+              decimal128(r.vv).c_str());
+    seriesWritten += rows.size();
+    return fclose(sf) == 0;
+  };
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!ckptPath.empty() && stepsDone > lastCkptStep) {
@@ -335,6 +391,7 @@ int main(int argc, char **argv) {
     }
     if (stopAfterSteps >= 0 && stepsDone >= stopAfterSteps) _exit(9);  // (no flush, no destructors: a kill)
     sim.dumpParticlebot(0, p.nCells, fp, cfg.dump_interval, p.testing, p.light_x, p.light_y);
+    if (!drainSeries()) return 1;
     if (!clustersPath.empty() && sim.dumpDue(cfg.dump_interval)) {
       pbClusterStats cs;
       if (!sim.clusterStats(clusterGap, cs)) return 1;
@@ -404,10 +461,12 @@ int main(int argc, char **argv) {
                                                                    ? ckptEverySteps - (stepsDone - lastCkptStep)
                                                                    : 1);
     else if (ckptEverySeconds > 0) batch = std::min(batch, 20000);  // look at the clock now and then
+    if (!seriesPath.empty()) batch = (int)std::min<long>(batch, seriesCapacity);  // records <= steps: none is lost
     const int ran = sim.advance(cfg.timestep, cfg.sort_interval, batch);
     if (ran == 0) break;
     stepsDone += ran;
   }
+  if (!drainSeries()) return 1;
   if (!finalCkptPath.empty() && !writeCheckpoint(finalCkptPath)) return 1;
   fclose(fp);
   if (!trailPath.empty()) {

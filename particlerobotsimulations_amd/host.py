@@ -54,6 +54,8 @@ _ANALYSES = {
     "pbHostContacts": [_F, _P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)], "pbHostContactVirial": [_F, _P],
     "pbHostRadialCounts": [_F, C.c_uint, _P], "pbHostStructureStats": [_F, _P], "pbHostHexatic": [_F, _P, _P],
     "pbHostMarkReference": [_F], "pbHostRearrangementStats": [_P], "pbHostRearrangementOf": [_P, _P, _P, _P],
+    "pbHostMoments": [_P], "pbHostSetSeries": [_F, C.c_uint], "pbHostSeriesInfo": [_P, _P, _P],
+    "pbHostSeriesRows": [C.c_ulonglong, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
 }
 
 
@@ -346,6 +348,40 @@ class HostSim:
         if lib().pbHostRearrangementOf(self._h, *[_ptr(out[k]) for k in ("disp", "marked", "now", "kept")]) != 0:
             raise RuntimeError("rearrangement_of: the rearrangement analysis needs the fused engine and a marked reference")
         return out
+
+    def moments(self):
+        """The row of integer moments of the state as it is now, on the device (pbSimMoments; fused engine only): a list
+        with one dict of Python ints, the 128-bit sums xx, yy, xy, rr, vv composed."""
+        row = _capi.pbMomentsRow()
+        if lib().pbHostMoments(self._h, C.byref(row)) != 0:
+            raise RuntimeError("moments: the time series needs the fused engine")
+        return [_capi.moments_row(row)]
+
+    def set_series(self, interval, capacity):
+        """Record such a row into a device ring of `capacity` rows in front of every step whose start time passes the
+        schedule's gate at `interval` (0: every step) while the simulation advances (pbSimSetSeries; fused engine only).
+        Restarts at record 0; capacity 0 switches the series off."""
+        if lib().pbHostSetSeries(self._h, float(interval), int(capacity)) != 0:
+            raise RuntimeError("set_series: the time series needs the fused engine, a finite interval >= 0 and a ring "
+                               "of at most 2^31 bytes")
+
+    def series_info(self):
+        """A dict of interval, capacity (0: off) and records taken so far (pbSimGetSeriesInfo; fused engine only)."""
+        i, c, r = C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
+        if lib().pbHostSeriesInfo(self._h, C.byref(i), C.byref(c), C.byref(r)) != 0:
+            raise RuntimeError("series_info: the time series needs the fused engine")
+        return {"interval": float(i.value), "capacity": int(c.value), "records": int(r.value)}
+
+    def series_rows(self, first=0):
+        """The records from number `first` up to the last one taken, in order, as moments() gives rows
+        (Particlebot::seriesRows; fused engine only)."""
+        info = self.series_info()
+        cap = max(info["records"] - int(first), 1)
+        rows, count = (_capi.pbMomentsRow * cap)(), C.c_ulonglong(0)
+        if lib().pbHostSeriesRows(self._h, int(first), rows, cap, C.byref(count)) != 0:
+            raise RuntimeError("series_rows: the time series needs the fused engine, the series on and records that the "
+                               "ring still holds")
+        return [_capi.moments_row(r) for r in rows[:int(count.value)]]
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
