@@ -231,6 +231,13 @@ class Particlebot {
   bool setSeries(float interval, unsigned capacity);
   bool seriesInfo(float &interval, unsigned &capacity, unsigned long long &records);
   bool seriesRows(unsigned long long first, std::vector<pbMomentsRow> &rows);
+  /* Pair correlations of the resident state on the device (pbSimPairCorrelation, include/particlebot_hip.h has the
+   * definition): `bins` rows of pairs binned by distance up to rMax with the sums of a_i . a_j, ax and ay, and the
+   * totals row; kind is PB_CORR_VELOCITY, PB_CORR_DISPLACEMENT (since markReference) or PB_CORR_RADIUS.  Fused engine
+   * only: Legacy and HostOnly instances return false with a message on stderr.  Also false on an unknown kind, a bad
+   * rMax or bins, and for displacements with no mark held. */
+  bool pairCorrelation(int kind, float rMax, unsigned bins, std::vector<pbCorrelationBin> &rows,
+                       pbCorrelationTotals &totals);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -631,6 +631,61 @@ int pbSimGetSeriesInfo(pbSim *sim, float *interval, unsigned *capacity, unsigned
 int pbSimGetSeriesOf(pbSim *sim, unsigned member, unsigned long long first, unsigned count, pbMomentsRow *rows);
 int pbSimGetSeriesTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
+/* Pair correlations on the device (csrc/pb_correlate.hip): how far a per-bot quantity is coordinated across the blob.
+ * All pairs of a member are binned by distance and the dot products a_i . a_j of a per-bot integer vector a = (ax, ay)
+ * are summed per bin: velocity alignment, the radius wave (a correlation that changes sign with distance) and
+ * cooperative rearrangement are this one measurement with three choices of a.  Read-only: state, slot layout,
+ * pbSimStats, time, the generators, the mark and the other analyses' results stay as they were.
+ * Nodes are all nCells bots of a member, dead bots and the payload bot included; a bot with a non-finite position or
+ * radius takes part in nothing, as in pbSimRadialCounts.  `kind` selects a; scaling is in fp32 and the conversion rounds
+ * to nearest even, as in pbSimMoments and pbSimRearrangementOf:
+ *     PB_CORR_VELOCITY      a = (rint(vx * 2^20), rint(vy * 2^20));  MEASURED iff the bot is a node and vx, vy are
+ *                           finite with fabsf(.) < 2048.0f
+ *     PB_CORR_DISPLACEMENT  a = (qx, qy) of the rearrangement analysis, since the mark; MEASURED iff the bot is a node
+ *                           and that analysis measures it (fabsf(dx) < 2048.0f and fabsf(dy) < 2048.0f).  Needs a mark
+ *                           (pbSimMarkReference), which the call leaves alone
+ *     PB_CORR_RADIUS        a = (rint(rad * 2^20), 0);  MEASURED iff the bot is a node and fabsf(rad) < 2048.0f
+ * An unmeasured bot is in no pair.  Distance and bin are pbSimRadialCounts', word for word: dist = sqrtf(rx*rx + ry*ry)
+ * without contraction, scale = (float)bins / rMax, the ORDERED pair (i, j) goes to bin b = (int)(dist * scale) iff
+ * fl(dist * scale) < (float)bins; coincident bots land in bin 0.  Per member and bin, over the ordered pairs (i, j),
+ * i != j, both measured, that fall into it:
+ *     pairs = their number (even);   dot = sum (ax_i*ax_j + ay_i*ay_j);   ax = sum ax_i;   ay = sum ay_i
+ * dot, ax and ay are signed 128-bit integers in units of 2^-40 (dot) and 2^-20: pbMoment128, value hi * 2^32 + lo,
+ * NORMALISED by the host to 0 <= lo < 2^32 with hi the floor quotient, the same form however the device splits its
+ * adds.  The totals row of a member (totals may be NULL): measured, sum_ax, sum_ay, sum_a2 = sum (ax^2 + ay^2)
+ * (normalised) over its measured bots, and pairs over all bins.  With m = sum_a / measured the connected correlation of
+ * a bin is (dot - 2 m . (ax, ay) + |m|^2 pairs) / pairs: it comes from these integers alone, with no second pass and no
+ * mean known in advance.
+ * EXACTNESS.  pairs is always exact.  The other sums are exact whenever no bin of any member holds 2^31 ordered pairs
+ * or more; the call checks the counts it is about to return, and if a bin holds more it answers PB_ERR_ARG ("a bin
+ * holds 2^31 pairs or more: raise bins or lower rMax") without writing rows or totals.
+ * pbSimGetCorrelationTimes: analyses run so far and the span of the last one on the batch's stream in milliseconds, from
+ * the first launch of its front end to its last kernel (HIP events), as pbSimGetClusterTimes; either pointer may be NULL.
+ * PB_ERR_ARG, before the device is touched: NULL handle or rows; unknown kind; rMax not finite or not > 0; bins outside
+ * 1 ... PB_CORR_MAX_BINS; a batch of 2^28 bots or more or of more than 65535 members; PB_CORR_DISPLACEMENT with no
+ * reference marked.
+ * Cost: the front end's re-filing on a grid of edge rMax (1 + 2^-10); one launch that writes a per sorted slot (8 bytes)
+ * and reduces the totals; one sweep over the nine cells, a pair met once, five 64-bit LDS atomics per counted pair into
+ * the workgroup's table of 40 bytes per bin, flushed once per workgroup.  Scratch on top of the cluster analysis': 8
+ * bytes per bot of the batch, 72 per bin and 40 per member.  Read back: 72 bytes per bin and 40 per member.
+ * Out of scope: phase correlations (they need a transcendental and would not be exact); correlations per series
+ * record; time correlations; normalisation to g(r); the ensemble layer's summary rows; the legacy engine. */
+#define PB_CORR_MAX_BINS 1024u
+enum { PB_CORR_VELOCITY = 0, PB_CORR_DISPLACEMENT = 1, PB_CORR_RADIUS = 2 };
+typedef struct pbCorrelationBin {      /* 56 bytes */
+  unsigned long long pairs;
+  pbMoment128 dot, ax, ay;
+} pbCorrelationBin;
+typedef struct pbCorrelationTotals {   /* 48 bytes */
+  unsigned measured, reserved;
+  long long sum_ax, sum_ay;
+  pbMoment128 sum_a2;
+  unsigned long long pairs;
+} pbCorrelationTotals;
+int pbSimPairCorrelation(pbSim *sim, int kind, float rMax, unsigned bins, pbCorrelationBin *rows /* nsims * bins */,
+                         pbCorrelationTotals *totals /* nsims entries, may be NULL */);
+int pbSimGetCorrelationTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

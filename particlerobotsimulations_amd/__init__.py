@@ -15,7 +15,8 @@ from . import _capi
 from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
-           "radial_distribution", "mean_squared_displacement", "moments_summary"]
+           "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
+           "connected_correlation"]
 
 
 def radial_distribution(counts, r_max, density, n):
@@ -43,6 +44,42 @@ def mean_squared_displacement(row, subtract_drift=False):
     if subtract_drift:
         num -= int(row["sum_qx"]) ** 2 + int(row["sum_qy"]) ** 2
     return float(Fraction(num, m * m << 40))
+
+
+def correlation_values(rows):
+    """One member's rows of pair_correlation() as a dict of lists of Python ints, one entry per bin: pairs, and dot, ax,
+    ay composed from their 128 bits (hi * 2^32 + lo).  dot is in units of 2^-40, ax and ay in units of 2^-20."""
+    rows = np.asarray(rows)
+    if rows.ndim != 1:
+        raise ValueError("correlation_values: the rows of one member, shaped (bins,)")
+    out = {"pairs": [int(v) for v in rows["pairs"]]}
+    for name in ("dot", "ax", "ay"):
+        out[name] = [(int(h) << 32) + int(l) for h, l in zip(rows[name + "_hi"], rows[name + "_lo"])]
+    return out
+
+
+def connected_correlation(rows, totals):
+    """(C, C / C0) of one member from pair_correlation(): float64[bins] each.  With m = sum_a / measured the connected
+    correlation of a bin is C = (dot - 2 m . (ax, ay) + |m|^2 pairs) / pairs / 2^40 and C0 = sum_a2 / measured - |m|^2,
+    the variance of a.  Every quotient is formed from the integers as one exact fraction and converted once; NaN for an
+    empty bin, and for the ratio when C0 is 0."""
+    from fractions import Fraction
+    v = correlation_values(rows)
+    M, sx, sy = int(totals["measured"]), int(totals["sum_ax"]), int(totals["sum_ay"])
+    nan = float("nan")
+    c = np.full(len(v["pairs"]), nan)
+    ratio = c.copy()
+    if M == 0:
+        return c, ratio
+    c0 = Fraction(int(totals["sum_a2"]) * M - sx * sx - sy * sy, M * M)  # units of 2^-40, like the numerators below
+    for b, pairs in enumerate(v["pairs"]):
+        if pairs:
+            num = v["dot"][b] * M * M - 2 * M * (sx * v["ax"][b] + sy * v["ay"][b]) + (sx * sx + sy * sy) * pairs
+            cb = Fraction(num, M * M * pairs)
+            c[b] = float(cb / (1 << 40))
+            if c0:
+                ratio[b] = float(cb / c0)
+    return c, ratio
 
 
 def moments_summary(row):
@@ -644,6 +681,28 @@ class Sim:
         """(records taken so far, device milliseconds of the last row's launches)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetSeriesTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetSeriesTimes")
+        return int(n.value), float(ms.value)
+
+    def pair_correlation(self, kind, r_max, bins, member=None):
+        """Pair correlations of every member's state as it is now, on the device (pbSimPairCorrelation): all pairs binned
+        by distance as radial_counts bins them, with the sums of a_i . a_j per bin.  kind: "velocity" (a = v),
+        "displacement" (a = the displacement since mark_reference) or "radius" (a = (rad, 0)), or the PB_CORR_* int; a is
+        in units of 2^-20.  Returns (rows, totals): rows a structured array (nsims, bins) of pairs, dot_lo / dot_hi,
+        ax_lo / ax_hi, ay_lo / ay_hi (each 128-bit value is hi * 2^32 + lo with 0 <= lo < 2^32; correlation_values()
+        composes them), totals a list of dicts (measured, sum_ax, sum_ay, sum_a2, pairs), one per member; with member=k
+        that member's (bins,) rows and its dict.  connected_correlation() turns both into C(r)."""
+        nsims = int(getattr(self, "nsims", 1))
+        rows = np.zeros((nsims, max(int(bins), 1)), _capi.CORRELATION_BIN_DTYPE)
+        tot = (_capi.pbCorrelationTotals * nsims)()
+        _capi.check(_capi.lib().pbSimPairCorrelation(self._h, _capi.correlation_kind(kind), float(r_max), int(bins),
+                                                     _capi.np_ptr(rows), tot), "pbSimPairCorrelation")
+        totals = [_capi.correlation_totals(t) for t in tot]
+        return (rows, totals) if member is None else (rows[int(member)], totals[int(member)])
+
+    def correlation_times(self):
+        """(pair correlations run so far, device milliseconds of the last one)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetCorrelationTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetCorrelationTimes")
         return int(n.value), float(ms.value)
 
 

@@ -144,6 +144,36 @@ def moments_row(r):
     return d
 
 
+class pbCorrelationBin(C.Structure):
+    _fields_ = [("pairs", C.c_ulonglong), ("dot", pbMoment128), ("ax", pbMoment128), ("ay", pbMoment128)]
+
+
+class pbCorrelationTotals(C.Structure):
+    _fields_ = [("measured", C.c_uint), ("reserved", C.c_uint), ("sum_ax", C.c_longlong), ("sum_ay", C.c_longlong),
+                ("sum_a2", pbMoment128), ("pairs", C.c_ulonglong)]
+
+
+PB_CORR_KINDS = {"velocity": 0, "displacement": 1, "radius": 2}
+# pbCorrelationBin as a numpy record: each 128-bit value is hi * 2^32 + lo, normalised to 0 <= lo < 2^32
+CORRELATION_BIN_DTYPE = np.dtype([("pairs", np.uint64), ("dot_lo", np.uint64), ("dot_hi", np.int64),
+                                  ("ax_lo", np.uint64), ("ax_hi", np.int64), ("ay_lo", np.uint64), ("ay_hi", np.int64)])
+
+
+def correlation_kind(kind):
+    """PB_CORR_* from an int or from "velocity" | "displacement" | "radius"."""
+    if isinstance(kind, str):
+        if kind not in PB_CORR_KINDS:
+            raise ValueError(f"pair_correlation: unknown kind {kind!r}")
+        return PB_CORR_KINDS[kind]
+    return int(kind)
+
+
+def correlation_totals(t):
+    """A pbCorrelationTotals row as a dict of Python ints, sum_a2 composed from its 128 bits."""
+    return {"measured": int(t.measured), "sum_ax": int(t.sum_ax), "sum_ay": int(t.sum_ay),
+            "sum_a2": (int(t.sum_a2.hi) << 32) + int(t.sum_a2.lo), "pairs": int(t.pairs)}
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -224,6 +254,8 @@ SYMBOLS = {
     "pbSimGetSeriesInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(C.c_ulonglong)]),
     "pbSimGetSeriesOf": (_I, [_VP, _U, C.c_ulonglong, _U, C.POINTER(pbMomentsRow)]),
     "pbSimGetSeriesTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimPairCorrelation": (_I, [_VP, _I, _F, _U, _VP, C.POINTER(pbCorrelationTotals)]),
+    "pbSimGetCorrelationTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

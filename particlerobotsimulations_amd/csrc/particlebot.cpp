@@ -1494,6 +1494,14 @@ bool Particlebot::seriesRows(unsigned long long first, std::vector<pbMomentsRow>
   });
 }
 
+bool Particlebot::pairCorrelation(int kind, float rMax, unsigned bins, std::vector<pbCorrelationBin> &rows,
+                                  pbCorrelationTotals &totals) {
+  return onFusedEngine("pairCorrelation", "correlation analysis", [&] {
+    rows.assign(bins >= 1 && bins <= PB_CORR_MAX_BINS ? bins : 1, pbCorrelationBin());
+    return pbSimPairCorrelation(sim, kind, rMax, bins, rows.data(), &totals);
+  });
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

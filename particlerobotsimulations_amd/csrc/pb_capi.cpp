@@ -390,6 +390,19 @@ int pbHostSeriesRows(void *hv, unsigned long long first, pbMomentsRow *rows, uns
   return 0;
 }
 
+// pair correlations of the resident state (Particlebot::pairCorrelation; fused engine only): `bins` 56-byte
+// pbCorrelationBin rows and, unless NULL, the 48-byte pbCorrelationTotals row.  -1 on the other engines, an unknown
+// kind, a bad rMax or bins, or displacements without a mark.
+int pbHostPairCorrelation(void *hv, int kind, float rMax, unsigned bins, pbCorrelationBin *rows,
+                          pbCorrelationTotals *totals) {
+  std::vector<pbCorrelationBin> r;
+  pbCorrelationTotals t;
+  if (!rows || !((HostSim *)hv)->bot->pairCorrelation(kind, rMax, bins, r, t)) return -1;
+  copyOut(rows, r);
+  if (totals) *totals = t;
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

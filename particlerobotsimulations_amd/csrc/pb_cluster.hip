@@ -402,6 +402,7 @@ void pbClusterFree(pbSim *S) {
   pbContactsFree(C);
   pbStructureFree(C);
   pbDynamicsFree(C);
+  pbCorrelateFree(C);
   delete C;
   S->cluster = nullptr;
 }

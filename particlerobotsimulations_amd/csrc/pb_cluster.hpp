@@ -1,5 +1,5 @@
-// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip and pb_dynamics.hip: the scratch
-// object with its four clocks, the fresh grid, the wave helpers, the workgroup scan, the walk over a bot's nine cells
+// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip, pb_dynamics.hip and
+// pb_correlate.hip: the scratch object with its five clocks, the fresh grid, the wave helpers, the workgroup scan, the walk over a bot's nine cells
 // (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour sweep of the analysis layer is built on, the front
 // end that files the bots (rmax, hash, sort, gather, cell starts) and the argument checks of the entry points.
 #pragma once
@@ -59,6 +59,12 @@ struct PbClusterScratch {
   float2 *dDisp = nullptr;                   // total, ORIGINAL order: dx, dy
   pbRearrangementStats *dRows = nullptr;     // nsims; sum_q2_lo / sum_q2_hi hold the two partial sums until the host
                                              // composes them
+  // pair correlations (pb_correlate.hip): allocated by the first call, the bins' words grown with bins
+  int2 *kA = nullptr;                        // total, SORTED order: the vector a, x = INT_MIN for an unmeasured bot
+  unsigned long long *kAcc = nullptr;        // nsims * kAccBins * 9: per bin the count and eight partial sums
+  unsigned kAccBins = 0;
+  unsigned long long *kTotals = nullptr;     // nsims * 5: measured, sum ax, sum ay, the two partial sums of a^2
+  PbAnalysisClock correlateClock;
 };
 
 namespace {
@@ -295,3 +301,5 @@ int pbContactScan(pbSim *S, const uint32_t *degree, uint32_t n, unsigned long lo
 void pbStructureFree(PbClusterScratch *C);
 // frees the rearrangement analysis' buffers and the mark, if any (pbClusterFree)                       pb_dynamics.hip
 void pbDynamicsFree(PbClusterScratch *C);
+// frees the pair correlations' buffers, if any (pbClusterFree)                                        pb_correlate.hip
+void pbCorrelateFree(PbClusterScratch *C);

@@ -6,6 +6,7 @@
 //                   [--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]]
 //                   [--rearrange FILE [--rearrange-gap G] [--rearrange-window]]
 //                   [--series FILE [--series-interval T] [--series-capacity N]]
+//                   [--correlate FILE [--correlate-kind velocity|radius] [--correlate-rmax R] [--correlate-bins B]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -60,6 +61,13 @@
 // once, then one line per record: Time as %.9g, every other number the integer it is (sums of q in units of 2^-20, sums
 // of products of 2^-40, in decimal from their 128 bits, SumXY signed).  A resumed run appends from the resume point (the
 // series is not part of a checkpoint).  (The usage line printed on a bad command line does not list these three.)
+// --correlate FILE writes the pair correlations of the FINAL state once, when the run ends
+// (Particlebot::pairCorrelation): line 1 the totals, `Kind, <kind>, Measured, <m>, SumAx, <..>, SumAy, <..>, SumA2, <..>,
+// Pairs, <..>`; line 2 the header `RLo, RHi, Pairs, Dot, SumAx, SumAy`; then one row per bin, the edges as --rdf prints
+// them, every other number the integer it is (Dot and SumA2 in units of 2^-40, the sums of a in units of 2^-20, in
+// decimal from their 128 bits).  --correlate-kind velocity|radius (default velocity; displacements need a mark and are
+// left to the API), --correlate-rmax R (default 10 * max_radius, finite and > 0) and --correlate-bins B (default 200,
+// 1 ... 1024).  (The usage line does not list these four either.)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -159,6 +167,10 @@ int main(int argc, char **argv) {
   std::string seriesPath;
   float seriesInterval = -1.0f;  // below 0: dump_interval, once the configuration is loaded
   long seriesCapacity = 4096;
+  std::string correlatePath;
+  int correlateKind = PB_CORR_VELOCITY;
+  float correlateRmax = 0.0f;  // 0: 10 * max_radius, once the configuration is loaded
+  long correlateBins = 200;
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -218,6 +230,19 @@ int main(int argc, char **argv) {
       char *end = nullptr;
       seriesCapacity = strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end || seriesCapacity < 1 || seriesCapacity > (1l << 20)) badArg = true;
+    } else if (!strcmp(argv[i], "--correlate") && i + 1 < argc) {
+      correlatePath = argv[++i];
+    } else if (!strcmp(argv[i], "--correlate-kind") && i + 1 < argc) {
+      const char *kind = argv[++i];
+      if (!strcmp(kind, "velocity")) correlateKind = PB_CORR_VELOCITY;
+      else if (!strcmp(kind, "radius")) correlateKind = PB_CORR_RADIUS;
+      else badArg = true;  // (displacement included: the runner holds no mark at the end of a run)
+    } else if (!strcmp(argv[i], "--correlate-rmax") && i + 1 < argc) {
+      badArg = !parseFloat(argv[++i], 0.0f, true, correlateRmax);
+    } else if (!strcmp(argv[i], "--correlate-bins") && i + 1 < argc) {
+      char *end = nullptr;
+      correlateBins = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || correlateBins < 1 || correlateBins > (long)PB_CORR_MAX_BINS) badArg = true;
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -248,7 +273,8 @@ int main(int argc, char **argv) {
   const struct { const char *flag; const std::string &path; const char *noun; } fusedOnly[] = {
       {"--clusters", clustersPath, "analysis"},   {"--contacts", contactsPath, "export"},
       {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
-      {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"}};
+      {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"},
+      {"--correlate", correlatePath, "analysis"}};
   for (const auto &f : fusedOnly)
     if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
       fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
@@ -508,6 +534,23 @@ int main(int argc, char **argv) {
       fprintf(rf, "%.9g, %.9g, %llu\n", (double)b * (double)rmax / (double)rdfBins,
               (double)(b + 1) * (double)rmax / (double)rdfBins, counts[b]);
     if (fclose(rf) != 0) return 1;
+  }
+  if (!correlatePath.empty()) {
+    const float rmax = correlateRmax > 0.0f ? correlateRmax : 10.0f * p.max_radius;
+    std::vector<pbCorrelationBin> rows;
+    pbCorrelationTotals tot;
+    if (!sim.pairCorrelation(correlateKind, rmax, (unsigned)correlateBins, rows, tot)) return 1;
+    FILE *kf = openOutput(correlatePath, "w");
+    if (!kf) return 1;
+    fprintf(kf, "Kind, %s, Measured, %u, SumAx, %lld, SumAy, %lld, SumA2, %s, Pairs, %llu\n",
+            correlateKind == PB_CORR_RADIUS ? "radius" : "velocity", tot.measured, tot.sum_ax, tot.sum_ay,
+            decimal128(tot.sum_a2).c_str(), tot.pairs);
+    fprintf(kf, "RLo, RHi, Pairs, Dot, SumAx, SumAy\n");
+    for (size_t b = 0; b < rows.size(); b++)
+      fprintf(kf, "%.9g, %.9g, %llu, %s, %s, %s\n", (double)b * (double)rmax / (double)correlateBins,
+              (double)(b + 1) * (double)rmax / (double)correlateBins, rows[b].pairs, decimal128(rows[b].dot).c_str(),
+              decimal128(rows[b].ax).c_str(), decimal128(rows[b].ay).c_str());
+    if (fclose(kf) != 0) return 1;
   }
   return 0;
 }

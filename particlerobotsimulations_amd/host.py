@@ -56,6 +56,7 @@ _ANALYSES = {
     "pbHostMarkReference": [_F], "pbHostRearrangementStats": [_P], "pbHostRearrangementOf": [_P, _P, _P, _P],
     "pbHostMoments": [_P], "pbHostSetSeries": [_F, C.c_uint], "pbHostSeriesInfo": [_P, _P, _P],
     "pbHostSeriesRows": [C.c_ulonglong, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
+    "pbHostPairCorrelation": [C.c_int, _F, C.c_uint, _P, _P],
 }
 
 
@@ -382,6 +383,19 @@ class HostSim:
             raise RuntimeError("series_rows: the time series needs the fused engine, the series on and records that the "
                                "ring still holds")
         return [_capi.moments_row(r) for r in rows[:int(count.value)]]
+
+    def pair_correlation(self, kind, r_max, bins, member=None):
+        """Pair correlations of the state as it is now, on the device (pbSimPairCorrelation; fused engine only): (rows,
+        totals) as Sim.pair_correlation gives them, rows shaped (1, bins), or (bins,) with a single totals dict for
+        member=0."""
+        rows = np.zeros((1, max(int(bins), 1)), _capi.CORRELATION_BIN_DTYPE)
+        tot = _capi.pbCorrelationTotals()
+        if lib().pbHostPairCorrelation(self._h, _capi.correlation_kind(kind), float(r_max), int(bins), _ptr(rows),
+                                       C.byref(tot)) != 0:
+            raise RuntimeError("pair_correlation: the correlation analysis needs the fused engine, a known kind, a "
+                               "finite r_max > 0 and 1 ... 1024 bins")
+        totals = [_capi.correlation_totals(tot)]
+        return (rows, totals) if member is None else (rows[int(member)], totals[int(member)])
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
