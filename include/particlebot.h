@@ -238,6 +238,19 @@ class Particlebot {
    * rMax or bins, and for displacements with no mark held. */
   bool pairCorrelation(int kind, float rMax, unsigned bins, std::vector<pbCorrelationBin> &rows,
                        pbCorrelationTotals &totals);
+  /* Time correlations of the resident state on the device (pbSimSetTimeCorrelation / pbSimGetTimeCorrelation,
+   * include/particlebot_hip.h has the definitions): setTimeCorrelation(interval, lags, overlapRadius) starts a device
+   * ring of `lags` snapshots, taken in front of every step whose start time passes the schedule's gate at `interval`
+   * (0: every step, -1: only by timeCorrelationRecord) while update() runs, and a table that sums squared displacement,
+   * velocity products and the overlap count per lag over all time origins; lags 0 switches it off.
+   * timeCorrelationRecord takes one record now; timeCorrelationInfo gives interval, lags, overlap radius and the records
+   * taken so far; timeCorrelationRows the `lags` rows, lag 0 first.  Fused engine only: Legacy and HostOnly instances
+   * return false with a message on stderr.  Also false on a bad interval, lags or radius, and for a record or a read
+   * with the correlation off.  The correlation is not part of a checkpoint. */
+  bool setTimeCorrelation(float interval, unsigned lags, float overlapRadius);
+  bool timeCorrelationRecord();
+  bool timeCorrelationInfo(float &interval, unsigned &lags, float &overlapRadius, unsigned long long &records);
+  bool timeCorrelationRows(std::vector<pbTimeCorrelationRow> &rows);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -669,7 +669,7 @@ int pbSimGetSeriesTimes(pbSim *sim, unsigned long long *records, float *last_dev
  * the workgroup's table of 40 bytes per bin, flushed once per workgroup.  Scratch on top of the cluster analysis': 8
  * bytes per bot of the batch, 72 per bin and 40 per member.  Read back: 72 bytes per bin and 40 per member.
  * Out of scope: phase correlations (they need a transcendental and would not be exact); correlations per series
- * record; time correlations; normalisation to g(r); the ensemble layer's summary rows; the legacy engine. */
+ * record; time correlations (pbSimSetTimeCorrelation, below); normalisation to g(r); the ensemble layer's summary rows; the legacy engine. */
 #define PB_CORR_MAX_BINS 1024u
 enum { PB_CORR_VELOCITY = 0, PB_CORR_DISPLACEMENT = 1, PB_CORR_RADIUS = 2 };
 typedef struct pbCorrelationBin {      /* 56 bytes */
@@ -685,6 +685,93 @@ typedef struct pbCorrelationTotals {   /* 48 bytes */
 int pbSimPairCorrelation(pbSim *sim, int kind, float rMax, unsigned bins, pbCorrelationBin *rows /* nsims * bins */,
                          pbCorrelationTotals *totals /* nsims entries, may be NULL */);
 int pbSimGetCorrelationTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+
+/* Time correlations on the device (csrc/pb_timecorr.hip): the mean squared displacement, the velocity autocorrelation
+ * and the overlap function per lag, averaged over time origins while pbSimStep runs.  The analyses above describe one
+ * instant or compare with one marked instant; a series row cannot supply sum x(t) . x(t - tau), which needs both
+ * instants per bot in ORIGINAL order while the slots are re-sorted in between.  Off by default; a run that does not ask
+ * for it is unchanged: same launches, same pbSimStats, same bits.
+ * A RECORD keeps (x, y, vx, vy) of every bot of every member, bit for bit, in ORIGINAL order: record number r, counted
+ * from 0, goes into slot r % lags of a device ring of 16 bytes per bot and slot.  The host keeps
+ * pbSimStats.steps per slot (lags are reported in steps; a record's time is not kept).  A record is the state pbSimGetState would return had the caller stopped pbSimStep just
+ * before that step: positions from the previous step's update, velocities from the previous step's kick (the state a
+ * series record describes).  After the snapshot is stored, record r is paired with the records r - l for
+ * l = 0 ... min(r, lags - 1); l = 0 pairs the record with itself, and its vacf is sum |w|^2, the normaliser.
+ * A PAIR.  Nodes are all nCells bots of a member, dead bots and the payload bot included.  For a bot and a pair of
+ * records (now, then), in fp32 without contraction, dx = x_now - x_then and dy likewise.  The pair is MEASURED iff all
+ * eight inputs are finite, fabsf(dx) < 2048.0f, fabsf(dy) < 2048.0f, and all four velocity components have
+ * fabsf(.) < 2048.0f (the rearrangement analysis' bound and scale).  Then, in fp32 scaling and with round-to-nearest-even
+ * conversion,
+ *     qx = (long long)rint(dx * 1048576.0f);   qy likewise;   wx, wy from the velocities of each instant likewise
+ *     s = qx*qx + qy*qy   (below 2^63);        p = wx_now*wx_then + wy_now*wy_then   (|p| below 2^63)
+ * and a2 = qa*qa with qa = rint(overlapRadius * 2^20), computed once on the host.  An unmeasured pair takes part in
+ * nothing.  Per member and lag, over the measured (bot, origin) pairs, one pbTimeCorrelationRow:
+ *     lag        in RECORDS: record r against record r - lag
+ *     origins    record pairs added so far;  sum_steps the sum over them of step(r) - step(r - lag), so that the mean
+ *                lag is sum_steps / origins steps (both are the same for every member)
+ *     samples    the measured pairs;  sum_qx, sum_qy the drift, units of 2^-20
+ *     msd = sum s,  vacf = sum p (signed), units of 2^-40, 128-bit sums as pbMoment128, value hi * 2^32 + lo: per
+ *                sample the 64-bit value v is split as lo += (unsigned)v and hi += v >> 32 with an arithmetic shift
+ *                (the two's-complement split of pbSimMoments); NORMALISED by the host to 0 <= lo < 2^32 with hi the
+ *                floor quotient, as pbSimPairCorrelation does
+ *     overlap    the samples with s < a2 (so overlapRadius == 0 counts nothing);  max_q2 the largest s, 0 with no sample
+ * One table cell per (member, lag) lives on the device; pbSimSetTimeCorrelation zeroes it and every record adds to it:
+ * the average over time origins happens on the device and nothing comes back per record.  Every added value is an
+ * integer: results do not depend on slot order, on the kernel form that stepped, or on the order in which the device
+ * adds, and can be compared exactly.  No float atomics and no 128-bit atomics.
+ * EXACTNESS.  samples, origins and sum_steps cannot wrap (a cell gains at most nCells < 2^28 samples per record).  The
+ * other sums are exact while a cell holds fewer than 2^31 samples: each half-accumulator then stays below 2^63 in
+ * magnitude (DESIGN.md has the derivation).  pbSimGetTimeCorrelation checks the counts it is about to return, and if a
+ * cell holds more it answers PB_ERR_ARG ("a lag holds 2^31 samples or more: restart the correlation") and writes no rows.
+ * WHEN RECORDS ARE TAKEN.  interval > 0: in front of every executed step whose fp32 start time t passes the schedule's
+ * own gate t - interval floorf(t / interval) < dt, the series' rule.  interval == 0: in front of every executed step.
+ * interval == -1.0f exactly: manual only.  pbSimTimeCorrelationRecord takes one record now, of the state as it is,
+ * whatever the interval, whenever the correlation is on, with the batch's time and pbSimStats.steps.  lags == 0 switches
+ * off and frees everything: no allocation and no launch (the default).  Calling pbSimSetTimeCorrelation again restarts
+ * from record 0.  Everything said about series records on the three stepping paths holds here: no launch is fused
+ * across a gate, a resident stretch ends in front of one, no record is taken for a step that does not run because
+ * t > max_time, and no state bit changes, only which launches carry the steps.  When the series and the correlation are
+ * both due in front of a step, the series record comes first.
+ * The correlation is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave the ring alone
+ * (snapshots are addressed by original index, so re-sorts do not invalidate them); pbSimDestroy frees it.  Reading or
+ * recording leaves alone: the slot layout, keys, cell lists, pbSimStats, time, RNG, the mark, the series and every other
+ * analysis' scratch.  Recording never waits for the device.
+ * pbSimGetTimeCorrelationInfo: the interval, the lags (0: off), the overlap radius and the records taken so far; any
+ * pointer may be NULL, not all.  pbSimGetTimeCorrelation: nsims * lags rows, member-major, lag 0 first; a lag that no
+ * record has reached yet has origins == 0 and zeros.  pbSimGetTimeCorrelationTimes: records so far and the span of the
+ * last record's launches on the batch's stream in milliseconds (HIP events), as pbSimGetSeriesTimes; either pointer may
+ * be NULL.
+ * PB_ERR_ARG, before the device is touched: NULL handle or rows; interval NaN, infinite, or negative other than -1;
+ * lags > PB_TCORR_MAX_LAGS; overlapRadius not in [0, 2048) or NaN; a ring above 2^33 bytes (lags x total x 16); a batch
+ * of 2^28 bots or more or of more than 65535 members; the pointers of pbSimGetTimeCorrelationInfo all NULL; a record or
+ * a read with the correlation off.
+ * Cost: a record is one pass over posrad, velocities and original indices in slot order that scatters 16 bytes per bot
+ * into the ring (the only uncoalesced access), and one launch for all lags that reads two snapshots per lag as coalesced
+ * 16-byte loads in original order, at most PB_TCORR_BLOCKS workgroups of 256 lanes per member and lag, each adding its
+ * nine sums into the cell with one set of 64-bit integer atomics.
+ * Out of scope: logarithmic or multi-tau lag spacing; the non-Gaussian parameter (sum s^2 does not fit the exact
+ * scheme); the self-intermediate scattering function and phase correlations (they need a transcendental); per-bot
+ * outputs; neighbour-based quantities per lag such as bond lifetime; recording inside the resident kernel without ending
+ * the stretch; the ensemble layer's summary rows and its RCCL gather; the legacy engine. */
+#define PB_TCORR_MAX_LAGS 64u
+#define PB_TCORR_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
+typedef struct pbTimeCorrelationRow {  /* 96 bytes */
+  unsigned lag, reserved;              /* lag in RECORDS: record r against record r - lag */
+  unsigned long long origins;          /* record pairs added so far (the same for every member) */
+  unsigned long long sum_steps;        /* sum over those pairs of step(r) - step(r - lag): mean lag = sum_steps / origins steps */
+  unsigned long long samples;          /* measured (bot, origin) pairs */
+  long long sum_qx, sum_qy;            /* sum of the displacement, units of 2^-20: the drift */
+  pbMoment128 msd;                     /* sum of s = qx*qx + qy*qy, units of 2^-40 */
+  pbMoment128 vacf;                    /* sum of wx_now*wx_then + wy_now*wy_then (signed), units of 2^-40 */
+  unsigned long long overlap;          /* samples with s < a2 */
+  unsigned long long max_q2;           /* largest s; 0 with no sample */
+} pbTimeCorrelationRow;
+int pbSimSetTimeCorrelation(pbSim *sim, float interval, unsigned lags, float overlapRadius);
+int pbSimTimeCorrelationRecord(pbSim *sim);   /* one record now, of the state as it is */
+int pbSimGetTimeCorrelationInfo(pbSim *sim, float *interval, unsigned *lags, float *overlapRadius,
+                                unsigned long long *records);
+int pbSimGetTimeCorrelation(pbSim *sim, pbTimeCorrelationRow *rows /* nsims * lags, member-major, lag 0 first */);
+int pbSimGetTimeCorrelationTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a

@@ -16,7 +16,7 @@ from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
-           "connected_correlation"]
+           "connected_correlation", "time_correlation_summary"]
 
 
 def radial_distribution(counts, r_max, density, n):
@@ -44,6 +44,35 @@ def mean_squared_displacement(row, subtract_drift=False):
     if subtract_drift:
         num -= int(row["sum_qx"]) ** 2 + int(row["sum_qy"]) ** 2
     return float(Fraction(num, m * m << 40))
+
+
+def time_correlation_summary(row, lag0=None):
+    """What one row of time_correlation() says about its lag, in float64 from the integers (pure Python; every quotient
+    is formed as one exact fraction and converted once).  Lengths in world units, from the units of 2^-20:
+      mean_lag_steps = sum_steps / origins;
+      msd = msd / samples;  msd_drift_corrected = (msd - (sum_qx^2 + sum_qy^2) / samples) / samples, the spread about
+      the common drift;
+      vacf = the mean of v(t) . v(t - lag);  vacf_normalised = that over the mean |v|^2 of `lag0`, the same member's
+      lag-0 row (None without one, or when its vacf is 0);
+      overlap = overlap / samples, the fraction Q of bots that moved less than the overlap radius.
+    Every value is None for a row with no samples."""
+    from fractions import Fraction
+    keys = ("mean_lag_steps", "msd", "msd_drift_corrected", "vacf", "vacf_normalised", "overlap")
+    m = int(row["samples"])
+    if m == 0:
+        return dict.fromkeys(keys)
+    two = 1 << 40
+    msd, vacf, sx, sy = (int(row[k]) for k in ("msd", "vacf", "sum_qx", "sum_qy"))
+    norm = None
+    if lag0 is not None and int(lag0["samples"]) and int(lag0["vacf"]):
+        norm = float(Fraction(vacf * int(lag0["samples"]), m * int(lag0["vacf"])))
+    origins = int(row["origins"])
+    return {"mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else None,
+            "msd": float(Fraction(msd, m * two)),
+            "msd_drift_corrected": float(Fraction(msd * m - sx * sx - sy * sy, m * m * two)),
+            "vacf": float(Fraction(vacf, m * two)),
+            "vacf_normalised": norm,
+            "overlap": float(Fraction(int(row["overlap"]), m))}
 
 
 def correlation_values(rows):
@@ -703,6 +732,44 @@ class Sim:
         """(pair correlations run so far, device milliseconds of the last one)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetCorrelationTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetCorrelationTimes")
+        return int(n.value), float(ms.value)
+
+    def set_time_correlation(self, interval, lags, overlap_radius):
+        """Keep a device ring of `lags` snapshots (x, y, vx, vy of every bot, original order), one taken in front of
+        every step whose start time passes the schedule's gate at `interval` (0: every step, -1: only by
+        time_correlation_record()) while step() runs, and add every record against the `lags` latest ones into a table
+        per member and lag (pbSimSetTimeCorrelation).  overlap_radius is the a of the overlap function.  Restarts at
+        record 0; lags 0 switches it off.  Recording changes no state bit."""
+        _capi.check(_capi.lib().pbSimSetTimeCorrelation(self._h, float(interval), int(lags), float(overlap_radius)),
+                    "pbSimSetTimeCorrelation")
+
+    def time_correlation_record(self):
+        """One record now, of the state as it is (pbSimTimeCorrelationRecord)."""
+        _capi.check(_capi.lib().pbSimTimeCorrelationRecord(self._h), "pbSimTimeCorrelationRecord")
+
+    def time_correlation_info(self):
+        """A dict of interval, lags (0: off), overlap_radius and records taken so far (pbSimGetTimeCorrelationInfo)."""
+        i, l, a, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_ulonglong(0)
+        _capi.check(_capi.lib().pbSimGetTimeCorrelationInfo(self._h, C.byref(i), C.byref(l), C.byref(a), C.byref(r)),
+                    "pbSimGetTimeCorrelationInfo")
+        return {"interval": float(i.value), "lags": int(l.value), "overlap_radius": float(a.value),
+                "records": int(r.value)}
+
+    def time_correlation(self):
+        """The table as it stands (pbSimGetTimeCorrelation): per member a list of `lags` dicts of Python ints, lag 0
+        first: lag, origins, sum_steps, samples, sum_qx / sum_qy (units of 2^-20), msd and vacf (the 128-bit sums
+        composed, units of 2^-40), overlap, max_q2.  time_correlation_summary() turns a row into MSD, VACF and Q."""
+        lags = self.time_correlation_info()["lags"]
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbTimeCorrelationRow * max(nsims * lags, 1))()
+        _capi.check(_capi.lib().pbSimGetTimeCorrelation(self._h, rows), "pbSimGetTimeCorrelation")
+        return [[_capi.time_correlation_row(rows[m * lags + l]) for l in range(lags)] for m in range(nsims)]
+
+    def time_correlation_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetTimeCorrelationTimes(self._h, C.byref(n), C.byref(ms)),
+                    "pbSimGetTimeCorrelationTimes")
         return int(n.value), float(ms.value)
 
 

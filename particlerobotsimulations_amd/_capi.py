@@ -174,6 +174,24 @@ def correlation_totals(t):
             "sum_a2": (int(t.sum_a2.hi) << 32) + int(t.sum_a2.lo), "pairs": int(t.pairs)}
 
 
+class pbTimeCorrelationRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
+                ("samples", C.c_ulonglong), ("sum_qx", C.c_longlong), ("sum_qy", C.c_longlong),
+                ("msd", pbMoment128), ("vacf", pbMoment128), ("overlap", C.c_ulonglong), ("max_q2", C.c_ulonglong)]
+
+
+def time_correlation_row(r):
+    """A pbTimeCorrelationRow as a dict of Python ints (reserved left out); msd and vacf are the 128-bit sums
+    hi * 2^32 + lo as one int.  sum_qx / sum_qy are in units of 2^-20, msd, vacf and max_q2 in units of 2^-40."""
+    d = {}
+    for name, kind in pbTimeCorrelationRow._fields_:
+        if name == "reserved":
+            continue
+        v = getattr(r, name)
+        d[name] = (int(v.hi) << 32) + int(v.lo) if kind is pbMoment128 else int(v)
+    return d
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -256,6 +274,11 @@ SYMBOLS = {
     "pbSimGetSeriesTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimPairCorrelation": (_I, [_VP, _I, _F, _U, _VP, C.POINTER(pbCorrelationTotals)]),
     "pbSimGetCorrelationTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimSetTimeCorrelation": (_I, [_VP, _F, _U, _F]),
+    "pbSimTimeCorrelationRecord": (_I, [_VP]),
+    "pbSimGetTimeCorrelationInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_F), C.POINTER(C.c_ulonglong)]),
+    "pbSimGetTimeCorrelation": (_I, [_VP, C.POINTER(pbTimeCorrelationRow)]),
+    "pbSimGetTimeCorrelationTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1502,6 +1502,32 @@ bool Particlebot::pairCorrelation(int kind, float rMax, unsigned bins, std::vect
   });
 }
 
+bool Particlebot::setTimeCorrelation(float interval, unsigned lags, float overlapRadius) {
+  auto call = [&] { return pbSimSetTimeCorrelation(sim, interval, lags, overlapRadius); };
+  return onFusedEngine("setTimeCorrelation", "time correlation", call);
+}
+
+bool Particlebot::timeCorrelationRecord() {
+  return onFusedEngine("timeCorrelationRecord", "time correlation", [&] { return pbSimTimeCorrelationRecord(sim); });
+}
+
+bool Particlebot::timeCorrelationInfo(float &interval, unsigned &lags, float &overlapRadius, unsigned long long &records) {
+  auto call = [&] { return pbSimGetTimeCorrelationInfo(sim, &interval, &lags, &overlapRadius, &records); };
+  return onFusedEngine("timeCorrelationInfo", "time correlation", call);
+}
+
+bool Particlebot::timeCorrelationRows(std::vector<pbTimeCorrelationRow> &rows) {
+  return onFusedEngine("timeCorrelationRows", "time correlation", [&] {
+    unsigned lags = 0;
+    const int rc = pbSimGetTimeCorrelationInfo(sim, nullptr, &lags, nullptr, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? lags : 1, pbTimeCorrelationRow());  // (the engine takes no NULL; with the correlation off it refuses)
+    const int got = pbSimGetTimeCorrelation(sim, rows.data());
+    if (got != PB_OK) rows.clear();
+    return got;
+  });
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

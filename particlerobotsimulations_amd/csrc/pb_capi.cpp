@@ -403,6 +403,38 @@ int pbHostPairCorrelation(void *hv, int kind, float rMax, unsigned bins, pbCorre
   return 0;
 }
 
+// time correlations of the resident state (Particlebot::setTimeCorrelation / timeCorrelationRecord / timeCorrelationInfo
+// / timeCorrelationRows; fused engine only): the recorder's switch, one record now, what it holds, and the 96-byte
+// pbTimeCorrelationRow of every lag (cap entries of room; *count = how many there are).  -1 on the other engines, a bad
+// interval, lags or radius, a record or a read with the correlation off, or too little room.
+int pbHostSetTimeCorrelation(void *hv, float interval, unsigned lags, float overlapRadius) {
+  return ((HostSim *)hv)->bot->setTimeCorrelation(interval, lags, overlapRadius) ? 0 : -1;
+}
+
+int pbHostTimeCorrelationRecord(void *hv) { return ((HostSim *)hv)->bot->timeCorrelationRecord() ? 0 : -1; }
+
+int pbHostTimeCorrelationInfo(void *hv, float *interval, unsigned *lags, float *overlapRadius,
+                              unsigned long long *records) {
+  float i = 0.0f, a = 0.0f;
+  unsigned l = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->timeCorrelationInfo(i, l, a, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (overlapRadius) *overlapRadius = a;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostTimeCorrelationRows(void *hv, pbTimeCorrelationRow *rows, unsigned long long cap, unsigned long long *count) {
+  std::vector<pbTimeCorrelationRow> v;
+  if (!count || !((HostSim *)hv)->bot->timeCorrelationRows(v)) return -1;
+  *count = v.size();
+  if (rows && cap < v.size()) return -1;
+  copyOut(rows, v);
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -622,10 +622,13 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const float ci = S->trailInt;
   // the time series (pb_moments.hip): a record in front of every step whose start time passes the gate, or of every
   // step at interval 0.  A record reads the state in front of its step, which a launch that runs ahead never leaves on
-  // the device: no launch is fused across a series gate, and a resident stretch ends in front of one.
-  const bool series = S->series != nullptr;
-  const float si = S->seriesInt;
+  // the device: no launch is fused across a record's gate, and a resident stretch ends in front of one.
+  // The time correlations (pb_timecorr.hip) take their snapshot by the same rule (interval -1: by hand only).
+  const bool series = S->series != nullptr, corr = S->tcRing != nullptr;
+  const float si = S->seriesInt, ti = S->tcInt;
   auto seriesGate = [&](float at) { return series && (si == 0.0f || gate(at, si, dt)); };
+  auto corrGate = [&](float at) { return corr && (ti == 0.0f || (ti > 0.0f && gate(at, ti, dt))); };
+  auto recordDue = [&](float at) { return seriesGate(at) || corrGate(at); };  // a record in front of the step at `at`
   int k = 0;
   for (; k < nsteps; k++) {
     const float t = S->time;
@@ -633,6 +636,10 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     if (!ahead) {
       if (seriesGate(t)) {
         const int rc = pbSeriesRecord(S, t);
+        if (rc) return rc;
+      }
+      if (corrGate(t)) {
+        const int rc = pbTimeCorrRecord(S);
         if (rc) return rc;
       }
       if (trail && gate(t, ci, dt)) {
@@ -649,7 +656,7 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
         int m = 1;
         float tt = t + dt;
         while (k + m < nsteps && !(tt > S->host.max_time) && !(lightWave && gate(tt, pui, dt)) &&
-               !(trail && gate(tt, ci, dt)) && !seriesGate(tt) && !gate(tt, sortInterval, dt)) {
+               !(trail && gate(tt, ci, dt)) && !recordDue(tt) && !gate(tt, sortInterval, dt)) {
           m++;
           tt += dt;
         }
@@ -674,7 +681,7 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     // next step will not run.  A phase update due at the start of the next step only needs the
     // positions of THIS step's integration, which are final now, so it runs before the launch.
     // (resident form: never run ahead, so that the next step can start a resident stretch)
-    const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time) && !seriesGate(tNext);
+    const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time) && !recordDue(tNext);
     if (fuse && trail && gate(tNext, ci, dt)) {
       const int rc = trailRecord(S, tNext);
       if (rc) return rc;
@@ -754,6 +761,7 @@ void pbSimDestroy(pbSim *S) {
   (void)hipFree(S->trail);
   (void)hipFree(S->trailTmp);
   pbMomentsFree(S);
+  pbTimeCorrFree(S);
   pbClusterFree(S);
   (void)hipFree(S->renderIds);
   (void)hipFree(S->renderOut);

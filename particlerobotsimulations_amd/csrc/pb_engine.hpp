@@ -12,6 +12,7 @@
 //   pb_structure.hip structure analysis: radial pair counts and the hexatic order (pbSimRadialCounts, pbSimStructureStats)
 //   pb_dynamics.hip  rearrangement analysis: a marked reference, bond survival and displacements (pbSimMarkReference)
 //   pb_moments.hip   time series: integer moment rows per member, now or recorded while stepping (pbSimSetSeries)
+//   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a ring of snapshots (pbSimSetTimeCorrelation)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 #pragma once
@@ -135,6 +136,17 @@ struct pbSim {
   std::vector<unsigned long long> seriesSteps;  // per slot: stats.steps at that moment
   hipEvent_t momEv0 = nullptr, momEv1 = nullptr;  // around the last pass' launches
   bool momTimed = false;
+  // time correlations (pb_timecorr.hip): the ring of snapshots and the table when on (pbSimSetTimeCorrelation)
+  float4 *tcRing = nullptr;               // tcLags x total, ORIGINAL order: record r at slot r % tcLags
+  unsigned long long *tcTable = nullptr;  // nsims x tcLags cells of nine words, member-major
+  float tcInt = 0.0f;                     // 0: in front of every step; -1: manual records only
+  float tcRadius = 0.0f;
+  unsigned tcLags = 0;
+  unsigned long long tcA2 = 0, tcRecords = 0;  // rint(tcRadius * 2^20) squared; records taken so far
+  std::vector<unsigned long long> tcSteps;     // per slot: stats.steps at that moment
+  std::vector<unsigned long long> tcOrigins, tcSumSteps;  // per lag: record pairs added, and their step differences
+  hipEvent_t tcEv0 = nullptr, tcEv1 = nullptr;  // around the last record's launches
+  bool tcTimed = false;
   pbSimStats stats{};
 };
 
@@ -194,3 +206,7 @@ void pbClusterFree(pbSim *S);
 int pbSeriesRecord(pbSim *S, float t);
 // frees the ring, the one-shot rows and the events (pbSimDestroy)
 void pbMomentsFree(pbSim *S);
+// one snapshot of every member, as it is now, into the ring's next slot and its lags into the table      pb_timecorr.hip
+int pbTimeCorrRecord(pbSim *S);
+// frees the ring, the table and the events (pbSimDestroy)
+void pbTimeCorrFree(pbSim *S);

@@ -7,6 +7,7 @@
 //                   [--rearrange FILE [--rearrange-gap G] [--rearrange-window]]
 //                   [--series FILE [--series-interval T] [--series-capacity N]]
 //                   [--correlate FILE [--correlate-kind velocity|radius] [--correlate-rmax R] [--correlate-bins B]]
+//                   [--timecorr FILE [--timecorr-interval T] [--timecorr-lags N] [--timecorr-overlap A]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -68,6 +69,19 @@
 // decimal from their 128 bits).  --correlate-kind velocity|radius (default velocity; displacements need a mark and are
 // left to the API), --correlate-rmax R (default 10 * max_radius, finite and > 0) and --correlate-bins B (default 200,
 // 1 ... 1024).  (The usage line does not list these four either.)
+// --timecorr FILE switches the device's time correlations on (Particlebot::setTimeCorrelation): while the engine steps,
+// a snapshot of positions and velocities is taken in front of every step whose start time passes the schedule's gate at
+// --timecorr-interval T (default dump_interval; 0: every step; finite and >= 0) into a device ring of --timecorr-lags N
+// snapshots (default 32, 1 ... 64), and every record is added against the N latest ones into one row per lag:
+// squared displacement, velocity products and the count of bots that moved less than --timecorr-overlap A (default the
+// configuration's min_radius, a default and not a claim; finite, 0 <= A < 2048).  Switched on behind a resume, like the
+// series (the correlation is not part of a checkpoint).  At the end of the run FILE gets the header `Lag, Origins,
+// SumSteps, Samples, SumQx, SumQy, SumQ2, SumWW, Overlap, MaxQ2`, then one line per lag, lag 0 first, every number the
+// integer it is (SumQx / SumQy in units of 2^-20, SumQ2, SumWW and MaxQ2 of 2^-40, the 128-bit sums in decimal, SumWW
+// signed); the mean lag of a row is SumSteps / Origins steps.  A lag's sums are exact only below 2^31 samples, and the
+// engine refuses a table that holds more: the records the run will take (from max_time, the start time and the
+// interval) times nCells must stay below 2^31 (10^6 bots: 2147 records), or the run is refused when it starts (exit
+// 2, "--timecorr: ... 2^31 samples"), before a step is taken.  (The usage line does not list these four either.)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -171,6 +185,9 @@ int main(int argc, char **argv) {
   int correlateKind = PB_CORR_VELOCITY;
   float correlateRmax = 0.0f;  // 0: 10 * max_radius, once the configuration is loaded
   long correlateBins = 200;
+  std::string timecorrPath;
+  float timecorrInterval = -1.0f, timecorrOverlap = -1.0f;  // below 0: dump_interval / min_radius, once the configuration is loaded
+  long timecorrLags = 32;
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -243,6 +260,16 @@ int main(int argc, char **argv) {
       char *end = nullptr;
       correlateBins = strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end || correlateBins < 1 || correlateBins > (long)PB_CORR_MAX_BINS) badArg = true;
+    } else if (!strcmp(argv[i], "--timecorr") && i + 1 < argc) {
+      timecorrPath = argv[++i];
+    } else if (!strcmp(argv[i], "--timecorr-interval") && i + 1 < argc) {
+      badArg = !parseFloat(argv[++i], 0.0f, false, timecorrInterval);
+    } else if (!strcmp(argv[i], "--timecorr-lags") && i + 1 < argc) {
+      char *end = nullptr;
+      timecorrLags = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || timecorrLags < 1 || timecorrLags > (long)PB_TCORR_MAX_LAGS) badArg = true;
+    } else if (!strcmp(argv[i], "--timecorr-overlap") && i + 1 < argc) {
+      badArg = !parseFloat(argv[++i], 0.0f, false, timecorrOverlap) || !(timecorrOverlap < 2048.0f);
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -274,7 +301,7 @@ int main(int argc, char **argv) {
       {"--clusters", clustersPath, "analysis"},   {"--contacts", contactsPath, "export"},
       {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
       {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"},
-      {"--correlate", correlatePath, "analysis"}};
+      {"--correlate", correlatePath, "analysis"}, {"--timecorr", timecorrPath, "recorder"}};
   for (const auto &f : fusedOnly)
     if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
       fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
@@ -388,6 +415,20 @@ int main(int argc, char **argv) {
       fprintf(sf, "Time, Step, Measured, SumQx, SumQy, MinQx, MaxQx, MinQy, MaxQy, SumXX, SumYY, SumXY, SumQr, SumRR, "
                   "SumWx, SumWy, SumVV\n");
     if (fclose(sf) != 0) return 1;
+  }
+  // the time correlations: switched on here too; their table stays on the device until the run ends, so a run whose
+  // lag 0 would pass the 2^31 samples that the engine's exact sums hold is refused now, not after its last step
+  if (!timecorrPath.empty()) {
+    const float every = timecorrInterval < 0.0f ? cfg.dump_interval : timecorrInterval;
+    const double left = std::max(0.0, (double)p.max_time - (double)sim.getTime());
+    const double records = left / (double)(every > 0.0f ? every : cfg.timestep) + 2.0;  // (the gate's rounding: at most one more)
+    if (!(records * (double)p.nCells < 2147483648.0)) {
+      fprintf(stderr, "--timecorr: about %.0f records of %u bots would pass 2^31 samples per lag: raise --timecorr-interval "
+                      "or lower max_time\n", records, (unsigned)p.nCells);
+      return 2;
+    }
+    if (!sim.setTimeCorrelation(every, (unsigned)timecorrLags, timecorrOverlap < 0.0f ? p.min_radius : timecorrOverlap))
+      return 1;
   }
   auto drainSeries = [&]() {
     if (seriesPath.empty()) return true;
@@ -534,6 +575,17 @@ int main(int argc, char **argv) {
       fprintf(rf, "%.9g, %.9g, %llu\n", (double)b * (double)rmax / (double)rdfBins,
               (double)(b + 1) * (double)rmax / (double)rdfBins, counts[b]);
     if (fclose(rf) != 0) return 1;
+  }
+  if (!timecorrPath.empty()) {
+    std::vector<pbTimeCorrelationRow> rows;
+    if (!sim.timeCorrelationRows(rows)) return 1;
+    FILE *tf = openOutput(timecorrPath, "w");
+    if (!tf) return 1;
+    fprintf(tf, "Lag, Origins, SumSteps, Samples, SumQx, SumQy, SumQ2, SumWW, Overlap, MaxQ2\n");
+    for (const pbTimeCorrelationRow &r : rows)
+      fprintf(tf, "%u, %llu, %llu, %llu, %lld, %lld, %s, %s, %llu, %llu\n", r.lag, r.origins, r.sum_steps, r.samples,
+              r.sum_qx, r.sum_qy, decimal128(r.msd).c_str(), decimal128(r.vacf).c_str(), r.overlap, r.max_q2);
+    if (fclose(tf) != 0) return 1;
   }
   if (!correlatePath.empty()) {
     const float rmax = correlateRmax > 0.0f ? correlateRmax : 10.0f * p.max_radius;

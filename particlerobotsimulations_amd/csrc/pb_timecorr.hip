@@ -1,0 +1,281 @@
+// pb_timecorr.hip -- time correlations on gfx950: the mean squared displacement, the velocity autocorrelation and the
+// overlap function per lag, averaged over time origins while pbSimStep runs (pbSimSetTimeCorrelation /
+// pbSimTimeCorrelationRecord / pbSimGetTimeCorrelation; include/particlebot_hip.h has the definitions).
+//
+//   k_tc_clear       zeroes the table: nine 64-bit words per (member, lag)
+//   k_tc_snapshot    one pass over pr[cur], vel[cur] and orig[cur] in SLOT order (coalesced reads); each lane writes one
+//                    float4 (x, y, vx, vy) to ring[slot][member * n + orig]: the scattered 16-byte store is the only
+//                    uncoalesced access
+//   k_tc_accumulate  entirely in ORIGINAL order: one workgroup of 256 lanes per (member, lag, block), at most
+//                    PB_TCORR_BLOCKS blocks per member and lag; each lane a grid-stride loop over two snapshots read as
+//                    coalesced 16-byte loads, nine 64-bit accumulators in registers; then a wave butterfly, the four
+//                    waves through 288 bytes of LDS, and one set of 64-bit integer atomics per workgroup into the cell
+//                    (atomicMax for max_q2).  All lags of a record go in one launch; the current snapshot is re-read
+//                    per lag, which L2 and the Infinity Cache serve.
+// Everything that is added is an integer, so nothing depends on the slot order, on the kernel form that stepped or on the
+// order of the adds.  No float atomics, no 128-bit atomics, no scratch memory.  A record is these launches on the batch's
+// stream between two events; the host never waits for them.
+// The bounds: a measured pair has |qx|, |qy|, |w| <= 2^31 - 128, so s < 2^63 and |p| < 2^63; per sample
+// a low half adds less than 2^32 and a high half at most 2^31 in magnitude, so with fewer than 2^31 samples in a cell
+// every word stays below 2^63 in magnitude.
+#include <math.h>
+
+#include "pb_engine.hpp"
+
+static_assert(sizeof(pbTimeCorrelationRow) == 96, "a lag's row is 96 bytes");
+
+namespace {
+
+constexpr int TT = 256;
+// the words of a table cell
+enum { T_SAMPLES, T_QX, T_QY, T_MSD_LO, T_MSD_HI, T_VACF_LO, T_VACF_HI, T_OVERLAP, T_SUMS, T_MAX_Q2 = T_SUMS, T_COLS };
+static_assert(T_COLS == 9, "nine accumulators per lane and per cell");
+
+__global__ __launch_bounds__(TT) void k_tc_clear(unsigned long long *__restrict__ table, uint32_t words) {
+  const uint32_t i = blockIdx.x * TT + threadIdx.x;
+  if (i < words) table[i] = 0ull;
+}
+
+__global__ __launch_bounds__(TT) void k_tc_snapshot(const float4 *__restrict__ pr, const float2 *__restrict__ vel,
+                                                    const uint32_t *__restrict__ orig, uint32_t n,
+                                                    float4 *__restrict__ snap) {
+  const uint32_t l = blockIdx.x * TT + threadIdx.x;
+  if (l >= n) return;
+  const uint32_t s = blockIdx.y * n + l;  // the batch is below 2^28 bots
+  const uint32_t o = orig[s];
+  // A layout is a permutation of 0 .. n - 1.  Were it not, nothing is written outside the member's block: the slot is
+  // skipped, and the bot it should have named keeps the entry of the record that used this ring slot before.
+  if (o >= n) return;
+  const float4 q = pr[s];
+  const float2 v = vel[s];
+  snap[blockIdx.y * n + o] = make_float4(q.x, q.y, v.x, v.y);
+}
+
+__device__ __forceinline__ unsigned long long tcShflXor64(unsigned long long v, int m) {
+  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
+  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+// (long long)rint(v * 2^20) of a value with |v| < 2048: the scaling is exact, v_rndne_f32 rounds to nearest even,
+// |.| <= 2^31 - 128
+__device__ __forceinline__ long long tcQuantise(float v) { return (long long)(int)__builtin_rintf(v * 1048576.0f); }
+
+__global__ __launch_bounds__(TT) void k_tc_accumulate(const float4 *__restrict__ ring, uint32_t n, uint32_t total,
+                                                      uint32_t lags, uint32_t slotNow, uint32_t nLags,
+                                                      uint32_t blocksPerLag, unsigned long long a2,
+                                                      unsigned long long *__restrict__ table) {
+  __shared__ unsigned long long sRed[TT / 64][T_COLS];
+  const uint32_t perMember = nLags * blocksPerLag;
+  const uint32_t member = blockIdx.x / perMember, rest = blockIdx.x - member * perMember;
+  const uint32_t lag = rest / blocksPerLag, b = rest - lag * blocksPerLag;  // lag < nLags <= lags
+  const uint32_t slotThen = slotNow >= lag ? slotNow - lag : slotNow + lags - lag;
+  const float4 *now = ring + (size_t)slotNow * total + (size_t)member * n;
+  const float4 *then = ring + (size_t)slotThen * total + (size_t)member * n;
+  unsigned long long a[T_SUMS];
+#pragma unroll
+  for (int c = 0; c < T_SUMS; c++) a[c] = 0ull;
+  unsigned long long maxQ2 = 0ull;
+#pragma unroll 1
+  for (uint32_t i = b * TT + threadIdx.x; i < n; i += blocksPerLag * TT) {
+    const float4 u = now[i], z = then[i];
+    const float dx = u.x - z.x, dy = u.y - z.y;
+    // (a NaN or an infinity in any of the eight inputs fails a comparison: inf - inf and inf - x are not below 2048)
+    if (fabsf(dx) < 2048.0f && fabsf(dy) < 2048.0f && fabsf(u.z) < 2048.0f && fabsf(u.w) < 2048.0f &&
+        fabsf(z.z) < 2048.0f && fabsf(z.w) < 2048.0f) {
+      const long long qx = tcQuantise(dx), qy = tcQuantise(dy);
+      const unsigned long long s = (unsigned long long)(qx * qx + qy * qy);                         // below 2^63
+      const long long p = tcQuantise(u.z) * tcQuantise(z.z) + tcQuantise(u.w) * tcQuantise(z.w);    // |p| below 2^63
+      a[T_SAMPLES] += 1ull;
+      a[T_QX] += (unsigned long long)qx, a[T_QY] += (unsigned long long)qy;
+      a[T_MSD_LO] += s & 0xFFFFFFFFull, a[T_MSD_HI] += s >> 32;
+      // the two's-complement split, so the signed product needs no special case
+      a[T_VACF_LO] += (unsigned long long)(uint32_t)p, a[T_VACF_HI] += (unsigned long long)(p >> 32);
+      a[T_OVERLAP] += s < a2 ? 1ull : 0ull;
+      maxQ2 = s > maxQ2 ? s : maxQ2;
+    }
+  }
+  // the wave's sums with a butterfly of 64-bit shuffles, the four waves through LDS, one set of atomics
+#pragma unroll 1
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int c = 0; c < T_SUMS; c++) a[c] += tcShflXor64(a[c], m);
+    const unsigned long long other = tcShflXor64(maxQ2, m);
+    maxQ2 = other > maxQ2 ? other : maxQ2;
+  }
+  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+  if (lane == 0u) {
+#pragma unroll
+    for (int c = 0; c < T_SUMS; c++) sRed[w][c] = a[c];
+    sRed[w][T_MAX_Q2] = maxQ2;
+  }
+  __syncthreads();
+  if (threadIdx.x >= (uint32_t)T_COLS) return;
+  const uint32_t c = threadIdx.x;
+  unsigned long long v = sRed[0][c];
+  for (int k = 1; k < TT / 64; k++) {
+    const unsigned long long x = sRed[k][c];
+    v = c == (uint32_t)T_MAX_Q2 ? (x > v ? x : v) : v + x;
+  }
+  if (!v) return;  // (a sum that is zero adds nothing, and 0 is the maximum's identity)
+  unsigned long long *cell = table + ((size_t)member * lags + lag) * T_COLS;
+  if (c == (uint32_t)T_MAX_Q2) atomicMax(cell + c, v);
+  else atomicAdd(cell + c, v);  // two's complement: a signed word takes its sum modulo 2^64
+}
+
+int fail(const char *fn, const char *what) {
+  pbLastError() = std::string(fn) + what;
+  return PB_ERR_ARG;
+}
+
+void freeAll(pbSim *S) {
+  (void)hipFree(S->tcRing);
+  (void)hipFree(S->tcTable);
+  S->tcRing = nullptr, S->tcTable = nullptr;
+  S->tcInt = 0.0f, S->tcRadius = 0.0f, S->tcLags = 0u, S->tcA2 = 0ull, S->tcRecords = 0ull;
+  S->tcSteps.clear(), S->tcOrigins.clear(), S->tcSumSteps.clear();
+  if (S->tcEv0) (void)hipEventDestroy(S->tcEv0);
+  if (S->tcEv1) (void)hipEventDestroy(S->tcEv1);
+  S->tcEv0 = S->tcEv1 = nullptr;
+  S->tcTimed = false;
+}
+
+// the ring, the zeroed table and the events of a correlation of `lags` lags; on an error the caller frees what was made
+int allocate(pbSim *S, unsigned lags) {
+  const size_t words = (size_t)S->nsims * lags * T_COLS;
+  PB_TRY(hipMalloc((void **)&S->tcRing, sizeof(float4) * (size_t)lags * S->total));
+  PB_TRY(hipMalloc((void **)&S->tcTable, sizeof(unsigned long long) * words));
+  PB_TRY(hipEventCreate(&S->tcEv0));
+  PB_TRY(hipEventCreate(&S->tcEv1));
+  hipLaunchKernelGGL(k_tc_clear, dim3(cdiv((uint32_t)words, TT)), dim3(TT), 0, S->stream, S->tcTable, (uint32_t)words);
+  PB_TRY(hipGetLastError());
+  return PB_OK;
+}
+
+// value = hi * 2^32 + lo with 0 <= lo < 2^32 and hi the floor quotient: the same form however the device split its adds
+pbMoment128 normalised(__int128 v) {
+  pbMoment128 m;
+  m.lo = (unsigned long long)(v & (__int128)0xFFFFFFFFull);
+  m.hi = (long long)(v >> 32);  // (arithmetic: the floor)
+  return m;
+}
+
+}  // namespace
+
+void pbTimeCorrFree(pbSim *S) { freeAll(S); }
+
+int pbTimeCorrRecord(pbSim *S) {
+  const uint32_t lags = S->tcLags, slot = (uint32_t)(S->tcRecords % lags);
+  const uint32_t nLags = (uint32_t)(S->tcRecords < lags - 1u ? S->tcRecords : lags - 1u) + 1u;
+  const uint32_t perMember = cdiv(S->n, TT);
+  const uint32_t bpl = perMember < PB_TCORR_BLOCKS ? perMember : PB_TCORR_BLOCKS;
+  const int c = S->cur;
+  PB_TRY(hipEventRecord(S->tcEv0, S->stream));
+  hipLaunchKernelGGL(k_tc_snapshot, dim3(cdiv(S->n, TT), S->nsims), dim3(TT), 0, S->stream, S->pr[c], S->vel[c],
+                     S->orig[c], S->n, S->tcRing + (size_t)slot * S->total);
+  hipLaunchKernelGGL(k_tc_accumulate, dim3(S->nsims * nLags * bpl), dim3(TT), 0, S->stream, S->tcRing, S->n, S->total,
+                     lags, slot, nLags, bpl, S->tcA2, S->tcTable);
+  PB_TRY(hipGetLastError());
+  PB_TRY(hipEventRecord(S->tcEv1, S->stream));
+  S->tcTimed = true;
+  S->tcSteps[slot] = S->stats.steps;
+  for (uint32_t l = 0; l < nLags; l++) {
+    S->tcOrigins[l]++;
+    S->tcSumSteps[l] += S->stats.steps - S->tcSteps[(slot + lags - l) % lags];
+  }
+  S->tcRecords++;
+  return PB_OK;
+}
+
+extern "C" {
+
+int pbSimSetTimeCorrelation(pbSim *S, float interval, unsigned lags, float overlapRadius) {
+  const char *fn = "pbSimSetTimeCorrelation";
+  if (!S) return fail(fn, ": null handle");
+  if (!(interval == -1.0f) && (!(interval >= 0.0f) || !(interval < __builtin_inff())))
+    return fail(fn, ": interval must be finite and >= 0, or -1 for manual records only");
+  if (lags > PB_TCORR_MAX_LAGS) return fail(fn, ": lags must be at most 64");
+  if (!(overlapRadius >= 0.0f) || !(overlapRadius < 2048.0f)) return fail(fn, ": overlapRadius must be in [0, 2048)");
+  if (S->nsims > 65535u) return fail(fn, ": the batch must hold at most 65535 members");  // the member is a grid's y
+  if (S->total >= (1u << 28)) return fail(fn, ": the batch must hold fewer than 2^28 bots");
+  if ((unsigned long long)lags * S->total * sizeof(float4) > (1ull << 33))
+    return fail(fn, ": the ring (lags x bots x 16 bytes) must not exceed 2^33 bytes");
+  useDevice(S);
+  PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
+  freeAll(S);
+  if (!lags) return PB_OK;
+  const int rc = allocate(S, lags);
+  if (rc != PB_OK) {  // (a ring that took the last free memory, say): whatever was made goes, the correlation stays off
+    freeAll(S);
+    (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
+    return rc;
+  }
+  const long long qa = (long long)rintf(overlapRadius * 1048576.0f);  // exact scaling, at most 2^31 - 128
+  S->tcInt = interval, S->tcLags = lags, S->tcRadius = overlapRadius, S->tcA2 = (unsigned long long)(qa * qa);
+  S->tcSteps.assign(lags, 0ull);
+  S->tcOrigins.assign(lags, 0ull);
+  S->tcSumSteps.assign(lags, 0ull);
+  return PB_OK;
+}
+
+int pbSimTimeCorrelationRecord(pbSim *S) {
+  if (!S) return fail("pbSimTimeCorrelationRecord", ": null handle");
+  if (!S->tcRing) return fail("pbSimTimeCorrelationRecord", ": the correlation is off");
+  useDevice(S);
+  return pbTimeCorrRecord(S);
+}
+
+int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float *overlapRadius,
+                                unsigned long long *records) {
+  if (!S) return fail("pbSimGetTimeCorrelationInfo", ": null handle");
+  if (!interval && !lags && !overlapRadius && !records)
+    return fail("pbSimGetTimeCorrelationInfo", ": interval, lags, overlapRadius and records are all null");
+  if (interval) *interval = S->tcInt;
+  if (lags) *lags = S->tcLags;
+  if (overlapRadius) *overlapRadius = S->tcRadius;
+  if (records) *records = S->tcRecords;
+  return PB_OK;
+}
+
+int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
+  if (!S || !rows) return fail("pbSimGetTimeCorrelation", ": null handle or rows");
+  if (!S->tcRing) return fail("pbSimGetTimeCorrelation", ": the correlation is off");
+  useDevice(S);
+  const size_t cells = (size_t)S->nsims * S->tcLags;
+  std::vector<unsigned long long> acc(cells * T_COLS);
+  PB_TRY(hipMemcpyAsync(acc.data(), S->tcTable, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost,
+                        S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  for (size_t k = 0; k < cells; k++)
+    if (acc[k * T_COLS + T_SAMPLES] >= (1ull << 31))  // the counts are exact whatever the state: the other sums may not be
+      return fail("pbSimGetTimeCorrelation", ": a lag holds 2^31 samples or more: restart the correlation");
+  for (size_t k = 0; k < cells; k++) {
+    const unsigned long long *w = &acc[k * T_COLS];
+    const unsigned lag = (unsigned)(k % S->tcLags);
+    pbTimeCorrelationRow &r = rows[k];
+    r.lag = lag, r.reserved = 0u;
+    r.origins = S->tcOrigins[lag], r.sum_steps = S->tcSumSteps[lag];
+    r.samples = w[T_SAMPLES];
+    r.sum_qx = (long long)w[T_QX], r.sum_qy = (long long)w[T_QY];
+    r.msd = normalised((__int128)w[T_MSD_LO] + (__int128)w[T_MSD_HI] * ((__int128)1 << 32));
+    r.vacf = normalised((__int128)w[T_VACF_LO] + (__int128)(long long)w[T_VACF_HI] * ((__int128)1 << 32));
+    r.overlap = w[T_OVERLAP], r.max_q2 = w[T_MAX_Q2];
+  }
+  return PB_OK;
+}
+
+int pbSimGetTimeCorrelationTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
+  if (!S) return fail("pbSimGetTimeCorrelationTimes", ": null handle");
+  if (records) *records = S->tcRecords;
+  if (last_device_ms) {
+    *last_device_ms = 0.0f;
+    if (S->tcTimed) {
+      useDevice(S);
+      PB_TRY(hipEventSynchronize(S->tcEv1));
+      PB_TRY(hipEventElapsedTime(last_device_ms, S->tcEv0, S->tcEv1));
+    }
+  }
+  return PB_OK;
+}
+
+}  // extern "C"

@@ -57,6 +57,9 @@ _ANALYSES = {
     "pbHostMoments": [_P], "pbHostSetSeries": [_F, C.c_uint], "pbHostSeriesInfo": [_P, _P, _P],
     "pbHostSeriesRows": [C.c_ulonglong, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
     "pbHostPairCorrelation": [C.c_int, _F, C.c_uint, _P, _P],
+    "pbHostSetTimeCorrelation": [_F, C.c_uint, _F], "pbHostTimeCorrelationRecord": [],
+    "pbHostTimeCorrelationInfo": [_P, _P, _P, _P],
+    "pbHostTimeCorrelationRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
 }
 
 
@@ -396,6 +399,40 @@ class HostSim:
                                "finite r_max > 0 and 1 ... 1024 bins")
         totals = [_capi.correlation_totals(tot)]
         return (rows, totals) if member is None else (rows[int(member)], totals[int(member)])
+
+    def set_time_correlation(self, interval, lags, overlap_radius):
+        """Keep a device ring of `lags` snapshots, one taken in front of every step whose start time passes the
+        schedule's gate at `interval` (0: every step, -1: only by time_correlation_record()) while the simulation
+        advances, and sum MSD, VACF and the overlap count per lag over all time origins (pbSimSetTimeCorrelation; fused
+        engine only).  Restarts at record 0; lags 0 switches it off."""
+        if lib().pbHostSetTimeCorrelation(self._h, float(interval), int(lags), float(overlap_radius)) != 0:
+            raise RuntimeError("set_time_correlation: the time correlation needs the fused engine, a finite interval "
+                               ">= 0 (or -1), at most 64 lags and an overlap radius in [0, 2048)")
+
+    def time_correlation_record(self):
+        """One record now, of the state as it is (pbSimTimeCorrelationRecord; fused engine only)."""
+        if lib().pbHostTimeCorrelationRecord(self._h) != 0:
+            raise RuntimeError("time_correlation_record: the time correlation needs the fused engine and the "
+                               "correlation on")
+
+    def time_correlation_info(self):
+        """A dict of interval, lags (0: off), overlap_radius and records taken so far (pbSimGetTimeCorrelationInfo;
+        fused engine only)."""
+        i, l, a, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_ulonglong(0)
+        if lib().pbHostTimeCorrelationInfo(self._h, C.byref(i), C.byref(l), C.byref(a), C.byref(r)) != 0:
+            raise RuntimeError("time_correlation_info: the time correlation needs the fused engine")
+        return {"interval": float(i.value), "lags": int(l.value), "overlap_radius": float(a.value),
+                "records": int(r.value)}
+
+    def time_correlation(self):
+        """The table as it stands, as Sim.time_correlation gives it: a list with one list of `lags` dicts of Python
+        ints, lag 0 first (Particlebot::timeCorrelationRows; fused engine only)."""
+        cap = max(self.time_correlation_info()["lags"], 1)
+        rows, count = (_capi.pbTimeCorrelationRow * cap)(), C.c_ulonglong(0)
+        if lib().pbHostTimeCorrelationRows(self._h, rows, cap, C.byref(count)) != 0:
+            raise RuntimeError("time_correlation: the time correlation needs the fused engine, the correlation on and "
+                               "fewer than 2^31 samples per lag")
+        return [[_capi.time_correlation_row(r) for r in rows[:int(count.value)]]]
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))

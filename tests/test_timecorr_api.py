@@ -1,0 +1,500 @@
+"""CPU side of the time correlations (pbSimSetTimeCorrelation / pbSimTimeCorrelationRecord / pbSimGetTimeCorrelation,
+csrc/pb_timecorr.hip).
+
+1. tests/timecorr_ref.py, the reference the GPU tests compare against: it equals a plain per-bot, per-pair Python loop
+   that keeps the device's two accumulators per 128-bit sum, and gives hand-built known answers.
+2. The recipes and rigid shifts of tests/test_gpu_timecorr.py keep every pair measured.
+3. The C-ABI entries are declared, exported and reject bad arguments before they touch the device.
+4. The runner knows --timecorr and its options; the placement-only host engine has no time correlation.
+5. time_correlation_summary on known integers."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import timecorr_ref as TR
+from helpers import jittered_blob
+from test_runner_analysis_flags import USAGE
+from test_series_api import CORNER, SIZES, recipe
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+RUN = os.path.join(ROOT, "particlerobotsimulations_amd", "bin", "particlebot_run")
+CFG = os.path.join(ROOT, "examples", "example.cfg")
+f32 = np.float32
+ONE = 1 << 20
+U = 2.0 ** -20
+BELOW = np.nextafter(f32(2048.0), f32(0.0))
+
+# what tests/test_gpu_timecorr.py applies between its manual records: a rigid shift per record (on top of the recipe)
+# and a per-bot jitter of exact binary fractions
+SHIFTS = [(0.0, 0.0), (0.5, -0.25), (1.75, 0.5), (-3.0, 2.0)]
+MANUAL_LAGS, MANUAL_RADIUS = 3, 0.75
+
+
+def manual_records(n, center=(0.0, 0.0), records=4):
+    """`records` states of the recipe: each rigidly shifted by SHIFTS[k], every bot jittered by multiples of 2^-10 and
+    its velocity changed by a multiple of 2^-6.  Returns [(pos, vel, rad)]."""
+    pos, vel, rad = recipe(n, center)
+    rng = np.random.default_rng(5000 + n)
+    out = []
+    for k in range(records):
+        jit = rng.integers(-8, 9, size=(n, 2)).astype(f32) / f32(1024.0)
+        dv = rng.integers(-4, 5, size=(n, 2)).astype(f32) / f32(64.0)
+        out.append(((pos + np.array(SHIFTS[k % len(SHIFTS)], f32) + jit).astype(f32), (vel + dv).astype(f32), rad))
+    return out
+
+
+BATCH_MEMBERS, BATCH_BOTS, BATCH_LAGS, BATCH_RADIUS = 3, 257, 3, 0.5
+
+
+def batch_records():
+    """What the GPU tests' batch of three members is set to, record by record: member k starts as a blob of its own
+    and is moved, cumulatively, by SHIFTS[r] * (k + 1) plus a jitter of multiples of 2^-8 per bot, its velocities
+    scaled by 1 - 0.75 k (member 2's reverse) plus an eighth of the jitter.  Returns [member][record] = (pos, vel, rad)."""
+    first = np.random.default_rng(77)
+    out = [[jittered_blob(BATCH_BOTS, 0.15 + 0.01 * k, first, center=(3.0 * k - 1.0, -2.0 * k), jitter=0.3)]
+           for k in range(BATCH_MEMBERS)]
+    rng = np.random.default_rng(9)
+    for r in range(1, 4):
+        for k in range(BATCH_MEMBERS):
+            pos, vel, rad = out[k][-1]
+            jit = rng.integers(-16, 17, size=(BATCH_BOTS, 2)).astype(f32) / f32(256.0)
+            out[k].append(((pos + np.array(SHIFTS[r], f32) * f32(k + 1) + jit).astype(f32),
+                           (vel * f32(1.0 - 0.75 * k) + jit * f32(0.125)).astype(f32), rad))
+    return out
+
+
+def known_answer_records():
+    """Three bots over three records: bot 0 moves (+1, 0) per record, bot 1 (0, -0.5), bot 2 is at rest; velocities are
+    constant.  With steps 0, 10, 20 and an overlap radius of 0.75."""
+    vel = np.array([[2.0, 0.0], [0.0, -1.0], [0.25, 0.5]], f32)
+    start = np.array([[3.0, 1.0], [-2.0, 4.0], [0.5, -0.5]], f32)
+    move = np.array([[1.0, 0.0], [0.0, -0.5], [0.0, 0.0]], f32)
+    return [((start + f32(k) * move).astype(f32), vel.copy()) for k in range(3)]
+
+
+W2 = (2 * ONE) ** 2 + ONE ** 2 + (ONE // 4) ** 2 + (ONE // 2) ** 2  # sum |w|^2 of one record
+KNOWN = [
+    {"lag": 0, "origins": 3, "sum_steps": 0, "samples": 9, "sum_qx": 0, "sum_qy": 0, "msd": 0, "vacf": 3 * W2,
+     "overlap": 9, "max_q2": 0},
+    {"lag": 1, "origins": 2, "sum_steps": 20, "samples": 6, "sum_qx": 2 * ONE, "sum_qy": -ONE,
+     "msd": 2 * (ONE ** 2 + (ONE // 2) ** 2), "vacf": 2 * W2, "overlap": 4, "max_q2": ONE ** 2},
+    {"lag": 2, "origins": 1, "sum_steps": 20, "samples": 3, "sum_qx": 2 * ONE, "sum_qy": -ONE,
+     "msd": (2 * ONE) ** 2 + ONE ** 2, "vacf": W2, "overlap": 1, "max_q2": (2 * ONE) ** 2},
+]
+
+
+def tie_records():
+    """Differences and velocities half way between two integers of the 2^-20 grid: 0.5 -> 0, 1.5 -> 2, 2.5 -> 2,
+    -1.5 -> -2, 3.5 -> 4.  Overlap radius 2.5 * 2^-20: qa = 2."""
+    then = np.zeros((3, 2), f32)
+    now = np.array([[0.5 * U, -0.5 * U], [1.5 * U, -1.5 * U], [2.5 * U, 3.5 * U]], f32)
+    vel = np.array([[2.5 * U, -2.5 * U], [1.5 * U, 0.5 * U], [0.5 * U, 3.5 * U]], f32)
+    return [(then, vel.copy()), (now, vel.copy())]
+
+
+TIES = [
+    {"lag": 0, "origins": 2, "sum_steps": 0, "samples": 6, "sum_qx": 0, "sum_qy": 0, "msd": 0, "vacf": 56,
+     "overlap": 6, "max_q2": 0},
+    {"lag": 1, "origins": 1, "sum_steps": 1, "samples": 3, "sum_qx": 4, "sum_qy": 2, "msd": 28, "vacf": 28,
+     "overlap": 1, "max_q2": 20},
+]
+
+
+def negative_vacf_records():
+    """Two bots whose velocities reverse between two records."""
+    pos = np.array([[0.0, 0.0], [1.0, 1.0]], f32)
+    v = np.array([[1.0, 2.0], [-0.5, 0.25]], f32)
+    return [(pos, v), (pos.copy(), (-v).astype(f32))]
+
+
+def unmeasured_records():
+    """257 bots of the recipe over two records with one bot of every unmeasured kind: NaN and the infinities in each of
+    x, y, vx, vy at either instant, |dx| and |dy| exactly 2048, |v| exactly 2048 at either instant; and bots just below
+    each bound, which are measured.  Returns the records, the bots unmeasured at lag 1, and per record the bots
+    unmeasured at lag 0."""
+    pos, vel, rad = recipe(257)
+    p = [pos.copy(), (pos + np.array([0.25, -0.5], f32)).astype(f32)]
+    v = [vel.copy(), vel.copy()]
+    bad1, bad0 = set(), [set(), set()]
+    i = 10
+    for when in (0, 1):
+        for arr in (p, v):
+            for col in (0, 1):
+                for val in (np.nan, np.inf, -np.inf):
+                    arr[when][i, col] = val
+                    bad1.add(i)
+                    bad0[when].add(i)
+                    i += 1
+    # a difference of exactly 2048 between finite positions: measured with itself, not across the lag
+    p[0][i], p[1][i] = (-1024.0, 5.0), (1024.0, 5.0)
+    p[0][i + 1], p[1][i + 1] = (5.0, 1024.0), (5.0, -1024.0)
+    bad1 |= {i, i + 1}
+    i += 2
+    for when, val in ((0, 2048.0), (1, -2048.0)):
+        v[when][i, when] = val
+        bad1.add(i)
+        bad0[when].add(i)
+        i += 1
+    assert i < 100
+    # just below each bound: measured
+    p[0][100], p[1][100] = (0.0, 7.0), (BELOW, 7.0)
+    p[0][101], p[1][101] = (7.0, BELOW), (7.0, 0.0)
+    v[0][102, 0], v[1][103, 1] = BELOW, -BELOW
+    return [(p[0], v[0]), (p[1], v[1])], sorted(bad1), [sorted(b) for b in bad0]
+
+
+# ---- 1. the reference --------------------------------------------------------------------------------------------------
+
+def plain_loop(snapshots, steps, lags, overlap_radius):
+    """The definition, record by record, pair by pair and bot by bot, with the device's two accumulators per 128-bit
+    sum.  Returns the rows and, per lag, the accumulators {msd: [lo, hi], vacf: [lo, hi]}."""
+    qa = int(np.rint(np.float64(f32(overlap_radius)) * 2.0 ** 20))  # float64: exact, ties to even
+    a2 = qa * qa
+    rows = [dict(dict.fromkeys(TR.FIELDS, 0), lag=l) for l in range(lags)]
+    accs = [{"msd": [0, 0], "vacf": [0, 0]} for _ in range(lags)]
+    quant = lambda v: int(np.rint(np.float64(v) * 2.0 ** 20))
+    for r, (pn, vn) in enumerate(snapshots):
+        for l in range(min(r, lags - 1) + 1):
+            pt, vt = snapshots[r - l]
+            row, acc = rows[l], accs[l]
+            row["origins"] += 1
+            row["sum_steps"] += steps[r] - steps[r - l]
+            for b in range(len(pn)):
+                eight = [f32(x) for x in (*pn[b], *pt[b], *vn[b], *vt[b])]
+                with np.errstate(invalid="ignore"):
+                    dx, dy = f32(eight[0] - eight[2]), f32(eight[1] - eight[3])
+                if not all(np.isfinite(x) for x in eight):
+                    continue
+                if not all(abs(x) < f32(2048.0) for x in (dx, dy, *eight[4:])):
+                    continue
+                qx, qy = quant(dx), quant(dy)
+                s = qx * qx + qy * qy
+                p = quant(eight[4]) * quant(eight[6]) + quant(eight[5]) * quant(eight[7])
+                assert 0 <= s < 1 << 63 and abs(p) < 1 << 63
+                row["samples"] += 1
+                row["sum_qx"] += qx
+                row["sum_qy"] += qy
+                for name, v in (("msd", s), ("vacf", p)):
+                    acc[name][0] += v & 0xFFFFFFFF  # (unsigned)v
+                    acc[name][1] += v >> 32         # arithmetic shift
+                row["overlap"] += s < a2
+                row["max_q2"] = max(row["max_q2"], s)
+    for row, acc in zip(rows, accs):
+        row["msd"] = (acc["msd"][1] << 32) + acc["msd"][0]
+        row["vacf"] = (acc["vacf"][1] << 32) + acc["vacf"][0]
+    return rows, accs
+
+
+def snaps(records):
+    return [(r[0], r[1]) for r in records]
+
+
+def test_reference_equals_a_plain_loop():
+    recs = snaps(manual_records(300, CORNER))
+    recs[1][0][17, 0] = np.nan
+    recs[2][1][18, 1] = 2048.0
+    steps = [0, 4, 9, 15]
+    want, accs = plain_loop(recs, steps, 3, MANUAL_RADIUS)
+    got = TR.table(recs, steps, 3, MANUAL_RADIUS)
+    assert got == want and all(tuple(g) == TR.FIELDS for g in got)
+    assert [g["origins"] for g in got] == [4, 3, 2] and [g["sum_steps"] for g in got] == [0, 15, 20]
+    assert got[0]["samples"] == 4 * 300 - 2 and got[1]["samples"] == 3 * 300 - 4 and got[2]["samples"] == 2 * 300 - 2
+    # the low accumulators carry past 2^32
+    assert all(a["msd"][0] >= 1 << 32 for a in accs[1:]) and all(a["vacf"][0] >= 1 << 32 for a in accs)
+    assert got[1]["msd"] >> 32 > 0 and 0 < got[1]["overlap"] < got[1]["samples"]
+
+
+def test_known_answer_of_three_bots_over_three_records():
+    recs = known_answer_records()
+    got = TR.table(recs, [0, 10, 20], 3, 0.75)
+    assert got == KNOWN
+    assert got == plain_loop(recs, [0, 10, 20], 3, 0.75)[0]
+    assert TR.a2_of(0.75) == (3 * ONE // 4) ** 2
+
+
+def test_vacf_can_be_negative():
+    recs = negative_vacf_records()
+    got = TR.table(recs, [0, 1], 2, 0.0)
+    w2 = (1 + 4) * ONE ** 2 + (ONE // 2) ** 2 + (ONE // 4) ** 2
+    assert got[0]["vacf"] == 2 * w2 and got[1]["vacf"] == -w2
+    assert got[1]["msd"] == 0 and got[1]["samples"] == 2
+    assert [g["overlap"] for g in got] == [0, 0]  # overlapRadius 0 counts nothing, not even a bot at rest
+    rows, accs = plain_loop(recs, [0, 1], 2, 0.0)
+    assert rows == got and accs[1]["vacf"][1] < 0  # the high accumulator of the signed sum goes negative
+
+
+def test_ties_round_to_even_in_the_difference_and_in_the_velocity():
+    recs = tie_records()
+    got = TR.table(recs, [0, 1], 2, 2.5 * U)
+    assert got == TIES and got == plain_loop(recs, [0, 1], 2, 2.5 * U)[0]
+    assert TR.a2_of(2.5 * U) == 4 and TR.a2_of(1.5 * U) == 4 and TR.a2_of(0.5 * U) == 0
+
+
+def test_ring_wrap_counts_every_origin():
+    rng = np.random.default_rng(11)
+    recs = [((rng.integers(-64, 65, (5, 2)) / 16.0).astype(f32), (rng.integers(-64, 65, (5, 2)) / 32.0).astype(f32))
+            for _ in range(8)]
+    steps = [0, 3, 7, 8, 20, 21, 30, 44]
+    got = TR.table(recs, steps, 3, 1.0)
+    assert [g["origins"] for g in got] == [8, 7, 6]
+    assert [g["sum_steps"] for g in got] == [0, 44, sum(steps[r] - steps[r - 2] for r in range(2, 8))]
+    assert [g["samples"] for g in got] == [40, 35, 30]
+    assert got == plain_loop(recs, steps, 3, 1.0)[0]
+
+
+def test_overlap_counts_below_the_radius_only():
+    a = 0.5
+    then = np.zeros((4, 2), f32)
+    now = np.array([[a - U, 0.0], [a, 0.0], [a + U, 0.0], [0.0, -a]], f32)
+    vel = np.zeros((4, 2), f32)
+    got = TR.table([(then, vel), (now, vel)], [0, 1], 2, a)
+    a2 = (ONE // 2) ** 2
+    assert TR.a2_of(a) == a2
+    assert got[1]["overlap"] == 1 and got[1]["samples"] == 4  # s == a2 twice: not counted; one above, one below
+    assert got[1]["max_q2"] == (ONE // 2 + 1) ** 2 and got[1]["msd"] == (ONE // 2 - 1) ** 2 + 2 * a2 + (ONE // 2 + 1) ** 2
+    assert got[0]["overlap"] == 8
+    assert got == plain_loop([(then, vel), (now, vel)], [0, 1], 2, a)[0]
+
+
+def test_unmeasured_pairs_take_part_in_nothing():
+    recs, bad1, bad0 = unmeasured_records()
+    assert len(bad1) == 24 + 2 + 2 and [len(b) for b in bad0] == [13, 13]
+    got = TR.table(recs, [0, 1], 2, 0.6)
+    assert got == plain_loop(recs, [0, 1], 2, 0.6)[0]
+    assert got[1]["samples"] == 257 - len(bad1) and got[0]["samples"] == 2 * 257 - 26
+    keep = np.setdiff1d(np.arange(257), bad1)
+    kept = TR.table([(p[keep], v[keep]) for p, v in recs], [0, 1], 2, 0.6)
+    assert kept[1] == got[1]
+    top = (1 << 31) - 128  # the largest q there is
+    assert got[1]["max_q2"] == top * top + 0 and got[1]["sum_qx"] != 0
+    # each kind on its own: one of eight bots unmeasured at lag 1
+    base = recipe(8)
+    for when in (0, 1):
+        for arr in (0, 1):
+            for col in (0, 1):
+                for val in (np.nan, np.inf, -np.inf) + ((2048.0, -2048.0) if arr == 1 else ()):
+                    st = [[base[0].copy(), base[1].copy()] for _ in range(2)]
+                    st[when][arr][3, col] = val
+                    rows = TR.table([tuple(s) for s in st], [0, 1], 2, 0.1)
+                    assert rows[1]["samples"] == 7 and rows[0]["samples"] == 15, (when, arr, col, val)
+    far = [(np.array([[-1024.0, 0.0]], f32), np.zeros((1, 2), f32)), (np.array([[1024.0, 0.0]], f32), np.zeros((1, 2), f32))]
+    assert [r["samples"] for r in TR.table(far, [0, 1], 2, 0.1)] == [2, 0]
+
+
+def test_no_measured_pair_gives_an_all_zero_table():
+    pos, vel, _ = recipe(5)
+    bad = np.full_like(vel, np.inf)
+    got = TR.table([(pos, bad), (pos, bad)], [3, 9], 2, 0.5)
+    assert got == [dict(dict.fromkeys(TR.FIELDS, 0), lag=0, origins=2), dict(dict.fromkeys(TR.FIELDS, 0), lag=1, origins=1,
+                                                                              sum_steps=6)]
+
+
+# ---- 2. the GPU tests' recipes -------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n", SIZES + [300])
+def test_the_gpu_tests_recipes_and_shifts_keep_every_pair_measured(n):
+    for center in ((0.0, 0.0), CORNER):
+        recs = snaps(manual_records(n, center))
+        rows = TR.table(recs, [0, 0, 0, 0], MANUAL_LAGS, MANUAL_RADIUS)
+        assert [r["origins"] for r in rows] == [4, 3, 2]
+        assert [r["samples"] for r in rows] == [4 * n, 3 * n, 2 * n], (n, center)
+        assert rows[1]["msd"] > 0 and rows[1]["sum_qx"] != 0
+    # every rigid shift on its own, whatever pair of records it separates
+    pos, vel, _ = recipe(n, CORNER)
+    for a in SHIFTS:
+        for b in SHIFTS:
+            pair = TR.pair(((pos + np.array(a, f32)).astype(f32), vel), ((pos + np.array(b, f32)).astype(f32), vel), 0)
+            assert pair["samples"] == n, (n, a, b)
+
+
+def test_the_gpu_tests_batch_keeps_every_pair_measured():
+    n = BATCH_BOTS
+    tables = [TR.table(snaps(recs), [0] * 4, BATCH_LAGS, BATCH_RADIUS) for recs in batch_records()]
+    for k, rows in enumerate(tables):
+        assert [r["samples"] for r in rows] == [4 * n, 3 * n, 2 * n], k
+        assert rows[1]["msd"] > 0, k
+    assert tables[0][1]["msd"] < tables[1][1]["msd"] < tables[2][1]["msd"]  # the shifts grow with the member
+    assert tables[0][1]["vacf"] > 0 > tables[2][1]["vacf"]                   # member 2's velocities reverse
+    # the cumulative shifts on their own, whatever pair of records they separate
+    for k in range(BATCH_MEMBERS):
+        at = np.cumsum(np.array(SHIFTS, f32) * f32(k + 1), axis=0)
+        pos, vel, _ = batch_records()[k][0]
+        for a in at:
+            for b in at:
+                assert TR.pair(((pos + a).astype(f32), vel), ((pos + b).astype(f32), vel), 0)["samples"] == n, (k, a, b)
+
+
+# ---- 3. the entry points -----------------------------------------------------------------------------------------------
+
+NAMES = ("pbSimSetTimeCorrelation", "pbSimTimeCorrelationRecord", "pbSimGetTimeCorrelationInfo",
+         "pbSimGetTimeCorrelation", "pbSimGetTimeCorrelationTimes")
+
+
+def test_symbols_are_declared_and_exported():
+    from particlerobotsimulations_amd import _capi, host
+    header = open(os.path.join(ROOT, "include", "particlebot_hip.h")).read()
+    for name in NAMES:
+        assert name in _capi.SYMBOLS and name + "(" in header
+        assert hasattr(_capi.lib(), name)
+    assert C.sizeof(_capi.pbTimeCorrelationRow) == 96
+    assert "pbTimeCorrelationRow" in header and "/* 96 bytes */" in header
+    assert "#define PB_TCORR_MAX_LAGS 64u" in header and "#define PB_TCORR_BLOCKS 256u" in header
+    source = open(os.path.join(ROOT, "particlerobotsimulations_amd", "csrc", "pb_timecorr.hip")).read()
+    assert "static_assert(sizeof(pbTimeCorrelationRow) == 96" in source
+    for name in ("pbHostSetTimeCorrelation", "pbHostTimeCorrelationRecord", "pbHostTimeCorrelationInfo",
+                 "pbHostTimeCorrelationRows"):
+        assert hasattr(host.lib(), name)
+    ens = open(os.path.join(ROOT, "include", "particlebot_ensemble.h")).read()
+    assert "TimeCorrelation" not in ens
+
+
+def test_bad_arguments_are_rejected_before_the_device_is_touched():
+    from particlerobotsimulations_amd import _capi
+    L = _capi.lib()
+    PB_ERR_ARG = 2
+    fake = C.c_void_p(1)  # never dereferenced: these checks come first
+    row = _capi.pbTimeCorrelationRow(lag=7, samples=7)
+    i, l, a, r, ms = C.c_float(7.0), C.c_uint(7), C.c_float(7.0), C.c_ulonglong(7), C.c_float(7.0)
+
+    def refused(rc, fn, word=None):
+        msg = L.pbGetLastErrorString()
+        assert rc == PB_ERR_ARG and fn.encode() in msg and (word is None or word.encode() in msg), (rc, msg)
+
+    refused(L.pbSimSetTimeCorrelation(None, 0.05, 8, 0.1), "pbSimSetTimeCorrelation", "null")
+    for bad in (-0.5, -2.0, -1e-30, np.nextafter(f32(-1.0), f32(0.0)), float("nan"), float("inf"), float("-inf")):
+        refused(L.pbSimSetTimeCorrelation(fake, float(bad), 8, 0.1), "pbSimSetTimeCorrelation", "interval")
+    for bad in (65, 1 << 31):
+        refused(L.pbSimSetTimeCorrelation(fake, 0.05, bad, 0.1), "pbSimSetTimeCorrelation", "lags")
+        refused(L.pbSimSetTimeCorrelation(fake, -1.0, bad, 0.1), "pbSimSetTimeCorrelation", "lags")  # -1 is an interval
+    for bad in (-0.1, -1e-30, 2048.0, 1e9, float("nan"), float("inf"), float("-inf")):
+        refused(L.pbSimSetTimeCorrelation(fake, 0.0, 8, bad), "pbSimSetTimeCorrelation", "overlapRadius")
+    refused(L.pbSimTimeCorrelationRecord(None), "pbSimTimeCorrelationRecord", "null")
+    refused(L.pbSimGetTimeCorrelationInfo(None, C.byref(i), C.byref(l), C.byref(a), C.byref(r)),
+            "pbSimGetTimeCorrelationInfo", "null")
+    refused(L.pbSimGetTimeCorrelationInfo(fake, None, None, None, None), "pbSimGetTimeCorrelationInfo", "all null")
+    refused(L.pbSimGetTimeCorrelation(None, C.byref(row)), "pbSimGetTimeCorrelation", "null")
+    refused(L.pbSimGetTimeCorrelation(fake, None), "pbSimGetTimeCorrelation", "null")
+    refused(L.pbSimGetTimeCorrelationTimes(None, C.byref(r), C.byref(ms)), "pbSimGetTimeCorrelationTimes", "null")
+    assert (i.value, l.value, a.value, r.value, ms.value) == (7.0, 7, 7.0, 7, 7.0) and row.lag == 7 and row.samples == 7
+
+
+# ---- 4. the runner and the host engine ---------------------------------------------------------------------------------
+
+NOT_A_NUMBER = ["", "abc", "-1", "-1e-30", "nan", "inf", "-inf", "0.1x"]
+BAD_FLAGS = ([("--timecorr-interval", v) for v in NOT_A_NUMBER]
+             + [("--timecorr-lags", v) for v in ("", "0", "-3", "1.5", "65", "many")]
+             + [("--timecorr-overlap", v) for v in NOT_A_NUMBER + ["2048", "1e9"]])
+
+
+@pytest.mark.parametrize("flag,value", BAD_FLAGS, ids=[f"{f}={v!r}" for f, v in BAD_FLAGS])
+def test_runner_refuses_a_bad_timecorr_value(tmp_path, flag, value):
+    for args in ([flag, value], [CFG, "--timecorr", "t.csv", flag, value, "--quiet"]):
+        r = subprocess.run([RUN] + args, capture_output=True, text=True, timeout=60, cwd=tmp_path)
+        assert (r.returncode, r.stdout, r.stderr) == (2, "", USAGE), args
+    assert not os.listdir(tmp_path)
+
+
+def test_runner_timecorr_flags_need_their_values_and_the_fused_engine(tmp_path):
+    for flag in ("--timecorr", "--timecorr-interval", "--timecorr-lags", "--timecorr-overlap"):
+        r = subprocess.run([RUN, CFG, flag], capture_output=True, text=True, timeout=60, cwd=tmp_path)
+        assert (r.returncode, r.stdout, r.stderr) == (2, "", USAGE), flag
+    said = "--timecorr needs the fused engine (the recorder runs on its resident state)\n"
+    for extra in ([], ["--timecorr-interval", "0"], ["--timecorr-interval", "3.4e38", "--timecorr-lags", "1"],
+                  ["--timecorr-lags", "64", "--timecorr-overlap", "0"], ["--timecorr-overlap", "2047.9"]):
+        r = subprocess.run([RUN, CFG, "--engine", "legacy", "--timecorr", "t.csv"] + extra, capture_output=True,
+                           text=True, timeout=60, cwd=tmp_path)
+        assert (r.returncode, r.stdout, r.stderr) == (2, "", said), extra
+    # last in the engine-check table: any earlier analysis flag speaks first
+    for flag, line in (("--correlate", "--correlate needs the fused engine (the analysis runs on its resident state)\n"),
+                       ("--series", "--series needs the fused engine (the recorder runs on its resident state)\n"),
+                       ("--clusters", "--clusters needs the fused engine (the analysis runs on its resident state)\n")):
+        r = subprocess.run([RUN, CFG, "--engine", "legacy", "--timecorr", "t.csv", flag, "a.csv"], capture_output=True,
+                           text=True, timeout=60, cwd=tmp_path)
+        assert (r.returncode, r.stderr) == (2, line)
+    assert not os.listdir(tmp_path)
+    source = open(os.path.join(ROOT, "particlerobotsimulations_amd", "csrc", "pb_runner.cpp")).read()
+    for flag in ("--timecorr FILE", "--timecorr-interval T", "--timecorr-lags N", "--timecorr-overlap A"):
+        assert flag in source and flag in open(os.path.join(ROOT, "README.md")).read(), flag
+        assert flag.split()[0] in open(os.path.join(ROOT, "INTEGRATION.md")).read(), flag
+    assert "Lag, Origins, SumSteps, Samples, SumQx, SumQy, SumQ2, SumWW, Overlap, MaxQ2" in source
+    assert "timecorr" not in USAGE  # the usage line stays as it is
+
+
+NEEDS = "the time correlation needs the fused engine"
+REFUSED = [
+    (lambda h: h.set_time_correlation(0.05, 8, 0.1),
+     "set_time_correlation: " + NEEDS + ", a finite interval >= 0 (or -1), at most 64 lags and an overlap radius in "
+     "[0, 2048)", "Particlebot::setTimeCorrelation: " + NEEDS + "\n"),
+    (lambda h: h.time_correlation_record(), "time_correlation_record: " + NEEDS + " and the correlation on",
+     "Particlebot::timeCorrelationRecord: " + NEEDS + "\n"),
+    (lambda h: h.time_correlation_info(), "time_correlation_info: " + NEEDS,
+     "Particlebot::timeCorrelationInfo: " + NEEDS + "\n"),
+    (lambda h: h.time_correlation(), "time_correlation_info: " + NEEDS,
+     "Particlebot::timeCorrelationInfo: " + NEEDS + "\n"),
+]
+
+
+@pytest.mark.parametrize("call,error,line", REFUSED, ids=["set", "record", "info", "rows"])
+def test_host_engine_has_no_time_correlation(capfd, call, error, line):
+    from particlerobotsimulations_amd import _capi, host
+    h = host.HostSim(CFG, engine="host")
+    capfd.readouterr()
+    with pytest.raises(RuntimeError) as caught:
+        call(h)
+    assert str(caught.value) == error
+    assert capfd.readouterr() == ("", line)
+    # the wrapper: a NULL count is refused before the class is asked; a refused call writes nothing
+    L = host.lib()
+    assert L.pbHostTimeCorrelationRows(h._h, None, 0, None) == -1
+    assert capfd.readouterr() == ("", "")
+    row, count = _capi.pbTimeCorrelationRow(lag=7), C.c_ulonglong(7)
+    assert L.pbHostTimeCorrelationRows(h._h, C.byref(row), 1, C.byref(count)) == -1 and (row.lag, count.value) == (7, 7)
+    assert capfd.readouterr() == ("", "Particlebot::timeCorrelationRows: " + NEEDS + "\n")
+    h.close()
+
+
+# ---- 5. the pure-Python helpers ----------------------------------------------------------------------------------------
+
+def test_time_correlation_row_composes_the_128_bit_sums():
+    from particlerobotsimulations_amd import _capi
+    r = _capi.pbTimeCorrelationRow(lag=3, reserved=0, origins=5, sum_steps=60, samples=15, sum_qx=-5, sum_qy=7, overlap=4,
+                                   max_q2=1 << 62)
+    r.msd.lo, r.msd.hi = 5, 3
+    r.vacf.lo, r.vacf.hi = 6, -2  # a negative signed sum, normalised: 0 <= lo < 2^32, hi the floor quotient
+    d = _capi.time_correlation_row(r)
+    assert d == {"lag": 3, "origins": 5, "sum_steps": 60, "samples": 15, "sum_qx": -5, "sum_qy": 7, "msd": (3 << 32) + 5,
+                 "vacf": -(2 << 32) + 6, "overlap": 4, "max_q2": 1 << 62}
+    assert tuple(d) == TR.FIELDS
+
+
+def test_time_correlation_summary_on_known_integers():
+    import particlerobotsimulations_amd as pb
+    assert "time_correlation_summary" in pb.__all__
+    rows = TR.table(known_answer_records(), [0, 10, 20], 3, 0.75)
+    s0 = pb.time_correlation_summary(rows[0], rows[0])
+    assert s0 == {"mean_lag_steps": 0.0, "msd": 0.0, "msd_drift_corrected": 0.0, "vacf": (4 + 1 + 0.0625 + 0.25) / 3,
+                  "vacf_normalised": 1.0, "overlap": 1.0}
+    s1 = pb.time_correlation_summary(rows[1], rows[0])
+    # per record pair the bots moved (1, 0), (0, -0.5), (0, 0): msd (1 + 0.25) / 3, drift (1/3, -1/6)
+    assert s1["mean_lag_steps"] == 10.0 and s1["msd"] == 1.25 / 3 and s1["overlap"] == 4 / 6
+    from fractions import Fraction
+    assert s1["msd_drift_corrected"] == float(Fraction(5, 12) - Fraction(5, 36))
+    assert s1["vacf_normalised"] == 1.0 and s1["vacf"] == s0["vacf"]  # constant velocities
+    s2 = pb.time_correlation_summary(rows[2])
+    assert s2["mean_lag_steps"] == 20.0 and s2["msd"] == 5 / 3 and s2["vacf_normalised"] is None
+    neg = TR.table(negative_vacf_records(), [0, 1], 2, 0.0)
+    assert pb.time_correlation_summary(neg[1], neg[0])["vacf_normalised"] == -1.0
+    # far from the origin of displacements the drift correction is a difference of large integers, formed exactly: two
+    # bots displaced by 2047 and 2047 + 2^-19 have a spread of 2^-40 about their common drift; float64 loses it
+    q = [2047 * ONE, 2047 * ONE + 2]
+    far = dict(dict.fromkeys(TR.FIELDS, 0), lag=1, origins=1, sum_steps=4, samples=2, sum_qx=sum(q),
+               msd=sum(v * v for v in q), max_q2=q[1] ** 2)
+    s = pb.time_correlation_summary(far)
+    assert s["msd_drift_corrected"] == 2.0 ** -40 and s["mean_lag_steps"] == 4.0
+    lossy = (float(far["msd"]) / 2 - (float(far["sum_qx"]) / 2) ** 2) / 2.0 ** 40
+    assert lossy != 2.0 ** -40
+    none = pb.time_correlation_summary(dict.fromkeys(TR.FIELDS, 0))
+    assert set(none) == set(s) and all(v is None for v in none.values())
