@@ -161,6 +161,11 @@ int pbSetDevice(int device);
 /* "0000:c1:00.0"-style PCI address of a device (cap >= 13): the key under /sys/bus/pci/devices whose numa_node /
  * local_cpulist say which host cores sit next to the GPU (pbHostGetResources, include/particlebot_ensemble.h). */
 int pbDevicePciBusId(int device, char *out, int cap);
+/* Device and pinned host memory this library holds right now, process-wide: blocks and their bytes, over every batch,
+ * analysis scratch and self-test (not the caller-owned arrays of the reference boundary, nor the XORWOW jump table).
+ * Either pointer may be NULL.  Equal values before a pbSimCreate* and after the pbSimDestroy say that nothing leaked,
+ * whatever other processes do on the device. */
+int pbDeviceMemoryLive(unsigned long long *buffers, unsigned long long *bytes);
 
 /* Creates a simulation of params->nCells bots on the current device.  The parameter block is
  * copied (obstacle arrays included, at most PB_MAX_OBSTACLES each).  wallHalf <= 0 selects the

@@ -236,6 +236,7 @@ SYMBOLS = {
     "pbGetLastErrorString": (C.c_char_p, []),
     "pbGetDevice": (_I, [C.POINTER(_I)]),
     "pbDevicePciBusId": (_I, [_I, C.c_char_p, _I]),
+    "pbDeviceMemoryLive": (_I, [C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "pbSetDevice": (_I, [_I]),
     "pbSimCreate": (_I, [C.POINTER(_VP), C.POINTER(SimParams), _F]),
     "pbSimDestroy": (None, [_VP]),

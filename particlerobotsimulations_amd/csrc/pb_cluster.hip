@@ -264,24 +264,24 @@ __global__ __launch_bounds__(CT) void k_cluster_labels(const uint32_t *__restric
 int ensureScratch(pbSim *S, uint32_t numKeys) {
   if (S->cluster) return PB_OK;
   PbClusterScratch *C = new PbClusterScratch();
-  S->cluster = C;  // pbSimDestroy frees whatever a failed allocation below leaves behind
+  S->cluster = C;  // ~pbSim frees whatever a failed allocation below leaves behind
   const size_t total = S->total;
   for (int k = 0; k < 2; k++) {
-    PB_TRY(hipMalloc((void **)&C->keys[k], sizeof(uint32_t) * total));
-    PB_TRY(hipMalloc((void **)&C->vals[k], sizeof(uint32_t) * total));
+    PB_TRY(C->keys[k].alloc(total));
+    PB_TRY(C->vals[k].alloc(total));
   }
-  PB_TRY(hipMalloc((void **)&C->hist, sizeof(uint32_t) * pbSortHistEntries(S->total)));
-  PB_TRY(hipMalloc((void **)&C->cpr, sizeof(float4) * (total + 2)));
+  PB_TRY(C->hist.alloc(pbSortHistEntries(S->total)));
+  PB_TRY(C->cpr.alloc(total + 2));
   PB_TRY(hipMemset(C->cpr, 0, sizeof(float4) * (total + 2)));
-  PB_TRY(hipMalloc((void **)&C->start, sizeof(uint32_t) * ((size_t)numKeys + 1)));
-  PB_TRY(hipMalloc((void **)&C->parent, sizeof(uint32_t) * total));
-  PB_TRY(hipMalloc((void **)&C->degree, sizeof(uint32_t) * total));
-  PB_TRY(hipMalloc((void **)&C->size, sizeof(uint32_t) * total));
-  PB_TRY(hipMalloc((void **)&C->labels, sizeof(uint32_t) * S->n));
-  PB_TRY(hipMalloc((void **)&C->acc, sizeof(unsigned long long) * 4 * S->nsims));
-  PB_TRY(hipMalloc((void **)&C->rows, sizeof(pbClusterStats) * S->nsims));
-  PB_TRY(hipMalloc((void **)&C->flag, sizeof(uint32_t) * 2));
-  PB_TRY(hipEventCreate(&C->ev0));
+  PB_TRY(C->start.alloc((size_t)numKeys + 1));
+  PB_TRY(C->parent.alloc(total));
+  PB_TRY(C->degree.alloc(total));
+  PB_TRY(C->size.alloc(total));
+  PB_TRY(C->labels.alloc(S->n));
+  PB_TRY(C->acc.alloc(4 * (size_t)S->nsims));
+  PB_TRY(C->rows.alloc(S->nsims));
+  PB_TRY(C->flag.alloc(2));
+  PB_TRY(C->ev0.create());
   return PB_OK;
 }
 
@@ -381,29 +381,7 @@ int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const u
 }
 
 void pbClusterFree(pbSim *S) {
-  PbClusterScratch *C = S->cluster;
-  if (!C) return;
-  for (int k = 0; k < 2; k++) {
-    (void)hipFree(C->keys[k]);
-    (void)hipFree(C->vals[k]);
-  }
-  (void)hipFree(C->hist);
-  (void)hipFree(C->cpr);
-  (void)hipFree(C->start);
-  (void)hipFree(C->parent);
-  (void)hipFree(C->degree);
-  (void)hipFree(C->size);
-  (void)hipFree(C->labels);
-  (void)hipFree(C->acc);
-  (void)hipFree(C->rows);
-  (void)hipFree(C->flag);
-  if (C->ev0) (void)hipEventDestroy(C->ev0);
-  pbClockFree(C->clusterClock);
-  pbContactsFree(C);
-  pbStructureFree(C);
-  pbDynamicsFree(C);
-  pbCorrelateFree(C);
-  delete C;
+  delete S->cluster;
   S->cluster = nullptr;
 }
 

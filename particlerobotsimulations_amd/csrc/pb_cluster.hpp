@@ -8,21 +8,22 @@
 
 // One analysis' clock: it starts at the front end's ev0 and ends at an event of its own (pbClockStop).
 struct PbAnalysisClock {
-  hipEvent_t end = nullptr;  // behind the analysis' last launch; created by the first stop
+  PbEvent end;  // behind the analysis' last launch; created by the first stop
   unsigned long long runs = 0;
   float lastMs = 0.0f;
 };
 
+// Every buffer is an owner: the scratch goes with `delete` (pbClusterFree).
 struct PbClusterScratch {
-  uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr;
-  float4 *cpr = nullptr;        // total + 2: sorted posrad, .w = global original index
-  uint32_t *start = nullptr;    // nsims * cells + 1
-  uint32_t *parent = nullptr, *degree = nullptr, *size = nullptr;  // total each, ORIGINAL order
-  uint32_t *labels = nullptr;   // n: one member's labels
-  unsigned long long *acc = nullptr;  // 4 words per member
-  pbClusterStats *rows = nullptr;     // nsims
-  uint32_t *flag = nullptr;           // [0] changed, [1] rmax bits
-  hipEvent_t ev0 = nullptr;           // the front end's first launch: where every clock starts
+  PbDevBuf<uint32_t> keys[2], vals[2], hist;
+  PbDevBuf<float4> cpr;        // total + 2: sorted posrad, .w = global original index
+  PbDevBuf<uint32_t> start;    // nsims * cells + 1
+  PbDevBuf<uint32_t> parent, degree, size;  // total each, ORIGINAL order
+  PbDevBuf<uint32_t> labels;   // n: one member's labels
+  PbDevBuf<unsigned long long> acc;  // 4 words per member
+  PbDevBuf<pbClusterStats> rows;     // nsims
+  PbDevBuf<uint32_t> flag;           // [0] changed, [1] rmax bits
+  PbEvent ev0;                       // the front end's first launch: where every clock starts
   PbAnalysisClock clusterClock, contactClock, structureClock, dynamicsClock;
   uint32_t gxLog2 = 2, gyLog2 = 2;
   unsigned rounds = 0;
@@ -30,40 +31,36 @@ struct PbClusterScratch {
   double invCell = 0.0;  // the grid's 1 / edge
   int sortedIn = 0;      // vals[sortedIn] holds the slots in sorted order
   // contact export (pb_contacts.hip): allocated by the first export, links grown when a call needs more
-  uint32_t *cOffsets = nullptr;              // n + 1, ORIGINAL order
-  unsigned long long *cParts = nullptr;      // ceil(n / 256) + 2: block sums, then [blocks] the total, [blocks + 1] the flag
-  float2 *cVel = nullptr;                    // n: the member's velocities in sorted order
-  float2 *cPos = nullptr;                    // n: the member's positions in ORIGINAL order
-  double *cVirial = nullptr;                 // 4 n, ORIGINAL order
-  uint4 *cLinks = nullptr;                   // cLinksCap entries of 16 bytes (pbContactLink)
-  unsigned long long cLinksCap = 0;
+  PbDevBuf<uint32_t> cOffsets;            // n + 1, ORIGINAL order
+  PbDevBuf<unsigned long long> cParts;    // ceil(n / 256) + 2: block sums, then [blocks] the total, [blocks + 1] the flag
+  PbDevBuf<float2> cVel;                  // n: the member's velocities in sorted order
+  PbDevBuf<float2> cPos;                  // n: the member's positions in ORIGINAL order
+  PbDevBuf<double> cVirial;               // 4 n, ORIGINAL order
+  PbDevBuf<uint4> cLinks;                 // entries of 16 bytes (pbContactLink)
   // structure analysis (pb_structure.hip): allocated by the first call that needs each, counts grown with bins
-  unsigned long long *sCounts = nullptr;     // nsims * sCountsBins: the radial histograms
-  unsigned sCountsBins = 0;
-  long long *sRe = nullptr, *sIm = nullptr;  // total each, ORIGINAL order: per-bot sums of qre, qim
-  uint32_t *sNb = nullptr;                   // total, ORIGINAL order: neighbours
-  pbStructureStats *sRows = nullptr;         // nsims
-  double *sPsi = nullptr;                    // 2 n: one member's psi6
+  PbDevBuf<unsigned long long> sCounts;   // nsims * the most bins asked for so far: the radial histograms
+  PbDevBuf<long long> sRe, sIm;           // total each, ORIGINAL order: per-bot sums of qre, qim
+  PbDevBuf<uint32_t> sNb;                 // total, ORIGINAL order: neighbours
+  PbDevBuf<pbStructureStats> sRows;       // nsims
+  PbDevBuf<double> sPsi;                  // 2 n: one member's psi6
   // rearrangement analysis (pb_dynamics.hip).  The mark: allocated by the first pbSimMarkReference, entries grown when a
   // mark needs more, kept until pbSimClearReference
-  bool dMarked = false;                      // a mark is held: everything below describes it
-  float dGap = 0.0f, dTime = 0.0f;           // its linkGap and the batch's fp32 time when it was taken
-  unsigned long long dEntries = 0;           // directed entries of the whole batch
-  float2 *dPos0 = nullptr;                   // total, ORIGINAL order: the marked positions, bit for bit
-  uint32_t *dOffsets = nullptr;              // total + 1, ORIGINAL order: the marked network's CSR over the whole batch
-  uint32_t *dOther = nullptr;                // dOtherCap entries: `other`, member-local original index
-  unsigned long long dOtherCap = 0;
-  unsigned long long *dParts = nullptr;      // ceil(total / 256) + 2: block sums, then the total, then the flag
-  // the compare: allocated by the first one, kept, freed by pbSimDestroy
-  uint32_t *dNow = nullptr, *dKept = nullptr;  // total each, ORIGINAL order
-  float2 *dDisp = nullptr;                   // total, ORIGINAL order: dx, dy
-  pbRearrangementStats *dRows = nullptr;     // nsims; sum_q2_lo / sum_q2_hi hold the two partial sums until the host
-                                             // composes them
+  bool dMarked = false;                   // a mark is held: everything below describes it
+  float dGap = 0.0f, dTime = 0.0f;        // its linkGap and the batch's fp32 time when it was taken
+  unsigned long long dEntries = 0;        // directed entries of the whole batch
+  PbDevBuf<float2> dPos0;                 // total, ORIGINAL order: the marked positions, bit for bit
+  PbDevBuf<uint32_t> dOffsets;            // total + 1, ORIGINAL order: the marked network's CSR over the whole batch
+  PbDevBuf<uint32_t> dOther;              // `other`, member-local original index
+  PbDevBuf<unsigned long long> dParts;    // ceil(total / 256) + 2: block sums, then the total, then the flag
+  // the compare: allocated by the first one, kept
+  PbDevBuf<uint32_t> dNow, dKept;         // total each, ORIGINAL order
+  PbDevBuf<float2> dDisp;                 // total, ORIGINAL order: dx, dy
+  PbDevBuf<pbRearrangementStats> dRows;   // nsims; sum_q2_lo / sum_q2_hi hold the two partial sums until the host
+                                          // composes them
   // pair correlations (pb_correlate.hip): allocated by the first call, the bins' words grown with bins
-  int2 *kA = nullptr;                        // total, SORTED order: the vector a, x = INT_MIN for an unmeasured bot
-  unsigned long long *kAcc = nullptr;        // nsims * kAccBins * 9: per bin the count and eight partial sums
-  unsigned kAccBins = 0;
-  unsigned long long *kTotals = nullptr;     // nsims * 5: measured, sum ax, sum ay, the two partial sums of a^2
+  PbDevBuf<int2> kA;                      // total, SORTED order: the vector a, x = INT_MIN for an unmeasured bot
+  PbDevBuf<unsigned long long> kAcc;      // nsims * the most bins so far * 9: per bin the count and eight partial sums
+  PbDevBuf<unsigned long long> kTotals;   // nsims * 5: measured, sum ax, sum ay, the two partial sums of a^2
   PbAnalysisClock correlateClock;
 };
 
@@ -244,7 +241,7 @@ PB_DEV void pbWhenLinked(uint32_t t, const float4 &me, uint32_t j, const float4 
 // pbClockMark records K's end event (created here the first time) behind what the stream holds; pbClockRead drains the
 // stream, takes the device time since the front end's ev0 and counts the run.  pbClockStop is both.
 inline int pbClockMark(pbSim *S, PbAnalysisClock &K) {
-  if (!K.end) PB_TRY(hipEventCreate(&K.end));
+  if (!K.end) PB_TRY(K.end.create());
   PB_TRY(hipEventRecord(K.end, S->stream));
   return PB_OK;
 }
@@ -257,10 +254,6 @@ inline int pbClockRead(pbSim *S, PbAnalysisClock &K) {
 inline int pbClockStop(pbSim *S, PbAnalysisClock &K) {
   const int rc = pbClockMark(S, K);
   return rc != PB_OK ? rc : pbClockRead(S, K);
-}
-inline void pbClockFree(PbAnalysisClock &K) {
-  if (K.end) (void)hipEventDestroy(K.end);
-  K = PbAnalysisClock();
 }
 // the body of pbSimGet{Cluster,Contact,Structure,Rearrangement}Times; K points into S's scratch object
 inline int pbClockGet(const char *fn, const pbSim *S, PbAnalysisClock PbClusterScratch::*K, unsigned long long *runs,
@@ -291,15 +284,7 @@ int pbClusterAnalyse(pbSim *S, float gap);
 // Nothing here touches the device; the gap check needs no look at the handle, the other two read the host-side batch
 // object, so they need a real one.                                                                       pb_cluster.hip
 int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const unsigned *member);
-// frees the contact export's buffers, if any (pbClusterFree)                                           pb_contacts.hip
-void pbContactsFree(PbClusterScratch *C);
 // k_contact_scan's three launches, queued on the batch's stream: offsets[0 .. n] = the exclusive prefix sum of
 // degree[0 .. n), parts (ceil(n / 256) + 1 words at the least) the scan's block sums with the 64-bit total in
 // parts[ceil(n / 256)].  Offsets are 32-bit: the caller reads the total before it trusts them.         pb_contacts.hip
 int pbContactScan(pbSim *S, const uint32_t *degree, uint32_t n, unsigned long long *parts, uint32_t *offsets);
-// frees the structure analysis' buffers, if any (pbClusterFree)                                       pb_structure.hip
-void pbStructureFree(PbClusterScratch *C);
-// frees the rearrangement analysis' buffers and the mark, if any (pbClusterFree)                       pb_dynamics.hip
-void pbDynamicsFree(PbClusterScratch *C);
-// frees the pair correlations' buffers, if any (pbClusterFree)                                        pb_correlate.hip
-void pbCorrelateFree(PbClusterScratch *C);

@@ -161,13 +161,12 @@ __global__ __launch_bounds__(CT) void k_contact_order(const uint32_t *__restrict
 
 int ensureContactScratch(pbSim *S) {
   PbClusterScratch *C = S->cluster;
-  if (C->cOffsets) return PB_OK;
-  const size_t n = S->n;
-  PB_TRY(hipMalloc((void **)&C->cOffsets, sizeof(uint32_t) * (n + 1)));
-  PB_TRY(hipMalloc((void **)&C->cParts, sizeof(unsigned long long) * ((size_t)cdiv(S->n, CT) + 2)));
-  PB_TRY(hipMalloc((void **)&C->cVel, sizeof(float2) * n));
-  PB_TRY(hipMalloc((void **)&C->cPos, sizeof(float2) * n));
-  PB_TRY(hipMalloc((void **)&C->cVirial, sizeof(double) * 4 * n));
+  const size_t n = S->n;  // (each on its own: a failed allocation leaves the rest to the next call)
+  PB_TRY(C->cOffsets.ensure(n + 1));
+  PB_TRY(C->cParts.ensure((size_t)cdiv(S->n, CT) + 2));
+  PB_TRY(C->cVel.ensure(n));
+  PB_TRY(C->cPos.ensure(n));
+  PB_TRY(C->cVirial.ensure(4 * n));
   return PB_OK;
 }
 
@@ -200,19 +199,13 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
   }
   unsigned long long raised = 0ull;
   if (wantLinks || wantVirial) {
-    if (!C->cLinks || C->cLinksCap < count) {
-      (void)hipFree(C->cLinks);
-      C->cLinks = nullptr, C->cLinksCap = 0;
-      const unsigned long long want = count ? count : 1ull;
-      PB_TRY(hipMalloc((void **)&C->cLinks, sizeof(uint4) * want));
-      C->cLinksCap = want;
-    }
+    PB_TRY(C->cLinks.ensure(count ? count : 1ull));
     const ClusterGrid G = gridOf(C);
     hipLaunchKernelGGL(k_contact_gather_vel, g, b, 0, S->stream, C->cpr, C->vals[C->sortedIn], S->vel[S->cur], base, n,
                        C->cVel, C->cPos);
     hipLaunchKernelGGL(k_contact_fill, g, b, 0, S->stream, C->cpr, C->start, C->cVel, S->dP, member, n, G, gap,
-                       C->cOffsets, (LinkBits *)C->cLinks, flag);
-    hipLaunchKernelGGL(k_contact_order, g, b, 0, S->stream, C->cOffsets, (LinkBits *)C->cLinks, C->cPos, n,
+                       C->cOffsets, (LinkBits *)C->cLinks.get(), flag);
+    hipLaunchKernelGGL(k_contact_order, g, b, 0, S->stream, C->cOffsets, (LinkBits *)C->cLinks.get(), C->cPos, n,
                        wantVirial ? C->cVirial : (double *)nullptr);
     PB_TRY(hipGetLastError());
     rc = pbClockMark(S, C->contactClock);  // the export ends here: the flag's way back is not part of its device time
@@ -231,18 +224,6 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
 }
 
 }  // namespace
-
-void pbContactsFree(PbClusterScratch *C) {
-  (void)hipFree(C->cOffsets);
-  (void)hipFree(C->cParts);
-  (void)hipFree(C->cVel);
-  (void)hipFree(C->cPos);
-  (void)hipFree(C->cVirial);
-  (void)hipFree(C->cLinks);
-  pbClockFree(C->contactClock);
-  C->cOffsets = nullptr, C->cParts = nullptr, C->cVel = nullptr, C->cPos = nullptr, C->cVirial = nullptr;
-  C->cLinks = nullptr, C->cLinksCap = 0;
-}
 
 int pbSimContactsOf(pbSim *S, unsigned member, float linkGap, unsigned *offsets, pbContactLink *links,
                     unsigned long long cap, unsigned long long *entries) {

@@ -166,14 +166,6 @@ __int128 composed(unsigned long long low, unsigned long long rest) {
 
 }  // namespace
 
-void pbCorrelateFree(PbClusterScratch *C) {
-  (void)hipFree(C->kA);
-  (void)hipFree(C->kAcc);
-  (void)hipFree(C->kTotals);
-  pbClockFree(C->correlateClock);
-  C->kA = nullptr, C->kAcc = nullptr, C->kAccBins = 0, C->kTotals = nullptr;
-}
-
 int pbSimPairCorrelation(pbSim *S, int kind, float rMax, unsigned bins, pbCorrelationBin *rows,
                          pbCorrelationTotals *totals) {
   if (!S || !rows) {
@@ -203,14 +195,9 @@ int pbSimPairCorrelation(pbSim *S, int kind, float rMax, unsigned bins, pbCorrel
   PbClusterScratch *C = S->cluster;
   const ClusterGrid G = gridOf(C);
   const size_t nsims = S->nsims;
-  if (!C->kA) PB_TRY(hipMalloc((void **)&C->kA, sizeof(int2) * (size_t)S->total));
-  if (!C->kTotals) PB_TRY(hipMalloc((void **)&C->kTotals, sizeof(unsigned long long) * nsims * S_WORDS));
-  if (C->kAccBins < bins) {
-    (void)hipFree(C->kAcc);
-    C->kAcc = nullptr, C->kAccBins = 0;
-    PB_TRY(hipMalloc((void **)&C->kAcc, sizeof(unsigned long long) * nsims * bins * G_WORDS));
-    C->kAccBins = bins;
-  }
+  PB_TRY(C->kA.ensure((size_t)S->total));
+  PB_TRY(C->kTotals.ensure(nsims * S_WORDS));
+  PB_TRY(C->kAcc.ensure(nsims * bins * G_WORDS));  // (grows with bins: the members of a batch are fixed)
   const size_t accWords = nsims * bins * G_WORDS, totWords = nsims * S_WORDS;
   const float scale = (float)bins / rMax;
   const float d2max = rMax * rMax * 1.0001f + 1e-30f;

@@ -230,11 +230,7 @@ void dropMark(PbClusterScratch *C) {
 }
 
 void freeMark(PbClusterScratch *C) {
-  (void)hipFree(C->dPos0);
-  (void)hipFree(C->dOffsets);
-  (void)hipFree(C->dOther);
-  (void)hipFree(C->dParts);
-  C->dPos0 = nullptr, C->dOffsets = nullptr, C->dOther = nullptr, C->dOtherCap = 0, C->dParts = nullptr;
+  C->dPos0.reset(), C->dOffsets.reset(), C->dOther.reset(), C->dParts.reset();
   dropMark(C);
 }
 
@@ -253,10 +249,10 @@ int compareSweep(pbSim *S) {
   PbClusterScratch *C = S->cluster;
   const ClusterGrid G = gridOf(C);
   const size_t total = S->total;  // (each on its own: a failed allocation leaves the rest to the next call)
-  if (!C->dNow) PB_TRY(hipMalloc((void **)&C->dNow, sizeof(uint32_t) * total));
-  if (!C->dKept) PB_TRY(hipMalloc((void **)&C->dKept, sizeof(uint32_t) * total));
-  if (!C->dDisp) PB_TRY(hipMalloc((void **)&C->dDisp, sizeof(float2) * total));
-  if (!C->dRows) PB_TRY(hipMalloc((void **)&C->dRows, sizeof(pbRearrangementStats) * S->nsims));
+  PB_TRY(C->dNow.ensure(total));
+  PB_TRY(C->dKept.ensure(total));
+  PB_TRY(C->dDisp.ensure(total));
+  PB_TRY(C->dRows.ensure(S->nsims));
   PB_TRY(hipMemsetAsync(C->dRows, 0, sizeof(pbRearrangementStats) * S->nsims, S->stream));
   hipLaunchKernelGGL(k_dyn_compare, dim3(cdiv(S->total, CT)), dim3(CT), 0, S->stream, C->cpr, C->start, S->pr[S->cur],
                      C->vals[C->sortedIn], S->n, S->total, G, gap, C->dOffsets, C->dOther, C->dPos0, C->dNow, C->dKept,
@@ -266,16 +262,6 @@ int compareSweep(pbSim *S) {
 }
 
 }  // namespace
-
-void pbDynamicsFree(PbClusterScratch *C) {
-  freeMark(C);
-  (void)hipFree(C->dNow);
-  (void)hipFree(C->dKept);
-  (void)hipFree(C->dDisp);
-  (void)hipFree(C->dRows);
-  pbClockFree(C->dynamicsClock);
-  C->dNow = nullptr, C->dKept = nullptr, C->dDisp = nullptr, C->dRows = nullptr;
-}
 
 int pbSimMarkReference(pbSim *S, float linkGap) {
   if (!S) {
@@ -290,9 +276,9 @@ int pbSimMarkReference(pbSim *S, float linkGap) {
   PbClusterScratch *C = S->cluster;
   const ClusterGrid G = gridOf(C);
   const uint32_t n = S->n, total = S->total, blocks = cdiv(total, CT);
-  if (!C->dPos0) PB_TRY(hipMalloc((void **)&C->dPos0, sizeof(float2) * (size_t)total));
-  if (!C->dOffsets) PB_TRY(hipMalloc((void **)&C->dOffsets, sizeof(uint32_t) * ((size_t)total + 1)));
-  if (!C->dParts) PB_TRY(hipMalloc((void **)&C->dParts, sizeof(unsigned long long) * ((size_t)blocks + 2)));
+  PB_TRY(C->dPos0.ensure((size_t)total));
+  PB_TRY(C->dOffsets.ensure((size_t)total + 1));
+  PB_TRY(C->dParts.ensure((size_t)blocks + 2));
   const dim3 b(CT), gBots(cdiv(n, CT), S->nsims);
   unsigned long long *sum = C->dParts + blocks, *flag = sum + 1;
   PB_TRY(hipMemsetAsync(sum, 0, sizeof(unsigned long long) * 2, S->stream));
@@ -307,13 +293,7 @@ int pbSimMarkReference(pbSim *S, float linkGap) {
     pbLastError() = "pbSimMarkReference: the batch has 2^31 directed entries or more (offsets are 32-bit)";
     return PB_ERR_ARG;
   }
-  if (!C->dOther || C->dOtherCap < count) {
-    (void)hipFree(C->dOther);
-    C->dOther = nullptr, C->dOtherCap = 0;
-    const unsigned long long want = count ? count : 1ull;
-    PB_TRY(hipMalloc((void **)&C->dOther, sizeof(uint32_t) * want));
-    C->dOtherCap = want;
-  }
+  PB_TRY(C->dOther.ensure(count ? count : 1ull));
   hipLaunchKernelGGL(k_dyn_fill, gBots, b, 0, S->stream, C->cpr, C->start, n, G, linkGap, C->dOffsets, C->dOther, flag);
   hipLaunchKernelGGL(k_dyn_order, dim3(blocks), b, 0, S->stream, C->dOffsets, C->dOther, total);
   hipLaunchKernelGGL(k_dyn_scatter, gBots, b, 0, S->stream, S->pr[S->cur], S->orig[S->cur], n, C->dPos0);

@@ -39,6 +39,7 @@
 #include <chrono>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -480,7 +481,7 @@ __global__ __launch_bounds__(TILE) void k_walk_trips(const PbDevParams *__restri
 // cache-line sharing wins).  Either walk gives the same bits.
 int chooseStreamWalk(pbSim *S) {
   if (!S->haveCells) return PB_OK;
-  if (!S->walkTrips) PB_TRY(hipMalloc((void **)&S->walkTrips, 2 * sizeof(unsigned long long)));
+  PB_TRY(S->walkTrips.ensure(2));
   PB_TRY(hipMemsetAsync(S->walkTrips, 0, 2 * sizeof(unsigned long long), S->stream));
   hipLaunchKernelGGL(k_walk_trips, gridOf(S), dim3(TILE), 0, S->stream, S->dP, S->pr[S->cur], S->cellS, S->n, S->walkTrips);
   PB_TRY(hipGetLastError());
@@ -564,7 +565,7 @@ int phaseUpdate(pbSim *S) {
   } else {
     // (the per-workgroup partial results borrow the centroid reduction's scratch: 16 bytes per workgroup
     //  there; dMin[nsims .. 2 nsims) holds the last-NaN indices)
-    uint32_t *partial = (uint32_t *)S->comPartial;
+    uint32_t *partial = (uint32_t *)S->comPartial.get();
     uint32_t *lastNan = S->dMin + S->nsims;
     const uint32_t nb = cdiv(n, TILE);
     hipLaunchKernelGGL(k_last_nan, g, b, 0, S->stream, S->dP, S->pr[c], S->orig[c], n, partial);
@@ -595,19 +596,20 @@ int phaseUpdate(pbSim *S) {
 
 // calcCOG of every member's positions at the start of the step at time t into its ring (particlebot.cpp:207-209)
 int trailRecord(pbSim *S, float t) {
-  const float q = t / S->trailInt;
+  const float q = t / S->trail.interval;
   if (!(q > -2147483648.0f && q < 2147483648.0f)) return PB_OK;
-  const int ind = ((int)q) % S->trailSteps;
+  const int ind = ((int)q) % S->trail.steps;
   if (ind < 0) return PB_OK;  // negative time: the reference would write in front of the ring (calcCOG)
   const uint32_t n = S->n;
   const int c = S->cur;
   hipLaunchKernelGGL(k_com_scatter, gridOf(S), dim3(TILE), 0, S->stream, S->orig[c], S->pr[c], S->comPos, n);
   const size_t tmpStride = cdiv(n, 64);
-  pbLaunchCentroid((const float *)S->comPos, n, n, (float *)S->trailTmp, (float *)(S->trailTmp + S->nsims * tmpStride),
-                   tmpStride, (float *)(S->trail + ind), (size_t)S->trailSteps, S->nsims, S->stream);
+  pbLaunchCentroid((const float *)S->comPos.get(), n, n, (float *)S->trail.tmp.get(),
+                   (float *)(S->trail.tmp + S->nsims * tmpStride), tmpStride, (float *)(S->trail.ring + ind),
+                   (size_t)S->trail.steps, S->nsims, S->stream);
   PB_TRY(hipGetLastError());
-  S->trailTimes[ind] = t;
-  S->trailRecords++;
+  S->trail.times[ind] = t;
+  S->trail.records++;
   return PB_OK;
 }
 
@@ -618,14 +620,14 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const bool lightWave = (S->host.control == LIGHT_WAVE);
   bool ahead = false;  // true: radius+integration of the coming step are already applied
   const bool resident = pbResidentWanted(S);
-  const bool trail = S->trail != nullptr;
-  const float ci = S->trailInt;
+  const bool trail = S->trail.ring != nullptr;
+  const float ci = S->trail.interval;
   // the time series (pb_moments.hip): a record in front of every step whose start time passes the gate, or of every
   // step at interval 0.  A record reads the state in front of its step, which a launch that runs ahead never leaves on
   // the device: no launch is fused across a record's gate, and a resident stretch ends in front of one.
   // The time correlations (pb_timecorr.hip) take their snapshot by the same rule (interval -1: by hand only).
-  const bool series = S->series != nullptr, corr = S->tcRing != nullptr;
-  const float si = S->seriesInt, ti = S->tcInt;
+  const bool series = S->series.ring != nullptr, corr = S->tc.ring != nullptr;
+  const float si = S->series.interval, ti = S->tc.interval;
   auto seriesGate = [&](float at) { return series && (si == 0.0f || gate(at, si, dt)); };
   auto corrGate = [&](float at) { return corr && (ti == 0.0f || (ti > 0.0f && gate(at, ti, dt))); };
   auto recordDue = [&](float at) { return seriesGate(at) || corrGate(at); };  // a record in front of the step at `at`
@@ -695,14 +697,8 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     if (fuse) S->stats.fused_launches++;
     else S->stats.plain_launches++;
     // pr/vel moved to the other copy; the remaining arrays did not.  Swap just those two.
-    {
-      float4 *tp = S->pr[c];
-      S->pr[c] = S->pr[o];
-      S->pr[o] = tp;
-      float2 *tv = S->vel[c];
-      S->vel[c] = S->vel[o];
-      S->vel[o] = tv;
-    }
+    S->pr[c].swap(S->pr[o]);
+    S->vel[c].swap(S->vel[o]);
     S->time = tNext;
     S->stats.steps++;
     ahead = fuse;
@@ -726,55 +722,18 @@ int gatherToStage(pbSim *S, uint32_t sim) {
 
 }  // namespace
 
+pbSim::~pbSim() {
+  useDevice(this);
+  if (stream) (void)hipStreamSynchronize(stream);
+  pbClusterFree(this);
+}
+
 extern "C" {
 
 const char *pbGetLastErrorString(void) { return pbLastError().c_str(); }
 
 void pbSimDestroy(pbSim *S) {
-  if (!S) return;
-  useDevice(S);
-  if (S->stream) (void)hipStreamSynchronize(S->stream);
-  for (int i = 0; i < 2; i++) {
-    (void)hipFree(S->pr[i]);
-    (void)hipFree(S->vel[i]);
-    (void)hipFree(S->phase[i]);
-    (void)hipFree(S->dead[i]);
-    (void)hipFree(S->absA[i]);
-    (void)hipFree(S->absR[i]);
-    (void)hipFree(S->orig[i]);
-    (void)hipFree(S->keys[i]);
-    (void)hipFree(S->vals[i]);
-  }
-  (void)hipFree(S->dP);
-  (void)hipFree(S->cellS);
-  (void)hipFree(S->hist);
-  (void)hipFree(S->slotOf);
-  (void)hipFree(S->rngState);
-  (void)hipFree(S->dMin);
-  (void)hipFree(S->dMinD);
-  (void)hipFree(S->stage);
-  (void)hipFree(S->comPos);
-  (void)hipFree(S->comPartial);
-  (void)hipFree(S->comOut);
-  (void)hipFree(S->walkTrips);
-  (void)hipFree(S->colors);
-  (void)hipFree(S->trail);
-  (void)hipFree(S->trailTmp);
-  pbMomentsFree(S);
-  pbTimeCorrFree(S);
-  pbClusterFree(S);
-  (void)hipFree(S->renderIds);
-  (void)hipFree(S->renderOut);
-  (void)hipFree(S->renderRgb8);
-  if (S->renderEv0) (void)hipEventDestroy(S->renderEv0);
-  if (S->renderEv1) (void)hipEventDestroy(S->renderEv1);
-  if (S->hMin) (void)hipHostFree(S->hMin);
-  if (S->hMinD) (void)hipHostFree(S->hMinD);
-  if (S->hCom) (void)hipHostFree(S->hCom);
-  if (S->ev0) (void)hipEventDestroy(S->ev0);
-  if (S->ev1) (void)hipEventDestroy(S->ev1);
-  if (S->stream) (void)hipStreamDestroy(S->stream);
-  delete S;
+  if (S) delete S;
 }
 
 int pbSimCreateBatch(pbSim **out, const SimParams *params, int nsims, float wallHalf) {
@@ -819,7 +778,8 @@ int pbSimCreateBatch(pbSim **out, const SimParams *params, int nsims, float wall
     pbLastError() = "pbSimCreate: no HIP device visible";
     return PB_ERR_NO_DEVICE;
   }
-  pbSim *S = new pbSim();
+  std::unique_ptr<pbSim> owner(new pbSim());  // a failure below frees what was made
+  pbSim *const S = owner.get();
   (void)hipGetDevice(&S->device);
   S->minDistanceMode = minDistanceDefault();
   S->host = params[0];
@@ -857,65 +817,54 @@ int pbSimCreateBatch(pbSim **out, const SimParams *params, int nsims, float wall
     if (const char *v = getenv("PB_STREAM_WALK")) rc |= pbSimSetStreamWalk(S, atoi(v));
     if (rc != PB_OK) {
       pbLastError() = "pbSimCreateBatch: PB_FORCE_VARIANT / PB_LANES_PER_BOT / PB_RESIDENT out of range";
-      delete S;
       return PB_ERR_ARG;
     }
   }
   const size_t n = S->n, total = S->total, G1 = (size_t)S->hP[0].numCells + 1;
-#define PB_TRY_NEW(expr)                                             \
-  do {                                                               \
-    hipError_t e_ = (expr);                                          \
-    if (e_ != hipSuccess) {                                          \
-      pbLastError() = std::string(hipGetErrorName(e_)) + " in " #expr; \
-      pbSimDestroy(S);                                               \
-      return PB_ERR_HIP;                                             \
-    }                                                                \
-  } while (0)
-  PB_TRY_NEW(hipStreamCreateWithFlags(&S->stream, hipStreamNonBlocking));
-  PB_TRY_NEW(hipEventCreate(&S->ev0));
-  PB_TRY_NEW(hipEventCreate(&S->ev1));
-  PB_TRY_NEW(hipMalloc((void **)&S->dP, sizeof(PbDevParams) * nsims));
-  PB_TRY_NEW(hipMemcpyAsync(S->dP, S->hP.data(), sizeof(PbDevParams) * nsims, hipMemcpyHostToDevice, S->stream));
+  PB_TRY(S->stream.create(hipStreamNonBlocking));
+  PB_TRY(S->ev0.create());
+  PB_TRY(S->ev1.create());
+  PB_TRY(S->dP.alloc(nsims));
+  PB_TRY(hipMemcpyAsync(S->dP, S->hP.data(), sizeof(PbDevParams) * nsims, hipMemcpyHostToDevice, S->stream));
   for (int i = 0; i < 2; i++) {
     // spare elements: the neighbour sweeps prefetch up to three slots past the range they are walking
-    PB_TRY_NEW(hipMalloc((void **)&S->pr[i], sizeof(float4) * (total + 4)));
-    PB_TRY_NEW(hipMalloc((void **)&S->vel[i], sizeof(float2) * (total + 4)));
-    PB_TRY_NEW(hipMalloc((void **)&S->phase[i], sizeof(float) * total));
-    PB_TRY_NEW(hipMalloc((void **)&S->dead[i], sizeof(int) * total));
-    PB_TRY_NEW(hipMalloc((void **)&S->absA[i], sizeof(float) * total));
-    PB_TRY_NEW(hipMalloc((void **)&S->absR[i], sizeof(float) * total));
-    PB_TRY_NEW(hipMalloc((void **)&S->orig[i], sizeof(uint32_t) * total));
-    PB_TRY_NEW(hipMalloc((void **)&S->keys[i], sizeof(uint32_t) * total));
-    PB_TRY_NEW(hipMalloc((void **)&S->vals[i], sizeof(uint32_t) * total));
-    PB_TRY_NEW(hipMemsetAsync(S->pr[i], 0, sizeof(float4) * (total + 4), S->stream));
-    PB_TRY_NEW(hipMemsetAsync(S->vel[i], 0, sizeof(float2) * (total + 4), S->stream));
-    PB_TRY_NEW(hipMemsetAsync(S->phase[i], 0, sizeof(float) * total, S->stream));
-    PB_TRY_NEW(hipMemsetAsync(S->dead[i], 0, sizeof(int) * total, S->stream));
-    PB_TRY_NEW(hipMemsetAsync(S->absA[i], 0, sizeof(float) * total, S->stream));
-    PB_TRY_NEW(hipMemsetAsync(S->absR[i], 0, sizeof(float) * total, S->stream));
+    PB_TRY(S->pr[i].alloc(total + 4));
+    PB_TRY(S->vel[i].alloc(total + 4));
+    PB_TRY(S->phase[i].alloc(total));
+    PB_TRY(S->dead[i].alloc(total));
+    PB_TRY(S->absA[i].alloc(total));
+    PB_TRY(S->absR[i].alloc(total));
+    PB_TRY(S->orig[i].alloc(total));
+    PB_TRY(S->keys[i].alloc(total));
+    PB_TRY(S->vals[i].alloc(total));
+    PB_TRY(hipMemsetAsync(S->pr[i], 0, sizeof(float4) * (total + 4), S->stream));
+    PB_TRY(hipMemsetAsync(S->vel[i], 0, sizeof(float2) * (total + 4), S->stream));
+    PB_TRY(hipMemsetAsync(S->phase[i], 0, sizeof(float) * total, S->stream));
+    PB_TRY(hipMemsetAsync(S->dead[i], 0, sizeof(int) * total, S->stream));
+    PB_TRY(hipMemsetAsync(S->absA[i], 0, sizeof(float) * total, S->stream));
+    PB_TRY(hipMemsetAsync(S->absR[i], 0, sizeof(float) * total, S->stream));
   }
-  PB_TRY_NEW(hipMalloc((void **)&S->cellS, sizeof(uint32_t) * G1 * nsims));
-  PB_TRY_NEW(hipMalloc((void **)&S->hist, sizeof(uint32_t) * pbSortHistEntries(S->total)));
-  PB_TRY_NEW(hipMalloc((void **)&S->slotOf, sizeof(uint32_t) * total));
-  PB_TRY_NEW(hipMalloc((void **)&S->dMin, sizeof(uint32_t) * 2 * nsims));  // minima | last-NaN indices
-  PB_TRY_NEW(hipMalloc((void **)&S->dMinD, sizeof(float) * nsims));
-  PB_TRY_NEW(hipMalloc((void **)&S->stage, 36 * n));
-  PB_TRY_NEW(hipMalloc((void **)&S->comPos, sizeof(float2) * total));
-  PB_TRY_NEW(hipMalloc((void **)&S->comPartial, sizeof(double2) * cdiv(S->n, TILE) * nsims));
-  PB_TRY_NEW(hipMalloc((void **)&S->comOut, sizeof(double2) * nsims));
-  PB_TRY_NEW(hipHostMalloc((void **)&S->hMin, sizeof(uint32_t) * 2 * nsims));
-  PB_TRY_NEW(hipHostMalloc((void **)&S->hMinD, sizeof(float) * nsims));
-  PB_TRY_NEW(hipHostMalloc((void **)&S->hCom, sizeof(double2) * nsims));
+  PB_TRY(S->cellS.alloc(G1 * nsims));
+  PB_TRY(S->hist.alloc(pbSortHistEntries(S->total)));
+  PB_TRY(S->slotOf.alloc(total));
+  PB_TRY(S->dMin.alloc(2 * nsims));  // minima | last-NaN indices
+  PB_TRY(S->dMinD.alloc(nsims));
+  PB_TRY(S->stage.alloc(36 * n));
+  PB_TRY(S->comPos.alloc(total));
+  PB_TRY(S->comPartial.alloc((size_t)cdiv(S->n, TILE) * nsims));
+  PB_TRY(S->comOut.alloc(nsims));
+  PB_TRY(S->hMin.alloc(2 * nsims));
+  PB_TRY(S->hMinD.alloc(nsims));
+  PB_TRY(S->hCom.alloc(nsims));
   hipLaunchKernelGGL(k_iota, gridOf(S), dim3(TILE), 0, S->stream, S->orig[0], S->n);
   // attraction factor column and a defined radius for every slot
   for (uint32_t k = 0; k < S->nsims; k++)
     hipLaunchKernelGGL(k_set_state, dim3(cdiv(S->n, TILE)), dim3(TILE), 0, S->stream, S->dP, k, S->orig[0], S->pr[0],
                        S->vel[0], S->phase[0], S->dead[0], (const float2 *)nullptr, (const float2 *)nullptr,
                        (const float *)nullptr, (const float *)nullptr, (const int *)nullptr, S->n, 0u, S->n);
-  PB_TRY_NEW(hipGetLastError());
-  PB_TRY_NEW(hipStreamSynchronize(S->stream));
-#undef PB_TRY_NEW
-  *out = S;
+  PB_TRY(hipGetLastError());
+  PB_TRY(hipStreamSynchronize(S->stream));
+  *out = owner.release();
   return PB_OK;
 }
 
@@ -1093,7 +1042,7 @@ int rngInit(pbSim *S, unsigned draws) {
   hipError_t e = hipSuccess;
   const uint32_t *jump = pbXorwowDeviceTable(&e);
   if (!jump) PB_TRY(e);
-  if (!S->rngState) PB_TRY(hipMalloc((void **)&S->rngState, sizeof(pbRngState) * (size_t)S->total));
+  PB_TRY(S->rngState.ensure((size_t)S->total));
   hipLaunchKernelGGL(k_rng_init, gridOf(S), dim3(TILE), 0, S->stream, S->dP, S->rngState, S->n, S->rng, jump, draws);
   PB_TRY(hipGetLastError());
   PB_TRY(hipStreamSynchronize(S->stream));
@@ -1217,7 +1166,7 @@ int pbSimCentroidSums(pbSim *S, float *sumxy) {
   if (!S || !sumxy) return PB_ERR_ARG;
   useDevice(S);
   const int c = S->cur;
-  float2 *const out = (float2 *)S->comOut;  // (8 of the 16 bytes per simulation the mean uses)
+  float2 *const out = (float2 *)S->comOut.get();  // (8 of the 16 bytes per simulation the mean uses)
   hipLaunchKernelGGL(k_com_scatter, gridOf(S), dim3(TILE), 0, S->stream, S->orig[c], S->pr[c], S->comPos, S->n);
   hipLaunchKernelGGL(k_com_serial, dim3(S->nsims), dim3(TILE), 0, S->stream, S->comPos, S->n, out);
   PB_TRY(hipGetLastError());
@@ -1243,7 +1192,7 @@ int pbSimGetColorsOf(pbSim *S, unsigned sim, float *rgba) {
     return PB_ERR_ARG;
   }
   useDevice(S);
-  if (!S->colors) PB_TRY(hipMalloc((void **)&S->colors, sizeof(float4) * S->n));
+  PB_TRY(S->colors.ensure(S->n));
   const int c = S->cur;
   pbLaunchEngineColors(S->dP, sim, S->displayShadow[sim], S->pr[c], S->dead[c], S->orig[c], S->n, S->colors, S->stream);
   PB_TRY(hipGetLastError());
@@ -1260,14 +1209,10 @@ int pbSimSetCentroidTrail(pbSim *S, int on) {
   useDevice(S);
   if (!on) {
     if (S->stream) PB_TRY(hipStreamSynchronize(S->stream));
-    PB_TRY(hipFree(S->trail));
-    PB_TRY(hipFree(S->trailTmp));
-    S->trail = S->trailTmp = nullptr;
-    S->trailTimes.clear();
-    S->trailRecords = 0;
+    S->trail = PbTrail();
     return PB_OK;
   }
-  if (S->trail) return PB_OK;
+  if (S->trail.ring) return PB_OK;
   const float ci = S->centroidInt[0];
   const int cs = S->centroidSteps[0];
   for (uint32_t k = 0; k < S->nsims; k++)
@@ -1277,29 +1222,29 @@ int pbSimSetCentroidTrail(pbSim *S, int on) {
     }
   const size_t ring = (size_t)S->nsims * (size_t)cs;
   std::vector<float2> init(ring, make_float2(-5000.0f, 0.0f));  // particlebot.cpp:776-779
-  PB_TRY(hipMalloc((void **)&S->trail, sizeof(float2) * ring));
-  PB_TRY(hipMalloc((void **)&S->trailTmp, sizeof(float2) * 2 * (size_t)S->nsims * cdiv(S->n, 64)));
-  PB_TRY(hipMemcpy(S->trail, init.data(), sizeof(float2) * ring, hipMemcpyHostToDevice));
-  S->trailInt = ci;
-  S->trailSteps = cs;
-  S->trailTimes.assign((size_t)cs, std::numeric_limits<float>::quiet_NaN());
-  S->trailRecords = 0;
+  PB_TRY(S->trail.ring.alloc(ring));
+  PB_TRY(S->trail.tmp.alloc(2 * (size_t)S->nsims * cdiv(S->n, 64)));
+  PB_TRY(hipMemcpy(S->trail.ring, init.data(), sizeof(float2) * ring, hipMemcpyHostToDevice));
+  S->trail.interval = ci;
+  S->trail.steps = cs;
+  S->trail.times.assign((size_t)cs, std::numeric_limits<float>::quiet_NaN());
+  S->trail.records = 0;
   return PB_OK;
 }
 
 int pbSimGetCentroidTrailOf(pbSim *S, unsigned sim, float *xy, float *times, unsigned *records) {
-  if (!S || sim >= S->nsims || !S->trail) {
+  if (!S || sim >= S->nsims || !S->trail.ring) {
     pbLastError() = "pbSimGetCentroidTrailOf: null handle, member out of range or trail off";
     return PB_ERR_ARG;
   }
   useDevice(S);
   if (xy) {
-    PB_TRY(hipMemcpyAsync(xy, S->trail + (size_t)sim * S->trailSteps, sizeof(float2) * S->trailSteps,
+    PB_TRY(hipMemcpyAsync(xy, S->trail.ring + (size_t)sim * S->trail.steps, sizeof(float2) * S->trail.steps,
                           hipMemcpyDeviceToHost, S->stream));
     PB_TRY(hipStreamSynchronize(S->stream));
   }
-  if (times) memcpy(times, S->trailTimes.data(), sizeof(float) * S->trailSteps);
-  if (records) *records = S->trailRecords;
+  if (times) memcpy(times, S->trail.times.data(), sizeof(float) * S->trail.steps);
+  if (records) *records = S->trail.records;
   return PB_OK;
 }
 
@@ -1323,19 +1268,16 @@ int pbSimRenderOf(pbSim *S, unsigned sim, const pbRenderView *view, unsigned cha
   }
   useDevice(S);
   const size_t pixels = (size_t)view->width * (size_t)view->height;
-  if (pixels > S->renderPixels) {
-    PB_TRY(hipStreamSynchronize(S->stream));
-    (void)hipFree(S->renderIds);
-    (void)hipFree(S->renderOut);
-    S->renderIds = S->renderOut = nullptr;
-    S->renderPixels = 0;
-    PB_TRY(hipMalloc((void **)&S->renderIds, sizeof(uint32_t) * pixels));
-    PB_TRY(hipMalloc((void **)&S->renderOut, 12 * ((pixels + 3) / 4)));
-    S->renderPixels = pixels;
+  if (pixels > S->render.ids.capacity()) {
+    PB_TRY(hipStreamSynchronize(S->stream));  // the frame buffers may still be in use
+    // ids' capacity stands for both buffers: it goes first and comes back last, so a failure in between leaves it 0
+    S->render.ids.reset();
+    PB_TRY(S->render.out.ensure(3 * ((pixels + 3) / 4)));
+    PB_TRY(S->render.ids.ensure(pixels));
   }
-  if (!S->renderRgb8) PB_TRY(hipMalloc((void **)&S->renderRgb8, sizeof(uint32_t) * S->n));
-  if (!S->renderEv0) PB_TRY(hipEventCreate(&S->renderEv0));
-  if (!S->renderEv1) PB_TRY(hipEventCreate(&S->renderEv1));
+  PB_TRY(S->render.rgb8.ensure(S->n));
+  if (!S->render.ev0) PB_TRY(S->render.ev0.create());
+  if (!S->render.ev1) PB_TRY(S->render.ev1.create());
   // the host writer's view, in its operations (Particlebot::writeFrame)
   PbRenderParams V;
   V.width = view->width, V.height = view->height;
@@ -1346,20 +1288,20 @@ int pbSimRenderOf(pbSim *S, unsigned sim, const pbRenderView *view, unsigned cha
   V.style = view->style;
   V.displayShadow = S->displayShadow[sim];
   const int c = S->cur;
-  PB_TRY(hipEventRecord(S->renderEv0, S->stream));
-  PB_TRY(hipMemsetAsync(S->renderIds, 0, sizeof(uint32_t) * pixels, S->stream));
-  pbLaunchRenderBots(S->dP, sim, V, S->hP[sim].max_radius, S->pr[c], S->dead[c], S->orig[c], S->n, S->renderIds,
-                     S->renderRgb8, S->stream);
-  if (view->style == 1 && S->trail)
-    pbLaunchRenderTrail(V, S->trail + (size_t)sim * S->trailSteps, (uint32_t)S->trailSteps, S->centroidRadius[sim],
-                        S->renderIds, S->stream);
-  pbLaunchRenderResolve(S->dP, sim, V, S->renderIds, S->renderRgb8, (uint32_t)pixels, S->renderOut, S->stream);
+  PB_TRY(hipEventRecord(S->render.ev0, S->stream));
+  PB_TRY(hipMemsetAsync(S->render.ids, 0, sizeof(uint32_t) * pixels, S->stream));
+  pbLaunchRenderBots(S->dP, sim, V, S->hP[sim].max_radius, S->pr[c], S->dead[c], S->orig[c], S->n, S->render.ids,
+                     S->render.rgb8, S->stream);
+  if (view->style == 1 && S->trail.ring)
+    pbLaunchRenderTrail(V, S->trail.ring + (size_t)sim * S->trail.steps, (uint32_t)S->trail.steps, S->centroidRadius[sim],
+                        S->render.ids, S->stream);
+  pbLaunchRenderResolve(S->dP, sim, V, S->render.ids, S->render.rgb8, (uint32_t)pixels, S->render.out, S->stream);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(S->renderEv1, S->stream));
-  PB_TRY(hipMemcpyAsync(rgb, S->renderOut, 3 * pixels, hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipEventRecord(S->render.ev1, S->stream));
+  PB_TRY(hipMemcpyAsync(rgb, S->render.out, 3 * pixels, hipMemcpyDeviceToHost, S->stream));
   PB_TRY(hipStreamSynchronize(S->stream));
-  PB_TRY(hipEventElapsedTime(&S->lastRenderMs, S->renderEv0, S->renderEv1));
-  S->renders++;
+  PB_TRY(hipEventElapsedTime(&S->render.lastMs, S->render.ev0, S->render.ev1));
+  S->render.renders++;
   return PB_OK;
 }
 
@@ -1368,8 +1310,8 @@ int pbSimGetRenderStats(pbSim *S, unsigned long long *renders, float *last_devic
     pbLastError() = "pbSimGetRenderStats: null handle";
     return PB_ERR_ARG;
   }
-  if (renders) *renders = S->renders;
-  if (last_device_ms) *last_device_ms = S->lastRenderMs;
+  if (renders) *renders = S->render.renders;
+  if (last_device_ms) *last_device_ms = S->render.lastMs;
   return PB_OK;
 }
 
@@ -1453,6 +1395,12 @@ int pbSimGetConfig(pbSim *S, pbSimConfig *cfg) {
   cfg->stream_walk = (p.stream && pbStreamWalk(S)) ? 1 : 0;
   cfg->tail_tiles = (int)pbForceTailTiles(S);
   cfg->tail_lanes = cfg->tail_tiles ? PB_TAIL_LANES : 0;
+  return PB_OK;
+}
+
+int pbDeviceMemoryLive(unsigned long long *buffers, unsigned long long *bytes) {
+  if (buffers) *buffers = PbMemoryLive::buffers.load();
+  if (bytes) *bytes = PbMemoryLive::bytes.load();
   return PB_OK;
 }
 

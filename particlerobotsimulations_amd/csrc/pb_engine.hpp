@@ -15,6 +15,7 @@
 //   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a ring of snapshots (pbSimSetTimeCorrelation)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
+//   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of
 #pragma once
 
 #include <string>
@@ -23,6 +24,7 @@
 #include "particlebot_hip.h"
 #include "pb_device.hpp"
 #include "pb_internal.hpp"
+#include "pb_memory.hpp"
 
 // thread-local text behind pbGetLastErrorString (defined in pb_engine.hip)
 std::string &pbLastError();
@@ -46,38 +48,83 @@ static inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 
 struct PbClusterScratch;  // pb_cluster.hpp
 
+// The state of a layer that is switched on and off as a unit: "off" is the assignment of a fresh value.
+// centroid trail (pb_display.hip, pbSimSetCentroidTrail)
+struct PbTrail {
+  PbDevBuf<float2> ring;  // nsims x steps rings; empty: trail off
+  PbDevBuf<float2> tmp;   // 2 x nsims x ceil(n / 64): the tree's temporaries
+  float interval = 0.0f;
+  int steps = 0;
+  std::vector<float> times;  // start time of the step that wrote each slot (NaN: never)
+  unsigned records = 0;
+};
+// frame rasteriser (pb_render.hip, pbSimRenderOf): allocated by the first render, re-allocated when the frame grows
+struct PbRender {
+  PbDevBuf<uint32_t> ids;   // one key per pixel; its capacity is the frame both buffers hold
+  PbDevBuf<uint32_t> out;   // packed RGB8, padded to whole groups of four pixels
+  PbDevBuf<uint32_t> rgb8;  // n: a member's bot colours in original order
+  PbEvent ev0, ev1;
+  unsigned long long renders = 0;
+  float lastMs = 0.0f;
+};
+// time series (pb_moments.hip): the ring when on (pbSimSetSeries)
+struct PbSeries {
+  PbDevBuf<pbMomentsRow> ring;  // nsims x cap, member-major: record r of member m at [m * cap + r % cap]
+  float interval = 0.0f;        // 0: in front of every step
+  unsigned cap = 0;
+  unsigned long long records = 0;
+  std::vector<float> times;               // per slot: start time of the step the record was taken in front of
+  std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
+};
+// time correlations (pb_timecorr.hip): the ring of snapshots and the table when on (pbSimSetTimeCorrelation)
+struct PbTimeCorr {
+  PbDevBuf<float4> ring;                // lags x total, ORIGINAL order: record r at slot r % lags
+  PbDevBuf<unsigned long long> table;   // nsims x lags cells of nine words, member-major
+  float interval = 0.0f;                // 0: in front of every step; -1: manual records only
+  float radius = 0.0f;
+  unsigned lags = 0;
+  unsigned long long a2 = 0, records = 0;  // rint(radius * 2^20) squared; records taken so far
+  std::vector<unsigned long long> steps;   // per slot: stats.steps at that moment
+  std::vector<unsigned long long> origins, sumSteps;  // per lag: record pairs added, and their step differences
+  PbEvent ev0, ev1;                        // around the last record's launches
+  bool timed = false;
+};
+
+// Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
+// and go last.
 struct pbSim {
+  ~pbSim();  // selects the device, drains the stream, frees the cluster analysis' scratch       pb_engine.hip
+  PbStream stream;
+  PbEvent ev0, ev1;
+  int device = 0;  // the device the batch lives on; every entry point makes it the calling thread's current one
   std::vector<PbDevParams> hP;  // one parameter block per simulation
-  PbDevParams *dP = nullptr;
+  PbDevBuf<PbDevParams> dP;
   SimParams host;  // schedule-relevant fields (shared by the batch): max_time, phase_update_interval, control
   uint32_t nsims = 1, n = 0, total = 0;
-  int device = 0;  // the device the batch lives on; every entry point makes it the calling thread's current one
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
 
-  float4 *pr[2] = {nullptr, nullptr};
-  float2 *vel[2] = {nullptr, nullptr};
-  float *phase[2] = {nullptr, nullptr};
-  int *dead[2] = {nullptr, nullptr};
-  float *absA[2] = {nullptr, nullptr};
-  float *absR[2] = {nullptr, nullptr};
-  uint32_t *orig[2] = {nullptr, nullptr};  // LOCAL original index of each slot
-  int cur = 0;                             // which copy of every array is live
+  PbDevBuf<float4> pr[2];
+  PbDevBuf<float2> vel[2];
+  PbDevBuf<float> phase[2];
+  PbDevBuf<int> dead[2];
+  PbDevBuf<float> absA[2];
+  PbDevBuf<float> absR[2];
+  PbDevBuf<uint32_t> orig[2];  // LOCAL original index of each slot
+  int cur = 0;                 // which copy of every array is live
 
-  uint32_t *cellS = nullptr;  // nsims x (numCells+1), global slot indices
-  uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *hist = nullptr, *slotOf = nullptr;
-  uint32_t *sortedKeys = nullptr;  // keys[0] or keys[1]: composite keys of the slots, as of the last sort
+  PbDevBuf<uint32_t> cellS;  // nsims x (numCells+1), global slot indices
+  PbDevBuf<uint32_t> keys[2], vals[2], hist, slotOf;
+  uint32_t *sortedKeys = nullptr;  // keys[0] or keys[1] (not owned): composite keys of the slots, as of the last sort
   std::vector<uint32_t> layoutOrig, layoutKeys;  // host staging of pbSimSetLayoutOf
   std::vector<char> layoutGiven;
-  pbRngState *rngState = nullptr;  // total, ORIGINAL order; only with an XORWOW generator (rng != 0)
-  uint32_t *dMin = nullptr;  // nsims
-  float *dMinD = nullptr;    // nsims
-  uint32_t *hMin = nullptr;  // pinned, nsims
-  float *hMinD = nullptr;    // pinned, nsims
-  char *stage = nullptr;     // 36 n bytes: pos 8n | vel 8n | rad 4n | phase 4n | dead 4n | absA 4n | absR 4n
-  float2 *comPos = nullptr;  // total
-  double2 *comPartial = nullptr, *comOut = nullptr;
-  double2 *hCom = nullptr;  // pinned, nsims
+  PbDevBuf<pbRngState> rngState;  // total, ORIGINAL order; only with an XORWOW generator (rng != 0)
+  PbDevBuf<uint32_t> dMin;  // 2 nsims: minima | last-NaN indices
+  PbDevBuf<float> dMinD;    // nsims
+  PbPinned<uint32_t> hMin;  // 2 nsims
+  PbPinned<float> hMinD;    // nsims
+  PbDevBuf<char> stage;     // 36 n bytes: pos 8n | vel 8n | rad 4n | phase 4n | dead 4n | absA 4n | absR 4n
+  PbDevBuf<float2> comPos;  // total
+  PbDevBuf<double2> comPartial, comOut;
+  PbPinned<double2> hCom;  // nsims
 
   float time = 0.0f;
   uint32_t phaseDraws = 0;
@@ -94,7 +141,8 @@ struct pbSim {
   // (chooseStreamWalk), 0 row by row, 1 flattened (pbSimSetStreamWalk).  Bit-identical either way.
   int streamWalk = -1;
   bool streamWalkAuto = false;
-  unsigned long long *walkTrips = nullptr, walkTripsHost[2] = {0, 0};
+  PbDevBuf<unsigned long long> walkTrips;  // 2, allocated by the first choice of the walk
+  unsigned long long walkTripsHost[2] = {0, 0};
   uint32_t cuCount = 0;  // compute units of the device (pbTailTiles; 0 until first asked)
   int tailTiles = -1;  // split-lane tail tiles per XCD of the throughput form: -1 automatic (pbTailTiles), else that many
   bool wideOffsets = false;  // run the 64-bit-offset throughput sweep on a batch below 2^28 bots (pbSimSelectForceForm, tests)
@@ -108,45 +156,19 @@ struct pbSim {
   std::vector<uint32_t> displayShadow;
   std::vector<float> centroidInt;
   std::vector<int> centroidSteps;
-  float4 *colors = nullptr;      // n, allocated by the first pbSimGetColorsOf
-  float2 *trail = nullptr;       // nsims x trailSteps rings; nullptr: trail off
-  float2 *trailTmp = nullptr;    // 2 x nsims x ceil(n / 64): the tree's temporaries
-  float trailInt = 0.0f;
-  int trailSteps = 0;
-  std::vector<float> trailTimes;  // start time of the step that wrote each slot (NaN: never)
-  unsigned trailRecords = 0;
-  // frame rasteriser (pb_render.hip, pbSimRenderOf): allocated by the first render, re-allocated when the frame grows
+  PbDevBuf<float4> colors;  // n, allocated by the first pbSimGetColorsOf
+  PbTrail trail;
   std::vector<float> centroidRadius;
-  uint32_t *renderIds = nullptr;   // one key per pixel
-  uint32_t *renderOut = nullptr;   // packed RGB8, padded to whole groups of four pixels
-  uint32_t *renderRgb8 = nullptr;  // n: a member's bot colours in original order
-  size_t renderPixels = 0;         // capacity of renderIds / renderOut
-  hipEvent_t renderEv0 = nullptr, renderEv1 = nullptr;
-  unsigned long long renders = 0;
-  float lastRenderMs = 0.0f;
-  // cluster analysis (pb_cluster.hip): scratch of its own, allocated by the first analysis, freed by pbSimDestroy
+  PbRender render;
+  // cluster analysis (pb_cluster.hip): scratch of its own, allocated by the first analysis, freed by ~pbSim
   PbClusterScratch *cluster = nullptr;
-  // time series (pb_moments.hip): the ring when on (pbSimSetSeries), the one-shot rows of pbSimMoments, the record's events
-  pbMomentsRow *series = nullptr;   // nsims x seriesCap, member-major: record r of member m at [m * seriesCap + r % seriesCap]
-  pbMomentsRow *momRows = nullptr;  // nsims, allocated by the first pbSimMoments
-  float seriesInt = 0.0f;           // 0: in front of every step
-  unsigned seriesCap = 0;
-  unsigned long long seriesRecords = 0;
-  std::vector<float> seriesTimes;   // per slot: start time of the step the record was taken in front of
-  std::vector<unsigned long long> seriesSteps;  // per slot: stats.steps at that moment
-  hipEvent_t momEv0 = nullptr, momEv1 = nullptr;  // around the last pass' launches
+  PbSeries series;
+  // the one-shot rows of pbSimMoments and the events around the last moments pass, series record or not: made on first
+  // use and kept when the series is switched
+  PbDevBuf<pbMomentsRow> momRows;  // nsims
+  PbEvent momEv0, momEv1;
   bool momTimed = false;
-  // time correlations (pb_timecorr.hip): the ring of snapshots and the table when on (pbSimSetTimeCorrelation)
-  float4 *tcRing = nullptr;               // tcLags x total, ORIGINAL order: record r at slot r % tcLags
-  unsigned long long *tcTable = nullptr;  // nsims x tcLags cells of nine words, member-major
-  float tcInt = 0.0f;                     // 0: in front of every step; -1: manual records only
-  float tcRadius = 0.0f;
-  unsigned tcLags = 0;
-  unsigned long long tcA2 = 0, tcRecords = 0;  // rint(tcRadius * 2^20) squared; records taken so far
-  std::vector<unsigned long long> tcSteps;     // per slot: stats.steps at that moment
-  std::vector<unsigned long long> tcOrigins, tcSumSteps;  // per lag: record pairs added, and their step differences
-  hipEvent_t tcEv0 = nullptr, tcEv1 = nullptr;  // around the last record's launches
-  bool tcTimed = false;
+  PbTimeCorr tc;
   pbSimStats stats{};
 };
 
@@ -200,13 +222,9 @@ std::string pbForceStreamName(const pbSim *S);                                  
 // m whole timesteps from time t0 in one launch (simulations of <= 1024 bots)
 bool pbResidentWanted(const pbSim *S);                                                                    // pb_resident.hip
 void pbLaunchResident(pbSim *S, float dt, float t0, int m, int lightWave);
-// frees the cluster analysis' scratch, if any (pbSimDestroy)                                             pb_cluster.hip
+// frees the cluster analysis' scratch, if any (~pbSim: PbClusterScratch is incomplete here)              pb_cluster.hip
 void pbClusterFree(pbSim *S);
 // one record of every member into the ring's next slot, in front of the step that starts at t (stepMany)   pb_moments.hip
 int pbSeriesRecord(pbSim *S, float t);
-// frees the ring, the one-shot rows and the events (pbSimDestroy)
-void pbMomentsFree(pbSim *S);
 // one snapshot of every member, as it is now, into the ring's next slot and its lags into the table      pb_timecorr.hip
 int pbTimeCorrRecord(pbSim *S);
-// frees the ring, the table and the events (pbSimDestroy)
-void pbTimeCorrFree(pbSim *S);

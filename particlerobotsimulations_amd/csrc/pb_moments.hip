@@ -164,8 +164,8 @@ int checkBatch(const char *fn, const pbSim *S) {
 
 // the rows of every member, rows[m * stride], from the state as it is: queued on the batch's stream, not waited for
 int momentsPass(pbSim *S, pbMomentsRow *rows, uint32_t stride) {
-  if (!S->momEv0) PB_TRY(hipEventCreate(&S->momEv0));
-  if (!S->momEv1) PB_TRY(hipEventCreate(&S->momEv1));
+  if (!S->momEv0) PB_TRY(S->momEv0.create());
+  if (!S->momEv1) PB_TRY(S->momEv1.create());
   const uint32_t perMember = cdiv(S->n, MT);
   const uint32_t bpm = perMember < PB_MOMENTS_BLOCKS ? perMember : PB_MOMENTS_BLOCKS;
   PB_TRY(hipEventRecord(S->momEv0, S->stream));
@@ -184,31 +184,14 @@ void finishRow(pbMomentsRow &r, float time, unsigned long long step) {
   if (!r.measured) r.min_qx = r.max_qx = r.min_qy = r.max_qy = 0;
 }
 
-void freeSeries(pbSim *S) {
-  (void)hipFree(S->series);
-  S->series = nullptr;
-  S->seriesInt = 0.0f, S->seriesCap = 0u, S->seriesRecords = 0ull;
-  S->seriesTimes.clear(), S->seriesSteps.clear();
-}
-
 }  // namespace
 
-void pbMomentsFree(pbSim *S) {
-  freeSeries(S);
-  (void)hipFree(S->momRows);
-  S->momRows = nullptr;
-  if (S->momEv0) (void)hipEventDestroy(S->momEv0);
-  if (S->momEv1) (void)hipEventDestroy(S->momEv1);
-  S->momEv0 = S->momEv1 = nullptr;
-  S->momTimed = false;
-}
-
 int pbSeriesRecord(pbSim *S, float t) {
-  const uint32_t slot = (uint32_t)(S->seriesRecords % S->seriesCap);
-  const int rc = momentsPass(S, S->series + slot, S->seriesCap);
+  const uint32_t slot = (uint32_t)(S->series.records % S->series.cap);
+  const int rc = momentsPass(S, S->series.ring + slot, S->series.cap);
   if (rc != PB_OK) return rc;
-  S->seriesTimes[slot] = t, S->seriesSteps[slot] = S->stats.steps;
-  S->seriesRecords++;
+  S->series.times[slot] = t, S->series.steps[slot] = S->stats.steps;
+  S->series.records++;
   return PB_OK;
 }
 
@@ -219,7 +202,7 @@ int pbSimMoments(pbSim *S, pbMomentsRow *rows) {
   int rc = checkBatch("pbSimMoments", S);
   if (rc != PB_OK) return rc;
   useDevice(S);
-  if (!S->momRows) PB_TRY(hipMalloc((void **)&S->momRows, sizeof(pbMomentsRow) * S->nsims));
+  PB_TRY(S->momRows.ensure(S->nsims));
   rc = momentsPass(S, S->momRows, 1u);
   if (rc != PB_OK) return rc;
   PB_TRY(hipMemcpyAsync(rows, S->momRows, sizeof(pbMomentsRow) * S->nsims, hipMemcpyDeviceToHost, S->stream));
@@ -238,36 +221,36 @@ int pbSimSetSeries(pbSim *S, float interval, unsigned capacity) {
   if (rc != PB_OK) return rc;
   useDevice(S);
   PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
-  freeSeries(S);
+  S->series = PbSeries();
   if (!capacity) return PB_OK;
-  PB_TRY(hipMalloc((void **)&S->series, sizeof(pbMomentsRow) * (size_t)capacity * S->nsims));
-  S->seriesInt = interval, S->seriesCap = capacity;
-  S->seriesTimes.assign(capacity, 0.0f);
-  S->seriesSteps.assign(capacity, 0ull);
+  PB_TRY(S->series.ring.alloc((size_t)capacity * S->nsims));
+  S->series.interval = interval, S->series.cap = capacity;
+  S->series.times.assign(capacity, 0.0f);
+  S->series.steps.assign(capacity, 0ull);
   return PB_OK;
 }
 
 int pbSimGetSeriesInfo(pbSim *S, float *interval, unsigned *capacity, unsigned long long *records) {
   if (!S) return fail("pbSimGetSeriesInfo", ": null handle");
   if (!interval && !capacity && !records) return fail("pbSimGetSeriesInfo", ": interval, capacity and records are all null");
-  if (interval) *interval = S->seriesInt;
-  if (capacity) *capacity = S->seriesCap;
-  if (records) *records = S->seriesRecords;
+  if (interval) *interval = S->series.interval;
+  if (capacity) *capacity = S->series.cap;
+  if (records) *records = S->series.records;
   return PB_OK;
 }
 
 int pbSimGetSeriesOf(pbSim *S, unsigned member, unsigned long long first, unsigned count, pbMomentsRow *rows) {
   if (!S || !rows) return fail("pbSimGetSeriesOf", ": null handle or rows");
   if (member >= S->nsims) return fail("pbSimGetSeriesOf", ": member out of range");
-  if (!S->series) return fail("pbSimGetSeriesOf", ": the series is off");
-  const unsigned long long have = S->seriesRecords, cap = S->seriesCap;
+  if (!S->series.ring) return fail("pbSimGetSeriesOf", ": the series is off");
+  const unsigned long long have = S->series.records, cap = S->series.cap;
   const unsigned long long oldest = have - (have < cap ? have : cap);
   if (first < oldest || first > have || count > have - first)
     return fail("pbSimGetSeriesOf", ": records outside the ring's window");
   if (!count) return PB_OK;
   useDevice(S);
   // the ring wraps at most once inside the range
-  const pbMomentsRow *ring = S->series + (size_t)member * cap;
+  const pbMomentsRow *ring = S->series.ring + (size_t)member * cap;
   const unsigned long long s0 = first % cap;
   const unsigned long long head = count < cap - s0 ? count : cap - s0;
   PB_TRY(hipMemcpyAsync(rows, ring + s0, sizeof(pbMomentsRow) * head, hipMemcpyDeviceToHost, S->stream));
@@ -276,14 +259,14 @@ int pbSimGetSeriesOf(pbSim *S, unsigned member, unsigned long long first, unsign
   PB_TRY(hipStreamSynchronize(S->stream));
   for (unsigned k = 0; k < count; k++) {
     const size_t slot = (size_t)((first + k) % cap);
-    finishRow(rows[k], S->seriesTimes[slot], S->seriesSteps[slot]);
+    finishRow(rows[k], S->series.times[slot], S->series.steps[slot]);
   }
   return PB_OK;
 }
 
 int pbSimGetSeriesTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
   if (!S) return fail("pbSimGetSeriesTimes", ": null handle");
-  if (records) *records = S->seriesRecords;
+  if (records) *records = S->series.records;
   if (last_device_ms) {
     *last_device_ms = 0.0f;
     if (S->momTimed) {

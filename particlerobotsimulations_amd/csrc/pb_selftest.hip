@@ -1,6 +1,8 @@
 // pb_selftest.hip -- on-device proofs that the fast exact forms of pb_device.hpp (pbSqrtFast, pbDiv2Fast,
 // pbDistUnitFast) equal the compiler's IEEE sqrtf and division (pbSelfTest*: every float / every mantissa
 // pair), and the shader-clock sampler of the roofline report.  Nothing here runs in a timestep.
+#include <memory>
+
 #include "pb_engine.hpp"
 
 namespace {
@@ -222,8 +224,8 @@ extern "C" {
 int pbSelfTest(unsigned long long div_samples, unsigned long long *sqrt_checked,
                unsigned long long *sqrt_mismatches, unsigned long long *div_checked,
                unsigned long long *div_mismatches) {
-  unsigned long long *d = nullptr;
-  PB_TRY(hipMalloc((void **)&d, 4 * sizeof(unsigned long long)));
+  PbDevBuf<unsigned long long> d;
+  PB_TRY(d.alloc(4));
   PB_TRY(hipMemset(d, 0, 4 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_selftest_sqrt, dim3(1u << 20), dim3(256), 0, 0, d + 1, d + 0);
   const unsigned threads = 4096u * 256u;
@@ -236,7 +238,6 @@ int pbSelfTest(unsigned long long div_samples, unsigned long long *sqrt_checked,
   PB_TRY(hipGetLastError());
   unsigned long long h[4];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  PB_TRY(hipFree(d));
   if (sqrt_checked) *sqrt_checked = h[0];
   if (sqrt_mismatches) *sqrt_mismatches = h[1];
   if (div_checked) *div_checked = h[2];
@@ -245,42 +246,39 @@ int pbSelfTest(unsigned long long div_samples, unsigned long long *sqrt_checked,
 }
 
 int pbSelfTestHoldThreshold(float c, unsigned long long *checked, unsigned long long *mismatches) {
-  unsigned long long *d = nullptr;
-  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PbDevBuf<unsigned long long> d;
+  PB_TRY(d.alloc(2));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_selftest_hold, dim3(1u << 19), dim3(256), 0, 0, c, pbSqrtThreshold(c), d + 1, d + 0);
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  PB_TRY(hipFree(d));
   if (checked) *checked = h[0];
   if (mismatches) *mismatches = h[1];
   return PB_OK;
 }
 
 int pbSelfTestMagnitudeRoot(unsigned long long *checked, unsigned long long *mismatches) {
-  unsigned long long *d = nullptr;
-  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PbDevBuf<unsigned long long> d;
+  PB_TRY(d.alloc(2));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_selftest_magroot, dim3(1u << 19), dim3(256), 0, 0, d + 1, d + 0);  // 2^31 bit patterns
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  PB_TRY(hipFree(d));
   if (checked) *checked = h[0];
   if (mismatches) *mismatches = h[1];
   return PB_OK;
 }
 
 int pbSelfTestTermRoot(unsigned long long *checked, unsigned long long *mismatches) {
-  unsigned long long *d = nullptr;
-  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PbDevBuf<unsigned long long> d;
+  PB_TRY(d.alloc(2));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   hipLaunchKernelGGL(k_selftest_termroot, dim3(1u << 20), dim3(256), 0, 0, d + 1, d + 0);  // 2^32 bit patterns
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  PB_TRY(hipFree(d));
   if (checked) *checked = h[0];
   if (mismatches) *mismatches = h[1];
   return PB_OK;
@@ -289,8 +287,8 @@ int pbSelfTestTermRoot(unsigned long long *checked, unsigned long long *mismatch
 int pbSelfTestPairGeometry(unsigned first_slice, unsigned slices, unsigned long long *checked,
                            unsigned long long *mismatches) {
   if (first_slice >= 64u || slices == 0u || first_slice + slices > 64u) return PB_ERR_ARG;
-  unsigned long long *d = nullptr;
-  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PbDevBuf<unsigned long long> d;
+  PB_TRY(d.alloc(2));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   const uint32_t perSlice = (1u << 24) / 64u;  // d2 values per slice
   for (unsigned sl = first_slice; sl < first_slice + slices; sl++)
@@ -298,7 +296,6 @@ int pbSelfTestPairGeometry(unsigned first_slice, unsigned slices, unsigned long 
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  PB_TRY(hipFree(d));
   if (checked) *checked = h[0];
   if (mismatches) *mismatches = h[1];
   return PB_OK;
@@ -307,8 +304,8 @@ int pbSelfTestPairGeometry(unsigned first_slice, unsigned slices, unsigned long 
 int pbSelfTestDivision(unsigned first_slice, unsigned slices, unsigned long long *checked,
                        unsigned long long *mismatches) {
   if (first_slice >= 64u || slices == 0u || first_slice + slices > 64u) return PB_ERR_ARG;
-  unsigned long long *d = nullptr;
-  PB_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
+  PbDevBuf<unsigned long long> d;
+  PB_TRY(d.alloc(2));
   PB_TRY(hipMemset(d, 0, 2 * sizeof(unsigned long long)));
   const uint32_t perSlice = (1u << 23) / 64u;  // denominators per slice
   for (unsigned sl = first_slice; sl < first_slice + slices; sl++)
@@ -316,29 +313,25 @@ int pbSelfTestDivision(unsigned first_slice, unsigned slices, unsigned long long
   PB_TRY(hipGetLastError());
   unsigned long long h[2];
   PB_TRY(hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost));
-  PB_TRY(hipFree(d));
   if (checked) *checked = h[0];
   if (mismatches) *mismatches = h[1];
   return PB_OK;
 }
 
 struct pbClockSample {
-  hipStream_t stream = nullptr;
-  unsigned long long *dev = nullptr;
+  PbStream stream;
+  PbDevBuf<unsigned long long> dev;  // (released in front of the stream)
 };
 
 int pbClockSampleBegin(pbClockSample **out, double seconds) {
   if (!out || !(seconds > 0.0) || seconds > 30.0) return PB_ERR_ARG;
-  pbClockSample *h = new pbClockSample();
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc((void **)&h->dev, 2 * sizeof(unsigned long long)) != hipSuccess) {
+  std::unique_ptr<pbClockSample> h(new pbClockSample());
+  if (h->stream.create(hipStreamNonBlocking) != hipSuccess || h->dev.alloc(2) != hipSuccess) {
     pbLastError() = "pbClockSampleBegin: stream/buffer creation failed";
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
     return PB_ERR_HIP;
   }
   hipLaunchKernelGGL(k_clock_sample, dim3(1), dim3(64), 0, h->stream, (unsigned long long)(seconds * 1e8), h->dev);
-  *out = h;
+  *out = h.release();
   return PB_OK;
 }
 
@@ -347,8 +340,6 @@ int pbClockSampleEnd(pbClockSample *h, double *mhz, double *seconds_sampled) {
   unsigned long long v[2] = {0, 0};
   hipError_t e = hipStreamSynchronize(h->stream);
   if (e == hipSuccess) e = hipMemcpy(v, h->dev, sizeof v, hipMemcpyDeviceToHost);
-  (void)hipFree(h->dev);
-  (void)hipStreamDestroy(h->stream);
   delete h;
   if (e != hipSuccess || v[1] == 0) {
     pbLastError() = "pbClockSampleEnd: sampler kernel failed";

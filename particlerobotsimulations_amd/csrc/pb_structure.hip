@@ -165,11 +165,11 @@ int hexaticSweep(pbSim *S, float gap) {
   PbClusterScratch *C = S->cluster;
   const ClusterGrid G = gridOf(C);
   const size_t total = S->total;  // (each on its own: a failed allocation leaves the rest to the next call)
-  if (!C->sRe) PB_TRY(hipMalloc((void **)&C->sRe, sizeof(long long) * total));
-  if (!C->sIm) PB_TRY(hipMalloc((void **)&C->sIm, sizeof(long long) * total));
-  if (!C->sNb) PB_TRY(hipMalloc((void **)&C->sNb, sizeof(uint32_t) * total));
-  if (!C->sRows) PB_TRY(hipMalloc((void **)&C->sRows, sizeof(pbStructureStats) * S->nsims));
-  if (!C->sPsi) PB_TRY(hipMalloc((void **)&C->sPsi, sizeof(double) * 2 * S->n));
+  PB_TRY(C->sRe.ensure(total));
+  PB_TRY(C->sIm.ensure(total));
+  PB_TRY(C->sNb.ensure(total));
+  PB_TRY(C->sRows.ensure(S->nsims));
+  PB_TRY(C->sPsi.ensure(2 * (size_t)S->n));
   PB_TRY(hipMemsetAsync(C->sRows, 0, sizeof(pbStructureStats) * S->nsims, S->stream));
   hipLaunchKernelGGL(k_struct_psi6, dim3(cdiv(S->n, CT), S->nsims), dim3(CT), 0, S->stream, C->cpr, C->start, S->n, G,
                      gap, C->sRe, C->sIm, C->sNb, C->sRows);
@@ -178,18 +178,6 @@ int hexaticSweep(pbSim *S, float gap) {
 }
 
 }  // namespace
-
-void pbStructureFree(PbClusterScratch *C) {
-  (void)hipFree(C->sCounts);
-  (void)hipFree(C->sRe);
-  (void)hipFree(C->sIm);
-  (void)hipFree(C->sNb);
-  (void)hipFree(C->sRows);
-  (void)hipFree(C->sPsi);
-  pbClockFree(C->structureClock);
-  C->sCounts = nullptr, C->sCountsBins = 0, C->sRe = nullptr, C->sIm = nullptr, C->sNb = nullptr, C->sRows = nullptr;
-  C->sPsi = nullptr;
-}
 
 int pbSimRadialCounts(pbSim *S, float rMax, unsigned bins, unsigned long long *counts) {
   if (!S || !counts) {
@@ -210,12 +198,7 @@ int pbSimRadialCounts(pbSim *S, float rMax, unsigned bins, unsigned long long *c
   if (rc != PB_OK) return rc;
   PbClusterScratch *C = S->cluster;
   const ClusterGrid G = gridOf(C);
-  if (C->sCountsBins < bins) {
-    (void)hipFree(C->sCounts);
-    C->sCounts = nullptr, C->sCountsBins = 0;
-    PB_TRY(hipMalloc((void **)&C->sCounts, sizeof(unsigned long long) * (size_t)S->nsims * bins));
-    C->sCountsBins = bins;
-  }
+  PB_TRY(C->sCounts.ensure((size_t)S->nsims * bins));  // (grows with bins: the members of a batch are fixed)
   const size_t bytes = sizeof(unsigned long long) * (size_t)S->nsims * bins;
   const float scale = (float)bins / rMax;
   const float d2max = rMax * rMax * 1.0001f + 1e-30f;

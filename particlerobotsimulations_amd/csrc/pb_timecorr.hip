@@ -128,26 +128,14 @@ int fail(const char *fn, const char *what) {
   return PB_ERR_ARG;
 }
 
-void freeAll(pbSim *S) {
-  (void)hipFree(S->tcRing);
-  (void)hipFree(S->tcTable);
-  S->tcRing = nullptr, S->tcTable = nullptr;
-  S->tcInt = 0.0f, S->tcRadius = 0.0f, S->tcLags = 0u, S->tcA2 = 0ull, S->tcRecords = 0ull;
-  S->tcSteps.clear(), S->tcOrigins.clear(), S->tcSumSteps.clear();
-  if (S->tcEv0) (void)hipEventDestroy(S->tcEv0);
-  if (S->tcEv1) (void)hipEventDestroy(S->tcEv1);
-  S->tcEv0 = S->tcEv1 = nullptr;
-  S->tcTimed = false;
-}
-
-// the ring, the zeroed table and the events of a correlation of `lags` lags; on an error the caller frees what was made
-int allocate(pbSim *S, unsigned lags) {
+// the ring, the zeroed table and the events of a correlation of `lags` lags into T; on an error the caller drops T
+int allocate(pbSim *S, PbTimeCorr &T, unsigned lags) {
   const size_t words = (size_t)S->nsims * lags * T_COLS;
-  PB_TRY(hipMalloc((void **)&S->tcRing, sizeof(float4) * (size_t)lags * S->total));
-  PB_TRY(hipMalloc((void **)&S->tcTable, sizeof(unsigned long long) * words));
-  PB_TRY(hipEventCreate(&S->tcEv0));
-  PB_TRY(hipEventCreate(&S->tcEv1));
-  hipLaunchKernelGGL(k_tc_clear, dim3(cdiv((uint32_t)words, TT)), dim3(TT), 0, S->stream, S->tcTable, (uint32_t)words);
+  PB_TRY(T.ring.alloc((size_t)lags * S->total));
+  PB_TRY(T.table.alloc(words));
+  PB_TRY(T.ev0.create());
+  PB_TRY(T.ev1.create());
+  hipLaunchKernelGGL(k_tc_clear, dim3(cdiv((uint32_t)words, TT)), dim3(TT), 0, S->stream, T.table, (uint32_t)words);
   PB_TRY(hipGetLastError());
   return PB_OK;
 }
@@ -162,28 +150,26 @@ pbMoment128 normalised(__int128 v) {
 
 }  // namespace
 
-void pbTimeCorrFree(pbSim *S) { freeAll(S); }
-
 int pbTimeCorrRecord(pbSim *S) {
-  const uint32_t lags = S->tcLags, slot = (uint32_t)(S->tcRecords % lags);
-  const uint32_t nLags = (uint32_t)(S->tcRecords < lags - 1u ? S->tcRecords : lags - 1u) + 1u;
+  const uint32_t lags = S->tc.lags, slot = (uint32_t)(S->tc.records % lags);
+  const uint32_t nLags = (uint32_t)(S->tc.records < lags - 1u ? S->tc.records : lags - 1u) + 1u;
   const uint32_t perMember = cdiv(S->n, TT);
   const uint32_t bpl = perMember < PB_TCORR_BLOCKS ? perMember : PB_TCORR_BLOCKS;
   const int c = S->cur;
-  PB_TRY(hipEventRecord(S->tcEv0, S->stream));
+  PB_TRY(hipEventRecord(S->tc.ev0, S->stream));
   hipLaunchKernelGGL(k_tc_snapshot, dim3(cdiv(S->n, TT), S->nsims), dim3(TT), 0, S->stream, S->pr[c], S->vel[c],
-                     S->orig[c], S->n, S->tcRing + (size_t)slot * S->total);
-  hipLaunchKernelGGL(k_tc_accumulate, dim3(S->nsims * nLags * bpl), dim3(TT), 0, S->stream, S->tcRing, S->n, S->total,
-                     lags, slot, nLags, bpl, S->tcA2, S->tcTable);
+                     S->orig[c], S->n, S->tc.ring + (size_t)slot * S->total);
+  hipLaunchKernelGGL(k_tc_accumulate, dim3(S->nsims * nLags * bpl), dim3(TT), 0, S->stream, S->tc.ring, S->n, S->total,
+                     lags, slot, nLags, bpl, S->tc.a2, S->tc.table);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(S->tcEv1, S->stream));
-  S->tcTimed = true;
-  S->tcSteps[slot] = S->stats.steps;
+  PB_TRY(hipEventRecord(S->tc.ev1, S->stream));
+  S->tc.timed = true;
+  S->tc.steps[slot] = S->stats.steps;
   for (uint32_t l = 0; l < nLags; l++) {
-    S->tcOrigins[l]++;
-    S->tcSumSteps[l] += S->stats.steps - S->tcSteps[(slot + lags - l) % lags];
+    S->tc.origins[l]++;
+    S->tc.sumSteps[l] += S->stats.steps - S->tc.steps[(slot + lags - l) % lags];
   }
-  S->tcRecords++;
+  S->tc.records++;
   return PB_OK;
 }
 
@@ -202,25 +188,25 @@ int pbSimSetTimeCorrelation(pbSim *S, float interval, unsigned lags, float overl
     return fail(fn, ": the ring (lags x bots x 16 bytes) must not exceed 2^33 bytes");
   useDevice(S);
   PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
-  freeAll(S);
+  S->tc = PbTimeCorr();
   if (!lags) return PB_OK;
-  const int rc = allocate(S, lags);
+  const int rc = allocate(S, S->tc, lags);
   if (rc != PB_OK) {  // (a ring that took the last free memory, say): whatever was made goes, the correlation stays off
-    freeAll(S);
+    S->tc = PbTimeCorr();
     (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
     return rc;
   }
   const long long qa = (long long)rintf(overlapRadius * 1048576.0f);  // exact scaling, at most 2^31 - 128
-  S->tcInt = interval, S->tcLags = lags, S->tcRadius = overlapRadius, S->tcA2 = (unsigned long long)(qa * qa);
-  S->tcSteps.assign(lags, 0ull);
-  S->tcOrigins.assign(lags, 0ull);
-  S->tcSumSteps.assign(lags, 0ull);
+  S->tc.interval = interval, S->tc.lags = lags, S->tc.radius = overlapRadius, S->tc.a2 = (unsigned long long)(qa * qa);
+  S->tc.steps.assign(lags, 0ull);
+  S->tc.origins.assign(lags, 0ull);
+  S->tc.sumSteps.assign(lags, 0ull);
   return PB_OK;
 }
 
 int pbSimTimeCorrelationRecord(pbSim *S) {
   if (!S) return fail("pbSimTimeCorrelationRecord", ": null handle");
-  if (!S->tcRing) return fail("pbSimTimeCorrelationRecord", ": the correlation is off");
+  if (!S->tc.ring) return fail("pbSimTimeCorrelationRecord", ": the correlation is off");
   useDevice(S);
   return pbTimeCorrRecord(S);
 }
@@ -230,20 +216,20 @@ int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float
   if (!S) return fail("pbSimGetTimeCorrelationInfo", ": null handle");
   if (!interval && !lags && !overlapRadius && !records)
     return fail("pbSimGetTimeCorrelationInfo", ": interval, lags, overlapRadius and records are all null");
-  if (interval) *interval = S->tcInt;
-  if (lags) *lags = S->tcLags;
-  if (overlapRadius) *overlapRadius = S->tcRadius;
-  if (records) *records = S->tcRecords;
+  if (interval) *interval = S->tc.interval;
+  if (lags) *lags = S->tc.lags;
+  if (overlapRadius) *overlapRadius = S->tc.radius;
+  if (records) *records = S->tc.records;
   return PB_OK;
 }
 
 int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
   if (!S || !rows) return fail("pbSimGetTimeCorrelation", ": null handle or rows");
-  if (!S->tcRing) return fail("pbSimGetTimeCorrelation", ": the correlation is off");
+  if (!S->tc.ring) return fail("pbSimGetTimeCorrelation", ": the correlation is off");
   useDevice(S);
-  const size_t cells = (size_t)S->nsims * S->tcLags;
+  const size_t cells = (size_t)S->nsims * S->tc.lags;
   std::vector<unsigned long long> acc(cells * T_COLS);
-  PB_TRY(hipMemcpyAsync(acc.data(), S->tcTable, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost,
+  PB_TRY(hipMemcpyAsync(acc.data(), S->tc.table, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost,
                         S->stream));
   PB_TRY(hipStreamSynchronize(S->stream));
   for (size_t k = 0; k < cells; k++)
@@ -251,10 +237,10 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
       return fail("pbSimGetTimeCorrelation", ": a lag holds 2^31 samples or more: restart the correlation");
   for (size_t k = 0; k < cells; k++) {
     const unsigned long long *w = &acc[k * T_COLS];
-    const unsigned lag = (unsigned)(k % S->tcLags);
+    const unsigned lag = (unsigned)(k % S->tc.lags);
     pbTimeCorrelationRow &r = rows[k];
     r.lag = lag, r.reserved = 0u;
-    r.origins = S->tcOrigins[lag], r.sum_steps = S->tcSumSteps[lag];
+    r.origins = S->tc.origins[lag], r.sum_steps = S->tc.sumSteps[lag];
     r.samples = w[T_SAMPLES];
     r.sum_qx = (long long)w[T_QX], r.sum_qy = (long long)w[T_QY];
     r.msd = normalised((__int128)w[T_MSD_LO] + (__int128)w[T_MSD_HI] * ((__int128)1 << 32));
@@ -266,13 +252,13 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
 
 int pbSimGetTimeCorrelationTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
   if (!S) return fail("pbSimGetTimeCorrelationTimes", ": null handle");
-  if (records) *records = S->tcRecords;
+  if (records) *records = S->tc.records;
   if (last_device_ms) {
     *last_device_ms = 0.0f;
-    if (S->tcTimed) {
+    if (S->tc.timed) {
       useDevice(S);
-      PB_TRY(hipEventSynchronize(S->tcEv1));
-      PB_TRY(hipEventElapsedTime(last_device_ms, S->tcEv0, S->tcEv1));
+      PB_TRY(hipEventSynchronize(S->tc.ev1));
+      PB_TRY(hipEventElapsedTime(last_device_ms, S->tc.ev0, S->tc.ev1));
     }
   }
   return PB_OK;
