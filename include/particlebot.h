@@ -251,6 +251,11 @@ class Particlebot {
   bool timeCorrelationRecord();
   bool timeCorrelationInfo(float &interval, unsigned &lags, float &overlapRadius, unsigned long long &records);
   bool timeCorrelationRows(std::vector<pbTimeCorrelationRow> &rows);
+  /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
+   * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
+   * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on
+   * nx or ny outside 1 ... PB_FIELD_MAX_AXIS and on a view whose half extents are not finite and > 0. */
+  bool fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -778,6 +778,63 @@ int pbSimGetTimeCorrelationInfo(pbSim *sim, float *interval, unsigned *lags, flo
 int pbSimGetTimeCorrelation(pbSim *sim, pbTimeCorrelationRow *rows /* nsims * lags, member-major, lag 0 first */);
 int pbSimGetTimeCorrelationTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
+/* Field maps on the device (csrc/pb_field.hip): WHERE in the blob something happens.  A regular grid of map cells is
+ * laid over a view, and per cell the call returns the bots in it, how many of them are dead, and the integer sums of
+ * radius, radius^2, velocity and |v|^2.  From these a caller forms number density, area fraction (sum r^2), the mean
+ * velocity field, the kinetic temperature (sum |v|^2 minus the mean flow) and the radius wave (mean radius per cell)
+ * with no second pass.  Nothing is allocated or launched unless a map is asked for.
+ * NODES.  All nCells bots of a member are nodes, dead bots and the payload bot included.
+ * MEASURED.  A bot is MEASURED by pbSimMoments' rule: x, y, vx, vy and rad are finite and each has fabsf(.) < 2048.0f.
+ * The quantisation is pbSimMoments': q = (long long)rint(v * 1048576.0f) in fp32 scaling, round to nearest even; it
+ * gives qr (from rad), wx (from vx) and wy (from vy).  Positions are not quantised; they only choose the cell.
+ * CELL OF A MEASURED BOT.  Everything is fp32 with no contraction.  The host computes once
+ *     x0 = centerX - halfX;   sx = (float)nx / (halfX + halfX)
+ * and the device computes tx = (x - x0) * sx, with two roundings.  The bot is inside in x iff tx >= 0.0f &&
+ * tx < (float)nx; then ix = (int)tx.  A tx of -0.0f is inside, in column 0.  y works the same way with y0, sy, ny; row 0
+ * is the lowest y.  The cell index is iy * nx + ix; cells are member-major: member m's cell at cells[(m * ny + iy) * nx + ix].
+ * COUNTING.  A measured bot that is inside in both axes adds to its cell: count += 1, dead += (dead != 0),
+ * sum_qr += qr, sum_wx += wx, sum_wy += wy, rr += qr*qr, vv += wx*wx + wy*wy.  rr and vv are 128-bit sums as
+ * pbMoment128, value hi * 2^32 + lo, added with the two's-complement lo/hi split of pbSimMoments and NORMALISED by the
+ * host to 0 <= lo < 2^32 with hi the floor quotient, as pbSimPairCorrelation does.  A measured bot that is outside adds
+ * only to totals.outside; an unmeasured bot adds only to totals.unmeasured.  Per member
+ *     measured = inside + outside   and   measured + unmeasured = nCells.
+ * Every number is an integer: results do not depend on slot order, on the kernel form, or on the order in which the
+ * device adds, and can be compared exactly.  No float atomics and no 128-bit atomics.
+ * EXACTNESS.  A cell holds fewer than 2^28 bots (the batch's bound), so every half-accumulator stays below 2^60
+ * (DESIGN.md 7h has the derivation): nothing wraps, whatever the state.
+ * pbSimFieldMap maps every member with the same view; pbSimFieldMapOf one member into ny * nx cells and one totals row.
+ * totals may be NULL.  pbSimGetFieldTimes: maps computed so far and the span of the last one's launches on the batch's
+ * stream in milliseconds (HIP events), as pbSimGetSeriesTimes; either pointer may be NULL.
+ * A call only reads: the state, slot layout, keys, cell lists, pbSimStats, time, RNG, the mark, the series, the time
+ * correlation and every other analysis' scratch stay as they were.
+ * PB_ERR_ARG, before the device is touched: a NULL handle, view or cells; a member out of range; nx or ny outside
+ * 1 ... PB_FIELD_MAX_AXIS; halfX or halfY not finite or not > 0; any of x0, y0, sx, sy not finite; nsims * nx * ny * 64
+ * above 2^31 bytes (pbSimFieldMapOf counts one member); a batch of 2^28 bots or more.
+ * Cost: one launch that zeroes the map and the totals; one pass over posrad, velocities and dead flags in slot order
+ * (28 bytes per bot, coalesced; the original indices are never read), at most PB_FIELD_BLOCKS workgroups of 256 lanes
+ * per member.  The state is kept cell-sorted, so the lanes of a wave mostly share a few map cells: lanes with the same
+ * cell are summed inside the wave first and go out as one 64-byte integer atomic; past a fixed number of distinct cells
+ * per wave (a map finer than the blob's spacing) the rest goes out as eight 64-bit atomics per bot.  Scratch: 64 bytes
+ * per cell of the largest map asked for so far plus 16 bytes per member, allocated by the first call, grown when a call
+ * needs more, freed by pbSimDestroy.  Read back: the same bytes.
+ * Out of scope: maps per series record; phase fields (they need a transcendental and would not be exact); per-member
+ * views in one call; stress fields (the per-bot virial is pbSimContactVirialOf's); normalisation to densities; the
+ * ensemble layer's summary rows; the legacy engine. */
+#define PB_FIELD_MAX_AXIS 1024u
+#define PB_FIELD_BLOCKS 256u /* workgroups per member: one pass of the launch covers 65536 bots of a member */
+typedef struct pbFieldView { unsigned nx, ny; float centerX, centerY, halfX, halfY; } pbFieldView;
+typedef struct pbFieldCell {            /* 64 bytes */
+  unsigned count, dead;                 /* measured bots in the cell; those of them with dead != 0 */
+  long long sum_qr, sum_wx, sum_wy;     /* units of 2^-20 */
+  pbMoment128 rr, vv;                   /* sum qr*qr, sum (wx*wx + wy*wy); units of 2^-40; normalised by the host */
+} pbFieldCell;
+typedef struct pbFieldTotals { unsigned measured, inside, outside, unmeasured; } pbFieldTotals;  /* 16 bytes */
+int pbSimFieldMap(pbSim *sim, const pbFieldView *view, pbFieldCell *cells /* nsims * ny * nx */,
+                  pbFieldTotals *totals /* nsims entries, may be NULL */);
+int pbSimFieldMapOf(pbSim *sim, unsigned member, const pbFieldView *view, pbFieldCell *cells /* ny * nx */,
+                    pbFieldTotals *totals /* 1 entry, may be NULL */);
+int pbSimGetFieldTimes(pbSim *sim, unsigned long long *maps, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

@@ -16,7 +16,7 @@ from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
-           "connected_correlation", "time_correlation_summary"]
+           "connected_correlation", "time_correlation_summary", "field_values"]
 
 
 def radial_distribution(counts, r_max, density, n):
@@ -73,6 +73,20 @@ def time_correlation_summary(row, lag0=None):
             "vacf": float(Fraction(vacf, m * two)),
             "vacf_normalised": norm,
             "overlap": float(Fraction(int(row["overlap"]), m))}
+
+
+def field_values(cells):
+    """The cells of field_map() as a dict of arrays of the cells' shape: count, dead, sum_qr, sum_wx, sum_wy as they are,
+    and rr, vv as object arrays of Python ints composed from their 128 bits (hi * 2^32 + lo).  The sums are in units of
+    2^-20, rr and vv in units of 2^-40."""
+    cells = np.asarray(cells)
+    out = {name: cells[name] for name in ("count", "dead", "sum_qr", "sum_wx", "sum_wy")}
+    for name in ("rr", "vv"):
+        flat = [(int(h) << 32) + int(l) for h, l in zip(cells[name + "_hi"].reshape(-1), cells[name + "_lo"].reshape(-1))]
+        big = np.empty(len(flat), object)
+        big[:] = flat
+        out[name] = big.reshape(cells.shape)
+    return out
 
 
 def correlation_values(rows):
@@ -770,6 +784,33 @@ class Sim:
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetTimeCorrelationTimes(self._h, C.byref(n), C.byref(ms)),
                     "pbSimGetTimeCorrelationTimes")
+        return int(n.value), float(ms.value)
+
+    def field_map(self, nx, ny, center, half, member=None):
+        """A field map of every member's state as it is now, on the device (pbSimFieldMap): nx x ny cells over the view
+        centred on center = (x, y) with half extent `half` (one number, or (halfX, halfY)).  Returns (cells, totals):
+        cells a structured array (nsims, ny, nx), row 0 the lowest y, of count, dead, sum_qr, sum_wx, sum_wy (units of
+        2^-20) and rr_lo / rr_hi, vv_lo / vv_hi (each 128-bit value is hi * 2^32 + lo with 0 <= lo < 2^32, units of
+        2^-40; field_values() composes them into Python ints); totals a list of dicts (measured, inside, outside,
+        unmeasured), one per member.  With member=k only that member is mapped (pbSimFieldMapOf): its (ny, nx) cells and
+        its dict."""
+        view = _capi.field_view(nx, ny, center, half)
+        nsims = int(getattr(self, "nsims", 1)) if member is None else 1
+        fits = 1 <= int(nx) <= 1024 and 1 <= int(ny) <= 1024 and nsims * int(nx) * int(ny) * 64 <= 1 << 31
+        shape = (int(ny), int(nx)) if fits else (1, 1)  # (a call that the engine refuses gets no buffer to speak of)
+        if member is not None:
+            cells, tot = np.zeros(shape, _capi.FIELD_CELL_DTYPE), _capi.pbFieldTotals()
+            _capi.check(_capi.lib().pbSimFieldMapOf(self._h, int(member), C.byref(view), _capi.np_ptr(cells),
+                                                    C.byref(tot)), "pbSimFieldMapOf")
+            return cells, _capi.field_totals(tot)
+        cells, tot = np.zeros((nsims,) + shape, _capi.FIELD_CELL_DTYPE), (_capi.pbFieldTotals * nsims)()
+        _capi.check(_capi.lib().pbSimFieldMap(self._h, C.byref(view), _capi.np_ptr(cells), tot), "pbSimFieldMap")
+        return cells, [_capi.field_totals(t) for t in tot]
+
+    def field_times(self):
+        """(field maps computed so far, device milliseconds of the last one's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetFieldTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetFieldTimes")
         return int(n.value), float(ms.value)
 
 

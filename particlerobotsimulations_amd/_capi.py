@@ -192,6 +192,37 @@ def time_correlation_row(r):
     return d
 
 
+class pbFieldView(C.Structure):
+    _fields_ = [("nx", C.c_uint), ("ny", C.c_uint), ("centerX", C.c_float), ("centerY", C.c_float),
+                ("halfX", C.c_float), ("halfY", C.c_float)]
+
+
+class pbFieldCell(C.Structure):
+    _fields_ = [("count", C.c_uint), ("dead", C.c_uint), ("sum_qr", C.c_longlong), ("sum_wx", C.c_longlong),
+                ("sum_wy", C.c_longlong), ("rr", pbMoment128), ("vv", pbMoment128)]
+
+
+class pbFieldTotals(C.Structure):
+    _fields_ = [("measured", C.c_uint), ("inside", C.c_uint), ("outside", C.c_uint), ("unmeasured", C.c_uint)]
+
+
+# pbFieldCell as a numpy record: each 128-bit value is hi * 2^32 + lo, normalised to 0 <= lo < 2^32
+FIELD_CELL_DTYPE = np.dtype([("count", np.uint32), ("dead", np.uint32), ("sum_qr", np.int64), ("sum_wx", np.int64),
+                             ("sum_wy", np.int64), ("rr_lo", np.uint64), ("rr_hi", np.int64), ("vv_lo", np.uint64),
+                             ("vv_hi", np.int64)])
+
+
+def field_view(nx, ny, center, half):
+    """A pbFieldView of nx x ny cells centred on `center` = (x, y); `half` is one half extent or (halfX, halfY)."""
+    hx, hy = (half, half) if np.isscalar(half) else half
+    return pbFieldView(int(nx), int(ny), float(center[0]), float(center[1]), float(hx), float(hy))
+
+
+def field_totals(t):
+    """A pbFieldTotals row as a dict of Python ints."""
+    return {name: int(getattr(t, name)) for name, _ in pbFieldTotals._fields_}
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -280,6 +311,9 @@ SYMBOLS = {
     "pbSimGetTimeCorrelationInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_F), C.POINTER(C.c_ulonglong)]),
     "pbSimGetTimeCorrelation": (_I, [_VP, C.POINTER(pbTimeCorrelationRow)]),
     "pbSimGetTimeCorrelationTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimFieldMap": (_I, [_VP, C.POINTER(pbFieldView), _VP, C.POINTER(pbFieldTotals)]),
+    "pbSimFieldMapOf": (_I, [_VP, _U, C.POINTER(pbFieldView), _VP, C.POINTER(pbFieldTotals)]),
+    "pbSimGetFieldTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

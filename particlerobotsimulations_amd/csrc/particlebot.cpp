@@ -1528,6 +1528,14 @@ bool Particlebot::timeCorrelationRows(std::vector<pbTimeCorrelationRow> &rows) {
   });
 }
 
+bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
+  return onFusedEngine("fieldMap", "field map", [&] {
+    const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;
+    cells.assign(fits ? (size_t)view.nx * view.ny : 1, pbFieldCell());
+    return pbSimFieldMap(sim, &view, cells.data(), &totals);
+  });
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

@@ -435,6 +435,17 @@ int pbHostTimeCorrelationRows(void *hv, pbTimeCorrelationRow *rows, unsigned lon
   return 0;
 }
 
+// a field map of the resident state (Particlebot::fieldMap; fused engine only): ny * nx 64-byte pbFieldCell entries and,
+// unless NULL, the 16-byte pbFieldTotals row.  -1 on the other engines and on a bad view.
+int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFieldTotals *totals) {
+  std::vector<pbFieldCell> c;
+  pbFieldTotals t;
+  if (!view || !cells || !((HostSim *)hv)->bot->fieldMap(*view, c, t)) return -1;
+  copyOut(cells, c);
+  if (totals) *totals = t;
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -13,6 +13,7 @@
 //   pb_dynamics.hip  rearrangement analysis: a marked reference, bond survival and displacements (pbSimMarkReference)
 //   pb_moments.hip   time series: integer moment rows per member, now or recorded while stepping (pbSimSetSeries)
 //   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a ring of snapshots (pbSimSetTimeCorrelation)
+//   pb_field.hip     field maps: count, dead and integer sums of radius and velocity per grid cell (pbSimFieldMap)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 //   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of
@@ -87,6 +88,15 @@ struct PbTimeCorr {
   std::vector<unsigned long long> steps;   // per slot: stats.steps at that moment
   std::vector<unsigned long long> origins, sumSteps;  // per lag: record pairs added, and their step differences
   PbEvent ev0, ev1;                        // around the last record's launches
+  bool timed = false;
+};
+
+// field maps (pb_field.hip): the scratch of the largest map asked for so far, made by the first call (pbSimFieldMap)
+struct PbField {
+  PbDevBuf<unsigned long long> cells;  // eight words per cell of the map a call computes
+  PbDevBuf<uint32_t> totals;           // four words per member
+  PbEvent ev0, ev1;                    // around the last map's launches
+  unsigned long long maps = 0;
   bool timed = false;
 };
 
@@ -169,6 +179,7 @@ struct pbSim {
   PbEvent momEv0, momEv1;
   bool momTimed = false;
   PbTimeCorr tc;
+  PbField field;
   pbSimStats stats{};
 };
 

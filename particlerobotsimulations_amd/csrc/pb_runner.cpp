@@ -8,6 +8,7 @@
 //                   [--series FILE [--series-interval T] [--series-capacity N]]
 //                   [--correlate FILE [--correlate-kind velocity|radius] [--correlate-rmax R] [--correlate-bins B]]
 //                   [--timecorr FILE [--timecorr-interval T] [--timecorr-lags N] [--timecorr-overlap A]]
+//                   [--field FILE [--field-cells N] [--field-half H]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -82,6 +83,13 @@
 // engine refuses a table that holds more: the records the run will take (from max_time, the start time and the
 // interval) times nCells must stay below 2^31 (10^6 bots: 2147 records), or the run is refused when it starts (exit
 // 2, "--timecorr: ... 2^31 samples"), before a step is taken.  (The usage line does not list these four either.)
+// --field FILE appends, at every dump time (the steps at which --clusters writes its rows), one block of the device's
+// field map of the state (Particlebot::fieldMap): a square map of --field-cells N x N cells (default 64, 1 ... 1024)
+// centred on (0, 0) with half extent --field-half H (default the wall half extent; finite and > 0).  FILE gets the
+// header `time,step,ix,iy,count,dead,sum_qr,sum_wx,sum_wy,rr,vv` once, then per block one line per NON-EMPTY cell, row 0
+// the lowest y: time as %.9g, step the steps taken so far, every other number the integer it is (the sums in units of
+// 2^-20, rr and vv of 2^-40, in decimal from their 128 bits as --correlate prints them).  (The usage line does not list
+// these three either.)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -188,6 +196,9 @@ int main(int argc, char **argv) {
   std::string timecorrPath;
   float timecorrInterval = -1.0f, timecorrOverlap = -1.0f;  // below 0: dump_interval / min_radius, once the configuration is loaded
   long timecorrLags = 32;
+  std::string fieldPath;
+  long fieldCells = 64;
+  float fieldHalf = 0.0f;  // 0: the wall half extent, once the configuration is loaded
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -270,6 +281,14 @@ int main(int argc, char **argv) {
       if (end == argv[i] || *end || timecorrLags < 1 || timecorrLags > (long)PB_TCORR_MAX_LAGS) badArg = true;
     } else if (!strcmp(argv[i], "--timecorr-overlap") && i + 1 < argc) {
       badArg = !parseFloat(argv[++i], 0.0f, false, timecorrOverlap) || !(timecorrOverlap < 2048.0f);
+    } else if (!strcmp(argv[i], "--field") && i + 1 < argc) {
+      fieldPath = argv[++i];
+    } else if (!strcmp(argv[i], "--field-cells") && i + 1 < argc) {
+      char *end = nullptr;
+      fieldCells = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || fieldCells < 1 || fieldCells > (long)PB_FIELD_MAX_AXIS) badArg = true;
+    } else if (!strcmp(argv[i], "--field-half") && i + 1 < argc) {
+      badArg = !parseFloat(argv[++i], 0.0f, true, fieldHalf);
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -301,7 +320,8 @@ int main(int argc, char **argv) {
       {"--clusters", clustersPath, "analysis"},   {"--contacts", contactsPath, "export"},
       {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
       {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"},
-      {"--correlate", correlatePath, "analysis"}, {"--timecorr", timecorrPath, "recorder"}};
+      {"--correlate", correlatePath, "analysis"}, {"--timecorr", timecorrPath, "recorder"},
+      {"--field", fieldPath, "analysis"}};
   for (const auto &f : fusedOnly)
     if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
       fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
@@ -479,6 +499,27 @@ int main(int argc, char **argv) {
       for (int k = 0; k < 8; k++) fprintf(sf, ", %u", ss.coordination[k]);
       fprintf(sf, "\n");
       if (fclose(sf) != 0) return 1;
+    }
+    if (!fieldPath.empty() && sim.dumpDue(cfg.dump_interval)) {
+      pbFieldView view;
+      view.nx = view.ny = (unsigned)fieldCells;
+      view.centerX = view.centerY = 0.0f;
+      view.halfX = view.halfY = fieldHalf > 0.0f ? fieldHalf : cfg.wallHalf();
+      std::vector<pbFieldCell> cells;
+      pbFieldTotals tot;
+      if (!sim.fieldMap(view, cells, tot)) return 1;
+      FILE *ff = openOutput(fieldPath, sim.getTime() == 0.0f ? "w" : "a");
+      if (!ff) return 1;
+      if (fseek(ff, 0, SEEK_END) == 0 && ftell(ff) == 0)  // a fresh file, or a resumed run that appends to none
+        fprintf(ff, "time,step,ix,iy,count,dead,sum_qr,sum_wx,sum_wy,rr,vv\n");
+      for (size_t k = 0; k < cells.size(); k++) {
+        const pbFieldCell &c = cells[k];
+        if (!c.count) continue;
+        fprintf(ff, "%.9g,%ld,%zu,%zu,%u,%u,%lld,%lld,%lld,%s,%s\n", (double)sim.getTime(), stepsDone, k % view.nx,
+                k / view.nx, c.count, c.dead, c.sum_qr, c.sum_wx, c.sum_wy, decimal128(c.rr).c_str(),
+                decimal128(c.vv).c_str());
+      }
+      if (fclose(ff) != 0) return 1;
     }
     if (!rearrangePath.empty() && sim.dumpDue(cfg.dump_interval)) {
       if (!referenceMarked) {  // the run's first dump time

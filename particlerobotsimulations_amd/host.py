@@ -60,6 +60,7 @@ _ANALYSES = {
     "pbHostSetTimeCorrelation": [_F, C.c_uint, _F], "pbHostTimeCorrelationRecord": [],
     "pbHostTimeCorrelationInfo": [_P, _P, _P, _P],
     "pbHostTimeCorrelationRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
+    "pbHostFieldMap": [_P, _P, _P],
 }
 
 
@@ -433,6 +434,19 @@ class HostSim:
             raise RuntimeError("time_correlation: the time correlation needs the fused engine, the correlation on and "
                                "fewer than 2^31 samples per lag")
         return [[_capi.time_correlation_row(r) for r in rows[:int(count.value)]]]
+
+    def field_map(self, nx, ny, center, half, member=None):
+        """A field map of the state as it is now, on the device (pbSimFieldMap; fused engine only): (cells, totals) as
+        Sim.field_map gives them, cells shaped (1, ny, nx), or (ny, nx) with a single totals dict for member=0."""
+        view = _capi.field_view(nx, ny, center, half)
+        fits = 1 <= int(nx) <= 1024 and 1 <= int(ny) <= 1024
+        cells = np.zeros((1, int(ny), int(nx)) if fits else (1, 1, 1), _capi.FIELD_CELL_DTYPE)
+        tot = _capi.pbFieldTotals()
+        if lib().pbHostFieldMap(self._h, C.byref(view), _ptr(cells), C.byref(tot)) != 0:
+            raise RuntimeError("field_map: the field map needs the fused engine, 1 ... 1024 cells per axis and finite "
+                               "half extents > 0")
+        totals = [_capi.field_totals(tot)]
+        return (cells, totals) if member is None else (cells[int(member)], totals[int(member)])
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
