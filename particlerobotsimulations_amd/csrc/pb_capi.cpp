@@ -205,6 +205,7 @@ int pbHostStepsUntilDump(void *hv, int maxSteps) {
 }
 
 float pbHostTime(void *hv) { return ((HostSim *)hv)->bot->getTime(); }
+void pbHostSetTime(void *hv, float t) { ((HostSim *)hv)->bot->setTime(t); }
 int pbHostFinished(void *hv) { return ((HostSim *)hv)->bot->finished() ? 1 : 0; }
 
 // display()'s `dumpParticlebot(0, nCells, fp, dump_interval, testing, light)` (main.cpp:360)

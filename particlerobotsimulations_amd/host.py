@@ -85,6 +85,8 @@ def lib():
     L.pbHostStepsUntilDump.restype = C.c_int
     L.pbHostTime.argtypes = [C.c_void_p]
     L.pbHostTime.restype = C.c_float
+    L.pbHostSetTime.argtypes = [C.c_void_p, C.c_float]
+    L.pbHostSetTime.restype = None
     L.pbHostFinished.argtypes = [C.c_void_p]
     L.pbHostFinished.restype = C.c_int
     L.pbHostDump.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
@@ -180,6 +182,11 @@ class HostSim:
     @property
     def time(self):
         return lib().pbHostTime(self._h)
+
+    @time.setter
+    def time(self, t):
+        """Particlebot::setTime: moves the clock, of the class and of its engine; nothing else changes."""
+        lib().pbHostSetTime(self._h, float(t))
 
     @property
     def finished(self):

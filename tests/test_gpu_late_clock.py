@@ -1,0 +1,412 @@
+"""GPU: the engine late in a run, where the fp32 clock `time = time + dt` steps unevenly, against the oracle started at
+the same time, bit for bit.  Behind 4096 s a step adds 0.009765625, 0.01171875, 0.0078125 or 0.015625 instead of 0.01,
+so the schedule's gates fire on consecutive steps; from 262144 s on the clock stands still and every gate fires on every
+step.  tests/test_late_clock_ref.py holds the start times, the window and the intervals, pins series_ref's replay of the
+clock to the oracle and asserts that the inputs used here show those regimes.  Nothing here has a tolerance."""
+import os
+
+import numpy as np
+import pytest
+
+import display_ref as R
+import series_ref as SR
+import test_late_clock_ref as LC
+import timecorr_ref as TR
+from helpers import assert_bit_equal, simparams_from_orc
+from test_gpu_series import reference_rows
+from test_late_clock_ref import DT, LATE, MARKS, NEGATIVE, PUI, REC, SORT, STANDING, STEPS, bits, clock, firing
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EX = lambda name: os.path.join(ROOT, "examples", name)
+f32 = np.float32
+STATE_KEYS = ("pos", "vel", "rad", "phase", "absForce_a", "absForce_r")
+# (lanes per bot, resident mode, force variant) of the forms; None: as created
+FORMS = {"auto": (None, None, None), "lanes1": (1, 1, None), "lanes8": (8, 1, None), "lanes64": (64, 1, None),
+         "resident": (None, 2, None), "variant0": (None, None, 0)}
+PAYLOAD = dict(nDead=-1, attractionFactor=0.5, massFactor=2.0, radFactor=2.0, n_cir_obstacles=2, x_cir_obs=[2.0, 6.5],
+               y_cir_obs=[0.5, -1.0], r_cir_obs=[0.4, 0.3], nobstacles=1, x1obs=[3.0], x2obs=[3.2], y1obs=[-2.0],
+               y2obs=[-0.6])
+
+
+@pytest.fixture(scope="module")
+def pb():
+    import particlerobotsimulations_amd as pb
+    pb.legacy.cudaInit(0, None)
+    return pb
+
+
+@pytest.fixture(scope="module")
+def host():
+    from particlerobotsimulations_amd import host
+    host.lib()
+    return host
+
+
+def shape(sim, form):
+    lanes, resident, variant = FORMS[form]
+    if lanes is not None:
+        sim.set_lanes_per_bot(lanes)
+    if resident is not None:
+        sim.set_resident(resident)
+    if variant is not None:
+        sim.set_force_variant(variant)
+    return sim
+
+
+def state_from(osim):
+    return dict(pos=osim.get("pos"), vel=osim.get("vel"), rad=osim.get("rad"), phase=osim.get("phase"),
+                dead=osim.get("dead"))
+
+
+def late_pair(pb, orc, t0, form="auto", **over):
+    """The oracle and the engine with the oracle's placement, both moved to t0."""
+    P = LC.late_params(orc, **over)
+    osim = LC.late_oracle(orc, P, t0)
+    sp, keep = simparams_from_orc(P)
+    gsim = shape(pb.Sim(sp, keepalive=keep), form)
+    gsim.set_state(**state_from(osim))
+    gsim.time = t0
+    assert bits(gsim.time) == bits(osim.time) == bits(f32(t0))
+    return osim, gsim
+
+
+def compare(osim, state, what):
+    for k in STATE_KEYS:
+        assert_bit_equal(state[k], osim.get(k), f"{what}: {k}")
+
+
+def counts(t0, upto, max_time=1e9):
+    """(re-sorts, phase updates) of the first `upto` steps from t0: the gates' firings, and the engine's first step,
+    which sorts whatever the clock says because it has no cell lists yet."""
+    sorts, updates = firing(t0, SORT, upto, max_time), firing(t0, PUI, upto, max_time)
+    return len(sorts) + (0 if upto == 0 or 0 in sorts else 1), len(updates)
+
+
+def run_to_marks(osim, gsim, t0, what, form):
+    want_t, step = clock(t0, STEPS), 0
+    assert gsim.phase_draws == 0 and gsim.stats()["steps"] == 0
+    for mark in MARKS:
+        assert osim.run(mark - step, dt=DT, sort_interval=SORT)
+        assert gsim.step(mark - step, dt=DT, sort_interval=SORT) == mark - step
+        step = mark
+        compare(osim, gsim.get_state(), f"{what} step {mark}")
+        assert bits(gsim.time) == bits(osim.time) == bits(want_t[mark]), (what, mark, gsim.time, osim.time, want_t[mark])
+        stats, (resorts, updates) = gsim.stats(), counts(t0, mark)
+        print(what, mark, gsim.time, stats)
+        assert (stats["steps"], stats["resorts"], stats["phase_updates"]) == (mark, resorts, updates), (what, mark, stats)
+        # phaseUpdate draws once per update while any member has phase noise (phase_std 0.6 here), as the oracle does
+        assert gsim.phase_draws == updates == osim._L.orc_sim_phase_draws(osim._h)
+    if form == "resident":
+        assert stats["resident_launches"] > 0
+    if form == "auto":
+        assert stats["fused_launches"] > 0
+
+
+# ---- parity from a late start ----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("t0", LATE)
+def test_parity_from_a_late_start(pb, orc, t0, form):
+    osim, gsim = late_pair(pb, orc, t0, form)
+    run_to_marks(osim, gsim, t0, f"t0 {t0} {form}", form)
+
+
+@pytest.mark.parametrize("form", ["auto", "resident"])
+def test_parity_with_a_payload_and_obstacles_from_16383_9(pb, orc, form):
+    osim, gsim = late_pair(pb, orc, 16383.9, form, seed=3, **PAYLOAD)
+    assert osim.get("dead").sum() == 1
+    run_to_marks(osim, gsim, 16383.9, f"payload {form}", form)
+
+
+# ---- records late ----------------------------------------------------------------------------------------------------
+
+TRAIL = dict(centroid_int=0.2, centroid_steps=8)
+LAGS, OVERLAP = 8, 0.05
+
+
+def expected_trail(recs, pos_of, slots):
+    """The ring, its slot times and the record count after the records `recs` of LC.trail_slots, pos_of(k) being the
+    positions in front of step k."""
+    xy = np.tile(np.array([-5000.0, 0.0], f32), (slots, 1))
+    times, n = np.full(slots, np.nan, f32), 0
+    for k, t, slot in recs:
+        if slot < 0:
+            continue
+        xy[slot], times[slot], n = R.centroid(pos_of(k)), t, n + 1
+    return xy, times, n
+
+
+@pytest.mark.parametrize("resident", [1, 2], ids=["per_step", "resident"])
+@pytest.mark.parametrize("t0", [16383.9, 65535.9])
+def test_records_from_a_late_start(pb, orc, t0, resident):
+    gates = SR.gate_steps(t0, DT, REC, STEPS, 1e9)
+    rec = [k for k, _ in gates]
+    trail = LC.trail_slots(t0, TRAIL["centroid_int"], TRAIL["centroid_steps"], STEPS)
+    assert LC.consecutive(rec) >= 16 and len(rec) > LAGS
+    stops = sorted(set(gates) | {(k, float(t)) for k, t, _ in trail})
+    P = LC.late_params(orc, **TRAIL)
+    start = state_from(LC.late_oracle(orc, P, t0))
+
+    def make():
+        sp, keep = simparams_from_orc(P)
+        sim = pb.Sim(sp, keepalive=keep)
+        sim.set_resident(resident)
+        sim.set_state(**start)
+        sim.time = t0
+        return sim
+
+    a, b = make(), make()
+    a.set_series(REC, 512)
+    a.set_time_correlation(REC, LAGS, OVERLAP)
+    a.set_centroid_trail(True)
+    assert a.step(STEPS, dt=DT, sort_interval=SORT) == STEPS  # one call
+    # the twin, nothing switched on, stopped in front of every step at which a records something
+    seen = {}
+
+    def state_of():
+        seen[len(seen)] = st = b.get_state()
+        return st
+
+    rows = reference_rows(b, stops, STEPS, state_of=state_of, sort_interval=SORT)
+    at = {k: (row[0], seen[i]) for i, ((k, _), row) in enumerate(zip(stops, rows))}
+    got = a.series_of(0)
+    assert [(g["step"], g["time"]) for g in got] == gates  # both steps of every consecutive pair among them
+    assert got == [at[k][0] for k in rec]
+    assert a.series_info()["records"] == a.time_correlation_info()["records"] == len(rec)
+    want = TR.table([(at[k][1]["pos"], at[k][1]["vel"]) for k in rec], rec, LAGS, OVERLAP)
+    assert a.time_correlation()[0] == want
+    xy, times, records = a.centroid_trail()
+    want_xy, want_t, want_n = expected_trail(trail, lambda k: at[k][1]["pos"], TRAIL["centroid_steps"])
+    assert records == want_n == len(trail)
+    assert np.array_equal(times.view(np.uint32), want_t.view(np.uint32)), (times, want_t)
+    assert_bit_equal(xy, want_xy, "trail ring")
+    sa, sb = a.get_state(), b.get_state()
+    for k in sa:
+        assert_bit_equal(sa[k], sb[k], k)
+    assert bits(a.time) == bits(b.time) == bits(clock(t0, STEPS)[-1])
+    resorts, updates = counts(t0, STEPS)
+    for s in (a, b):
+        assert (s.stats()["steps"], s.stats()["resorts"], s.stats()["phase_updates"]) == (STEPS, resorts, updates)
+    if resident == 2:
+        assert a.stats()["resident_launches"] > 0
+
+
+# ---- a batch, the stop, the standing clock, a negative clock ---------------------------------------------------------
+
+@pytest.mark.parametrize("resident", [1, 2], ids=["per_step", "resident"])
+def test_batch_of_three_members_from_16383_9(pb, orc, resident):
+    t0 = 16383.9
+    lights = [(-2.0, 4.0), (6.0, -3.0), (-7.5, -1.5)]
+    Ps = [LC.late_params(orc, seed=70 + k, light_x=lx, light_y=ly) for k, (lx, ly) in enumerate(lights)]
+    osims = [LC.late_oracle(orc, P, t0) for P in Ps]
+    pairs = [simparams_from_orc(P) for P in Ps]
+    ens = pb.Ensemble([p for p, _ in pairs], keepalive=[k for _, k in pairs])
+    ens.set_resident(resident)
+    for k, osim in enumerate(osims):
+        ens.set_state_of(k, **state_from(osim))
+    ens.time = t0
+    assert not np.array_equal(osims[0].get("pos"), osims[1].get("pos"))
+    want_t, step = clock(t0, STEPS), 0
+    for mark in MARKS:
+        assert ens.step(mark - step, dt=DT, sort_interval=SORT) == mark - step
+        for k, osim in enumerate(osims):
+            assert osim.run(mark - step, dt=DT, sort_interval=SORT)
+            compare(osim, ens.get_state_of(k), f"member {k} step {mark}")
+            assert bits(osim.time) == bits(want_t[mark])
+        step = mark
+        assert bits(ens.time) == bits(want_t[mark])
+        stats, (resorts, updates) = ens.stats(), counts(t0, mark)
+        assert (stats["steps"], stats["resorts"], stats["phase_updates"]) == (mark, resorts, updates)
+        assert ens.phase_draws == updates
+    if resident == 2:
+        assert stats["resident_launches"] > 0
+
+
+@pytest.mark.parametrize("form", ["auto", "resident"])
+def test_max_time_inside_the_window_stops_both_at_the_same_step(pb, orc, form):
+    t0, max_time = LC.STOP_T0, LC.STOP_MAX_TIME
+    k = LC.steps_run(t0, STEPS, max_time)
+    assert 0 < k < STEPS
+    osim, gsim = late_pair(pb, orc, t0, form, max_time=max_time)
+    assert gsim.step(STEPS, dt=DT, sort_interval=SORT) == k
+    done = 0
+    while osim.update(DT, SORT) == 0:
+        done += 1
+    assert done == k
+    compare(osim, gsim.get_state(), f"stopped by max_time, {form}")
+    assert bits(gsim.time) == bits(osim.time) == bits(clock(t0, STEPS, max_time)[-1])
+    stats, (resorts, updates) = gsim.stats(), counts(t0, STEPS, max_time)
+    assert (stats["steps"], stats["resorts"], stats["phase_updates"]) == (k, resorts, updates), stats
+    assert gsim.phase_draws == updates  # none for the step that did not run, though its gate fires
+    assert gsim.step(5, dt=DT, sort_interval=SORT) == 0 and gsim.stats() == stats
+    if form == "resident":
+        assert stats["resident_launches"] > 0
+    else:
+        assert stats["fused_launches"] > 0
+
+
+@pytest.mark.parametrize("form", ["auto", "resident", "lanes8"])
+def test_standing_clock(pb, orc, form):
+    """From 262144 s on time + dt == time: every gate fires on every step and no max_time above ends the run, so only
+    a call of a given number of steps may be made here (the run loops would never return, as the reference's)."""
+    n, max_time = LC.STANDING_STEPS, LC.STANDING_MAX_TIME
+    osim, gsim = late_pair(pb, orc, STANDING, form, max_time=max_time)
+    assert gsim.step(n, dt=DT, sort_interval=SORT) == n
+    for _ in range(n):
+        assert osim.update(DT, SORT) == 0
+    assert gsim.time == osim.time == 262144.0
+    compare(osim, gsim.get_state(), f"standing clock, {form}")
+    stats, (resorts, updates) = gsim.stats(), counts(STANDING, n, max_time)
+    assert updates >= n - 12 and resorts >= n - 12
+    assert (stats["steps"], stats["resorts"], stats["phase_updates"]) == (n, resorts, updates), stats
+    assert gsim.phase_draws == updates == osim._L.orc_sim_phase_draws(osim._h)
+    # and again from the standing clock itself: every step sorts and updates
+    assert gsim.step(5, dt=DT, sort_interval=SORT) == 5 and gsim.time == 262144.0
+    for _ in range(5):
+        assert osim.update(DT, SORT) == 0
+    compare(osim, gsim.get_state(), f"standing clock, {form}, five more")
+    assert gsim.stats()["resorts"] == resorts + 5 and gsim.stats()["phase_updates"] == updates + 5
+
+
+@pytest.mark.parametrize("form", ["auto", "resident"])
+def test_negative_clock(pb, orc, form):
+    n, slots = 20, LC.NEG_TRAIL["centroid_steps"]
+    t = clock(NEGATIVE, n)
+    first = next(k for k in range(n) if t[k] >= 0)
+    osim, gsim = late_pair(pb, orc, NEGATIVE, form, **LC.NEG_TRAIL)
+    gsim.set_centroid_trail(True)
+    rad0, before = osim.get("rad"), {}
+    for k in range(n):  # the oracle one step at a time: its positions in front of every step
+        before[k] = osim.get("pos")
+        assert osim.update(DT, SORT) == 0
+        assert np.array_equal(osim.get("rad"), rad0) == (k < first)  # the oracle's radii move from step `first` on
+    # the engine in three calls: up to the first step at t >= 0, that step, the rest
+    assert gsim.step(first, dt=DT, sort_interval=SORT) == first
+    assert_bit_equal(gsim.get_state()["rad"], rad0, "radii while the clock is negative")
+    assert gsim.stats()["phase_updates"] == 0 and bits(gsim.time) == bits(t[first])
+    assert gsim.step(1, dt=DT, sort_interval=SORT) == 1
+    assert not np.array_equal(gsim.get_state()["rad"], rad0) and gsim.stats()["phase_updates"] == 1
+    assert gsim.step(n - first - 1, dt=DT, sort_interval=SORT) == n - first - 1
+    compare(osim, gsim.get_state(), f"negative clock, {form}")
+    assert bits(gsim.time) == bits(osim.time) == bits(t[n])
+    resorts, updates = counts(NEGATIVE, n)
+    assert (gsim.stats()["resorts"], gsim.stats()["phase_updates"]) == (resorts, updates)
+    recs = LC.trail_slots(NEGATIVE, LC.NEG_TRAIL["centroid_int"], slots, n)
+    want_xy, want_t, want_n = expected_trail(recs, lambda k: before[k], slots)
+    xy, times, records = gsim.centroid_trail()
+    assert records == want_n == len(recs) - 2  # the two records with a slot below 0 are dropped
+    assert np.array_equal(times.view(np.uint32), want_t.view(np.uint32)), (times, want_t)
+    assert_bit_equal(xy, want_xy, "trail ring")
+    assert np.isnan(times[7]) and xy[7, 0] == -5000.0  # slots -2 and -1 did not wrap to the ring's end
+
+
+def test_negative_clock_in_one_call(pb, orc):
+    osim, gsim = late_pair(pb, orc, NEGATIVE, "auto", **LC.NEG_TRAIL)
+    assert osim.run(20, dt=DT, sort_interval=SORT) and gsim.step(20, dt=DT, sort_interval=SORT) == 20
+    compare(osim, gsim.get_state(), "negative clock, one fused call")
+    assert bits(gsim.time) == bits(osim.time) and gsim.stats()["fused_launches"] > 0
+
+
+# ---- the class: checkpoint, dump rows and the dead-bot window late ---------------------------------------------------
+
+OVER = dict(max_time="1e9", phase_update_interval="2", sort_interval="0.5", dump_interval="0.5", testing="1")
+
+
+def host_state(h):
+    return {k: h.get(k) for k in ("pos", "vel", "rad", "phase", "dead")}
+
+
+def test_checkpoint_and_resume_from_16383_9(host, tmp_path):
+    t0, ck = 16383.9, str(tmp_path / "late.pbck")
+    t = clock(t0, 300)
+    # a dump row is due at the end of the first piece of each run below, and after both steps of the pair 215 / 216
+    assert all(LC.dump_due(t[k], 0.5) for k in (164, 215, 216)) and not LC.dump_due(t[300], 0.5)
+    a = host.HostSim(EX("example.cfg"), **OVER)
+    a.time = t0
+    assert bits(a.time) == bits(t[0])
+    assert a.advance(150) == 150 and bits(a.time) == bits(t[150])
+    a.save_checkpoint(ck)
+    b = host.HostSim(EX("example.cfg"), reset=False, **OVER)
+    b.load_checkpoint(ck)
+    assert bits(b.time) == bits(t[150])
+    files = []
+    for name, h in (("a", a), ("b", b)):
+        path = str(tmp_path / f"{name}.csv")
+        for piece in (14, 51, 1, 84):  # to the steps 164, 215, 216 and 300
+            assert h.advance(piece) == piece
+            h.dump(path)
+        files.append(open(path, "rb").read())
+    assert bits(a.time) == bits(b.time) == bits(t[300])
+    assert files[0] == files[1] and files[0].count(b"\n") == 3
+    sa, sb = host_state(a), host_state(b)
+    for k in sa:
+        assert_bit_equal(sa[k], sb[k], f"resumed {k}")
+
+
+def test_dump_rows_from_16383_9_equal_the_oracles(host, orc, tmp_path):
+    """The class's lookahead to the next dump row against the oracle, which tries to dump in front of every step."""
+    t0, n = 16383.9, 300
+    pa, pb_ = str(tmp_path / "oracle.csv"), str(tmp_path / "product.csv")
+    h = host.HostSim(EX("example.cfg"), **OVER)
+    h.time = t0
+    P = orc.load_cfg(EX("example.cfg"), max_time=1e9, phase_update_interval=2.0, sort_interval=0.5, dump_interval=0.5,
+                     testing=1)
+    osim = orc.Sim(P)
+    osim.time = t0
+    osim.force_sort_once()
+    open(pa, "w").close(), open(pb_, "w").close()
+    rows = 0
+    for _ in range(n):
+        rows += osim.dump(pa)
+        assert osim.update() == 0
+    rows += osim.dump(pa)
+    done = 0
+    while True:
+        h.dump(pb_)
+        if done == n:
+            break
+        done += h.advance(h.steps_until_dump(n - done))
+    t = clock(t0, n)
+    assert rows == len([k for k in range(n + 1) if LC.dump_due(t[k], 0.5)]) == 7
+    da, db = open(pa, "rb").read(), open(pb_, "rb").read()
+    assert da == db and da.count(b"\n") == rows
+    assert bits(h.time) == bits(osim.time) == bits(t[n])
+    for k in ("pos", "vel", "rad", "phase"):
+        assert_bit_equal(h.get(k), osim.get(k), k)
+
+
+def test_bots_die_late_on_the_step_the_replay_names(host, orc, tmp_path):
+    t0, ck = 16383.9, str(tmp_path / "dead.pbck")
+    (die,) = LC.dead_steps(t0, LC.DEAD_AT, STEPS)
+    assert 40 < die < 100
+    over = dict(OVER, nDead="20", time_to_dead=str(LC.DEAD_AT))
+    # the product first: creating it calls srand(), which would rewind the libc stream the oracle draws from
+    a = host.HostSim(EX("example.cfg"), **over)
+    a.time = t0
+    P = orc.load_cfg(EX("example.cfg"), max_time=1e9, phase_update_interval=2.0, sort_interval=0.5, nDead=20,
+                     time_to_dead=LC.DEAD_AT)
+    osim = orc.Sim(P)
+    osim.time = t0
+    osim.force_sort_once()
+    assert a.advance(40) == 40
+    a.save_checkpoint(ck)
+    assert a.advance(die - 40) == die - 40 and a.get("dead").sum() == 0  # one call across..., stopped in front of `die`
+    assert a.advance(1) == 1 and a.get("dead").sum() == 20
+    for k in range(die + 1):
+        assert osim.update() == 0
+        assert osim.get("dead").sum() == (20 if k == die else 0)
+    assert_bit_equal(a.get("dead"), osim.get("dead"), "dead set")
+    assert a.advance(100) == 100 and osim.run(100)  # one call; the window does not open again
+    assert bits(a.time) == bits(osim.time) == bits(clock(t0, die + 101)[-1])
+    assert_bit_equal(a.get("dead"), osim.get("dead"), "dead set, later")
+    for k in ("pos", "vel", "rad", "phase"):
+        assert_bit_equal(a.get(k), osim.get(k), k)
+    # resumed in front of the window: one call across it draws the same set on the same step
+    b = host.HostSim(EX("example.cfg"), reset=False, **over)
+    b.load_checkpoint(ck)
+    assert b.advance(die + 101 - 40) == die + 101 - 40
+    sa, sb = host_state(a), host_state(b)
+    for k in sa:
+        assert_bit_equal(sa[k], sb[k], f"resumed {k}")
