@@ -370,14 +370,11 @@ int pbClusterAnalyse(pbSim *S, float gap) {
 
 // The argument checks of the entry points (pb_cluster.hpp).
 int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const unsigned *member) {
-  const char *what = nullptr;
-  if (gap && (!(*gap >= 0.0f) || !(*gap < __builtin_inff()))) what = ": linkGap must be finite and >= 0";
-  else if (member && *member >= S->nsims) what = ": member out of range";
-  else if (S->nsims > 65535u) what = ": the batch must hold at most 65535 members";  // the member is a launch's grid y
-  else if (S->total >= (1u << 28)) what = ": the batch must hold fewer than 2^28 bots";
-  if (!what) return PB_OK;
-  pbLastError() = std::string(fn) + what;
-  return PB_ERR_ARG;
+  if (gap && (!(*gap >= 0.0f) || !(*gap < __builtin_inff()))) return pbFail(fn, ": linkGap must be finite and >= 0");
+  if (member && *member >= S->nsims) return pbFail(fn, ": member out of range");
+  if (S->nsims > 65535u)  // the member is a launch's grid y
+    return pbFail(fn, ": the batch must hold at most 65535 members");
+  return pbCheckBatch(fn, S);
 }
 
 void pbClusterFree(pbSim *S) {
@@ -386,10 +383,7 @@ void pbClusterFree(pbSim *S) {
 }
 
 int pbSimClusterStats(pbSim *S, float linkGap, pbClusterStats *stats) {
-  if (!S || !stats) {
-    pbLastError() = "pbSimClusterStats: null handle or stats";
-    return PB_ERR_ARG;
-  }
+  if (!S || !stats) return pbFail("pbSimClusterStats", ": null handle or stats");
   int rc = pbClusterCheckArgs("pbSimClusterStats", S, &linkGap, nullptr);
   if (rc != PB_OK) return rc;
   rc = pbClusterAnalyse(S, linkGap);
@@ -399,14 +393,8 @@ int pbSimClusterStats(pbSim *S, float linkGap, pbClusterStats *stats) {
 }
 
 int pbSimClusterLabelsOf(pbSim *S, unsigned member, float linkGap, unsigned *labels, unsigned *degree) {
-  if (!S) {
-    pbLastError() = "pbSimClusterLabelsOf: null handle";
-    return PB_ERR_ARG;
-  }
-  if (!labels && !degree) {
-    pbLastError() = "pbSimClusterLabelsOf: labels and degree are both null";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail("pbSimClusterLabelsOf", ": null handle");
+  if (!labels && !degree) return pbFail("pbSimClusterLabelsOf", ": labels and degree are both null");
   int rc = pbClusterCheckArgs("pbSimClusterLabelsOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   rc = pbClusterAnalyse(S, linkGap);

@@ -1,10 +1,12 @@
 // pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip, pb_dynamics.hip and
-// pb_correlate.hip: the scratch object with its five clocks, the fresh grid, the wave helpers, the workgroup scan, the walk over a bot's nine cells
-// (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour sweep of the analysis layer is built on, the front
-// end that files the bots (rmax, hash, sort, gather, cell starts) and the argument checks of the entry points.
+// pb_correlate.hip: the scratch object with its five clocks, the fresh grid, the workgroup scan (the wave helpers are
+// pb_fixed.hpp's), the walk over a bot's nine cells (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour
+// sweep of the analysis layer is built on, the front end that files the bots (rmax, hash, sort, gather, cell starts) and
+// the argument checks of the entry points.
 #pragma once
 
 #include "pb_engine.hpp"
+#include "pb_fixed.hpp"
 
 // One analysis' clock: it starts at the front end's ev0 and ends at an event of its own (pbClockStop).
 struct PbAnalysisClock {
@@ -97,44 +99,6 @@ PB_DEV uint32_t cellX(const ClusterGrid &G, float x) {
 }
 PB_DEV uint32_t cellY(const ClusterGrid &G, float y) {
   return (uint32_t)cellCoord((double)y * G.invCell) & ((1u << G.gyLog2) - 1u);
-}
-
-// ---- wave helpers (wave64) ---------------------------------------------------------------------------------------------
-PB_DEV uint32_t waveMaxU32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const uint32_t o = (uint32_t)__shfl_xor((int)v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-PB_DEV uint32_t waveSumU32(uint32_t v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m);
-  return v;
-}
-PB_DEV unsigned long long shflXor64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-PB_DEV unsigned long long shflUp64(unsigned long long v, int d) {
-  const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d);
-  const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d);
-  return ((unsigned long long)hi << 32) | lo;
-}
-PB_DEV unsigned long long waveMaxU64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const unsigned long long o = shflXor64(v, m);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-PB_DEV unsigned long long waveSumU64(unsigned long long v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += shflXor64(v, m);
-  return v;
 }
 
 // exclusive prefix of v over the workgroup and the workgroup's total: an inclusive scan inside each wave with
@@ -258,10 +222,7 @@ inline int pbClockStop(pbSim *S, PbAnalysisClock &K) {
 // the body of pbSimGet{Cluster,Contact,Structure,Rearrangement}Times; K points into S's scratch object
 inline int pbClockGet(const char *fn, const pbSim *S, PbAnalysisClock PbClusterScratch::*K, unsigned long long *runs,
                       float *last_device_ms) {
-  if (!S) {
-    pbLastError() = std::string(fn) + ": null handle";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail(fn, ": null handle");
   if (runs) *runs = S->cluster ? (S->cluster->*K).runs : 0ull;
   if (last_device_ms) *last_device_ms = S->cluster ? (S->cluster->*K).lastMs : 0.0f;
   return PB_OK;

@@ -189,14 +189,9 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
   PB_TRY(hipMemcpyAsync(&count, total, sizeof count, hipMemcpyDeviceToHost, S->stream));
   PB_TRY(hipStreamSynchronize(S->stream));
   *entries = count;
-  if (count >= (1ull << 31)) {
-    pbLastError() = std::string(fn) + ": the member has 2^31 directed entries or more (offsets are 32-bit)";
-    return PB_ERR_ARG;
-  }
-  if (wantLinks && cap < count) {
-    pbLastError() = std::string(fn) + ": links holds fewer entries than the member has (call with links NULL to size)";
-    return PB_ERR_ARG;
-  }
+  if (count >= (1ull << 31)) return pbFail(fn, ": the member has 2^31 directed entries or more (offsets are 32-bit)");
+  if (wantLinks && cap < count)
+    return pbFail(fn, ": links holds fewer entries than the member has (call with links NULL to size)");
   unsigned long long raised = 0ull;
   if (wantLinks || wantVirial) {
     PB_TRY(C->cLinks.ensure(count ? count : 1ull));
@@ -227,10 +222,7 @@ int exportContacts(const char *fn, pbSim *S, uint32_t member, float gap, bool wa
 
 int pbSimContactsOf(pbSim *S, unsigned member, float linkGap, unsigned *offsets, pbContactLink *links,
                     unsigned long long cap, unsigned long long *entries) {
-  if (!S || !entries) {
-    pbLastError() = "pbSimContactsOf: null handle or entries";
-    return PB_ERR_ARG;
-  }
+  if (!S || !entries) return pbFail("pbSimContactsOf", ": null handle or entries");
   int rc = pbClusterCheckArgs("pbSimContactsOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   rc = exportContacts("pbSimContactsOf", S, member, linkGap, links != nullptr, cap, false, entries);
@@ -245,10 +237,7 @@ int pbSimContactsOf(pbSim *S, unsigned member, float linkGap, unsigned *offsets,
 }
 
 int pbSimContactVirialOf(pbSim *S, unsigned member, float linkGap, double *virial) {
-  if (!S || !virial) {
-    pbLastError() = "pbSimContactVirialOf: null handle or virial";
-    return PB_ERR_ARG;
-  }
+  if (!S || !virial) return pbFail("pbSimContactVirialOf", ": null handle or virial");
   int rc = pbClusterCheckArgs("pbSimContactVirialOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   unsigned long long entries = 0ull;

@@ -21,7 +21,7 @@
 // EXACTNESS.  Everything that is added is an integer modulo 2^64, so nothing depends on the order of the adds; what is
 // left to show is that no word wraps.  pairs: a member holds fewer than 2^28 bots, hence fewer than 2^56 ordered pairs:
 // the LDS word and the global word hold the count whatever the state is.  The other words, for a bin that holds P < 2^31
-// ordered pairs of its member (any workgroup's share is at most that): |a| <= 2^31 - 128 per component, so |d| < 2^63,
+// ordered pairs of its member (any workgroup's share is at most that): by pb_fixed.hpp's bound |d| < 2^63,
 // 0 <= lo32(d) < 2^32 and |d >> 32| <= 2^31.  The LDS word of the low halves stays below P 2^32 < 2^63; the signed words
 // (high halves, ax, ay) stay within P 2^31 <= 2^62 in magnitude, which two's complement holds.  A flush adds a low part
 // below 2^32 and a rest within 2^31 in magnitude; a member has at most 2^20 workgroups, so the global words stay within
@@ -67,29 +67,21 @@ __global__ __launch_bounds__(CT) void k_corr_gather(const float4 *__restrict__ c
       fx = me.z;
     }
   }
-  // |f| < 2048 implies that f is finite, and for a displacement that both of its coordinates are
-  const bool measured = fabsf(fx) < 2048.0f && fabsf(fy) < 2048.0f;
+  // an f in range is finite, and for a displacement both of its coordinates are
+  const bool measured = pbFixedInRange(fx) && pbFixedInRange(fy);
   long long qx = 0ll, qy = 0ll;
   unsigned long long s = 0ull;
   if (measured) {
-    qx = (long long)(int)__builtin_rintf(fx * 1048576.0f);  // |.| <= 2^31 - 128; v_rndne_f32 rounds to nearest even
-    qy = (long long)(int)__builtin_rintf(fy * 1048576.0f);
+    qx = pbFixedQuantise(fx), qy = pbFixedQuantise(fy);
     s = (unsigned long long)(qx * qx) + (unsigned long long)(qy * qy);
   }
   if (live) a[t] = make_int2(measured ? (int)qx : INT_MIN, (int)qy);
   // the member's totals: sums over the wave, the four waves through LDS, one set of atomics per workgroup
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  const unsigned long long vMeasured = __popcll(__ballot(measured));
-  const unsigned long long vAx = waveSumU64((unsigned long long)qx), vAy = waveSumU64((unsigned long long)qy);
-  const unsigned long long vLo = waveSumU64(s & 0xFFFFFFFFull), vHi = waveSumU64(s >> 32);
-  if (lane == 0u) {
-    unsigned long long *r = sRed[w];
-    r[S_MEASURED] = vMeasured, r[S_AX] = vAx, r[S_AY] = vAy, r[S_A2LO] = vLo, r[S_A2HI] = vHi;
-  }
-  __syncthreads();
-  if (threadIdx.x < (uint32_t)S_WORDS) {
-    unsigned long long v = 0ull;
-    for (int k = 0; k < CT / 64; k++) v += sRed[k][threadIdx.x];
+  unsigned long long r[S_WORDS], v;
+  r[S_MEASURED] = __popcll(__ballot(measured));
+  r[S_AX] = waveSumU64((unsigned long long)qx), r[S_AY] = waveSumU64((unsigned long long)qy);
+  r[S_A2LO] = waveSumU64(pbFixedLow(s)), r[S_A2HI] = waveSumU64(pbFixedRest(s));
+  if (blockFold(sRed, r, [](uint32_t) { return PB_FOLD_SUM; }, v)) {
     // (two's complement: a signed sum modulo 2^64; one that is zero adds nothing either)
     if (v) atomicAdd(totals + (size_t)blockIdx.y * S_WORDS + threadIdx.x, v);
   }
@@ -151,45 +143,20 @@ __global__ __launch_bounds__(CT) void k_corr_sweep(const float4 *__restrict__ cp
   }
 }
 
-// value = hi * 2^32 + lo with 0 <= lo < 2^32 and hi the floor quotient: the same form however the device split its adds
-pbMoment128 normalised(__int128 v) {
-  pbMoment128 m;
-  m.lo = (unsigned long long)(v & (__int128)0xFFFFFFFFull);
-  m.hi = (long long)(v >> 32);  // (arithmetic: the floor)
-  return m;
-}
-
-// low part (a sum of 32-bit values) and rest (a signed sum) of one of a bin's signed words
-__int128 composed(unsigned long long low, unsigned long long rest) {
-  return (__int128)low + (__int128)(long long)rest * ((__int128)1 << 32);
-}
-
 }  // namespace
 
 int pbSimPairCorrelation(pbSim *S, int kind, float rMax, unsigned bins, pbCorrelationBin *rows,
                          pbCorrelationTotals *totals) {
-  if (!S || !rows) {
-    pbLastError() = "pbSimPairCorrelation: null handle or rows";
-    return PB_ERR_ARG;
-  }
-  if (kind != PB_CORR_VELOCITY && kind != PB_CORR_DISPLACEMENT && kind != PB_CORR_RADIUS) {
-    pbLastError() = "pbSimPairCorrelation: unknown kind";
-    return PB_ERR_ARG;
-  }
-  if (!(rMax > 0.0f) || !(rMax < __builtin_inff())) {
-    pbLastError() = "pbSimPairCorrelation: rMax must be finite and > 0";
-    return PB_ERR_ARG;
-  }
-  if (bins < 1u || bins > PB_CORR_MAX_BINS) {
-    pbLastError() = "pbSimPairCorrelation: bins must be 1 ... 1024";
-    return PB_ERR_ARG;
-  }
+  if (!S || !rows) return pbFail("pbSimPairCorrelation", ": null handle or rows");
+  if (kind != PB_CORR_VELOCITY && kind != PB_CORR_DISPLACEMENT && kind != PB_CORR_RADIUS)
+    return pbFail("pbSimPairCorrelation", ": unknown kind");
+  if (!(rMax > 0.0f) || !(rMax < __builtin_inff()))
+    return pbFail("pbSimPairCorrelation", ": rMax must be finite and > 0");
+  if (bins < 1u || bins > PB_CORR_MAX_BINS) return pbFail("pbSimPairCorrelation", ": bins must be 1 ... 1024");
   int rc = pbClusterCheckArgs("pbSimPairCorrelation", S, nullptr, nullptr);
   if (rc != PB_OK) return rc;
-  if (kind == PB_CORR_DISPLACEMENT && !(S->cluster && S->cluster->dMarked)) {  // known without the device
-    pbLastError() = "pbSimPairCorrelation: no reference marked";
-    return PB_ERR_ARG;
-  }
+  if (kind == PB_CORR_DISPLACEMENT && !(S->cluster && S->cluster->dMarked))  // known without the device
+    return pbFail("pbSimPairCorrelation", ": no reference marked");
   rc = pbClusterFile(S, (double)rMax, 0.0);
   if (rc != PB_OK) return rc;
   PbClusterScratch *C = S->cluster;
@@ -215,20 +182,17 @@ int pbSimPairCorrelation(pbSim *S, int kind, float rMax, unsigned bins, pbCorrel
   PB_TRY(hipMemcpy(acc.data(), C->kAcc, sizeof(unsigned long long) * accWords, hipMemcpyDeviceToHost));
   PB_TRY(hipMemcpy(tot.data(), C->kTotals, sizeof(unsigned long long) * totWords, hipMemcpyDeviceToHost));
   for (size_t k = 0; k < nsims * bins; k++)
-    if (acc[k * G_WORDS] >= (1ull << 31)) {  // the counts are exact whatever the state: the other sums may not be
-      pbLastError() = "pbSimPairCorrelation: a bin holds 2^31 pairs or more: raise bins or lower rMax";
-      return PB_ERR_ARG;
-    }
+    if (acc[k * G_WORDS] >= (1ull << 31))  // the counts are exact whatever the state: the other sums may not be
+      return pbFail("pbSimPairCorrelation", ": a bin holds 2^31 pairs or more: raise bins or lower rMax");
   for (size_t m = 0; m < nsims; m++) {
     unsigned long long pairs = 0ull;
     for (size_t k = m * bins; k < (m + 1) * bins; k++) {
       const unsigned long long *w = &acc[k * G_WORDS];
       pbCorrelationBin &row = rows[k];
       row.pairs = w[0];
-      row.dot = normalised((__int128)w[1] + (__int128)w[2] * ((__int128)1 << 32) +
-                           composed(w[3], w[4]) * ((__int128)1 << 32));
-      row.ax = normalised(composed(w[5], w[6]));
-      row.ay = normalised(composed(w[7], w[8]));
+      row.dot = pbFixedNormalised(pbFixedCompose(w[1], w[2]) + pbFixedCompose(w[3], w[4]) * ((__int128)1 << 32));
+      row.ax = pbFixedNormalised(pbFixedCompose(w[5], w[6]));
+      row.ay = pbFixedNormalised(pbFixedCompose(w[7], w[8]));
       pairs += w[0];
     }
     if (totals) {
@@ -236,7 +200,7 @@ int pbSimPairCorrelation(pbSim *S, int kind, float rMax, unsigned bins, pbCorrel
       pbCorrelationTotals &out = totals[m];
       out.measured = (unsigned)w[S_MEASURED], out.reserved = 0u;
       out.sum_ax = (long long)w[S_AX], out.sum_ay = (long long)w[S_AY];
-      out.sum_a2 = normalised((__int128)w[S_A2LO] + (__int128)w[S_A2HI] * ((__int128)1 << 32));
+      out.sum_a2 = pbFixedNormalised(pbFixedCompose(w[S_A2LO], w[S_A2HI]));
       out.pairs = pairs;
     }
   }

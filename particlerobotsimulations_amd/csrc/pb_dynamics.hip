@@ -156,13 +156,12 @@ __global__ __launch_bounds__(CT) void k_dyn_compare(const float4 *__restrict__ c
     }
   }
   const float dx = xn - p0.x, dy = yn - p0.y;
-  // |dx| < 2048 implies that both of its coordinates are finite (inf - inf is NaN, inf - finite is inf)
-  const bool measured = live && fabsf(dx) < 2048.0f && fabsf(dy) < 2048.0f;
+  // a dx in range implies that both of its coordinates are finite (inf - inf is NaN, inf - finite is inf)
+  const bool measured = live && pbFixedInRange(dx) && pbFixedInRange(dy);
   long long qx = 0ll, qy = 0ll;
   unsigned long long s = 0ull;
   if (measured) {
-    qx = (long long)(int)__builtin_rintf(dx * 1048576.0f);  // |.| <= 2^31 - 128; v_rndne_f32 rounds to nearest even
-    qy = (long long)(int)__builtin_rintf(dy * 1048576.0f);
+    qx = pbFixedQuantise(dx), qy = pbFixedQuantise(dy);
     s = (unsigned long long)(qx * qx) + (unsigned long long)(qy * qy);
   }
   if (live) {
@@ -171,38 +170,26 @@ __global__ __launch_bounds__(CT) void k_dyn_compare(const float4 *__restrict__ c
     disp[o] = make_float2(dx, dy);
   }
   // the members' rows: per member the sums over each wave, the four waves through LDS, one set of atomics
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   const uint32_t tLast = (total - t0 < (uint32_t)CT ? total : t0 + CT) - 1u;
   const uint32_t mFirst = t0 / n, mLast = tLast / n;
 #pragma unroll 1
   for (uint32_t m = mFirst; m <= mLast; m++) {
     const bool mine = live && member == m;
-    const unsigned long long vMarked = waveSumU64(mine ? len : 0u), vNow = waveSumU64(mine ? nw : 0u);
-    const unsigned long long vKept = waveSumU64(mine ? kp : 0u);
-    const unsigned long long vUnchanged = __popcll(__ballot(mine && kp == len && kp == nw));
-    const unsigned long long vLost = __popcll(__ballot(mine && kp < len));
-    const unsigned long long vGained = __popcll(__ballot(mine && kp < nw));
-    const unsigned long long vMeasured = __popcll(__ballot(mine && measured));
     const bool add = mine && measured;
-    const unsigned long long vQx = waveSumU64(add ? (unsigned long long)qx : 0ull);
-    const unsigned long long vQy = waveSumU64(add ? (unsigned long long)qy : 0ull);
-    const unsigned long long vLo = waveSumU64(add ? (s & 0xFFFFFFFFull) : 0ull);
-    const unsigned long long vHi = waveSumU64(add ? (s >> 32) : 0ull);
-    const unsigned long long vMax = waveMaxU64(add ? s : 0ull);
-    if (lane == 0u) {
-      unsigned long long *r = sRed[w];
-      r[R_MARKED] = vMarked, r[R_NOW] = vNow, r[R_KEPT] = vKept, r[R_UNCHANGED] = vUnchanged, r[R_LOST] = vLost;
-      r[R_GAINED] = vGained, r[R_MEASURED] = vMeasured, r[R_QX] = vQx, r[R_QY] = vQy, r[R_LO] = vLo, r[R_HI] = vHi;
-      r[R_MAX] = vMax;
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)R_COLS) {
+    unsigned long long r[R_COLS], v;
+    r[R_MARKED] = waveSumU64(mine ? len : 0u), r[R_NOW] = waveSumU64(mine ? nw : 0u);
+    r[R_KEPT] = waveSumU64(mine ? kp : 0u);
+    r[R_UNCHANGED] = __popcll(__ballot(mine && kp == len && kp == nw));
+    r[R_LOST] = __popcll(__ballot(mine && kp < len));
+    r[R_GAINED] = __popcll(__ballot(mine && kp < nw));
+    r[R_MEASURED] = __popcll(__ballot(add));
+    r[R_QX] = waveSumU64(add ? (unsigned long long)qx : 0ull);
+    r[R_QY] = waveSumU64(add ? (unsigned long long)qy : 0ull);
+    r[R_LO] = waveSumU64(add ? pbFixedLow(s) : 0ull), r[R_HI] = waveSumU64(add ? pbFixedRest(s) : 0ull);
+    r[R_MAX] = waveMaxU64(add ? s : 0ull);
+    const auto opOf = [](uint32_t c) { return c == (uint32_t)R_MAX ? PB_FOLD_MAX_UNSIGNED : PB_FOLD_SUM; };
+    if (blockFold(sRed, r, opOf, v)) {
       const uint32_t c = threadIdx.x;
-      unsigned long long v = sRed[0][c];
-      for (int k = 1; k < CT / 64; k++) {
-        const unsigned long long u = sRed[k][c];
-        v = c == (uint32_t)R_MAX ? (u > v ? u : v) : v + u;
-      }
       pbRearrangementStats *row = rows + m;
       if (v) {  // (a signed sum that is zero adds nothing either)
         if (c == R_MARKED) atomicAdd(&row->bonds_marked, v);
@@ -236,9 +223,7 @@ void freeMark(PbClusterScratch *C) {
 
 // "no reference marked" is known without the device
 int needMark(const char *fn, const pbSim *S) {
-  if (S->cluster && S->cluster->dMarked) return PB_OK;
-  pbLastError() = std::string(fn) + ": no reference marked";
-  return PB_ERR_ARG;
+  return S->cluster && S->cluster->dMarked ? PB_OK : pbFail(fn, ": no reference marked");
 }
 
 // files the bots at the mark's gap and leaves now, kept, disp and the rows (partial sums in sum_q2_*) on the device
@@ -264,10 +249,7 @@ int compareSweep(pbSim *S) {
 }  // namespace
 
 int pbSimMarkReference(pbSim *S, float linkGap) {
-  if (!S) {
-    pbLastError() = "pbSimMarkReference: null handle";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail("pbSimMarkReference", ": null handle");
   int rc = pbClusterCheckArgs("pbSimMarkReference", S, &linkGap, nullptr);
   if (rc != PB_OK) return rc;
   if (S->cluster) dropMark(S->cluster);  // whatever happens below, the old mark is gone
@@ -289,10 +271,8 @@ int pbSimMarkReference(pbSim *S, float linkGap) {
   unsigned long long count = 0ull;
   PB_TRY(hipMemcpyAsync(&count, sum, sizeof count, hipMemcpyDeviceToHost, S->stream));
   PB_TRY(hipStreamSynchronize(S->stream));
-  if (count >= (1ull << 31)) {
-    pbLastError() = "pbSimMarkReference: the batch has 2^31 directed entries or more (offsets are 32-bit)";
-    return PB_ERR_ARG;
-  }
+  if (count >= (1ull << 31))
+    return pbFail("pbSimMarkReference", ": the batch has 2^31 directed entries or more (offsets are 32-bit)");
   PB_TRY(C->dOther.ensure(count ? count : 1ull));
   hipLaunchKernelGGL(k_dyn_fill, gBots, b, 0, S->stream, C->cpr, C->start, n, G, linkGap, C->dOffsets, C->dOther, flag);
   hipLaunchKernelGGL(k_dyn_order, dim3(blocks), b, 0, S->stream, C->dOffsets, C->dOther, total);
@@ -315,10 +295,7 @@ int pbSimMarkReference(pbSim *S, float linkGap) {
 }
 
 int pbSimClearReference(pbSim *S) {
-  if (!S) {
-    pbLastError() = "pbSimClearReference: null handle";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail("pbSimClearReference", ": null handle");
   if (S->cluster) {
     useDevice(S);
     freeMark(S->cluster);
@@ -327,10 +304,7 @@ int pbSimClearReference(pbSim *S) {
 }
 
 int pbSimGetReferenceInfo(pbSim *S, int *marked, float *linkGap, float *time, unsigned long long *entries) {
-  if (!S) {
-    pbLastError() = "pbSimGetReferenceInfo: null handle";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail("pbSimGetReferenceInfo", ": null handle");
   const PbClusterScratch *C = S->cluster;
   const bool held = C && C->dMarked;
   if (marked) *marked = held ? 1 : 0;
@@ -341,17 +315,14 @@ int pbSimGetReferenceInfo(pbSim *S, int *marked, float *linkGap, float *time, un
 }
 
 int pbSimRearrangementStats(pbSim *S, pbRearrangementStats *rows) {
-  if (!S || !rows) {
-    pbLastError() = "pbSimRearrangementStats: null handle or rows";
-    return PB_ERR_ARG;
-  }
+  if (!S || !rows) return pbFail("pbSimRearrangementStats", ": null handle or rows");
   int rc = pbClusterCheckArgs("pbSimRearrangementStats", S, nullptr, nullptr);
   if (rc == PB_OK) rc = needMark("pbSimRearrangementStats", S);
   if (rc == PB_OK) rc = compareSweep(S);
   if (rc != PB_OK) return rc;
   PB_TRY(hipMemcpy(rows, S->cluster->dRows, sizeof(pbRearrangementStats) * S->nsims, hipMemcpyDeviceToHost));
-  for (uint32_t m = 0; m < S->nsims; m++) {  // sum s = hi_part * 2^32 + lo_part, as one 128-bit integer
-    const unsigned __int128 v = ((unsigned __int128)rows[m].sum_q2_hi << 32) + rows[m].sum_q2_lo;
+  for (uint32_t m = 0; m < S->nsims; m++) {  // the two partial sums as one 128-bit integer
+    const unsigned __int128 v = (unsigned __int128)pbFixedCompose(rows[m].sum_q2_lo, rows[m].sum_q2_hi);
     rows[m].sum_q2_lo = (unsigned long long)v;
     rows[m].sum_q2_hi = (unsigned long long)(v >> 64);
   }
@@ -359,14 +330,9 @@ int pbSimRearrangementStats(pbSim *S, pbRearrangementStats *rows) {
 }
 
 int pbSimRearrangementOf(pbSim *S, unsigned member, float *disp, unsigned *marked, unsigned *now, unsigned *kept) {
-  if (!S) {
-    pbLastError() = "pbSimRearrangementOf: null handle";
-    return PB_ERR_ARG;
-  }
-  if (!disp && !marked && !now && !kept) {
-    pbLastError() = "pbSimRearrangementOf: disp, marked, now and kept are all null";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail("pbSimRearrangementOf", ": null handle");
+  if (!disp && !marked && !now && !kept)
+    return pbFail("pbSimRearrangementOf", ": disp, marked, now and kept are all null");
   int rc = pbClusterCheckArgs("pbSimRearrangementOf", S, nullptr, &member);
   if (rc == PB_OK) rc = needMark("pbSimRearrangementOf", S);
   if (rc == PB_OK) rc = compareSweep(S);

@@ -1276,8 +1276,6 @@ int pbSimRenderOf(pbSim *S, unsigned sim, const pbRenderView *view, unsigned cha
     PB_TRY(S->render.ids.ensure(pixels));
   }
   PB_TRY(S->render.rgb8.ensure(S->n));
-  if (!S->render.ev0) PB_TRY(S->render.ev0.create());
-  if (!S->render.ev1) PB_TRY(S->render.ev1.create());
   // the host writer's view, in its operations (Particlebot::writeFrame)
   PbRenderParams V;
   V.width = view->width, V.height = view->height;
@@ -1288,7 +1286,7 @@ int pbSimRenderOf(pbSim *S, unsigned sim, const pbRenderView *view, unsigned cha
   V.style = view->style;
   V.displayShadow = S->displayShadow[sim];
   const int c = S->cur;
-  PB_TRY(hipEventRecord(S->render.ev0, S->stream));
+  PB_TRY(S->render.clock.start(S->stream));
   PB_TRY(hipMemsetAsync(S->render.ids, 0, sizeof(uint32_t) * pixels, S->stream));
   pbLaunchRenderBots(S->dP, sim, V, S->hP[sim].max_radius, S->pr[c], S->dead[c], S->orig[c], S->n, S->render.ids,
                      S->render.rgb8, S->stream);
@@ -1297,10 +1295,10 @@ int pbSimRenderOf(pbSim *S, unsigned sim, const pbRenderView *view, unsigned cha
                         S->render.ids, S->stream);
   pbLaunchRenderResolve(S->dP, sim, V, S->render.ids, S->render.rgb8, (uint32_t)pixels, S->render.out, S->stream);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(S->render.ev1, S->stream));
+  PB_TRY(S->render.clock.stop(S->stream));
   PB_TRY(hipMemcpyAsync(rgb, S->render.out, 3 * pixels, hipMemcpyDeviceToHost, S->stream));
   PB_TRY(hipStreamSynchronize(S->stream));
-  PB_TRY(hipEventElapsedTime(&S->render.lastMs, S->render.ev0, S->render.ev1));
+  PB_TRY(S->render.clock.ms(&S->render.lastMs));
   S->render.renders++;
   return PB_OK;
 }

@@ -16,7 +16,10 @@
 //   pb_field.hip     field maps: count, dead and integer sums of radius and velocity per grid cell (pbSimFieldMap)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
-//   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of
+//   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of, and
+//                    the span clock (two events around a span of launches)
+//   pb_fixed.hpp     the fixed-point kit of the integer analyses: quantiser, split accumulators, wave and workgroup
+//                    sums, the host's way back to a pbMoment128; the one statement of their bound
 #pragma once
 
 #include <string>
@@ -39,6 +42,12 @@ std::string &pbLastError();
       return PB_ERR_HIP;                                                                              \
     }                                                                                                 \
   } while (0)
+
+// an argument the entry point `fn` refuses: the text behind pbGetLastErrorString is fn + what
+inline int pbFail(const char *fn, const char *what) {
+  pbLastError() = std::string(fn) + what;
+  return PB_ERR_ARG;
+}
 
 #ifndef PB_TILE
 #define PB_TILE 256
@@ -64,7 +73,7 @@ struct PbRender {
   PbDevBuf<uint32_t> ids;   // one key per pixel; its capacity is the frame both buffers hold
   PbDevBuf<uint32_t> out;   // packed RGB8, padded to whole groups of four pixels
   PbDevBuf<uint32_t> rgb8;  // n: a member's bot colours in original order
-  PbEvent ev0, ev1;
+  PbSpanClock clock;
   unsigned long long renders = 0;
   float lastMs = 0.0f;
 };
@@ -87,17 +96,15 @@ struct PbTimeCorr {
   unsigned long long a2 = 0, records = 0;  // rint(radius * 2^20) squared; records taken so far
   std::vector<unsigned long long> steps;   // per slot: stats.steps at that moment
   std::vector<unsigned long long> origins, sumSteps;  // per lag: record pairs added, and their step differences
-  PbEvent ev0, ev1;                        // around the last record's launches
-  bool timed = false;
+  PbSpanClock clock;                       // around the last record's launches
 };
 
 // field maps (pb_field.hip): the scratch of the largest map asked for so far, made by the first call (pbSimFieldMap)
 struct PbField {
   PbDevBuf<unsigned long long> cells;  // eight words per cell of the map a call computes
   PbDevBuf<uint32_t> totals;           // four words per member
-  PbEvent ev0, ev1;                    // around the last map's launches
+  PbSpanClock clock;                   // around the last map's launches
   unsigned long long maps = 0;
-  bool timed = false;
 };
 
 // Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
@@ -173,11 +180,10 @@ struct pbSim {
   // cluster analysis (pb_cluster.hip): scratch of its own, allocated by the first analysis, freed by ~pbSim
   PbClusterScratch *cluster = nullptr;
   PbSeries series;
-  // the one-shot rows of pbSimMoments and the events around the last moments pass, series record or not: made on first
+  // the one-shot rows of pbSimMoments and the clock around the last moments pass, series record or not: made on first
   // use and kept when the series is switched
   PbDevBuf<pbMomentsRow> momRows;  // nsims
-  PbEvent momEv0, momEv1;
-  bool momTimed = false;
+  PbSpanClock momClock;
   PbTimeCorr tc;
   PbField field;
   pbSimStats stats{};
@@ -188,6 +194,22 @@ static inline dim3 gridOf(const pbSim *S) { return dim3(cdiv(S->n, TILE), S->nsi
 // HIP's current device is per host thread (a new thread starts on device 0): a caller that drives
 // several batches from several threads must not have to remember that
 static inline void useDevice(const pbSim *S) { (void)hipSetDevice(S->device); }
+
+// a launch of the analysis layer indexes the batch's bots with 32 bits and room to spare
+inline int pbCheckBatch(const char *fn, const pbSim *S) {
+  return S->total >= (1u << 28) ? pbFail(fn, ": the batch must hold fewer than 2^28 bots") : PB_OK;
+}
+// the body of pbSimGet{Series,TimeCorrelation,Field}Times behind the handle check: `count` spans so far, and the device
+// time of the last one (0 before any; the call waits for its end)
+inline int pbSpanGet(const pbSim *S, const PbSpanClock &K, unsigned long long count, unsigned long long *spans,
+                     float *last_device_ms) {
+  if (spans) *spans = count;
+  if (last_device_ms) {
+    if (K.timed()) useDevice(S);
+    PB_TRY(K.ms(last_device_ms));
+  }
+  return PB_OK;
+}
 
 // absForce_a has a reader (impl.cuh:167-169) or the caller asked for it (pbSimSetForceSums)
 static inline bool pbStreamWalk(const pbSim *S) { return S->streamWalk >= 0 ? S->streamWalk == 1 : S->streamWalkAuto; }

@@ -17,12 +17,13 @@
 // The counters of a member (measured, inside, outside, unmeasured) are ballots' popcounts kept wave-uniform and added
 // once per wave.
 // Everything that is added is an integer, so nothing depends on the slot order, on the kernel form or on the order of the
-// adds.  No float atomics, no 128-bit atomics, no scratch memory.  The bounds: a cell holds fewer than
-// 2^28 bots; per bot a low half adds less than 2^32 and a high half less than 2^31, so every word stays below 2^60.
+// adds.  No float atomics, no 128-bit atomics, no scratch memory.  The bounds are pb_fixed.hpp's: a cell
+// holds fewer than 2^28 bots, so every word stays below 2^60.
 #include <math.h>
 #include <string.h>
 
 #include "pb_engine.hpp"
+#include "pb_fixed.hpp"
 
 static_assert(sizeof(pbFieldCell) == 64, "a map cell is 64 bytes");
 static_assert(sizeof(pbFieldTotals) == 16, "a member's totals are 16 bytes");
@@ -54,16 +55,6 @@ __global__ __launch_bounds__(FT) void k_field_clear(unsigned long long *__restri
   if (i < words) cells[i] = 0ull;
   if (i < totalWords) totals[i] = 0u;
 }
-
-__device__ __forceinline__ unsigned long long fieldShflXor64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// (long long)rint(v * 2^20) of a value with |v| < 2048: the scaling is exact, v_rndne_f32 rounds to nearest even,
-// |.| <= 2^31 - 128
-__device__ __forceinline__ long long fieldQuantise(float v) { return (long long)(int)__builtin_rintf(v * 1048576.0f); }
 
 __device__ __forceinline__ void fieldAdd(unsigned long long *p, unsigned long long v) {
   (void)__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // no-return
@@ -101,9 +92,8 @@ __global__ __launch_bounds__(FT) void k_field_accumulate(const float4 *__restric
       const uint32_t s = base + (next + lane < n ? next + lane : next);
       qNext = pr[s], vNext = vel[s], deadNext = dead[s];
     }
-    // (a NaN or an infinity fails its comparison)
-    const bool measured = live && fabsf(q.x) < 2048.0f && fabsf(q.y) < 2048.0f && fabsf(v.x) < 2048.0f &&
-                          fabsf(v.y) < 2048.0f && fabsf(q.z) < 2048.0f;
+    const bool measured = live && pbFixedInRange(q.x) && pbFixedInRange(q.y) && pbFixedInRange(v.x) &&
+                          pbFixedInRange(v.y) && pbFixedInRange(q.z);
     const float tx = (q.x - G.x0) * G.sx, ty = (q.y - G.y0) * G.sy;  // two roundings each
     const bool inside = measured && tx >= 0.0f && tx < G.fnx && ty >= 0.0f && ty < G.fny;  // (-0.0f is inside, in 0)
     const uint32_t key = inside ? (uint32_t)(int)ty * G.nx + (uint32_t)(int)tx : NO_CELL;
@@ -114,14 +104,13 @@ __global__ __launch_bounds__(FT) void k_field_accumulate(const float4 *__restric
     unsigned long long a[F_WORDS];
     {
       // (a bot that is not counted stands in as zeros: its values are read by no one, and none is converted)
-      const long long qr = fieldQuantise(inside ? q.z : 0.0f), wx = fieldQuantise(inside ? v.x : 0.0f);
-      const long long wy = fieldQuantise(inside ? v.y : 0.0f);
+      const long long qr = pbFixedQuantise(inside ? q.z : 0.0f), wx = pbFixedQuantise(inside ? v.x : 0.0f);
+      const long long wy = pbFixedQuantise(inside ? v.y : 0.0f);
       const long long rr = qr * qr, vv = wx * wx + wy * wy;  // below 2^62 and 2^63
       a[F_COUNT] = 1ull + ((unsigned long long)(isDead != 0) << 32);
       a[F_QR] = (unsigned long long)qr, a[F_WX] = (unsigned long long)wx, a[F_WY] = (unsigned long long)wy;
-      // the two's-complement split of pbSimMoments
-      a[F_RR_LO] = (unsigned long long)(uint32_t)rr, a[F_RR_HI] = (unsigned long long)(rr >> 32);
-      a[F_VV_LO] = (unsigned long long)(uint32_t)vv, a[F_VV_HI] = (unsigned long long)(vv >> 32);
+      a[F_RR_LO] = pbFixedLow(rr), a[F_RR_HI] = pbFixedRest(rr);
+      a[F_VV_LO] = pbFixedLow(vv), a[F_VV_HI] = pbFixedRest(vv);
     }
 #pragma unroll 1
     for (int round = 0; round < PB_FIELD_ROUNDS && remaining; round++) {
@@ -142,12 +131,7 @@ __global__ __launch_bounds__(FT) void k_field_accumulate(const float4 *__restric
       unsigned long long t[F_WORDS];
 #pragma unroll
       for (int c = 0; c < F_WORDS; c++) t[c] = same ? a[c] : 0ull;
-      // (one butterfly stage in the code, run six times, as k_mom_accumulate's)
-#pragma unroll 1
-      for (int x = 32; x >= 1; x >>= 1) {
-#pragma unroll
-        for (int c = 0; c < F_WORDS; c++) t[c] += fieldShflXor64(t[c], x);
-      }
+      waveSumRolled(t, [](int) {});
       // every lane holds the group's eight sums: lane c adds word c, one 64-byte atomic instruction
       unsigned long long mine = t[0];
 #pragma unroll
@@ -171,59 +155,44 @@ __global__ __launch_bounds__(FT) void k_field_accumulate(const float4 *__restric
   }
 }
 
-int fail(const char *fn, const char *what) {
-  pbLastError() = std::string(fn) + what;
-  return PB_ERR_ARG;
-}
-
-// value = hi * 2^32 + lo with 0 <= lo < 2^32 and hi the floor quotient: the same form however the device split its adds
-pbMoment128 normalised(unsigned long long lo, unsigned long long hi) {
-  const __int128 v = (__int128)lo + (__int128)(long long)hi * ((__int128)1 << 32);
-  pbMoment128 m;
-  m.lo = (unsigned long long)(v & (__int128)0xFFFFFFFFull);
-  m.hi = (long long)(v >> 32);  // (arithmetic: the floor)
-  return m;
-}
-
 // one map of every member, or of member `firstMember` alone: the checks, the two launches, the read-back
 int fieldMap(const char *fn, pbSim *S, uint32_t firstMember, bool one, const pbFieldView *view, pbFieldCell *out,
              pbFieldTotals *totals) {
-  if (!S || !view || !out) return fail(fn, ": null handle, view or cells");
+  if (!S || !view || !out) return pbFail(fn, ": null handle, view or cells");
   if (view->nx < 1u || view->nx > PB_FIELD_MAX_AXIS || view->ny < 1u || view->ny > PB_FIELD_MAX_AXIS)
-    return fail(fn, ": nx and ny must be 1 ... 1024");
+    return pbFail(fn, ": nx and ny must be 1 ... 1024");
   const float inf = __builtin_inff();
   if (!(view->halfX > 0.0f) || !(view->halfX < inf) || !(view->halfY > 0.0f) || !(view->halfY < inf))
-    return fail(fn, ": halfX and halfY must be finite and > 0");
+    return pbFail(fn, ": halfX and halfY must be finite and > 0");
   FieldGrid G;
   G.x0 = view->centerX - view->halfX, G.y0 = view->centerY - view->halfY;
   G.sx = (float)view->nx / (view->halfX + view->halfX), G.sy = (float)view->ny / (view->halfY + view->halfY);
   G.fnx = (float)view->nx, G.fny = (float)view->ny;
   G.nx = view->nx, G.cells = view->nx * view->ny;
   if (!(fabsf(G.x0) < inf) || !(fabsf(G.y0) < inf) || !(fabsf(G.sx) < inf) || !(fabsf(G.sy) < inf))
-    return fail(fn, ": the view's origin and scale must be finite");
+    return pbFail(fn, ": the view's origin and scale must be finite");
   // (the handle is read from here on: what comes before holds for any handle)
-  if (one && firstMember >= S->nsims) return fail(fn, ": member out of range");
+  if (one && firstMember >= S->nsims) return pbFail(fn, ": member out of range");
   const uint32_t members = one ? 1u : S->nsims;
   if ((unsigned long long)members * G.cells * sizeof(pbFieldCell) > (1ull << 31))
-    return fail(fn, ": members x nx x ny x 64 bytes must not exceed 2^31 bytes");
-  if (S->total >= (1u << 28)) return fail(fn, ": the batch must hold fewer than 2^28 bots");
+    return pbFail(fn, ": members x nx x ny x 64 bytes must not exceed 2^31 bytes");
+  const int rc = pbCheckBatch(fn, S);
+  if (rc != PB_OK) return rc;
   useDevice(S);
   PbField &F = S->field;
   const size_t words = (size_t)members * G.cells * F_WORDS, totalWords = (size_t)S->nsims * N_WORDS;
   PB_TRY(F.cells.ensure(words));
   PB_TRY(F.totals.ensure(totalWords));  // (16 bytes per member, whichever entry asks first)
-  if (!F.ev0) PB_TRY(F.ev0.create());
-  if (!F.ev1) PB_TRY(F.ev1.create());
   const uint32_t perMember = cdiv(S->n, FT);
   const uint32_t bpm = perMember < PB_FIELD_BLOCKS ? perMember : PB_FIELD_BLOCKS;
-  PB_TRY(hipEventRecord(F.ev0, S->stream));
+  PB_TRY(F.clock.start(S->stream));
   hipLaunchKernelGGL(k_field_clear, dim3(cdiv((uint32_t)words, FT)), dim3(FT), 0, S->stream, F.cells, (uint32_t)words,
                      F.totals, members * (uint32_t)N_WORDS);
   hipLaunchKernelGGL(k_field_accumulate, dim3(members * bpm), dim3(FT), 0, S->stream, S->pr[S->cur], S->vel[S->cur],
                      S->dead[S->cur], S->n, firstMember, bpm, G, F.cells, F.totals);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(F.ev1, S->stream));
-  F.timed = true, F.maps++;
+  PB_TRY(F.clock.stop(S->stream));
+  F.maps++;
   // the device cell has the size of the caller's: it lands in place and is rewritten there
   PB_TRY(hipMemcpyAsync(out, F.cells, sizeof(pbFieldCell) * (size_t)members * G.cells, hipMemcpyDeviceToHost, S->stream));
   uint32_t counters[4 * N_WORDS];
@@ -240,8 +209,8 @@ int fieldMap(const char *fn, pbSim *S, uint32_t firstMember, bool one, const pbF
     pbFieldCell &c = out[k];
     c.count = (unsigned)w[F_COUNT], c.dead = (unsigned)(w[F_COUNT] >> 32);
     c.sum_qr = (long long)w[F_QR], c.sum_wx = (long long)w[F_WX], c.sum_wy = (long long)w[F_WY];
-    c.rr = normalised(w[F_RR_LO], w[F_RR_HI]);
-    c.vv = normalised(w[F_VV_LO], w[F_VV_HI]);
+    c.rr = pbFixedNormalised(pbFixedCompose(w[F_RR_LO], w[F_RR_HI]));
+    c.vv = pbFixedNormalised(pbFixedCompose(w[F_VV_LO], w[F_VV_HI]));
   }
   if (totals)
     for (uint32_t k = 0; k < members; k++) {
@@ -265,17 +234,8 @@ int pbSimFieldMapOf(pbSim *S, unsigned member, const pbFieldView *view, pbFieldC
 }
 
 int pbSimGetFieldTimes(pbSim *S, unsigned long long *maps, float *last_device_ms) {
-  if (!S) return fail("pbSimGetFieldTimes", ": null handle");
-  if (maps) *maps = S->field.maps;
-  if (last_device_ms) {
-    *last_device_ms = 0.0f;
-    if (S->field.timed) {
-      useDevice(S);
-      PB_TRY(hipEventSynchronize(S->field.ev1));
-      PB_TRY(hipEventElapsedTime(last_device_ms, S->field.ev0, S->field.ev1));
-    }
-  }
-  return PB_OK;
+  if (!S) return pbFail("pbSimGetFieldTimes", ": null handle");
+  return pbSpanGet(S, S->field.clock, S->field.maps, maps, last_device_ms);
 }
 
 }  // extern "C"

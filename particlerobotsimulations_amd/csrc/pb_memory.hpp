@@ -102,6 +102,34 @@ struct PbEvent : PbHandle<hipEvent_t, hipEventDestroy> {
     return hipEventCreate(&h_);
   }
 };
+// The device time of the last span of launches that start() and stop() bracketed on a stream.  Neither waits; ms()
+// waits for the span's end.  The events are made by the first start.
+class PbSpanClock {
+ public:
+  hipError_t start(hipStream_t stream) {
+    hipError_t e = hipSuccess;
+    if (!ev0_) e = ev0_.create();
+    if (e == hipSuccess && !ev1_) e = ev1_.create();
+    return e != hipSuccess ? e : hipEventRecord(ev0_, stream);
+  }
+  hipError_t stop(hipStream_t stream) {
+    const hipError_t e = hipEventRecord(ev1_, stream);
+    if (e == hipSuccess) timed_ = true;
+    return e;
+  }
+  bool timed() const { return timed_; }  // a span was recorded: ms() will touch the device
+  // 0 before any span; else the last span's device time, once its end has passed
+  hipError_t ms(float *out) const {
+    *out = 0.0f;
+    if (!timed_) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(ev1_);
+    return e != hipSuccess ? e : hipEventElapsedTime(out, ev0_, ev1_);
+  }
+
+ private:
+  PbEvent ev0_, ev1_;
+  bool timed_ = false;
+};
 struct PbStream : PbHandle<hipStream_t, hipStreamDestroy> {
   hipError_t create(unsigned flags) {
     reset();

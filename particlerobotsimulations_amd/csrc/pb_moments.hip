@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "pb_engine.hpp"
+#include "pb_fixed.hpp"
 
 static_assert(sizeof(pbMoment128) == 16, "a 128-bit sum is two 64-bit accumulators");
 static_assert(sizeof(pbMomentsRow) == 152, "a member's row is 152 bytes");
@@ -43,22 +44,6 @@ __global__ __launch_bounds__(MT) void k_mom_init(pbMomentsRow *__restrict__ rows
   r->xx.hi = r->yy.hi = r->xy.hi = r->rr.hi = r->vv.hi = 0ll;
 }
 
-__device__ __forceinline__ unsigned long long momShflXor64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// (long long)rint(v * 2^20) of a value with |v| < 2048: the scaling is exact, v_rndne_f32 rounds to nearest even,
-// |.| <= 2^31 - 128
-__device__ __forceinline__ long long momQuantise(float v) { return (long long)(int)__builtin_rintf(v * 1048576.0f); }
-
-// the 64-bit product p into its two accumulators: the two's-complement split, so a signed p needs no special case
-__device__ __forceinline__ void momSplit(long long p, unsigned long long &lo, unsigned long long &hi) {
-  lo += (unsigned long long)(uint32_t)p;
-  hi += (unsigned long long)(p >> 32);  // arithmetic shift; the accumulator wraps like the signed sum it stands for
-}
-
 __global__ __launch_bounds__(MT) void k_mom_accumulate(const float4 *__restrict__ pr, const float2 *__restrict__ vel,
                                                        uint32_t n, uint32_t blocksPerMember,
                                                        pbMomentsRow *__restrict__ rows, uint32_t stride) {
@@ -73,52 +58,43 @@ __global__ __launch_bounds__(MT) void k_mom_accumulate(const float4 *__restrict_
   for (uint32_t i = b * MT + threadIdx.x; i < n; i += blocksPerMember * MT) {
     const float4 q = pr[base + i];
     const float2 v = vel[base + i];
-    // (a NaN or an infinity fails its comparison)
-    if (fabsf(q.x) < 2048.0f && fabsf(q.y) < 2048.0f && fabsf(v.x) < 2048.0f && fabsf(v.y) < 2048.0f &&
-        fabsf(q.z) < 2048.0f) {
-      const long long qx = momQuantise(q.x), qy = momQuantise(q.y), qr = momQuantise(q.z);
-      const long long wx = momQuantise(v.x), wy = momQuantise(v.y);
+    if (pbFixedInRange(q.x) && pbFixedInRange(q.y) && pbFixedInRange(v.x) && pbFixedInRange(v.y) &&
+        pbFixedInRange(q.z)) {
+      const long long qx = pbFixedQuantise(q.x), qy = pbFixedQuantise(q.y), qr = pbFixedQuantise(q.z);
+      const long long wx = pbFixedQuantise(v.x), wy = pbFixedQuantise(v.y);
       a[M_MEASURED] += 1ull;
       a[M_QX] += (unsigned long long)qx, a[M_QY] += (unsigned long long)qy, a[M_QR] += (unsigned long long)qr;
       a[M_WX] += (unsigned long long)wx, a[M_WY] += (unsigned long long)wy;
-      momSplit(qx * qx, a[M_XX_LO], a[M_XX_HI]);
-      momSplit(qy * qy, a[M_YY_LO], a[M_YY_HI]);
-      momSplit(qx * qy, a[M_XY_LO], a[M_XY_HI]);
-      momSplit(qr * qr, a[M_RR_LO], a[M_RR_HI]);
-      momSplit(wx * wx + wy * wy, a[M_VV_LO], a[M_VV_HI]);  // below 2^63
+      pbFixedSplitAdd(qx * qx, a[M_XX_LO], a[M_XX_HI]);
+      pbFixedSplitAdd(qy * qy, a[M_YY_LO], a[M_YY_HI]);
+      pbFixedSplitAdd(qx * qy, a[M_XY_LO], a[M_XY_HI]);
+      pbFixedSplitAdd(qr * qr, a[M_RR_LO], a[M_RR_HI]);
+      pbFixedSplitAdd(wx * wx + wy * wy, a[M_VV_LO], a[M_VV_HI]);  // below 2^63
       minX = min(minX, (int)qx), maxX = max(maxX, (int)qx);
       minY = min(minY, (int)qy), maxY = max(maxY, (int)qy);
     }
   }
   // the wave's sums with shuffles, the four waves through LDS, one set of atomics
-  // (one butterfly stage in the code, run six times: unrolled, the stages' temporaries cost registers that the pass
-  //  once per workgroup does not earn back)
-#pragma unroll 1
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int c = 0; c < M_SUMS; c++) a[c] += momShflXor64(a[c], m);
+  // (the butterfly stays rolled: waveSumRolled, pb_fixed.hpp, has the reason)
+  waveSumRolled(a, [&](int m) {
     minX = min(minX, __shfl_xor(minX, m)), maxX = max(maxX, __shfl_xor(maxX, m));
     minY = min(minY, __shfl_xor(minY, m)), maxY = max(maxY, __shfl_xor(maxY, m));
-  }
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (lane == 0u) {
+  });
+  // the fold's columns (an array of their own: the sums keep the shape the loop and the butterfly compile best with);
+  // the box as sign-extended 64-bit values, so that one signed compare serves all four
+  unsigned long long cols[M_COLS];
 #pragma unroll
-    for (int c = 0; c < M_SUMS; c++) sRed[w][c] = a[c];
-    // the box as sign-extended 64-bit values, so that one signed compare serves all four columns
-    sRed[w][M_MIN_X] = (unsigned long long)(long long)minX, sRed[w][M_MAX_X] = (unsigned long long)(long long)maxX;
-    sRed[w][M_MIN_Y] = (unsigned long long)(long long)minY, sRed[w][M_MAX_Y] = (unsigned long long)(long long)maxY;
-  }
-  __syncthreads();
-  if (threadIdx.x >= (uint32_t)M_COLS) return;
+  for (int c = 0; c < M_SUMS; c++) cols[c] = a[c];
+  cols[M_MIN_X] = (unsigned long long)(long long)minX, cols[M_MAX_X] = (unsigned long long)(long long)maxX;
+  cols[M_MIN_Y] = (unsigned long long)(long long)minY, cols[M_MAX_Y] = (unsigned long long)(long long)maxY;
+  unsigned long long s;
+  const auto opOf = [](uint32_t c) {
+    return c < (uint32_t)M_SUMS ? PB_FOLD_SUM
+           : c == (uint32_t)M_MIN_X || c == (uint32_t)M_MIN_Y ? PB_FOLD_MIN_SIGNED : PB_FOLD_MAX_SIGNED;
+  };
+  if (!blockFold(sRed, cols, opOf, s)) return;
   const uint32_t c = threadIdx.x;
   const bool isMin = c == (uint32_t)M_MIN_X || c == (uint32_t)M_MIN_Y;
-  unsigned long long s = sRed[0][c];
-  for (int k = 1; k < MT / 64; k++) {
-    const unsigned long long u = sRed[k][c];
-    if (c < (uint32_t)M_SUMS) s += u;
-    else if (isMin) s = (long long)u < (long long)s ? u : s;
-    else s = (long long)u > (long long)s ? u : s;
-  }
   pbMomentsRow *row = rows + (size_t)member * stride;
   if (c >= (uint32_t)M_SUMS) {  // (a workgroup without a measured bot holds the identities: they change nothing)
     int *f = c == (uint32_t)M_MIN_X ? &row->min_qx : c == (uint32_t)M_MAX_X ? &row->max_qx
@@ -153,28 +129,16 @@ __global__ __launch_bounds__(MT) void k_mom_accumulate(const float4 *__restrict_
   atomicAdd(f, s);
 }
 
-int fail(const char *fn, const char *what) {
-  pbLastError() = std::string(fn) + what;
-  return PB_ERR_ARG;
-}
-
-int checkBatch(const char *fn, const pbSim *S) {
-  return S->total >= (1u << 28) ? fail(fn, ": the batch must hold fewer than 2^28 bots") : PB_OK;
-}
-
 // the rows of every member, rows[m * stride], from the state as it is: queued on the batch's stream, not waited for
 int momentsPass(pbSim *S, pbMomentsRow *rows, uint32_t stride) {
-  if (!S->momEv0) PB_TRY(S->momEv0.create());
-  if (!S->momEv1) PB_TRY(S->momEv1.create());
   const uint32_t perMember = cdiv(S->n, MT);
   const uint32_t bpm = perMember < PB_MOMENTS_BLOCKS ? perMember : PB_MOMENTS_BLOCKS;
-  PB_TRY(hipEventRecord(S->momEv0, S->stream));
+  PB_TRY(S->momClock.start(S->stream));
   hipLaunchKernelGGL(k_mom_init, dim3(cdiv(S->nsims, MT)), dim3(MT), 0, S->stream, rows, stride, S->nsims);
   hipLaunchKernelGGL(k_mom_accumulate, dim3(S->nsims * bpm), dim3(MT), 0, S->stream, S->pr[S->cur], S->vel[S->cur],
                      S->n, bpm, rows, stride);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(S->momEv1, S->stream));
-  S->momTimed = true;
+  PB_TRY(S->momClock.stop(S->stream));
   return PB_OK;
 }
 
@@ -198,8 +162,8 @@ int pbSeriesRecord(pbSim *S, float t) {
 extern "C" {
 
 int pbSimMoments(pbSim *S, pbMomentsRow *rows) {
-  if (!S || !rows) return fail("pbSimMoments", ": null handle or rows");
-  int rc = checkBatch("pbSimMoments", S);
+  if (!S || !rows) return pbFail("pbSimMoments", ": null handle or rows");
+  int rc = pbCheckBatch("pbSimMoments", S);
   if (rc != PB_OK) return rc;
   useDevice(S);
   PB_TRY(S->momRows.ensure(S->nsims));
@@ -212,12 +176,12 @@ int pbSimMoments(pbSim *S, pbMomentsRow *rows) {
 }
 
 int pbSimSetSeries(pbSim *S, float interval, unsigned capacity) {
-  if (!S) return fail("pbSimSetSeries", ": null handle");
+  if (!S) return pbFail("pbSimSetSeries", ": null handle");
   if (!(interval >= 0.0f) || !(interval < __builtin_inff()))
-    return fail("pbSimSetSeries", ": interval must be finite and >= 0");
+    return pbFail("pbSimSetSeries", ": interval must be finite and >= 0");
   if ((unsigned long long)capacity * S->nsims * sizeof(pbMomentsRow) > (1ull << 31))
-    return fail("pbSimSetSeries", ": capacity x members x 152 bytes must not exceed 2^31 bytes");
-  const int rc = checkBatch("pbSimSetSeries", S);
+    return pbFail("pbSimSetSeries", ": capacity x members x 152 bytes must not exceed 2^31 bytes");
+  const int rc = pbCheckBatch("pbSimSetSeries", S);
   if (rc != PB_OK) return rc;
   useDevice(S);
   PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
@@ -231,8 +195,9 @@ int pbSimSetSeries(pbSim *S, float interval, unsigned capacity) {
 }
 
 int pbSimGetSeriesInfo(pbSim *S, float *interval, unsigned *capacity, unsigned long long *records) {
-  if (!S) return fail("pbSimGetSeriesInfo", ": null handle");
-  if (!interval && !capacity && !records) return fail("pbSimGetSeriesInfo", ": interval, capacity and records are all null");
+  if (!S) return pbFail("pbSimGetSeriesInfo", ": null handle");
+  if (!interval && !capacity && !records)
+    return pbFail("pbSimGetSeriesInfo", ": interval, capacity and records are all null");
   if (interval) *interval = S->series.interval;
   if (capacity) *capacity = S->series.cap;
   if (records) *records = S->series.records;
@@ -240,13 +205,13 @@ int pbSimGetSeriesInfo(pbSim *S, float *interval, unsigned *capacity, unsigned l
 }
 
 int pbSimGetSeriesOf(pbSim *S, unsigned member, unsigned long long first, unsigned count, pbMomentsRow *rows) {
-  if (!S || !rows) return fail("pbSimGetSeriesOf", ": null handle or rows");
-  if (member >= S->nsims) return fail("pbSimGetSeriesOf", ": member out of range");
-  if (!S->series.ring) return fail("pbSimGetSeriesOf", ": the series is off");
+  if (!S || !rows) return pbFail("pbSimGetSeriesOf", ": null handle or rows");
+  if (member >= S->nsims) return pbFail("pbSimGetSeriesOf", ": member out of range");
+  if (!S->series.ring) return pbFail("pbSimGetSeriesOf", ": the series is off");
   const unsigned long long have = S->series.records, cap = S->series.cap;
   const unsigned long long oldest = have - (have < cap ? have : cap);
   if (first < oldest || first > have || count > have - first)
-    return fail("pbSimGetSeriesOf", ": records outside the ring's window");
+    return pbFail("pbSimGetSeriesOf", ": records outside the ring's window");
   if (!count) return PB_OK;
   useDevice(S);
   // the ring wraps at most once inside the range
@@ -265,17 +230,8 @@ int pbSimGetSeriesOf(pbSim *S, unsigned member, unsigned long long first, unsign
 }
 
 int pbSimGetSeriesTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
-  if (!S) return fail("pbSimGetSeriesTimes", ": null handle");
-  if (records) *records = S->series.records;
-  if (last_device_ms) {
-    *last_device_ms = 0.0f;
-    if (S->momTimed) {
-      useDevice(S);
-      PB_TRY(hipEventSynchronize(S->momEv1));
-      PB_TRY(hipEventElapsedTime(last_device_ms, S->momEv0, S->momEv1));
-    }
-  }
-  return PB_OK;
+  if (!S) return pbFail("pbSimGetSeriesTimes", ": null handle");
+  return pbSpanGet(S, S->momClock, S->series.records, records, last_device_ms);
 }
 
 }  // extern "C"

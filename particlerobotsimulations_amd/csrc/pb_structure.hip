@@ -180,18 +180,9 @@ int hexaticSweep(pbSim *S, float gap) {
 }  // namespace
 
 int pbSimRadialCounts(pbSim *S, float rMax, unsigned bins, unsigned long long *counts) {
-  if (!S || !counts) {
-    pbLastError() = "pbSimRadialCounts: null handle or counts";
-    return PB_ERR_ARG;
-  }
-  if (!(rMax > 0.0f) || !(rMax < __builtin_inff())) {
-    pbLastError() = "pbSimRadialCounts: rMax must be finite and > 0";
-    return PB_ERR_ARG;
-  }
-  if (bins < 1u || bins > PB_RADIAL_MAX_BINS) {
-    pbLastError() = "pbSimRadialCounts: bins must be 1 ... 4096";
-    return PB_ERR_ARG;
-  }
+  if (!S || !counts) return pbFail("pbSimRadialCounts", ": null handle or counts");
+  if (!(rMax > 0.0f) || !(rMax < __builtin_inff())) return pbFail("pbSimRadialCounts", ": rMax must be finite and > 0");
+  if (bins < 1u || bins > PB_RADIAL_MAX_BINS) return pbFail("pbSimRadialCounts", ": bins must be 1 ... 4096");
   int rc = pbClusterCheckArgs("pbSimRadialCounts", S, nullptr, nullptr);
   if (rc != PB_OK) return rc;
   rc = pbClusterFile(S, (double)rMax, 0.0);
@@ -213,10 +204,7 @@ int pbSimRadialCounts(pbSim *S, float rMax, unsigned bins, unsigned long long *c
 }
 
 int pbSimStructureStats(pbSim *S, float linkGap, pbStructureStats *rows) {
-  if (!S || !rows) {
-    pbLastError() = "pbSimStructureStats: null handle or rows";
-    return PB_ERR_ARG;
-  }
+  if (!S || !rows) return pbFail("pbSimStructureStats", ": null handle or rows");
   int rc = pbClusterCheckArgs("pbSimStructureStats", S, &linkGap, nullptr);
   if (rc != PB_OK) return rc;
   rc = hexaticSweep(S, linkGap);
@@ -227,14 +215,8 @@ int pbSimStructureStats(pbSim *S, float linkGap, pbStructureStats *rows) {
 }
 
 int pbSimHexaticOf(pbSim *S, unsigned member, float linkGap, double *psi6, unsigned *neighbours) {
-  if (!S) {
-    pbLastError() = "pbSimHexaticOf: null handle";
-    return PB_ERR_ARG;
-  }
-  if (!psi6 && !neighbours) {
-    pbLastError() = "pbSimHexaticOf: psi6 and neighbours are both null";
-    return PB_ERR_ARG;
-  }
+  if (!S) return pbFail("pbSimHexaticOf", ": null handle");
+  if (!psi6 && !neighbours) return pbFail("pbSimHexaticOf", ": psi6 and neighbours are both null");
   int rc = pbClusterCheckArgs("pbSimHexaticOf", S, &linkGap, &member);
   if (rc != PB_OK) return rc;
   rc = hexaticSweep(S, linkGap);

@@ -15,12 +15,11 @@
 // Everything that is added is an integer, so nothing depends on the slot order, on the kernel form that stepped or on the
 // order of the adds.  No float atomics, no 128-bit atomics, no scratch memory.  A record is these launches on the batch's
 // stream between two events; the host never waits for them.
-// The bounds: a measured pair has |qx|, |qy|, |w| <= 2^31 - 128, so s < 2^63 and |p| < 2^63; per sample
-// a low half adds less than 2^32 and a high half at most 2^31 in magnitude, so with fewer than 2^31 samples in a cell
-// every word stays below 2^63 in magnitude.
+// The bounds are pb_fixed.hpp's: the cap is 2^31 samples in a cell.
 #include <math.h>
 
 #include "pb_engine.hpp"
+#include "pb_fixed.hpp"
 
 static_assert(sizeof(pbTimeCorrelationRow) == 96, "a lag's row is 96 bytes");
 
@@ -51,16 +50,6 @@ __global__ __launch_bounds__(TT) void k_tc_snapshot(const float4 *__restrict__ p
   snap[blockIdx.y * n + o] = make_float4(q.x, q.y, v.x, v.y);
 }
 
-__device__ __forceinline__ unsigned long long tcShflXor64(unsigned long long v, int m) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, m);
-  const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), m);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// (long long)rint(v * 2^20) of a value with |v| < 2048: the scaling is exact, v_rndne_f32 rounds to nearest even,
-// |.| <= 2^31 - 128
-__device__ __forceinline__ long long tcQuantise(float v) { return (long long)(int)__builtin_rintf(v * 1048576.0f); }
-
 __global__ __launch_bounds__(TT) void k_tc_accumulate(const float4 *__restrict__ ring, uint32_t n, uint32_t total,
                                                       uint32_t lags, uint32_t slotNow, uint32_t nLags,
                                                       uint32_t blocksPerLag, unsigned long long a2,
@@ -80,72 +69,47 @@ __global__ __launch_bounds__(TT) void k_tc_accumulate(const float4 *__restrict__
   for (uint32_t i = b * TT + threadIdx.x; i < n; i += blocksPerLag * TT) {
     const float4 u = now[i], z = then[i];
     const float dx = u.x - z.x, dy = u.y - z.y;
-    // (a NaN or an infinity in any of the eight inputs fails a comparison: inf - inf and inf - x are not below 2048)
-    if (fabsf(dx) < 2048.0f && fabsf(dy) < 2048.0f && fabsf(u.z) < 2048.0f && fabsf(u.w) < 2048.0f &&
-        fabsf(z.z) < 2048.0f && fabsf(z.w) < 2048.0f) {
-      const long long qx = tcQuantise(dx), qy = tcQuantise(dy);
-      const unsigned long long s = (unsigned long long)(qx * qx + qy * qy);                         // below 2^63
-      const long long p = tcQuantise(u.z) * tcQuantise(z.z) + tcQuantise(u.w) * tcQuantise(z.w);    // |p| below 2^63
+    // (a NaN or an infinity in any of the eight inputs is out of range: inf - inf and inf - x are not below 2048)
+    if (pbFixedInRange(dx) && pbFixedInRange(dy) && pbFixedInRange(u.z) && pbFixedInRange(u.w) &&
+        pbFixedInRange(z.z) && pbFixedInRange(z.w)) {
+      const long long qx = pbFixedQuantise(dx), qy = pbFixedQuantise(dy);
+      const unsigned long long s = (unsigned long long)(qx * qx + qy * qy);  // below 2^63
+      const long long p = pbFixedQuantise(u.z) * pbFixedQuantise(z.z) + pbFixedQuantise(u.w) * pbFixedQuantise(z.w);
       a[T_SAMPLES] += 1ull;
       a[T_QX] += (unsigned long long)qx, a[T_QY] += (unsigned long long)qy;
-      a[T_MSD_LO] += s & 0xFFFFFFFFull, a[T_MSD_HI] += s >> 32;
-      // the two's-complement split, so the signed product needs no special case
-      a[T_VACF_LO] += (unsigned long long)(uint32_t)p, a[T_VACF_HI] += (unsigned long long)(p >> 32);
+      pbFixedSplitAdd(s, a[T_MSD_LO], a[T_MSD_HI]);
+      pbFixedSplitAdd(p, a[T_VACF_LO], a[T_VACF_HI]);
       a[T_OVERLAP] += s < a2 ? 1ull : 0ull;
       maxQ2 = s > maxQ2 ? s : maxQ2;
     }
   }
   // the wave's sums with a butterfly of 64-bit shuffles, the four waves through LDS, one set of atomics
-#pragma unroll 1
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int c = 0; c < T_SUMS; c++) a[c] += tcShflXor64(a[c], m);
-    const unsigned long long other = tcShflXor64(maxQ2, m);
+  waveSumRolled(a, [&](int m) {
+    const unsigned long long other = shflXor64(maxQ2, m);
     maxQ2 = other > maxQ2 ? other : maxQ2;
-  }
-  const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-  if (lane == 0u) {
+  });
+  unsigned long long cols[T_COLS];  // (an array of their own, as k_mom_accumulate's)
 #pragma unroll
-    for (int c = 0; c < T_SUMS; c++) sRed[w][c] = a[c];
-    sRed[w][T_MAX_Q2] = maxQ2;
-  }
-  __syncthreads();
-  if (threadIdx.x >= (uint32_t)T_COLS) return;
+  for (int c = 0; c < T_SUMS; c++) cols[c] = a[c];
+  cols[T_MAX_Q2] = maxQ2;
+  unsigned long long v;
+  const auto opOf = [](uint32_t c) { return c == (uint32_t)T_MAX_Q2 ? PB_FOLD_MAX_UNSIGNED : PB_FOLD_SUM; };
+  if (!blockFold(sRed, cols, opOf, v)) return;
   const uint32_t c = threadIdx.x;
-  unsigned long long v = sRed[0][c];
-  for (int k = 1; k < TT / 64; k++) {
-    const unsigned long long x = sRed[k][c];
-    v = c == (uint32_t)T_MAX_Q2 ? (x > v ? x : v) : v + x;
-  }
   if (!v) return;  // (a sum that is zero adds nothing, and 0 is the maximum's identity)
   unsigned long long *cell = table + ((size_t)member * lags + lag) * T_COLS;
   if (c == (uint32_t)T_MAX_Q2) atomicMax(cell + c, v);
   else atomicAdd(cell + c, v);  // two's complement: a signed word takes its sum modulo 2^64
 }
 
-int fail(const char *fn, const char *what) {
-  pbLastError() = std::string(fn) + what;
-  return PB_ERR_ARG;
-}
-
-// the ring, the zeroed table and the events of a correlation of `lags` lags into T; on an error the caller drops T
+// the ring and the zeroed table of a correlation of `lags` lags into T; on an error the caller drops T
 int allocate(pbSim *S, PbTimeCorr &T, unsigned lags) {
   const size_t words = (size_t)S->nsims * lags * T_COLS;
   PB_TRY(T.ring.alloc((size_t)lags * S->total));
   PB_TRY(T.table.alloc(words));
-  PB_TRY(T.ev0.create());
-  PB_TRY(T.ev1.create());
   hipLaunchKernelGGL(k_tc_clear, dim3(cdiv((uint32_t)words, TT)), dim3(TT), 0, S->stream, T.table, (uint32_t)words);
   PB_TRY(hipGetLastError());
   return PB_OK;
-}
-
-// value = hi * 2^32 + lo with 0 <= lo < 2^32 and hi the floor quotient: the same form however the device split its adds
-pbMoment128 normalised(__int128 v) {
-  pbMoment128 m;
-  m.lo = (unsigned long long)(v & (__int128)0xFFFFFFFFull);
-  m.hi = (long long)(v >> 32);  // (arithmetic: the floor)
-  return m;
 }
 
 }  // namespace
@@ -156,14 +120,13 @@ int pbTimeCorrRecord(pbSim *S) {
   const uint32_t perMember = cdiv(S->n, TT);
   const uint32_t bpl = perMember < PB_TCORR_BLOCKS ? perMember : PB_TCORR_BLOCKS;
   const int c = S->cur;
-  PB_TRY(hipEventRecord(S->tc.ev0, S->stream));
+  PB_TRY(S->tc.clock.start(S->stream));
   hipLaunchKernelGGL(k_tc_snapshot, dim3(cdiv(S->n, TT), S->nsims), dim3(TT), 0, S->stream, S->pr[c], S->vel[c],
                      S->orig[c], S->n, S->tc.ring + (size_t)slot * S->total);
   hipLaunchKernelGGL(k_tc_accumulate, dim3(S->nsims * nLags * bpl), dim3(TT), 0, S->stream, S->tc.ring, S->n, S->total,
                      lags, slot, nLags, bpl, S->tc.a2, S->tc.table);
   PB_TRY(hipGetLastError());
-  PB_TRY(hipEventRecord(S->tc.ev1, S->stream));
-  S->tc.timed = true;
+  PB_TRY(S->tc.clock.stop(S->stream));
   S->tc.steps[slot] = S->stats.steps;
   for (uint32_t l = 0; l < nLags; l++) {
     S->tc.origins[l]++;
@@ -177,26 +140,28 @@ extern "C" {
 
 int pbSimSetTimeCorrelation(pbSim *S, float interval, unsigned lags, float overlapRadius) {
   const char *fn = "pbSimSetTimeCorrelation";
-  if (!S) return fail(fn, ": null handle");
+  if (!S) return pbFail(fn, ": null handle");
   if (!(interval == -1.0f) && (!(interval >= 0.0f) || !(interval < __builtin_inff())))
-    return fail(fn, ": interval must be finite and >= 0, or -1 for manual records only");
-  if (lags > PB_TCORR_MAX_LAGS) return fail(fn, ": lags must be at most 64");
-  if (!(overlapRadius >= 0.0f) || !(overlapRadius < 2048.0f)) return fail(fn, ": overlapRadius must be in [0, 2048)");
-  if (S->nsims > 65535u) return fail(fn, ": the batch must hold at most 65535 members");  // the member is a grid's y
-  if (S->total >= (1u << 28)) return fail(fn, ": the batch must hold fewer than 2^28 bots");
+    return pbFail(fn, ": interval must be finite and >= 0, or -1 for manual records only");
+  if (lags > PB_TCORR_MAX_LAGS) return pbFail(fn, ": lags must be at most 64");
+  if (!(overlapRadius >= 0.0f) || !pbFixedInRange(overlapRadius))
+    return pbFail(fn, ": overlapRadius must be in [0, 2048)");
+  if (S->nsims > 65535u) return pbFail(fn, ": the batch must hold at most 65535 members");  // the member is a grid's y
+  int rc = pbCheckBatch(fn, S);
+  if (rc != PB_OK) return rc;
   if ((unsigned long long)lags * S->total * sizeof(float4) > (1ull << 33))
-    return fail(fn, ": the ring (lags x bots x 16 bytes) must not exceed 2^33 bytes");
+    return pbFail(fn, ": the ring (lags x bots x 16 bytes) must not exceed 2^33 bytes");
   useDevice(S);
   PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
   S->tc = PbTimeCorr();
   if (!lags) return PB_OK;
-  const int rc = allocate(S, S->tc, lags);
+  rc = allocate(S, S->tc, lags);
   if (rc != PB_OK) {  // (a ring that took the last free memory, say): whatever was made goes, the correlation stays off
     S->tc = PbTimeCorr();
     (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
     return rc;
   }
-  const long long qa = (long long)rintf(overlapRadius * 1048576.0f);  // exact scaling, at most 2^31 - 128
+  const long long qa = pbFixedQuantise(overlapRadius);
   S->tc.interval = interval, S->tc.lags = lags, S->tc.radius = overlapRadius, S->tc.a2 = (unsigned long long)(qa * qa);
   S->tc.steps.assign(lags, 0ull);
   S->tc.origins.assign(lags, 0ull);
@@ -205,17 +170,17 @@ int pbSimSetTimeCorrelation(pbSim *S, float interval, unsigned lags, float overl
 }
 
 int pbSimTimeCorrelationRecord(pbSim *S) {
-  if (!S) return fail("pbSimTimeCorrelationRecord", ": null handle");
-  if (!S->tc.ring) return fail("pbSimTimeCorrelationRecord", ": the correlation is off");
+  if (!S) return pbFail("pbSimTimeCorrelationRecord", ": null handle");
+  if (!S->tc.ring) return pbFail("pbSimTimeCorrelationRecord", ": the correlation is off");
   useDevice(S);
   return pbTimeCorrRecord(S);
 }
 
 int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float *overlapRadius,
                                 unsigned long long *records) {
-  if (!S) return fail("pbSimGetTimeCorrelationInfo", ": null handle");
+  if (!S) return pbFail("pbSimGetTimeCorrelationInfo", ": null handle");
   if (!interval && !lags && !overlapRadius && !records)
-    return fail("pbSimGetTimeCorrelationInfo", ": interval, lags, overlapRadius and records are all null");
+    return pbFail("pbSimGetTimeCorrelationInfo", ": interval, lags, overlapRadius and records are all null");
   if (interval) *interval = S->tc.interval;
   if (lags) *lags = S->tc.lags;
   if (overlapRadius) *overlapRadius = S->tc.radius;
@@ -224,8 +189,8 @@ int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float
 }
 
 int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
-  if (!S || !rows) return fail("pbSimGetTimeCorrelation", ": null handle or rows");
-  if (!S->tc.ring) return fail("pbSimGetTimeCorrelation", ": the correlation is off");
+  if (!S || !rows) return pbFail("pbSimGetTimeCorrelation", ": null handle or rows");
+  if (!S->tc.ring) return pbFail("pbSimGetTimeCorrelation", ": the correlation is off");
   useDevice(S);
   const size_t cells = (size_t)S->nsims * S->tc.lags;
   std::vector<unsigned long long> acc(cells * T_COLS);
@@ -234,7 +199,7 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
   PB_TRY(hipStreamSynchronize(S->stream));
   for (size_t k = 0; k < cells; k++)
     if (acc[k * T_COLS + T_SAMPLES] >= (1ull << 31))  // the counts are exact whatever the state: the other sums may not be
-      return fail("pbSimGetTimeCorrelation", ": a lag holds 2^31 samples or more: restart the correlation");
+      return pbFail("pbSimGetTimeCorrelation", ": a lag holds 2^31 samples or more: restart the correlation");
   for (size_t k = 0; k < cells; k++) {
     const unsigned long long *w = &acc[k * T_COLS];
     const unsigned lag = (unsigned)(k % S->tc.lags);
@@ -243,25 +208,16 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
     r.origins = S->tc.origins[lag], r.sum_steps = S->tc.sumSteps[lag];
     r.samples = w[T_SAMPLES];
     r.sum_qx = (long long)w[T_QX], r.sum_qy = (long long)w[T_QY];
-    r.msd = normalised((__int128)w[T_MSD_LO] + (__int128)w[T_MSD_HI] * ((__int128)1 << 32));
-    r.vacf = normalised((__int128)w[T_VACF_LO] + (__int128)(long long)w[T_VACF_HI] * ((__int128)1 << 32));
+    r.msd = pbFixedNormalised(pbFixedCompose(w[T_MSD_LO], w[T_MSD_HI]));
+    r.vacf = pbFixedNormalised(pbFixedCompose(w[T_VACF_LO], w[T_VACF_HI]));
     r.overlap = w[T_OVERLAP], r.max_q2 = w[T_MAX_Q2];
   }
   return PB_OK;
 }
 
 int pbSimGetTimeCorrelationTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
-  if (!S) return fail("pbSimGetTimeCorrelationTimes", ": null handle");
-  if (records) *records = S->tc.records;
-  if (last_device_ms) {
-    *last_device_ms = 0.0f;
-    if (S->tc.timed) {
-      useDevice(S);
-      PB_TRY(hipEventSynchronize(S->tc.ev1));
-      PB_TRY(hipEventElapsedTime(last_device_ms, S->tc.ev0, S->tc.ev1));
-    }
-  }
-  return PB_OK;
+  if (!S) return pbFail("pbSimGetTimeCorrelationTimes", ": null handle");
+  return pbSpanGet(S, S->tc.clock, S->tc.records, records, last_device_ms);
 }
 
 }  // extern "C"
