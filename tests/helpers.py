@@ -25,6 +25,55 @@ def simparams_from_orc(P):
     return make_params(d)
 
 
+def with_geometry(P, gx, gy, cell=None, origin=None, wall_half=None):
+    """A copy of an OrcParams with the grid geometry set AFTER orc_params_derive (which only makes squares with
+    equal cell edges and origins): gridSizeX/Y and numCells = gx * gy, and, where given, cellSizeX/Y = cell,
+    worldOriginX/Y = origin and wallHalf.  simparams_from_orc forwards all of them."""
+    Q = type(P).from_buffer_copy(P)
+    Q.gridSizeX, Q.gridSizeY, Q.numCells = int(gx), int(gy), int(gx) * int(gy)
+    if cell is not None:
+        Q.cellSizeX, Q.cellSizeY = float(cell[0]), float(cell[1])
+    if origin is not None:
+        Q.worldOriginX, Q.worldOriginY = float(origin[0]), float(origin[1])
+    if wall_half is not None:
+        Q.wallHalf = float(wall_half)
+    return Q
+
+
+# The grid shapes the geometry tests share: name -> (gridX, gridY, cell, origin, walls).  None keeps what
+# orc_params_derive gave (cell = 2 max_radius, origin -64, walls 64); "fit" makes the grid cover the arena exactly.
+GEOMETRIES = {
+    "g8": (8, 8, None, None, None),            # 545-fold aliasing under the +-64 walls, wrap everywhere, 6 key bits
+    "g8fit": (8, 8, None, "fit", "fit"),       # nothing aliases; every bot within two cells of a wall and the wrap
+    "g16": (16, 16, None, None, None),         # 8 key bits: exactly one full radix pass
+    "g32": (32, 32, None, None, None),         # 10 bits: two passes
+    "r8x64": (8, 64, None, None, None),
+    "r64x8": (64, 8, None, None, None),
+    "r16x512": (16, 512, None, None, None),    # gridXLog2 = 4 under a tall grid
+    "aniso": (64, 8, (0.235, 0.31), (-3.0, -64.0), None),
+}
+
+
+def geometry(P, name):
+    """P under the named geometry of GEOMETRIES."""
+    gx, gy, cell, origin, wall = GEOMETRIES[name]
+    if origin == "fit":   # the grid spans [-G/2 cell, G/2 cell) and the walls stand on its edge (exact: powers of two)
+        half = (np.float32(gx // 2) * np.float32(P.cellSizeX), np.float32(gy // 2) * np.float32(P.cellSizeY))
+        assert half[0] == half[1]
+        origin, wall = (-half[0], -half[1]), half[0]
+    return with_geometry(P, gx, gy, cell, origin, wall)
+
+
+def wrap_centre(P, near=3.0):
+    """A point on a wrap line of the grid in x and in y (origin + k * gridSize * cellSize), the one nearest to `near`
+    with k >= 1: a blob centred there straddles both wraps."""
+    out = []
+    for o, g, c in ((P.worldOriginX, P.gridSizeX, P.cellSizeX), (P.worldOriginY, P.gridSizeY, P.cellSizeY)):
+        period = float(g) * float(c)
+        out.append(float(o) + max(1, round((near - float(o)) / period)) * period)
+    return tuple(out)
+
+
 def bits(a):
     a = np.ascontiguousarray(a)
     return a.view(np.uint32) if a.dtype == np.float32 else a

@@ -331,11 +331,16 @@ BLOB_SIZES = (1, 2, 63, 65, TILE - 1, TILE + 1, 4 * TILE + 1, 64 * TILE - 7)
 DRIFT = np.float32([0.9, 0.5])   # |drift| = 1.03: far above the hold speed 1e-6 and above mu g dt = 0.022
 
 
-def make_params(orc, n, **kw):
+def make_params(orc, n, geometry=None, **kw):
+    """geometry: a name of helpers.GEOMETRIES, applied after the derive step (which only makes square grids)"""
     base = dict(nCells=n, nDead=0, seed=7, phase_std=0.0, max_time=1e9, light_x=-3.0, light_y=2.0,
                 phase_update_interval=FAR_PUI)
     base.update(kw)
-    return orc.default_params(**base)
+    P = orc.default_params(**base)
+    if geometry is not None:
+        import helpers
+        P = helpers.geometry(P, geometry)
+    return P
 
 
 def ladder_gaps(npairs):
@@ -460,6 +465,8 @@ def _spec(name):
         return {}, 700, (lambda orc, P: pile_state()), 0.0
     if name == "wrap":
         return {}, 3000, (lambda orc, P: blob_state(3000, 0.16, 5, center=(57.0, 61.0))), 0.0
+    if name.startswith("geom_"):   # the wrap blob on a small, a rectangular and an anisotropic grid
+        return dict(geometry=name[5:]), 3000, (lambda orc, P: blob_state(3000, 0.16, 5, center=(57.0, 61.0))), 0.0
     if name == "alias":
         return dict(arena_half=2000.0, grid=512), 3600, (lambda orc, P: alias_state()), 2000.0
     if name.startswith("batch"):
@@ -475,7 +482,8 @@ LADDERS = ("ladder", "ladder_alt", "ladder_noattr") + tuple(f"ladder_payload{k}"
 BLOBS = tuple(f"blob_{n}_{s}" for n in BLOB_SIZES for s in (16, 17))
 RESTS = tuple(f"rest_{n}_{s}" for n, s in ((4 * TILE + 1, 16), (4 * TILE + 1, 17), (64 * TILE - 7, 16)))
 BATCH = tuple(f"batch{m}" for m in range(3))
-STEP_INPUTS = LADDERS + BLOBS + ("blob_payload",) + RESTS + ("pile", "wrap", "alias") + BATCH
+GEOMS = ("geom_g8", "geom_r8x64", "geom_aniso")
+STEP_INPUTS = LADDERS + BLOBS + ("blob_payload",) + RESTS + ("pile", "wrap", "alias") + BATCH + GEOMS
 
 
 @functools.lru_cache(maxsize=None)

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import assert_bit_equal, jittered_blob, simparams_from_orc
+from helpers import assert_bit_equal, geometry, jittered_blob, simparams_from_orc
 
 pytestmark = pytest.mark.gpu
 
@@ -59,11 +59,27 @@ def test_integrate(pb, orc, wall):
     del keep
 
 
+GRIDS = ["g8", "g32", "aniso"]   # helpers.GEOMETRIES: 6 and 10 key bits (one and two sort passes), unequal axes
+
+
 def test_hash_sort_reorder(pb, orc):
     """calcHash (impl.cuh:446-465) with negative / wrapped cells, the stable sort
     (particlebot_cuda.cu:377-382) and reorderDataAndFindCellStart (impl.cuh:469-538)."""
+    hash_sort_reorder(pb, orc, None)
+
+
+@pytest.mark.parametrize("grid", GRIDS)
+def test_hash_sort_reorder_on_small_and_anisotropic_grids(pb, orc, grid):
+    """The same chain on 8 x 8 (every cell aliased, one radix pass, the result copied back), 32 x 32 (two passes,
+    sorted in place) and 64 x 8 with cells 0.235 x 0.31 and origin (-3, -64)."""
+    hash_sort_reorder(pb, orc, grid)
+
+
+def hash_sort_reorder(pb, orc, grid):
     rng = np.random.default_rng(2)
     P = orc.default_params(nCells=20000, nDead=0, seed=2)
+    if grid is not None:
+        P = geometry(P, grid)
     n, G = P.nCells, P.numCells
     pos, vel, rad = jittered_blob(n, 0.16, rng, center=(5.0, 0.0))
     # a few bots far away: beyond the 120.3-wide grid span (wrap aliasing) and left of the origin
@@ -210,8 +226,21 @@ def test_collide(pb, orc, name):
     """collide (impl.cuh:657-831): contact spring/dashpot/shear, the three attraction regimes,
     circle + rectangle obstacles, payload factors, static/kinetic friction, scatter to original
     index.  Inputs go through the real hash -> sort -> reorder chain first."""
+    collide(pb, orc, name, None)
+
+
+@pytest.mark.parametrize("grid", GRIDS)
+@pytest.mark.parametrize("name", ["plain", "payload", "circles", "rects"])
+def test_collide_on_small_and_anisotropic_grids(pb, orc, name, grid):
+    """The same on 8 x 8 (a bot's 25 cells hold 25/64 of all bots), 32 x 32 and the anisotropic 64 x 8 grid."""
+    collide(pb, orc, name, grid)
+
+
+def collide(pb, orc, name, grid):
     rng = np.random.default_rng(6)
     P = variants(orc)[name]
+    if grid is not None:
+        P = geometry(P, grid)
     n, G = P.nCells, P.numCells
     keep = upload_params(pb, P)
     pos, vel, rad = jittered_blob(n, 0.158, rng, center=(0.5, 0.6), jitter=0.12)

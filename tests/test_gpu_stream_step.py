@@ -22,7 +22,10 @@ rounded up (profiles/stream_step_errors.txt has every figure):
     absForce_a        1.00  (every input)                                             2
     rad               1.00  (both actuation inputs, fused and in two calls)           2
 
-662 figures in all, none above 1.12: nothing to explain (a ratio above 8 would point to a wrong term).
+662 figures in all, none above 1.12: nothing to explain (a ratio above 8 would point to a wrong term).  The three
+inputs on small, rectangular and anisotropic grids (geom_g8, geom_r8x64, geom_aniso: 60 figures more) were measured
+afterwards under the same K: vel 1.25 at most (geom_aniso, maximum; 2 x 1.25 still rounds up to 3), absForce_r 1.00,
+absForce_a 1.00 -- also with the 1187 candidates per bot of the 8 x 8 grid.
 
 Where the yardstick is 0 (an output that is exactly 0 in every build, e.g. Sum|F_attr| of a bot without candidates)
 the kernel must give exactly 0 too.  Bots excluded by a decision margin still have to be finite and within one jump
@@ -232,6 +235,30 @@ def test_pile_wrap_alias(pb, name, walk):
         h = sr.cell_hashes(orclib, inp["P"], inp["pos1"]) % inp["P"].gridSizeX
         assert (h < 3).any() and (h > inp["P"].gridSizeX - 4).any()
     run_step(pb, name, False, walk, sums=1)
+
+
+@pytest.mark.parametrize("walk", [0, 1])
+@pytest.mark.parametrize("sums", [0, 1])
+@pytest.mark.parametrize("name", sr.GEOMS)
+def test_small_rectangular_and_anisotropic_grids(pb, name, sums, walk):
+    """the wrap blob on an 8 x 8 grid (every cell aliased 545-fold under the +-64 walls: 1187 candidates per bot,
+    half of the bots wrap in x), on 8 x 64 and on 64 x 8 with cells 0.235 x 0.31 and origin (-3, -64)"""
+    inp = sr.step_input(name)
+    P = inp["P"]
+    gx = int(P.gridSizeX)
+    h = sr.cell_hashes(orclib, P, inp["pos1"]).astype(np.int64)
+    cx = np.sort(h, kind="stable") % gx
+    wraps = (cx < 2) | (cx >= gx - 2)           # the bot's stencil rows split in two at the x-wrap (nseg == 2)
+    assert wraps.any() and not wraps.all()
+    if name == "geom_g8":
+        assert wraps.mean() >= 0.25
+        if walk == 1:
+            # a wave is 64 consecutive slots of the sorted order (lanes behind the last bot shadow it): it takes the
+            # flattened walk only when none of its bots wraps
+            pad = np.concatenate([wraps, np.full(-len(wraps) % 64, wraps[-1])]).reshape(-1, 64)
+            falls_back = pad.any(1)
+            assert falls_back.any() and not falls_back.all(), falls_back.mean()
+    run_step(pb, name, False, walk, sums=sums)
 
 
 # ---- f. a batch ---------------------------------------------------------------------------------------------------
