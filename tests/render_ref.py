@@ -49,6 +49,8 @@ def _box(v, c, pr):
 def _paint_disc(img, V, x, y, r, rgb):
     cx, cy = V.px(x), V.py(y)
     pr = f32(f32(r) * V.scale)
+    if not (np.isfinite(cx) and np.isfinite(cy) and np.isfinite(pr)):
+        return  # the rule of _paint_many's `ok`: such a disc paints nothing
     (x0, x1), (y0, y1) = _box(V.w, cx, pr), _box(V.h, cy, pr)
     if x0 > x1 or y0 > y1:
         return
