@@ -256,6 +256,11 @@ class Particlebot {
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on
    * nx or ny outside 1 ... PB_FIELD_MAX_AXIS and on a view whose half extents are not finite and > 0. */
   bool fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals);
+  /* The structure factor of the resident state on the device (pbSimStructureFactor, include/particlebot_hip.h has the
+   * definition): one row of exact integer phasor sums per wavevector (2 pi / 2^boxLog2)(nx, ny) of `vectors`, which
+   * holds nx, ny pairs.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also
+   * false on an unknown kind, on boxLog2 outside -8 ... 12 and on fewer than 1 or more than PB_SK_MAX_VECTORS pairs. */
+  bool structureFactor(int kind, int boxLog2, const std::vector<int> &vectors, std::vector<pbStructureFactorRow> &rows);
   /* Extension: the reference's display state (off by default; call before reset()).  Legacy engine: POSITION / RADII
    * carry the reference's centroid_steps + 1 display entries, a colour buffer of (nCells + centroid_steps + 1) x 4
    * floats with the reference's fills (particlebot.cpp:105-141) exists, and every update runs calcCOG and updateCol at

@@ -835,6 +835,79 @@ int pbSimFieldMapOf(pbSim *sim, unsigned member, const pbFieldView *view, pbFiel
                     pbFieldTotals *totals /* 1 entry, may be NULL */);
 int pbSimGetFieldTimes(pbSim *sim, unsigned long long *maps, float *last_device_ms);
 
+/* Structure factor on the device (csrc/pb_sfactor.hip, csrc/pb_phasor.hpp): the reciprocal-space companion of the
+ * analyses above.  Per member and wavevector of a caller's list the call returns rho(k) = sum a exp(i k.r) over the
+ * bots as exact integers: the phasor of a bot is one entry of an integer cosine/sine table, chosen by integer
+ * arithmetic on the quantised position, so no transcendental is evaluated and every sum can be compared with ==.
+ * Nothing is allocated or launched unless a structure factor is asked for.
+ * NODES.  All nCells bots of a member are nodes, dead bots and the payload bot included.
+ * QUANTISATION.  pbSimMoments': q = (long long)rint(v * 1048576.0f) of a value with fabsf(v) < 2048.0f, in fp32 scaling,
+ * round to nearest even.  It gives qx, qy from the position, qr from rad, and wx, wy from the velocity.
+ * KINDS.  PB_SK_DENSITY: weight a = 1; a bot is MEASURED iff x and y are in range.  PB_SK_RADIUS: a = qr; measured iff
+ * x, y and rad are in range.  PB_SK_VELOCITY: two weights, a = wx and a2 = wy; measured iff x, y, vx and vy are in
+ * range.  A NaN or an infinity is out of range.  An unmeasured bot takes part in nothing.
+ * WAVEVECTORS.  The box is L = 2^e with the integer e = boxLog2, PB_SK_MIN_LOG2 <= e <= PB_SK_MAX_LOG2; L = 4096 is the
+ * whole measured range.  The caller passes nvec integer pairs (nx, ny), each any int; the wavevector is
+ * k = (2 pi / L)(nx, ny).
+ * TURN OF A BOT.  All arithmetic is on 32-bit unsigned words and wraps mod 2^32:
+ *     u = (uint32)nx * (uint32)qx + (uint32)ny * (uint32)qy
+ *     t = u << (12 - e)                          k.r / 2 pi mod 1 as a 32-bit binary fraction
+ *     idx = ((t + 0x80000u) >> 20) & 4095u       the phase rounded to the nearest of 4096 table steps
+ * so huge |n| are well defined: they alias, as they must.
+ * THE TABLE (PB_PHASOR_BITS = 12).  C[j] = rint(cos(2 pi j / 4096) * 2^30), S[j] = rint(sin(2 pi j / 4096) * 2^30), both
+ * int, and S[j] = C[(j - 1024) & 4095].  The table is a property of the library, not of the host's libm: every entry
+ * is at least 7e-4 away from a rounding tie, and the CRC-32 (zlib) of the 4096 interleaved little-endian int32 pairs
+ * (C[j], S[j]) is 3228437924.  pbPhasorTable exports it (2 * 4096 ints, interleaved; PB_ERR_ARG on a NULL pointer or
+ * cap < 8192), so tests and callers see exactly what the device adds.
+ * PER MEMBER AND WAVEVECTOR, over the measured bots, one pbStructureFactorRow: nx, ny as passed; measured;
+ *     re = sum a * C[idx],   im = sum a * S[idx],   and for PB_SK_VELOCITY re2, im2 with a2 (zero otherwise)
+ * each a signed 128-bit sum as pbMoment128, value hi * 2^32 + lo, NORMALISED by the host to 0 <= lo < 2^32 with hi the
+ * floor quotient.  Units: 2^-30 for PB_SK_DENSITY, 2^-50 otherwise.  The caller forms
+ * S(k) = (re^2 + im^2) / (2^60 * measured) from the integers.
+ * EXACTNESS.  |a * C| <= 2^61 and a batch has fewer than 2^28 bots, so with the two's-complement split of pbSimMoments
+ * the low accumulator stays below 2^60 and the rest below 2^57 (PB_SK_DENSITY adds |C| <= 2^30 to one 64-bit word,
+ * below 2^58): nothing wraps, whatever the state.  Integer adds commute: results do not depend on slot
+ * order, on the kernel form or on the order in which the device adds.  No float atomics and no 128-bit atomics.
+ * ERROR AGAINST THE CONTINUOUS DEFINITION (derived, not measured).  Per bot the phase is off by at most pi / 4096 from
+ * the table step plus 2 pi (|nx| + |ny|) 2^-21 / L from the position quantum, and the entry by 2^-30 from its rounding:
+ *     |rho_device / 2^30 - rho_float64| <= measured * (pi / 4096 + 2 pi (|nx| + |ny|) 2^-21 / L + 2^-30)
+ * for PB_SK_DENSITY when u does not wrap.  The mean amplitude loss is sinc(pi / 4096), about 1 - 1e-7.
+ * pbSimStructureFactor computes every member's rows with the same list; pbSimStructureFactorOf one member's nvec rows.
+ * pbSimGetStructureFactorTimes: analyses so far and the span of the last one's launches on the batch's stream in
+ * milliseconds (HIP events), as pbSimGetFieldTimes; either pointer may be NULL.
+ * A call only reads: the state, slot layout, keys, cell lists, pbSimStats, time, RNG, the mark, the series, the time
+ * correlation and every other analysis' scratch stay as they were.
+ * PB_ERR_ARG, before the device is touched: a NULL handle, vectors or rows; an unknown kind; boxLog2 outside
+ * PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2; nvec outside 1 ... PB_SK_MAX_VECTORS; a member out of range; nsims * nvec * 80
+ * above 2^31 bytes (pbSimStructureFactorOf counts one member); a batch of 2^28 bots or more.
+ * Cost: measured * nvec table look-ups with 64-bit adds.  The launch grid is (tile of 256 wavevectors, bot chunk,
+ * member), at most PB_SK_BLOCKS chunks per member.  A workgroup of 256 lanes keeps the table in LDS (32 KiB, cosine and
+ * sine interleaved), stages 256 quantised bots at a time (posrad, and velocities for PB_SK_VELOCITY, in slot order,
+ * coalesced; the original indices are never read) and walks them: every lane owns one wavevector, keeps its sums in
+ * registers and reads the same bot as its neighbours, so nothing is reduced per (bot, k); at the end a lane adds its
+ * sums into the (member, k) cell with 64-bit integer atomics.  Scratch: the table and the list (32 KiB each), 4 bytes
+ * per member, and 16 / 32 / 64 bytes per member and wavevector (density / radius / velocity) of the largest call so
+ * far, allocated by the first call, grown when a call needs more, freed by pbSimDestroy.
+ * Out of scope: the self-intermediate scattering function and any per-lag k-space quantity; phase moments, phase
+ * correlations and phase fields on the table; a finer table or an angle-addition refinement; radial averaging of S(k)
+ * and normalisations; records inside the series ring; the ensemble layer's summary rows; the legacy engine. */
+#define PB_SK_MAX_VECTORS 4096u
+enum { PB_SK_MIN_LOG2 = -8, PB_SK_MAX_LOG2 = 12 };
+#define PB_SK_BLOCKS 256u /* bot chunks per member and tile of wavevectors: one pass covers 65536 bots of a member */
+#define PB_PHASOR_BITS 12
+enum { PB_SK_DENSITY = 0, PB_SK_RADIUS = 1, PB_SK_VELOCITY = 2 };
+typedef struct pbStructureFactorRow {   /* 80 bytes */
+  int nx, ny;                           /* the wavevector's integers, as passed */
+  unsigned measured, reserved;          /* measured bots of the member (the same in all its rows); 0 */
+  pbMoment128 re, im, re2, im2;         /* units of 2^-30 (density) or 2^-50; re2, im2 zero unless PB_SK_VELOCITY */
+} pbStructureFactorRow;
+int pbSimStructureFactor(pbSim *sim, int kind, int boxLog2, const int *vectors /* 2 * nvec */, unsigned nvec,
+                         pbStructureFactorRow *rows /* nsims * nvec, member-major */);
+int pbSimStructureFactorOf(pbSim *sim, unsigned member, int kind, int boxLog2, const int *vectors, unsigned nvec,
+                           pbStructureFactorRow *rows /* nvec */);
+int pbSimGetStructureFactorTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+int pbPhasorTable(int *cosSin /* 2 * 4096, interleaved */, unsigned cap);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

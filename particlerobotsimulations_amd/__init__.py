@@ -16,7 +16,46 @@ from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
-           "connected_correlation", "time_correlation_summary", "field_values"]
+           "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
+           "half_plane_vectors", "phasor_table"]
+
+
+def phasor_table():
+    """The phasor table the device adds (pbPhasorTable): an int32 array (4096, 2), row j = (C[j], S[j]) =
+    (rint(cos(2 pi j / 4096) 2^30), rint(sin(2 pi j / 4096) 2^30)).  Needs no GPU."""
+    table = np.zeros((_capi.PHASOR_STEPS, 2), np.int32)
+    _capi.check(_capi.lib().pbPhasorTable(_capi.np_ptr(table), table.size), "pbPhasorTable")
+    return table
+
+
+def half_plane_vectors(nmax):
+    """All (nx, ny) with |nx|, |ny| <= nmax and (ny > 0 or (ny == 0 and nx > 0)) as an int32 array (2 nmax^2 + 2 nmax, 2):
+    one of every pair k, -k (S(-k) adds nothing), without (0, 0)."""
+    nmax = int(nmax)
+    if nmax < 0:
+        raise ValueError("half_plane_vectors: nmax must be >= 0")
+    out = [(nx, 0) for nx in range(1, nmax + 1)]
+    out += [(nx, ny) for ny in range(1, nmax + 1) for nx in range(-nmax, nmax + 1)]
+    return np.array(out, np.int32).reshape(-1, 2)
+
+
+def structure_factor_values(rows):
+    """The rows of structure_factor() as a dict of arrays of the rows' shape: nx, ny, measured as they are; re, im, re2,
+    im2 as object arrays of Python ints composed from their 128 bits (hi * 2^32 + lo; units of 2^-30 for the density,
+    2^-50 otherwise); and "s" = (re^2 + im^2) / (2^60 measured) as floats, NaN where nothing was measured: S(k) for
+    the density."""
+    from fractions import Fraction
+    rows = np.asarray(rows)
+    out = {name: rows[name] for name in ("nx", "ny", "measured")}
+    for name in ("re", "im", "re2", "im2"):
+        flat = [(int(h) << 32) + int(l) for h, l in zip(rows[name + "_hi"].reshape(-1), rows[name + "_lo"].reshape(-1))]
+        big = np.empty(len(flat), object)
+        big[:] = flat
+        out[name] = big.reshape(rows.shape)
+    s = [float(Fraction(re * re + im * im, int(m) << 60)) if m else float("nan")
+         for re, im, m in zip(out["re"].reshape(-1), out["im"].reshape(-1), rows["measured"].reshape(-1))]
+    out["s"] = np.array(s, np.float64).reshape(rows.shape)
+    return out
 
 
 def radial_distribution(counts, r_max, density, n):
@@ -811,6 +850,39 @@ class Sim:
         """(field maps computed so far, device milliseconds of the last one's launches)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetFieldTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetFieldTimes")
+        return int(n.value), float(ms.value)
+
+    def structure_factor(self, vectors, box_log2, kind="density", member=None):
+        """The structure factor of every member's state as it is now, on the device (pbSimStructureFactor): per member
+        and wavevector k = (2 pi / 2^box_log2)(nx, ny) of `vectors`, an (nvec, 2) array of ints, the exact integer sums
+        of a exp(i k.r) over the measured bots, the phasor being an entry of phasor_table().  kind: "density" (a = 1),
+        "radius" (a = the quantised radius) or "velocity" (a = wx into re / im, wy into re2 / im2).  Returns a
+        structured array (nsims, nvec) of nx, ny, measured and re_lo / re_hi, im_lo / im_hi, re2_lo / re2_hi, im2_lo /
+        im2_hi (each 128-bit value is hi * 2^32 + lo with 0 <= lo < 2^32; units of 2^-30 for the density, 2^-50
+        otherwise; structure_factor_values() composes them and S(k)).  With member=k only that member's (nvec,) rows
+        (pbSimStructureFactorOf)."""
+        vec, code = _capi.sk_vectors(vectors), _capi.sk_kind(kind)
+        nvec = vec.shape[0]
+        nsims = int(getattr(self, "nsims", 1)) if member is None else 1
+        fits = 1 <= nvec <= _capi.SK_MAX_VECTORS and nsims * nvec * 80 <= 1 << 31
+        shape = (nvec,) if fits else (1,)  # (a call that the engine refuses gets no buffer to speak of)
+        held = vec if nvec else np.zeros((1, 2), np.int32)  # (an empty list still has an address; the engine refuses it)
+        ptr = _capi.np_ptr(held)
+        if member is not None:
+            rows = np.zeros(shape, _capi.SK_ROW_DTYPE)
+            _capi.check(_capi.lib().pbSimStructureFactorOf(self._h, int(member), code, int(box_log2), ptr, nvec,
+                                                           _capi.np_ptr(rows)), "pbSimStructureFactorOf")
+            return rows
+        rows = np.zeros((nsims,) + shape, _capi.SK_ROW_DTYPE)
+        _capi.check(_capi.lib().pbSimStructureFactor(self._h, code, int(box_log2), ptr, nvec, _capi.np_ptr(rows)),
+                    "pbSimStructureFactor")
+        return rows
+
+    def structure_factor_times(self):
+        """(structure factors computed so far, device milliseconds of the last one's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetStructureFactorTimes(self._h, C.byref(n), C.byref(ms)),
+                    "pbSimGetStructureFactorTimes")
         return int(n.value), float(ms.value)
 
 

@@ -223,6 +223,39 @@ def field_totals(t):
     return {name: int(getattr(t, name)) for name, _ in pbFieldTotals._fields_}
 
 
+class pbStructureFactorRow(C.Structure):
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("measured", C.c_uint), ("reserved", C.c_uint),
+                ("re", pbMoment128), ("im", pbMoment128), ("re2", pbMoment128), ("im2", pbMoment128)]
+
+
+# pbStructureFactorRow as a numpy record: each 128-bit value is hi * 2^32 + lo, normalised to 0 <= lo < 2^32
+SK_ROW_DTYPE = np.dtype([("nx", np.int32), ("ny", np.int32), ("measured", np.uint32), ("reserved", np.uint32),
+                         ("re_lo", np.uint64), ("re_hi", np.int64), ("im_lo", np.uint64), ("im_hi", np.int64),
+                         ("re2_lo", np.uint64), ("re2_hi", np.int64), ("im2_lo", np.uint64), ("im2_hi", np.int64)])
+SK_KINDS = {"density": 0, "radius": 1, "velocity": 2}
+SK_MAX_VECTORS = 4096
+PHASOR_STEPS = 4096
+
+
+def sk_kind(kind):
+    """PB_SK_* of a kind given by name or by number; a number the engine does not know goes through for it to refuse."""
+    if isinstance(kind, str):
+        if kind not in SK_KINDS:
+            raise ValueError("structure_factor: kind must be 'density', 'radius' or 'velocity', not %r" % (kind,))
+        return SK_KINDS[kind]
+    return int(kind)
+
+
+def sk_vectors(vectors):
+    """The caller's wavevectors as a C-contiguous (nvec, 2) int32 array; every entry must be an int32's."""
+    v = np.asarray(vectors)
+    if v.ndim != 2 or v.shape[1] != 2 or v.dtype.kind not in "iu":
+        raise ValueError("structure_factor: vectors must be an (nvec, 2) array of integers")
+    if v.size and (int(v.min()) < -(1 << 31) or int(v.max()) >= 1 << 31):
+        raise ValueError("structure_factor: every nx and ny must fit an int")
+    return np.ascontiguousarray(v, np.int32)
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -314,6 +347,10 @@ SYMBOLS = {
     "pbSimFieldMap": (_I, [_VP, C.POINTER(pbFieldView), _VP, C.POINTER(pbFieldTotals)]),
     "pbSimFieldMapOf": (_I, [_VP, _U, C.POINTER(pbFieldView), _VP, C.POINTER(pbFieldTotals)]),
     "pbSimGetFieldTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimStructureFactor": (_I, [_VP, _I, _I, _VP, _U, _VP]),
+    "pbSimStructureFactorOf": (_I, [_VP, _U, _I, _I, _VP, _U, _VP]),
+    "pbSimGetStructureFactorTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbPhasorTable": (_I, [_VP, _U]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

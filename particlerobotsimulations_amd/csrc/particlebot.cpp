@@ -1536,6 +1536,18 @@ bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &ce
   });
 }
 
+bool Particlebot::structureFactor(int kind, int boxLog2, const std::vector<int> &vectors,
+                                  std::vector<pbStructureFactorRow> &rows) {
+  return onFusedEngine("structureFactor", "structure factor", [&] {
+    const size_t nvec = vectors.size() / 2;
+    const bool fits = nvec >= 1 && nvec <= PB_SK_MAX_VECTORS;
+    rows.assign(fits ? nvec : 1, pbStructureFactorRow());
+    const int none[2] = {0, 0};  // (the engine takes no NULL; it refuses an empty list and one that is too long)
+    const unsigned count = (unsigned)(nvec <= PB_SK_MAX_VECTORS ? nvec : PB_SK_MAX_VECTORS + 1u);
+    return pbSimStructureFactor(sim, kind, boxLog2, nvec ? vectors.data() : none, count, rows.data());
+  });
+}
+
 bool Particlebot::writeFramePPMDevice(const char *path, int width, int height, float centerX, float centerY,
                                       float halfExtent, float lightRadius, bool referenceStyle) {
   if (!path || !renderFrame(frameV, width, height, centerX, centerY, halfExtent, lightRadius, referenceStyle))

@@ -447,6 +447,17 @@ int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFiel
   return 0;
 }
 
+// the structure factor of the resident state (Particlebot::structureFactor; fused engine only): nvec 80-byte
+// pbStructureFactorRow entries for the nvec (nx, ny) pairs of `vectors`.  -1 on the other engines and on a bad argument.
+int pbHostStructureFactor(void *hv, int kind, int boxLog2, const int *vectors, unsigned nvec, pbStructureFactorRow *rows) {
+  if (!vectors || !rows) return -1;
+  std::vector<pbStructureFactorRow> r;
+  if (!((HostSim *)hv)->bot->structureFactor(kind, boxLog2, std::vector<int>(vectors, vectors + 2 * (size_t)nvec), r))
+    return -1;
+  copyOut(rows, r);
+  return 0;
+}
+
 void pbHostSetDisplay(void *hv, int on) { ((HostSim *)hv)->bot->setDisplay(on != 0); }
 
 // the centroid ring (2 centroid_steps floats), the slots' start times and the record count; -1 with display off

@@ -14,12 +14,14 @@
 //   pb_moments.hip   time series: integer moment rows per member, now or recorded while stepping (pbSimSetSeries)
 //   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a ring of snapshots (pbSimSetTimeCorrelation)
 //   pb_field.hip     field maps: count, dead and integer sums of radius and velocity per grid cell (pbSimFieldMap)
+//   pb_sfactor.hip   structure factor: integer phasor sums per member and wavevector (pbSimStructureFactor)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 //   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of, and
 //                    the span clock (two events around a span of launches)
 //   pb_fixed.hpp     the fixed-point kit of the integer analyses: quantiser, split accumulators, wave and workgroup
 //                    sums, the host's way back to a pbMoment128; the one statement of their bound
+//   pb_phasor.hpp    the phasor kit of the reciprocal-space analyses: the turn of a bot, its table index, the table
 #pragma once
 
 #include <string>
@@ -107,6 +109,18 @@ struct PbField {
   unsigned long long maps = 0;
 };
 
+// structure factor (pb_sfactor.hip): the phasor table, the wavevectors and the sums of the largest call so far, made
+// by the first call (pbSimStructureFactor)
+struct PbSfactor {
+  PbDevBuf<int2> table;                // the 4096 (cos, sin) entries of pb_phasor.hpp
+  PbDevBuf<int2> vectors;              // PB_SK_MAX_VECTORS (nx, ny) pairs
+  PbDevBuf<unsigned long long> cells;  // 2 / 4 / 8 words per member and wavevector of the call in flight
+  PbDevBuf<uint32_t> measured;         // one word per member
+  std::vector<unsigned long long> host;  // the read-back before it is written as rows
+  PbSpanClock clock;                   // around the last analysis' launches
+  unsigned long long analyses = 0;
+};
+
 // Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
 // and go last.
 struct pbSim {
@@ -186,6 +200,7 @@ struct pbSim {
   PbSpanClock momClock;
   PbTimeCorr tc;
   PbField field;
+  PbSfactor sk;
   pbSimStats stats{};
 };
 

@@ -9,6 +9,7 @@
 //                   [--correlate FILE [--correlate-kind velocity|radius] [--correlate-rmax R] [--correlate-bins B]]
 //                   [--timecorr FILE [--timecorr-interval T] [--timecorr-lags N] [--timecorr-overlap A]]
 //                   [--field FILE [--field-cells N] [--field-half H]]
+//                   [--sk FILE [--sk-kind density|radius|velocity] [--sk-box-log2 E] [--sk-nmax M]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -90,6 +91,14 @@
 // the lowest y: time as %.9g, step the steps taken so far, every other number the integer it is (the sums in units of
 // 2^-20, rr and vv of 2^-40, in decimal from their 128 bits as --correlate prints them).  (The usage line does not list
 // these three either.)
+// --sk FILE appends, at every dump time, one block of the device's structure factor of the state
+// (Particlebot::structureFactor): the wavevectors (2 pi / 2^E)(nx, ny) of the half plane ny > 0 || (ny == 0 && nx > 0)
+// with |nx|, |ny| <= --sk-nmax M (default 16: 544 vectors; 1 ... 44, 45 would pass PB_SK_MAX_VECTORS), the box
+// --sk-box-log2 E (default the smallest E with 2^E >= twice the wall half extent, at most 12; -8 ... 12) and the weight
+// --sk-kind density|radius|velocity (default density).  A block is the line `time,<%.9g>,step,<steps so far>,kind,<kind>,
+// box_log2,<E>,vectors,<count>` and then one line per vector, `nx,ny,measured,re,im,re2,im2`, every number the integer it
+// is (units of 2^-30 for the density, 2^-50 otherwise, in decimal from their 128 bits, signed).  (The usage line does
+// not list these four either.)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -199,6 +208,10 @@ int main(int argc, char **argv) {
   std::string fieldPath;
   long fieldCells = 64;
   float fieldHalf = 0.0f;  // 0: the wall half extent, once the configuration is loaded
+  std::string skPath;
+  int skKind = PB_SK_DENSITY;
+  long skBoxLog2 = 0, skNmax = 16;
+  bool skBoxGiven = false;  // else: the smallest box that holds the walls, once the configuration is loaded
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -289,6 +302,23 @@ int main(int argc, char **argv) {
       if (end == argv[i] || *end || fieldCells < 1 || fieldCells > (long)PB_FIELD_MAX_AXIS) badArg = true;
     } else if (!strcmp(argv[i], "--field-half") && i + 1 < argc) {
       badArg = !parseFloat(argv[++i], 0.0f, true, fieldHalf);
+    } else if (!strcmp(argv[i], "--sk") && i + 1 < argc) {
+      skPath = argv[++i];
+    } else if (!strcmp(argv[i], "--sk-kind") && i + 1 < argc) {
+      const char *kind = argv[++i];
+      if (!strcmp(kind, "density")) skKind = PB_SK_DENSITY;
+      else if (!strcmp(kind, "radius")) skKind = PB_SK_RADIUS;
+      else if (!strcmp(kind, "velocity")) skKind = PB_SK_VELOCITY;
+      else badArg = true;
+    } else if (!strcmp(argv[i], "--sk-box-log2") && i + 1 < argc) {
+      char *end = nullptr;
+      skBoxLog2 = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || skBoxLog2 < PB_SK_MIN_LOG2 || skBoxLog2 > PB_SK_MAX_LOG2) badArg = true;
+      skBoxGiven = true;
+    } else if (!strcmp(argv[i], "--sk-nmax") && i + 1 < argc) {
+      char *end = nullptr;
+      skNmax = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || skNmax < 1 || skNmax > 44) badArg = true;  // (45: 4140 vectors, past PB_SK_MAX_VECTORS)
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -321,7 +351,7 @@ int main(int argc, char **argv) {
       {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
       {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"},
       {"--correlate", correlatePath, "analysis"}, {"--timecorr", timecorrPath, "recorder"},
-      {"--field", fieldPath, "analysis"}};
+      {"--field", fieldPath, "analysis"},         {"--sk", skPath, "analysis"}};
   for (const auto &f : fusedOnly)
     if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
       fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
@@ -424,6 +454,7 @@ int main(int argc, char **argv) {
   long lastCkptStep = stepsDone;
   bool referenceMarked = false;
   float markTime = 0.0f;
+  std::vector<int> skVectors;  // --sk: the (nx, ny) pairs, made at the first dump time
   // the time series: switched on here, behind a resume, so that the records start at the run's first step; drained at
   // every host stop below
   unsigned long long seriesWritten = 0;
@@ -520,6 +551,28 @@ int main(int argc, char **argv) {
                 decimal128(c.vv).c_str());
       }
       if (fclose(ff) != 0) return 1;
+    }
+    if (!skPath.empty() && sim.dumpDue(cfg.dump_interval)) {
+      if (skVectors.empty()) {  // the run's first dump time: the half plane ny > 0 || (ny == 0 && nx > 0), and the box
+        for (int nx = 1; nx <= (int)skNmax; nx++) skVectors.push_back(nx), skVectors.push_back(0);
+        for (int ny = 1; ny <= (int)skNmax; ny++)
+          for (int nx = -(int)skNmax; nx <= (int)skNmax; nx++) skVectors.push_back(nx), skVectors.push_back(ny);
+        if (!skBoxGiven) {
+          skBoxLog2 = PB_SK_MIN_LOG2;
+          while (skBoxLog2 < PB_SK_MAX_LOG2 && std::ldexp(1.0, (int)skBoxLog2) < 2.0 * (double)cfg.wallHalf()) skBoxLog2++;
+        }
+      }
+      std::vector<pbStructureFactorRow> rows;
+      if (!sim.structureFactor(skKind, (int)skBoxLog2, skVectors, rows)) return 1;
+      FILE *kf = openOutput(skPath, sim.getTime() == 0.0f ? "w" : "a");
+      if (!kf) return 1;
+      static const char *const kinds[] = {"density", "radius", "velocity"};
+      fprintf(kf, "time,%.9g,step,%ld,kind,%s,box_log2,%ld,vectors,%zu\n", (double)sim.getTime(), stepsDone, kinds[skKind],
+              skBoxLog2, rows.size());
+      for (const pbStructureFactorRow &r : rows)
+        fprintf(kf, "%d,%d,%u,%s,%s,%s,%s\n", r.nx, r.ny, r.measured, decimal128(r.re).c_str(), decimal128(r.im).c_str(),
+                decimal128(r.re2).c_str(), decimal128(r.im2).c_str());
+      if (fclose(kf) != 0) return 1;
     }
     if (!rearrangePath.empty() && sim.dumpDue(cfg.dump_interval)) {
       if (!referenceMarked) {  // the run's first dump time

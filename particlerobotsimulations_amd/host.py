@@ -61,6 +61,7 @@ _ANALYSES = {
     "pbHostTimeCorrelationInfo": [_P, _P, _P, _P],
     "pbHostTimeCorrelationRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
     "pbHostFieldMap": [_P, _P, _P],
+    "pbHostStructureFactor": [C.c_int, C.c_int, _P, C.c_uint, _P],
 }
 
 
@@ -454,6 +455,19 @@ class HostSim:
                                "half extents > 0")
         totals = [_capi.field_totals(tot)]
         return (cells, totals) if member is None else (cells[int(member)], totals[int(member)])
+
+    def structure_factor(self, vectors, box_log2, kind="density", member=None):
+        """The structure factor of the state as it is now, on the device (pbSimStructureFactor; fused engine only): the
+        rows as Sim.structure_factor gives them, shaped (1, nvec), or (nvec,) for member=0."""
+        vec, code = _capi.sk_vectors(vectors), _capi.sk_kind(kind)
+        nvec = vec.shape[0]
+        fits = 1 <= nvec <= _capi.SK_MAX_VECTORS
+        rows = np.zeros((1, nvec if fits else 1), _capi.SK_ROW_DTYPE)
+        held = vec if nvec else np.zeros((1, 2), np.int32)
+        if lib().pbHostStructureFactor(self._h, code, int(box_log2), _ptr(held), nvec, _ptr(rows)) != 0:
+            raise RuntimeError("structure_factor: the structure factor needs the fused engine, a known kind, box_log2 "
+                               "in -8 ... 12 and 1 ... 4096 vectors")
+        return rows if member is None else rows[int(member)]
 
     def save_checkpoint(self, path):
         rc = lib().pbHostSaveCheckpoint(self._h, os.fsencode(path))
