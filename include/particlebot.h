@@ -251,6 +251,19 @@ class Particlebot {
   bool timeCorrelationRecord();
   bool timeCorrelationInfo(float &interval, unsigned &lags, float &overlapRadius, unsigned long long &records);
   bool timeCorrelationRows(std::vector<pbTimeCorrelationRow> &rows);
+  /* The self-intermediate scattering function of the resident state on the device (pbSimSetScattering /
+   * pbSimGetScattering, include/particlebot_hip.h has the definitions): setScattering(interval, lags, boxLog2, vectors)
+   * starts a device ring of `lags` snapshots of the quantised positions, taken as the time correlation takes its own
+   * (0: every step, -1: only by scatteringRecord), and a table of exact integer phasor sums per lag and wavevector
+   * (2 pi / 2^boxLog2)(nx, ny) of `vectors`, which holds nx, ny pairs; lags 0 switches it off.  scatteringRecord takes
+   * one record now; scatteringInfo gives interval, lags, boxLog2, the vectors' count and the records taken so far;
+   * scatteringRows the lags * nvec rows, lag-major.  Fused engine only: Legacy and HostOnly instances return false with
+   * a message on stderr.  Also false on a bad interval, lags, boxLog2 or list, and for a record or a read with the
+   * scattering off.  The scattering is not part of a checkpoint. */
+  bool setScattering(float interval, unsigned lags, int boxLog2, const std::vector<int> &vectors);
+  bool scatteringRecord();
+  bool scatteringInfo(float &interval, unsigned &lags, int &boxLog2, unsigned &nvec, unsigned long long &records);
+  bool scatteringRows(std::vector<pbScatteringRow> &rows);
   /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
    * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on

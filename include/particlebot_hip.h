@@ -755,7 +755,8 @@ int pbSimGetCorrelationTimes(pbSim *sim, unsigned long long *analyses, float *la
  * 16-byte loads in original order, at most PB_TCORR_BLOCKS workgroups of 256 lanes per member and lag, each adding its
  * nine sums into the cell with one set of 64-bit integer atomics.
  * Out of scope: logarithmic or multi-tau lag spacing; the non-Gaussian parameter (sum s^2 does not fit the exact
- * scheme); the self-intermediate scattering function and phase correlations (they need a transcendental); per-bot
+ * scheme); phase correlations (they need a transcendental; the self-intermediate scattering function does not any more:
+ * pbSimSetScattering, below); per-bot
  * outputs; neighbour-based quantities per lag such as bond lifetime; recording inside the resident kernel without ending
  * the stretch; the ensemble layer's summary rows and its RCCL gather; the legacy engine. */
 #define PB_TCORR_MAX_LAGS 64u
@@ -888,7 +889,8 @@ int pbSimGetFieldTimes(pbSim *sim, unsigned long long *maps, float *last_device_
  * sums into the (member, k) cell with 64-bit integer atomics.  Scratch: the table and the list (32 KiB each), 4 bytes
  * per member, and 16 / 32 / 64 bytes per member and wavevector (density / radius / velocity) of the largest call so
  * far, allocated by the first call, grown when a call needs more, freed by pbSimDestroy.
- * Out of scope: the self-intermediate scattering function and any per-lag k-space quantity; phase moments, phase
+ * Out of scope: per-lag k-space quantities other than the self-intermediate scattering function (pbSimSetScattering,
+ * below); phase moments, phase
  * correlations and phase fields on the table; a finer table or an angle-addition refinement; radial averaging of S(k)
  * and normalisations; records inside the series ring; the ensemble layer's summary rows; the legacy engine. */
 #define PB_SK_MAX_VECTORS 4096u
@@ -907,6 +909,93 @@ int pbSimStructureFactorOf(pbSim *sim, unsigned member, int kind, int boxLog2, c
                            pbStructureFactorRow *rows /* nvec */);
 int pbSimGetStructureFactorTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
 int pbPhasorTable(int *cosSin /* 2 * 4096, interleaved */, unsigned cap);
+
+/* Self-intermediate scattering on the device (csrc/pb_scatter.hip): where the time correlations and the phasor kit meet.
+ *     F_s(k, tau) = < (1/N) sum_i exp(i k . (r_i(t + tau) - r_i(t))) >_t
+ * per member, lag and wavevector of a caller's list, averaged over time origins while pbSimStep runs, as exact integers:
+ * relaxation times at a chosen wavelength, caging, and a k-resolved separation of collective drift (the imaginary part)
+ * from rearrangement (the decay of the real part).  The ring, the records and the pairing are the time correlation's
+ * (pbSimSetTimeCorrelation, above); the turn, the index and the table are the structure factor's.  Off by default: a run
+ * that does not ask for it makes the same launches, has the same pbSimStats and the same bits.
+ * pbSimSetScattering(sim, interval, lags, boxLog2, vectors, nvec).  interval follows the time correlation's rules
+ * exactly: > 0 the schedule's gate, 0 every step, -1.0f manual only.  lags is 1 ... PB_SCATTER_MAX_LAGS; lags == 0
+ * switches off and frees everything (boxLog2, vectors and nvec are then not read).  boxLog2 is e of the box L = 2^e,
+ * PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2.  vectors holds nvec int pairs (nx, ny), nvec 1 ... PB_SCATTER_MAX_VECTORS, each any
+ * int; k = (2 pi / L)(nx, ny).  The list is copied at the call.  Calling again restarts from record 0.
+ * A RECORD is taken at the same instant and describes the same state as a time-correlation record.  It stores, per bot
+ * of every member in ORIGINAL order, the quantised position (qx, qy) = (rint(x * 2^20), rint(y * 2^20)) (pbSimMoments'
+ * quantisation, units of 2^-20): 8 bytes per bot and ring slot, into slot r % lags.  A bot whose x or y is out of range
+ * (not fabsf(.) < 2048.0f; a NaN or an infinity is out of range) is stored as UNMEASURED (qx == INT32_MIN, which no
+ * measured bot has: |q| <= 2^31 - 128).  Quantising once at the snapshot means that the pairing does not do it up to 64
+ * times.
+ * A PAIR (now, then) of a bot is MEASURED iff both instants are.  Then, on 32-bit unsigned words mod 2^32,
+ *     u   = nx * (qx_now - qx_then) + ny * (qy_now - qy_then)      == u_now - u_then of the structure factor's turn
+ *     t   = u << (12 - e);   idx = ((t + 0x80000u) >> 20) & 4095u
+ *     re += C[idx];   im += S[idx]                                  the structure factor's table, nothing new
+ * The displacement here is the DIFFERENCE OF THE QUANTISED POSITIONS, not the quantised fp32 difference that the time
+ * correlation uses: only this choice makes the turn linear in the position and exact.
+ * PAIRING.  Record r is paired with the records r - l for l = 0 ... min(r, lags - 1).  Lag 0 pairs a record with itself:
+ * re = samples * 2^30, im = 0.
+ * PER MEMBER, LAG AND WAVEVECTOR one pbScatteringRow: lag in RECORDS; nx, ny as passed; origins, sum_steps and samples
+ * as in pbTimeCorrelationRow (samples is the same for every vector of a member and lag); re and im in units of 2^-30.
+ * The caller forms F_s = re / (2^30 samples) and the imaginary part likewise.
+ * EXACTNESS.  |C|, |S| <= 2^30, so a cell with fewer than 2^31 samples keeps |re|, |im| < 2^61 in one signed 64-bit
+ * word: no split accumulators, no float atomics, no 128-bit atomics.  Integer adds commute: results do not depend on
+ * slot order, on the kernel form that stepped or on the order in which the device adds.  pbSimGetScattering checks the
+ * counts it is about to return, and if a cell holds 2^31 samples or more it answers PB_ERR_ARG ("a lag holds 2^31
+ * samples or more: restart the scattering") and writes no rows.
+ * ERROR AGAINST THE CONTINUOUS DEFINITION (derived, not measured).  Per measured pair the phase is off by at most
+ *     pi / 4096  +  2 pi (|nx| + |ny|) 2^-20 / L
+ * (the table step, plus two position quanta of 2^-21 each per axis, one per instant), and the table entry by 2^-30 from
+ * its rounding; cos and sin have slope at most 1, so, when u does not wrap,
+ *     |re / (2^30 samples) - mean cos(k . dr)| <= pi / 4096 + 2 pi (|nx| + |ny|) 2^-20 / L + 2^-30
+ * with dr the float64 difference of the fp32 positions, and the same for im and sin.
+ * OTHER CALLS.  pbSimScatteringRecord: one record now, of the state as it is, whatever the interval.
+ * pbSimGetScatteringInfo: interval, lags (0: off), boxLog2, nvec and the records taken so far; any pointer may be NULL,
+ * not all.  pbSimGetScattering: nsims * lags * nvec rows, member-major, then the lag, then the vector in list order; a
+ * lag that no record has reached yet has origins == 0 and zeros.  pbSimGetScatteringTimes: records so far and the span of
+ * the last record's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
+ * When several records are due in front of a step the order is: series, time correlation, scattering.  No launch is
+ * fused across the scattering's gate and a resident stretch ends in front of it, as for the other two.
+ * The scattering ring is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it alone;
+ * pbSimDestroy frees it.  Recording never waits for the device.  It only reads: the state, slot layout, keys, cell
+ * lists, pbSimStats, time, RNG, the mark, the series, the time correlation and every other analysis' scratch stay as
+ * they were.
+ * PB_ERR_ARG, before the device is touched: a NULL handle, vectors or rows; interval NaN, infinite, or negative other
+ * than -1; lags > PB_SCATTER_MAX_LAGS; boxLog2 outside PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2; nvec outside
+ * 1 ... PB_SCATTER_MAX_VECTORS; a ring above 2^33 bytes (lags x total x 8); a table above 2^31 bytes (nsims x lags x
+ * nvec x 16); a batch of 2^28 bots or more or of more than 65535 members; the pointers of pbSimGetScatteringInfo all
+ * NULL; a record or a read with the scattering off.
+ * Cost: a record is one pass over posrad and original indices in slot order that scatters 8 bytes per bot into the ring,
+ * and one launch for all lags: one workgroup of 256 lanes per (member, lag, bot block), at most PB_SCATTER_BLOCKS blocks
+ * per member and lag.  A workgroup keeps the table in LDS (32 KiB), stages 256 displacements at a time from coalesced
+ * 8-byte loads of the two snapshots and walks them with its lanes laid out as (stripe, vector): nvec is rounded up to a
+ * power of two Vp, and 256 / Vp stripes each take their share of the tile, so that 8 ... 64 vectors keep every lane
+ * busy.  A lane owns one vector and keeps re and im in registers; at the end the stripes of a wave are folded with
+ * shuffles and one lane per wave and vector adds into the cell with 64-bit integer atomics.  Read back: 16 bytes per
+ * (member, lag, vector) and 8 per (member, lag).
+ * Out of scope: the coherent F(k, tau) (a product of two rho(k) sums does not fit the exact scheme; a caller can form it
+ * from pbSimStructureFactor per record); chi_4; weights other than 1; logarithmic lag spacing; the ensemble layer's
+ * summary rows; the legacy engine. */
+#define PB_SCATTER_MAX_LAGS 64u
+#define PB_SCATTER_MAX_VECTORS 256u
+#define PB_SCATTER_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
+typedef struct pbScatteringRow {       /* 56 bytes */
+  unsigned lag;                        /* lag in RECORDS: record r against record r - lag */
+  int nx, ny;                          /* the wavevector's integers, as passed */
+  unsigned reserved;                   /* 0 */
+  unsigned long long origins;          /* record pairs added so far (the same for every member and vector) */
+  unsigned long long sum_steps;        /* sum over those pairs of step(r) - step(r - lag) */
+  unsigned long long samples;          /* measured (bot, origin) pairs (the same for every vector of a member and lag) */
+  long long re, im;                    /* sum C[idx], sum S[idx]; units of 2^-30 */
+} pbScatteringRow;
+int pbSimSetScattering(pbSim *sim, float interval, unsigned lags, int boxLog2, const int *vectors /* 2 * nvec */,
+                       unsigned nvec);
+int pbSimScatteringRecord(pbSim *sim);   /* one record now, of the state as it is */
+int pbSimGetScatteringInfo(pbSim *sim, float *interval, unsigned *lags, int *boxLog2, unsigned *nvec,
+                           unsigned long long *records);
+int pbSimGetScattering(pbSim *sim, pbScatteringRow *rows /* nsims * lags * nvec: member, lag, vector */);
+int pbSimGetScatteringTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a

@@ -17,7 +17,7 @@ from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
            "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
-           "half_plane_vectors", "phasor_table"]
+           "half_plane_vectors", "phasor_table", "scattering_summary"]
 
 
 def phasor_table():
@@ -112,6 +112,19 @@ def time_correlation_summary(row, lag0=None):
             "vacf": float(Fraction(vacf, m * two)),
             "vacf_normalised": norm,
             "overlap": float(Fraction(int(row["overlap"]), m))}
+
+
+def scattering_summary(row):
+    """What one row of scattering() says, in float64 from the integers (pure Python; every quotient is formed as one
+    exact fraction and converted once): fs_re = re / (2^30 samples), the self-intermediate scattering function
+    F_s(k, lag); fs_im = im / (2^30 samples), its imaginary part (collective drift along k);
+    mean_lag_steps = sum_steps / origins.  The first two are None for a row with no samples, the last for one with no
+    origins."""
+    from fractions import Fraction
+    m, origins = int(row["samples"]), int(row["origins"])
+    return {"fs_re": float(Fraction(int(row["re"]), m << 30)) if m else None,
+            "fs_im": float(Fraction(int(row["im"]), m << 30)) if m else None,
+            "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else None}
 
 
 def field_values(cells):
@@ -883,6 +896,51 @@ class Sim:
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetStructureFactorTimes(self._h, C.byref(n), C.byref(ms)),
                     "pbSimGetStructureFactorTimes")
+        return int(n.value), float(ms.value)
+
+    def set_scattering(self, interval, lags, box_log2, vectors):
+        """Keep a device ring of `lags` snapshots of the quantised positions (original order), one taken in front of
+        every step whose start time passes the schedule's gate at `interval` (0: every step, -1: only by
+        scattering_record()) while step() runs, and add every record against the `lags` latest ones into a table per
+        member, lag and wavevector k = (2 pi / 2^box_log2)(nx, ny) of `vectors`, an (nvec, 2) array of ints, nvec
+        1 ... 256 (pbSimSetScattering): the self-intermediate scattering function as exact integer phasor sums.
+        Restarts at record 0; lags 0 switches it off (vectors may then be None).  Recording changes no state bit."""
+        if int(lags) == 0 and vectors is None:
+            vec = np.zeros((0, 2), np.int32)
+        else:
+            vec = _capi.sk_vectors(vectors)
+        held = vec if vec.shape[0] else np.zeros((1, 2), np.int32)  # (an empty list still has an address)
+        _capi.check(_capi.lib().pbSimSetScattering(self._h, float(interval), int(lags), int(box_log2),
+                                                   _capi.np_ptr(held), vec.shape[0]), "pbSimSetScattering")
+
+    def scattering_record(self):
+        """One record now, of the state as it is (pbSimScatteringRecord)."""
+        _capi.check(_capi.lib().pbSimScatteringRecord(self._h), "pbSimScatteringRecord")
+
+    def scattering_info(self):
+        """A dict of interval, lags (0: off), box_log2, nvec and records taken so far (pbSimGetScatteringInfo)."""
+        i, l, e, k, r = C.c_float(0.0), C.c_uint(0), C.c_int(0), C.c_uint(0), C.c_ulonglong(0)
+        _capi.check(_capi.lib().pbSimGetScatteringInfo(self._h, C.byref(i), C.byref(l), C.byref(e), C.byref(k),
+                                                       C.byref(r)), "pbSimGetScatteringInfo")
+        return {"interval": float(i.value), "lags": int(l.value), "box_log2": int(e.value), "nvec": int(k.value),
+                "records": int(r.value)}
+
+    def scattering(self):
+        """The table as it stands (pbSimGetScattering): per member a list over lags (lag 0 first) of lists over the
+        vectors (list order) of dicts of Python ints: lag, nx, ny, origins, sum_steps, samples, re, im (units of 2^-30).
+        scattering_summary() turns a row into F_s."""
+        info = self.scattering_info()
+        lags, nvec = info["lags"], info["nvec"]
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbScatteringRow * max(nsims * lags * nvec, 1))()
+        _capi.check(_capi.lib().pbSimGetScattering(self._h, rows), "pbSimGetScattering")
+        return [[[_capi.scattering_row(rows[(m * lags + l) * nvec + k]) for k in range(nvec)] for l in range(lags)]
+                for m in range(nsims)]
+
+    def scattering_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetScatteringTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetScatteringTimes")
         return int(n.value), float(ms.value)
 
 

@@ -256,6 +256,21 @@ def sk_vectors(vectors):
     return np.ascontiguousarray(v, np.int32)
 
 
+class pbScatteringRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("nx", C.c_int), ("ny", C.c_int), ("reserved", C.c_uint),
+                ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong), ("samples", C.c_ulonglong),
+                ("re", C.c_longlong), ("im", C.c_longlong)]
+
+
+SCATTER_MAX_LAGS = 64
+SCATTER_MAX_VECTORS = 256
+
+
+def scattering_row(r):
+    """A pbScatteringRow as a dict of Python ints (reserved left out); re and im are in units of 2^-30."""
+    return {name: int(getattr(r, name)) for name, _ in pbScatteringRow._fields_ if name != "reserved"}
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -351,6 +366,12 @@ SYMBOLS = {
     "pbSimStructureFactorOf": (_I, [_VP, _U, _I, _I, _VP, _U, _VP]),
     "pbSimGetStructureFactorTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbPhasorTable": (_I, [_VP, _U]),
+    "pbSimSetScattering": (_I, [_VP, _F, _U, _I, _VP, _U]),
+    "pbSimScatteringRecord": (_I, [_VP]),
+    "pbSimGetScatteringInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_I), C.POINTER(_U),
+                                    C.POINTER(C.c_ulonglong)]),
+    "pbSimGetScattering": (_I, [_VP, C.POINTER(pbScatteringRow)]),
+    "pbSimGetScatteringTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

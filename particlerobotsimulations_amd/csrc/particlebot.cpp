@@ -1528,6 +1528,37 @@ bool Particlebot::timeCorrelationRows(std::vector<pbTimeCorrelationRow> &rows) {
   });
 }
 
+bool Particlebot::setScattering(float interval, unsigned lags, int boxLog2, const std::vector<int> &vectors) {
+  return onFusedEngine("setScattering", "scattering", [&] {
+    const size_t nvec = vectors.size() / 2;
+    const int none[2] = {0, 0};  // (the engine takes no NULL; it refuses an empty list and one that is too long)
+    const unsigned count = (unsigned)(nvec <= PB_SCATTER_MAX_VECTORS ? nvec : PB_SCATTER_MAX_VECTORS + 1u);
+    return pbSimSetScattering(sim, interval, lags, boxLog2, nvec ? vectors.data() : none, count);
+  });
+}
+
+bool Particlebot::scatteringRecord() {
+  return onFusedEngine("scatteringRecord", "scattering", [&] { return pbSimScatteringRecord(sim); });
+}
+
+bool Particlebot::scatteringInfo(float &interval, unsigned &lags, int &boxLog2, unsigned &nvec,
+                                 unsigned long long &records) {
+  auto call = [&] { return pbSimGetScatteringInfo(sim, &interval, &lags, &boxLog2, &nvec, &records); };
+  return onFusedEngine("scatteringInfo", "scattering", call);
+}
+
+bool Particlebot::scatteringRows(std::vector<pbScatteringRow> &rows) {
+  return onFusedEngine("scatteringRows", "scattering", [&] {
+    unsigned lags = 0, nvec = 0;
+    const int rc = pbSimGetScatteringInfo(sim, nullptr, &lags, nullptr, &nvec, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? (size_t)lags * nvec : 1, pbScatteringRow());  // (the engine takes no NULL; with the scattering off it refuses)
+    const int got = pbSimGetScattering(sim, rows.data());
+    if (got != PB_OK) rows.clear();
+    return got;
+  });
+}
+
 bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
   return onFusedEngine("fieldMap", "field map", [&] {
     const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;

@@ -436,6 +436,43 @@ int pbHostTimeCorrelationRows(void *hv, pbTimeCorrelationRow *rows, unsigned lon
   return 0;
 }
 
+// the self-intermediate scattering function of the resident state (Particlebot::setScattering / scatteringRecord /
+// scatteringInfo / scatteringRows; fused engine only): the recorder's switch, one record now, what it holds, and the
+// 56-byte pbScatteringRow of every lag and vector (cap entries of room; *count = how many there are).  -1 on the other
+// engines, a bad interval, lags, box or list, a record or a read with the scattering off, or too little room.
+int pbHostSetScattering(void *hv, float interval, unsigned lags, int boxLog2, const int *vectors, unsigned nvec) {
+  if (!vectors && nvec) return -1;
+  return ((HostSim *)hv)->bot->setScattering(interval, lags, boxLog2, std::vector<int>(vectors, vectors + 2 * (size_t)nvec))
+             ? 0
+             : -1;
+}
+
+int pbHostScatteringRecord(void *hv) { return ((HostSim *)hv)->bot->scatteringRecord() ? 0 : -1; }
+
+int pbHostScatteringInfo(void *hv, float *interval, unsigned *lags, int *boxLog2, unsigned *nvec,
+                         unsigned long long *records) {
+  float i = 0.0f;
+  unsigned l = 0, k = 0;
+  int e = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->scatteringInfo(i, l, e, k, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (boxLog2) *boxLog2 = e;
+  if (nvec) *nvec = k;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostScatteringRows(void *hv, pbScatteringRow *rows, unsigned long long cap, unsigned long long *count) {
+  std::vector<pbScatteringRow> v;
+  if (!count || !((HostSim *)hv)->bot->scatteringRows(v)) return -1;
+  *count = v.size();
+  if (rows && cap < v.size()) return -1;
+  copyOut(rows, v);
+  return 0;
+}
+
 // a field map of the resident state (Particlebot::fieldMap; fused engine only): ny * nx 64-byte pbFieldCell entries and,
 // unless NULL, the 16-byte pbFieldTotals row.  -1 on the other engines and on a bad view.
 int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFieldTotals *totals) {

@@ -625,12 +625,14 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   // the time series (pb_moments.hip): a record in front of every step whose start time passes the gate, or of every
   // step at interval 0.  A record reads the state in front of its step, which a launch that runs ahead never leaves on
   // the device: no launch is fused across a record's gate, and a resident stretch ends in front of one.
-  // The time correlations (pb_timecorr.hip) take their snapshot by the same rule (interval -1: by hand only).
-  const bool series = S->series.ring != nullptr, corr = S->tc.ring != nullptr;
-  const float si = S->series.interval, ti = S->tc.interval;
+  // The time correlations (pb_timecorr.hip) and the scattering (pb_scatter.hip) take their snapshots by the same rule
+  // (interval -1: by hand only).
+  const bool series = S->series.ring != nullptr, corr = S->tc.ring != nullptr, scat = S->sc.ring != nullptr;
+  const float si = S->series.interval, ti = S->tc.interval, ki = S->sc.interval;
   auto seriesGate = [&](float at) { return series && (si == 0.0f || gate(at, si, dt)); };
   auto corrGate = [&](float at) { return corr && (ti == 0.0f || (ti > 0.0f && gate(at, ti, dt))); };
-  auto recordDue = [&](float at) { return seriesGate(at) || corrGate(at); };  // a record in front of the step at `at`
+  auto scatGate = [&](float at) { return scat && (ki == 0.0f || (ki > 0.0f && gate(at, ki, dt))); };
+  auto recordDue = [&](float at) { return seriesGate(at) || corrGate(at) || scatGate(at); };  // a record in front of the step at `at`
   int k = 0;
   for (; k < nsteps; k++) {
     const float t = S->time;
@@ -642,6 +644,10 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
       }
       if (corrGate(t)) {
         const int rc = pbTimeCorrRecord(S);
+        if (rc) return rc;
+      }
+      if (scatGate(t)) {
+        const int rc = pbScatteringRecord(S);
         if (rc) return rc;
       }
       if (trail && gate(t, ci, dt)) {

@@ -15,6 +15,7 @@
 //   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a ring of snapshots (pbSimSetTimeCorrelation)
 //   pb_field.hip     field maps: count, dead and integer sums of radius and velocity per grid cell (pbSimFieldMap)
 //   pb_sfactor.hip   structure factor: integer phasor sums per member and wavevector (pbSimStructureFactor)
+//   pb_scatter.hip  self-intermediate scattering: integer phasor sums per member, lag and wavevector (pbSimSetScattering)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 //   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of, and
@@ -88,17 +89,35 @@ struct PbSeries {
   std::vector<float> times;               // per slot: start time of the step the record was taken in front of
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
+// The host's book of a ring of records that are paired lag by lag (pb_timecorr.hip, pb_scatter.hip): record r goes into
+// slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1).
+struct PbLagBook {
+  unsigned lags = 0;
+  unsigned long long records = 0;                     // records taken so far
+  std::vector<unsigned long long> steps;              // per slot: stats.steps at that moment
+  std::vector<unsigned long long> origins, sumSteps;  // per lag: record pairs added, and their step differences
+  void start(unsigned n) {
+    lags = n, records = 0;
+    steps.assign(n, 0ull), origins.assign(n, 0ull), sumSteps.assign(n, 0ull);
+  }
+  uint32_t slot() const { return (uint32_t)(records % lags); }  // where the next record goes
+  uint32_t paired() const { return (uint32_t)(records < lags - 1u ? records : lags - 1u) + 1u; }  // the lags it is paired with
+  void recorded(unsigned long long stepsNow) {  // the next record was taken at stats.steps == stepsNow
+    const uint32_t s = slot(), n = paired();
+    steps[s] = stepsNow;
+    for (uint32_t l = 0; l < n; l++) origins[l]++, sumSteps[l] += stepsNow - steps[(s + lags - l) % lags];
+    records++;
+  }
+};
 // time correlations (pb_timecorr.hip): the ring of snapshots and the table when on (pbSimSetTimeCorrelation)
 struct PbTimeCorr {
   PbDevBuf<float4> ring;                // lags x total, ORIGINAL order: record r at slot r % lags
   PbDevBuf<unsigned long long> table;   // nsims x lags cells of nine words, member-major
   float interval = 0.0f;                // 0: in front of every step; -1: manual records only
   float radius = 0.0f;
-  unsigned lags = 0;
-  unsigned long long a2 = 0, records = 0;  // rint(radius * 2^20) squared; records taken so far
-  std::vector<unsigned long long> steps;   // per slot: stats.steps at that moment
-  std::vector<unsigned long long> origins, sumSteps;  // per lag: record pairs added, and their step differences
-  PbSpanClock clock;                       // around the last record's launches
+  unsigned long long a2 = 0;            // rint(radius * 2^20) squared
+  PbLagBook book;                       // lags (0: off), records, steps per slot, origins and step sums per lag
+  PbSpanClock clock;                    // around the last record's launches
 };
 
 // field maps (pb_field.hip): the scratch of the largest map asked for so far, made by the first call (pbSimFieldMap)
@@ -119,6 +138,20 @@ struct PbSfactor {
   std::vector<unsigned long long> host;  // the read-back before it is written as rows
   PbSpanClock clock;                   // around the last analysis' launches
   unsigned long long analyses = 0;
+};
+
+// self-intermediate scattering (pb_scatter.hip): the ring of quantised snapshots and the table when on (pbSimSetScattering)
+struct PbScattering {
+  PbDevBuf<int2> ring;                 // lags x total, ORIGINAL order: record r at slot r % lags; (INT32_MIN, 0): unmeasured
+  PbDevBuf<unsigned long long> table;  // nsims x lags x nvec cells of (re, im), then nsims x lags sample counters
+  PbDevBuf<int2> phasors;              // the 4096 (cos, sin) entries of pb_phasor.hpp
+  PbDevBuf<int2> vectors;              // nvec (nx, ny) pairs
+  std::vector<int> list;               // the host's copy of the list, as passed
+  float interval = 0.0f;               // 0: in front of every step; -1: manual records only
+  unsigned nvec = 0;
+  int boxLog2 = 0;
+  PbLagBook book;                      // lags (0: off), records, steps per slot, origins and step sums per lag
+  PbSpanClock clock;                   // around the last record's launches
 };
 
 // Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
@@ -201,6 +234,7 @@ struct pbSim {
   PbTimeCorr tc;
   PbField field;
   PbSfactor sk;
+  PbScattering sc;
   pbSimStats stats{};
 };
 
@@ -276,3 +310,5 @@ void pbClusterFree(pbSim *S);
 int pbSeriesRecord(pbSim *S, float t);
 // one snapshot of every member, as it is now, into the ring's next slot and its lags into the table      pb_timecorr.hip
 int pbTimeCorrRecord(pbSim *S);
+// one quantised snapshot of every member, as it is now, into the ring's next slot and its lags into the table  pb_scatter.hip
+int pbScatteringRecord(pbSim *S);

@@ -1,4 +1,4 @@
-// pb_phasor.hpp -- the phasor kit of the reciprocal-space analyses (pb_sfactor.hip): exp(i k.r) of a bot as one entry of
+// pb_phasor.hpp -- the phasor kit of the reciprocal-space analyses (pb_sfactor.hip, pb_scatter.hip): exp(i k.r) as one entry of
 // an integer cosine/sine table, so that sums of phasors are integers like every other sum of the analysis layer.
 // The arithmetic part compiles as plain C++ (tests/pb_phasor_check.cpp); nothing here needs hipcc.
 //

@@ -10,6 +10,7 @@
 //                   [--timecorr FILE [--timecorr-interval T] [--timecorr-lags N] [--timecorr-overlap A]]
 //                   [--field FILE [--field-cells N] [--field-half H]]
 //                   [--sk FILE [--sk-kind density|radius|velocity] [--sk-box-log2 E] [--sk-nmax M]]
+//                   [--scatter FILE [--scatter-interval T] [--scatter-lags N] [--scatter-box-log2 E] [--scatter-nmax M]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -99,6 +100,18 @@
 // box_log2,<E>,vectors,<count>` and then one line per vector, `nx,ny,measured,re,im,re2,im2`, every number the integer it
 // is (units of 2^-30 for the density, 2^-50 otherwise, in decimal from their 128 bits, signed).  (The usage line does
 // not list these four either.)
+// --scatter FILE switches the device's self-intermediate scattering function on (Particlebot::setScattering): while the
+// engine steps, a snapshot of the quantised positions is taken in front of every step whose start time passes the
+// schedule's gate at --scatter-interval T (default dump_interval; 0: every step; finite and >= 0) into a device ring of
+// --scatter-lags N snapshots (default 32, 1 ... 64), and every record is added against the N latest ones into one row
+// per lag and wavevector: the integer phasor sums of every bot's displacement.  The wavevectors are --sk's half plane
+// with |nx|, |ny| <= --scatter-nmax M (default 3: 24 vectors; 1 ... 10, 11 would pass PB_SCATTER_MAX_VECTORS) in the box
+// --scatter-box-log2 E (default as --sk chooses it; -8 ... 12).  Switched on behind a resume, like --timecorr (the ring
+// is not part of a checkpoint).  At the end of the run FILE gets the header `Lag, Nx, Ny, Origins, SumSteps, Samples, Re,
+// Im, FsRe, FsIm`, then one line per lag and vector, lag 0 first, the vectors in list order: the integers as they are (Re
+// and Im in units of 2^-30), then FsRe = Re / (2^30 Samples) and FsIm likewise as %.9g (nan with no sample).  As with
+// --timecorr, a run whose records times nCells would reach 2^31 is refused when it starts (exit 2, "--scatter: ... 2^31
+// samples").  (The usage line does not list these five either.)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -212,6 +225,10 @@ int main(int argc, char **argv) {
   int skKind = PB_SK_DENSITY;
   long skBoxLog2 = 0, skNmax = 16;
   bool skBoxGiven = false;  // else: the smallest box that holds the walls, once the configuration is loaded
+  std::string scatterPath;
+  float scatterInterval = -1.0f;  // below 0: dump_interval, once the configuration is loaded
+  long scatterLags = 32, scatterBoxLog2 = 0, scatterNmax = 3;
+  bool scatterBoxGiven = false;  // else: as --sk chooses it
   bool badArg = false;
   double ckptEverySeconds = 0.0;
   long ckptEverySteps = 0, stopAfterSteps = -1;
@@ -319,6 +336,23 @@ int main(int argc, char **argv) {
       char *end = nullptr;
       skNmax = strtol(argv[++i], &end, 10);
       if (end == argv[i] || *end || skNmax < 1 || skNmax > 44) badArg = true;  // (45: 4140 vectors, past PB_SK_MAX_VECTORS)
+    } else if (!strcmp(argv[i], "--scatter") && i + 1 < argc) {
+      scatterPath = argv[++i];
+    } else if (!strcmp(argv[i], "--scatter-interval") && i + 1 < argc) {
+      badArg = !parseFloat(argv[++i], 0.0f, false, scatterInterval);
+    } else if (!strcmp(argv[i], "--scatter-lags") && i + 1 < argc) {
+      char *end = nullptr;
+      scatterLags = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || scatterLags < 1 || scatterLags > (long)PB_SCATTER_MAX_LAGS) badArg = true;
+    } else if (!strcmp(argv[i], "--scatter-box-log2") && i + 1 < argc) {
+      char *end = nullptr;
+      scatterBoxLog2 = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || scatterBoxLog2 < PB_SK_MIN_LOG2 || scatterBoxLog2 > PB_SK_MAX_LOG2) badArg = true;
+      scatterBoxGiven = true;
+    } else if (!strcmp(argv[i], "--scatter-nmax") && i + 1 < argc) {
+      char *end = nullptr;
+      scatterNmax = strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end || scatterNmax < 1 || scatterNmax > 10) badArg = true;  // (11: 264 vectors, past PB_SCATTER_MAX_VECTORS)
     } else if (!strcmp(argv[i], "--resume") && i + 1 < argc) {
       resumePath = argv[++i];
     } else if (!strcmp(argv[i], "--checkpoint") && i + 1 < argc) {
@@ -351,7 +385,8 @@ int main(int argc, char **argv) {
       {"--structure", structurePath, "analysis"}, {"--rdf", rdfPath, "analysis"},
       {"--rearrange", rearrangePath, "analysis"}, {"--series", seriesPath, "recorder"},
       {"--correlate", correlatePath, "analysis"}, {"--timecorr", timecorrPath, "recorder"},
-      {"--field", fieldPath, "analysis"},         {"--sk", skPath, "analysis"}};
+      {"--field", fieldPath, "analysis"},         {"--sk", skPath, "analysis"},
+      {"--scatter", scatterPath, "recorder"}};
   for (const auto &f : fusedOnly)
     if (!f.path.empty() && engine != Particlebot::Engine::Fused) {
       fprintf(stderr, "%s needs the fused engine (the %s runs on its resident state)\n", f.flag, f.noun);
@@ -480,6 +515,27 @@ int main(int argc, char **argv) {
     }
     if (!sim.setTimeCorrelation(every, (unsigned)timecorrLags, timecorrOverlap < 0.0f ? p.min_radius : timecorrOverlap))
       return 1;
+  }
+  // the scattering function: switched on here as well, and refused by the same count
+  if (!scatterPath.empty()) {
+    const float every = scatterInterval < 0.0f ? cfg.dump_interval : scatterInterval;
+    const double left = std::max(0.0, (double)p.max_time - (double)sim.getTime());
+    const double records = left / (double)(every > 0.0f ? every : cfg.timestep) + 2.0;  // (the gate's rounding: at most one more)
+    if (!(records * (double)p.nCells < 2147483648.0)) {
+      fprintf(stderr, "--scatter: about %.0f records of %u bots would pass 2^31 samples per lag: raise --scatter-interval "
+                      "or lower max_time\n", records, (unsigned)p.nCells);
+      return 2;
+    }
+    std::vector<int> vectors;  // the half plane ny > 0 || (ny == 0 && nx > 0), as --sk lists it
+    for (int nx = 1; nx <= (int)scatterNmax; nx++) vectors.push_back(nx), vectors.push_back(0);
+    for (int ny = 1; ny <= (int)scatterNmax; ny++)
+      for (int nx = -(int)scatterNmax; nx <= (int)scatterNmax; nx++) vectors.push_back(nx), vectors.push_back(ny);
+    if (!scatterBoxGiven) {
+      scatterBoxLog2 = PB_SK_MIN_LOG2;
+      while (scatterBoxLog2 < PB_SK_MAX_LOG2 && std::ldexp(1.0, (int)scatterBoxLog2) < 2.0 * (double)cfg.wallHalf())
+        scatterBoxLog2++;
+    }
+    if (!sim.setScattering(every, (unsigned)scatterLags, (int)scatterBoxLog2, vectors)) return 1;
   }
   auto drainSeries = [&]() {
     if (seriesPath.empty()) return true;
@@ -680,6 +736,21 @@ int main(int argc, char **argv) {
       fprintf(tf, "%u, %llu, %llu, %llu, %lld, %lld, %s, %s, %llu, %llu\n", r.lag, r.origins, r.sum_steps, r.samples,
               r.sum_qx, r.sum_qy, decimal128(r.msd).c_str(), decimal128(r.vacf).c_str(), r.overlap, r.max_q2);
     if (fclose(tf) != 0) return 1;
+  }
+  if (!scatterPath.empty()) {
+    std::vector<pbScatteringRow> rows;
+    if (!sim.scatteringRows(rows)) return 1;
+    FILE *kf = openOutput(scatterPath, "w");
+    if (!kf) return 1;
+    fprintf(kf, "Lag, Nx, Ny, Origins, SumSteps, Samples, Re, Im, FsRe, FsIm\n");
+    for (const pbScatteringRow &r : rows) {
+      const long double unit = 1073741824.0L * (long double)r.samples;  // (both operands are exact in a long double)
+      const double fsRe = r.samples ? (double)((long double)r.re / unit) : std::nan("");
+      const double fsIm = r.samples ? (double)((long double)r.im / unit) : std::nan("");
+      fprintf(kf, "%u, %d, %d, %llu, %llu, %llu, %lld, %lld, %.9g, %.9g\n", r.lag, r.nx, r.ny, r.origins, r.sum_steps,
+              r.samples, r.re, r.im, fsRe, fsIm);
+    }
+    if (fclose(kf) != 0) return 1;
   }
   if (!correlatePath.empty()) {
     const float rmax = correlateRmax > 0.0f ? correlateRmax : 10.0f * p.max_radius;

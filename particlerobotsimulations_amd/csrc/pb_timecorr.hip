@@ -115,8 +115,7 @@ int allocate(pbSim *S, PbTimeCorr &T, unsigned lags) {
 }  // namespace
 
 int pbTimeCorrRecord(pbSim *S) {
-  const uint32_t lags = S->tc.lags, slot = (uint32_t)(S->tc.records % lags);
-  const uint32_t nLags = (uint32_t)(S->tc.records < lags - 1u ? S->tc.records : lags - 1u) + 1u;
+  const uint32_t lags = S->tc.book.lags, slot = S->tc.book.slot(), nLags = S->tc.book.paired();
   const uint32_t perMember = cdiv(S->n, TT);
   const uint32_t bpl = perMember < PB_TCORR_BLOCKS ? perMember : PB_TCORR_BLOCKS;
   const int c = S->cur;
@@ -127,12 +126,7 @@ int pbTimeCorrRecord(pbSim *S) {
                      lags, slot, nLags, bpl, S->tc.a2, S->tc.table);
   PB_TRY(hipGetLastError());
   PB_TRY(S->tc.clock.stop(S->stream));
-  S->tc.steps[slot] = S->stats.steps;
-  for (uint32_t l = 0; l < nLags; l++) {
-    S->tc.origins[l]++;
-    S->tc.sumSteps[l] += S->stats.steps - S->tc.steps[(slot + lags - l) % lags];
-  }
-  S->tc.records++;
+  S->tc.book.recorded(S->stats.steps);
   return PB_OK;
 }
 
@@ -162,10 +156,8 @@ int pbSimSetTimeCorrelation(pbSim *S, float interval, unsigned lags, float overl
     return rc;
   }
   const long long qa = pbFixedQuantise(overlapRadius);
-  S->tc.interval = interval, S->tc.lags = lags, S->tc.radius = overlapRadius, S->tc.a2 = (unsigned long long)(qa * qa);
-  S->tc.steps.assign(lags, 0ull);
-  S->tc.origins.assign(lags, 0ull);
-  S->tc.sumSteps.assign(lags, 0ull);
+  S->tc.interval = interval, S->tc.radius = overlapRadius, S->tc.a2 = (unsigned long long)(qa * qa);
+  S->tc.book.start(lags);
   return PB_OK;
 }
 
@@ -182,9 +174,9 @@ int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float
   if (!interval && !lags && !overlapRadius && !records)
     return pbFail("pbSimGetTimeCorrelationInfo", ": interval, lags, overlapRadius and records are all null");
   if (interval) *interval = S->tc.interval;
-  if (lags) *lags = S->tc.lags;
+  if (lags) *lags = S->tc.book.lags;
   if (overlapRadius) *overlapRadius = S->tc.radius;
-  if (records) *records = S->tc.records;
+  if (records) *records = S->tc.book.records;
   return PB_OK;
 }
 
@@ -192,7 +184,7 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
   if (!S || !rows) return pbFail("pbSimGetTimeCorrelation", ": null handle or rows");
   if (!S->tc.ring) return pbFail("pbSimGetTimeCorrelation", ": the correlation is off");
   useDevice(S);
-  const size_t cells = (size_t)S->nsims * S->tc.lags;
+  const size_t cells = (size_t)S->nsims * S->tc.book.lags;
   std::vector<unsigned long long> acc(cells * T_COLS);
   PB_TRY(hipMemcpyAsync(acc.data(), S->tc.table, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost,
                         S->stream));
@@ -202,10 +194,10 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
       return pbFail("pbSimGetTimeCorrelation", ": a lag holds 2^31 samples or more: restart the correlation");
   for (size_t k = 0; k < cells; k++) {
     const unsigned long long *w = &acc[k * T_COLS];
-    const unsigned lag = (unsigned)(k % S->tc.lags);
+    const unsigned lag = (unsigned)(k % S->tc.book.lags);
     pbTimeCorrelationRow &r = rows[k];
     r.lag = lag, r.reserved = 0u;
-    r.origins = S->tc.origins[lag], r.sum_steps = S->tc.sumSteps[lag];
+    r.origins = S->tc.book.origins[lag], r.sum_steps = S->tc.book.sumSteps[lag];
     r.samples = w[T_SAMPLES];
     r.sum_qx = (long long)w[T_QX], r.sum_qy = (long long)w[T_QY];
     r.msd = pbFixedNormalised(pbFixedCompose(w[T_MSD_LO], w[T_MSD_HI]));
@@ -217,7 +209,7 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
 
 int pbSimGetTimeCorrelationTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
   if (!S) return pbFail("pbSimGetTimeCorrelationTimes", ": null handle");
-  return pbSpanGet(S, S->tc.clock, S->tc.records, records, last_device_ms);
+  return pbSpanGet(S, S->tc.clock, S->tc.book.records, records, last_device_ms);
 }
 
 }  // extern "C"

@@ -60,6 +60,9 @@ _ANALYSES = {
     "pbHostSetTimeCorrelation": [_F, C.c_uint, _F], "pbHostTimeCorrelationRecord": [],
     "pbHostTimeCorrelationInfo": [_P, _P, _P, _P],
     "pbHostTimeCorrelationRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
+    "pbHostSetScattering": [_F, C.c_uint, C.c_int, _P, C.c_uint], "pbHostScatteringRecord": [],
+    "pbHostScatteringInfo": [_P, _P, _P, _P, _P],
+    "pbHostScatteringRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
     "pbHostFieldMap": [_P, _P, _P],
     "pbHostStructureFactor": [C.c_int, C.c_int, _P, C.c_uint, _P],
 }
@@ -442,6 +445,43 @@ class HostSim:
             raise RuntimeError("time_correlation: the time correlation needs the fused engine, the correlation on and "
                                "fewer than 2^31 samples per lag")
         return [[_capi.time_correlation_row(r) for r in rows[:int(count.value)]]]
+
+    def set_scattering(self, interval, lags, box_log2, vectors):
+        """Keep a device ring of `lags` snapshots of the quantised positions, taken as the time correlation takes its
+        own, and sum the integer phasors of every bot's displacement per lag and wavevector
+        (2 pi / 2^box_log2)(nx, ny) of `vectors` over all time origins (pbSimSetScattering; fused engine only).
+        Restarts at record 0; lags 0 switches it off."""
+        vec = _capi.sk_vectors(vectors if vectors is not None else np.zeros((0, 2), np.int32))
+        held = vec if vec.shape[0] else np.zeros((1, 2), np.int32)
+        if lib().pbHostSetScattering(self._h, float(interval), int(lags), int(box_log2), _ptr(held), vec.shape[0]) != 0:
+            raise RuntimeError("set_scattering: the scattering needs the fused engine, a finite interval >= 0 (or -1), "
+                               "at most 64 lags, box_log2 in -8 ... 12 and 1 ... 256 vectors")
+
+    def scattering_record(self):
+        """One record now, of the state as it is (pbSimScatteringRecord; fused engine only)."""
+        if lib().pbHostScatteringRecord(self._h) != 0:
+            raise RuntimeError("scattering_record: the scattering needs the fused engine and the scattering on")
+
+    def scattering_info(self):
+        """A dict of interval, lags (0: off), box_log2, nvec and records taken so far (pbSimGetScatteringInfo; fused
+        engine only)."""
+        i, l, e, k, r = C.c_float(0.0), C.c_uint(0), C.c_int(0), C.c_uint(0), C.c_ulonglong(0)
+        if lib().pbHostScatteringInfo(self._h, C.byref(i), C.byref(l), C.byref(e), C.byref(k), C.byref(r)) != 0:
+            raise RuntimeError("scattering_info: the scattering needs the fused engine")
+        return {"interval": float(i.value), "lags": int(l.value), "box_log2": int(e.value), "nvec": int(k.value),
+                "records": int(r.value)}
+
+    def scattering(self):
+        """The table as it stands, as Sim.scattering gives it: a list with one list over lags of lists over the vectors
+        of dicts of Python ints (Particlebot::scatteringRows; fused engine only)."""
+        info = self.scattering_info()
+        lags, nvec = info["lags"], info["nvec"]
+        cap = max(lags * nvec, 1)
+        rows, count = (_capi.pbScatteringRow * cap)(), C.c_ulonglong(0)
+        if lib().pbHostScatteringRows(self._h, rows, cap, C.byref(count)) != 0:
+            raise RuntimeError("scattering: the scattering needs the fused engine, the scattering on and fewer than "
+                               "2^31 samples per lag")
+        return [[[_capi.scattering_row(rows[l * nvec + k]) for k in range(nvec)] for l in range(lags)]]
 
     def field_map(self, nx, ny, center, half, member=None):
         """A field map of the state as it is now, on the device (pbSimFieldMap; fused engine only): (cells, totals) as
