@@ -182,6 +182,49 @@ def test_headless_runner_binary(orc, tmp_path):
     assert open(ref, "rb").read() == out.read_bytes()
 
 
+# every output of the runner: the file it writes and the flags that ask for it, with small parameters
+RUNNER_OUTPUTS = {
+    "trail.csv": ["--trail", "trail.csv"],
+    "clusters.csv": ["--clusters", "clusters.csv"],
+    "contacts.csv": ["--contacts", "contacts.csv"],
+    "structure.csv": ["--structure", "structure.csv"],
+    "rdf.csv": ["--rdf", "rdf.csv", "--rdf-bins", "16"],
+    "rearrange.csv": ["--rearrange", "rearrange.csv", "--rearrange-window"],
+    # a record every 0.5 s into a ring of 8: 21 records, so the drain goes round the ring
+    "series.csv": ["--series", "series.csv", "--series-interval", "0.5", "--series-capacity", "8"],
+    "correlate.csv": ["--correlate", "correlate.csv", "--correlate-bins", "16"],
+    "timecorr.csv": ["--timecorr", "timecorr.csv", "--timecorr-lags", "4"],
+    "field.csv": ["--field", "field.csv", "--field-cells", "8"],
+    "sk.csv": ["--sk", "sk.csv", "--sk-nmax", "2"],
+    "scatter.csv": ["--scatter", "scatter.csv", "--scatter-lags", "4", "--scatter-nmax", "2"],
+}
+
+
+def test_runner_outputs_do_not_disturb_each_other(tmp_path):
+    """A run that is given every output flag at once writes, for each output and for the main CSV, the very bytes of a
+    run that is given that output's flags alone: no analysis changes the state, and no writer another's file."""
+    exe = os.path.join(ROOT, "particlerobotsimulations_amd", "bin", "particlebot_run")
+    common = [exe, EX("example.cfg"), "--quiet", "--set", "max_time", "10", "--set", "dump_interval", "2.5", "--set",
+              "csv_filename", "run.csv"]
+
+    def files_of(name, flags):
+        cwd = tmp_path / name
+        cwd.mkdir()
+        r = subprocess.run(common + flags, capture_output=True, text=True, timeout=300, cwd=cwd)
+        assert r.returncode == 0, (name, r.stderr)
+        return {f: (cwd / f).read_bytes() for f in sorted(os.listdir(cwd))}
+
+    together = files_of("all", [a for flags in RUNNER_OUTPUTS.values() for a in flags])
+    assert sorted(together) == sorted(list(RUNNER_OUTPUTS) + ["run.csv"])
+    assert together["run.csv"].count(b"\n") >= 5 and all(together.values())
+    assert together["series.csv"].count(b"\n") > 1 + 8
+    for name, flags in RUNNER_OUTPUTS.items():
+        alone = files_of(name[:-4], flags)
+        assert sorted(alone) == sorted([name, "run.csv"])
+        assert alone[name] == together[name], name
+        assert alone["run.csv"] == together["run.csv"], name
+
+
 def test_ensemble_members_equal_individual_runs(host, tmp_path):
     """a batched ensemble (one pbSim, one launch per timestep for all members) gives
     every member exactly the state a stand-alone run with that seed gives: placement, dead-bot draw
