@@ -442,6 +442,11 @@ inline bool gate(float t, float interval, float dt) {
   // the reference's fp32 schedule test (particlebot.cpp:207,212,256)
   return t - interval * floorf(t / interval) < dt;
 }
+// A recorder's rule on top of it (the intervals pbCheckInterval lets through): 0 every step, > 0 the gate, else (-1, by
+// hand only) never.  Not the same arithmetic as the bare gate at 0 or below, which the trail and the phase update keep.
+inline bool pbRecordDue(float t, float interval, float dt) {
+  return interval == 0.0f || (interval > 0.0f && gate(t, interval, dt));
+}
 
 // Trips per wave of the streamlined kernel's neighbour loop under its two walks (pb_stream.hip, WALK), summed over all
 // waves: out[0] row by row (per stencil row the longest range of the wave's 64 lanes), out[1] flattened (the longest
@@ -613,58 +618,59 @@ int trailRecord(pbSim *S, float t) {
   return PB_OK;
 }
 
+// Something the host does in front of a step: an entry of stepMany's table.
+struct PbHostEvent {
+  bool record;      // due by the recorders' rule (pbRecordDue); else by the bare gate, whatever the interval's value
+  bool readsState;  // reads more than positions: the state in front of its step, which a launch that runs ahead never
+                    // leaves on the device; else the positions alone, which are final once the step before has integrated
+  float interval;
+  int (*fire)(pbSim *S, float t);  // in front of the step that starts at t
+  bool due(float t, float dt) const { return record ? pbRecordDue(t, interval, dt) : gate(t, interval, dt); }
+};
+
 int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const uint32_t n = S->n;
   const dim3 gA = gridOf(S), b(TILE);
-  const float pui = S->host.phase_update_interval;
   const bool lightWave = (S->host.control == LIGHT_WAVE);
   bool ahead = false;  // true: radius+integration of the coming step are already applied
   const bool resident = pbResidentWanted(S);
-  const bool trail = S->trail.ring != nullptr;
-  const float ci = S->trail.interval;
-  // the time series (pb_moments.hip): a record in front of every step whose start time passes the gate, or of every
-  // step at interval 0.  A record reads the state in front of its step, which a launch that runs ahead never leaves on
-  // the device: no launch is fused across a record's gate, and a resident stretch ends in front of one.
-  // The time correlations (pb_timecorr.hip) and the scattering (pb_scatter.hip) take their snapshots by the same rule
-  // (interval -1: by hand only).
-  const bool series = S->series.ring != nullptr, corr = S->tc.ring != nullptr, scat = S->sc.ring != nullptr;
-  const float si = S->series.interval, ti = S->tc.interval, ki = S->sc.interval;
-  auto seriesGate = [&](float at) { return series && (si == 0.0f || gate(at, si, dt)); };
-  auto corrGate = [&](float at) { return corr && (ti == 0.0f || (ti > 0.0f && gate(at, ti, dt))); };
-  auto scatGate = [&](float at) { return scat && (ki == 0.0f || (ki > 0.0f && gate(at, ki, dt))); };
-  auto recordDue = [&](float at) { return seriesGate(at) || corrGate(at) || scatGate(at); };  // a record in front of the step at `at`
+  // The host events that are on, in firing order: the records of the time series (pb_moments.hip), the time
+  // correlations (pb_timecorr.hip) and the scattering (pb_scatter.hip), the centroid trail, the phase update.  A new
+  // recorder is one more entry; the loop below does not name them.
+  PbHostEvent events[5];
+  int nEvents = 0;
+  if (S->series.ring) events[nEvents++] = {true, true, S->series.interval, pbSeriesRecord};
+  if (S->tc.lag.ring)
+    events[nEvents++] = {true, true, S->tc.lag.interval, [](pbSim *B, float) { return pbTimeCorrRecord(B); }};
+  if (S->sc.lag.ring)
+    events[nEvents++] = {true, true, S->sc.lag.interval, [](pbSim *B, float) { return pbScatteringRecord(B); }};
+  if (S->trail.ring) events[nEvents++] = {false, false, S->trail.interval, trailRecord};
+  if (lightWave)
+    events[nEvents++] = {false, false, S->host.phase_update_interval, [](pbSim *B, float) { return phaseUpdate(B); }};
+  // an event (stateOnly: one that reads more than positions) is due in front of the step that starts at `at`
+  const auto anyDue = [&](float at, bool stateOnly) {
+    for (int e = 0; e < nEvents; e++)
+      if ((events[e].readsState || !stateOnly) && events[e].due(at, dt)) return true;
+    return false;
+  };
+  const auto fireDue = [&](float at) {
+    for (int e = 0; e < nEvents; e++)
+      if (events[e].due(at, dt))
+        if (const int rc = events[e].fire(S, at)) return rc;
+    return (int)PB_OK;
+  };
   int k = 0;
   for (; k < nsteps; k++) {
     const float t = S->time;
     if (t > S->host.max_time) break;  // particlebot.cpp:174-176 (the reference exits the process)
     if (!ahead) {
-      if (seriesGate(t)) {
-        const int rc = pbSeriesRecord(S, t);
-        if (rc) return rc;
-      }
-      if (corrGate(t)) {
-        const int rc = pbTimeCorrRecord(S);
-        if (rc) return rc;
-      }
-      if (scatGate(t)) {
-        const int rc = pbScatteringRecord(S);
-        if (rc) return rc;
-      }
-      if (trail && gate(t, ci, dt)) {
-        const int rc = trailRecord(S, t);
-        if (rc) return rc;
-      }
-      if (lightWave && gate(t, pui, dt)) {
-        const int rc = phaseUpdate(S);
-        if (rc) return rc;
-      }
+      if (const int rc = fireDue(t)) return rc;
       if (resident && S->haveCells && !gate(t, sortInterval, dt)) {
-        // whole steps up to (not including) the next one that needs the host: a re-sort, a phase
-        // update, the end of the run or of this call.  tt repeats the fp32 time accumulation.
+        // whole steps up to (not including) the next one that needs the host: an event, a re-sort, the end of the
+        // run or of this call.  tt repeats the fp32 time accumulation.
         int m = 1;
         float tt = t + dt;
-        while (k + m < nsteps && !(tt > S->host.max_time) && !(lightWave && gate(tt, pui, dt)) &&
-               !(trail && gate(tt, ci, dt)) && !recordDue(tt) && !gate(tt, sortInterval, dt)) {
+        while (k + m < nsteps && !(tt > S->host.max_time) && !anyDue(tt, false) && !gate(tt, sortInterval, dt)) {
           m++;
           tt += dt;
         }
@@ -685,19 +691,12 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
       if (rc) return rc;
     }
     const float tNext = t + dt;
-    // Fuse the next step's radius+integration unless this is the last step of the batch or the
-    // next step will not run.  A phase update due at the start of the next step only needs the
-    // positions of THIS step's integration, which are final now, so it runs before the launch.
+    // Fuse the next step's radius+integration unless this is the last step of the batch, the next step will not run,
+    // or an event that reads more than positions is due in front of it.  What else is due there (the trail, a phase
+    // update) only needs the positions of THIS step's integration, which are final now, so it fires before the launch.
     // (resident form: never run ahead, so that the next step can start a resident stretch)
-    const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time) && !recordDue(tNext);
-    if (fuse && trail && gate(tNext, ci, dt)) {
-      const int rc = trailRecord(S, tNext);
-      if (rc) return rc;
-    }
-    if (fuse && lightWave && gate(tNext, pui, dt)) {
-      const int rc = phaseUpdate(S);
-      if (rc) return rc;
-    }
+    const bool fuse = !resident && (k + 1 < nsteps) && !(tNext > S->host.max_time) && !anyDue(tNext, true);
+    if (const int rc = fuse ? fireDue(tNext) : (int)PB_OK) return rc;
     const int c = S->cur, o = c ^ 1;
     pbLaunchForce(S, fuse, c, o, dt, tNext, (int)(fuse && lightWave && tNext >= 0));
     if (fuse) S->stats.fused_launches++;

@@ -1,7 +1,9 @@
 // pb_engine.hpp -- what the translation units of the pbSim engine share (not part of the public C-ABI):
-// the batch object, the launch plan, and the launchers each kernel family exports.
+// the batch object, the launch plan, the launchers each kernel family exports, and the lag ring of the lagged analyses
+// (PbLagBook, PbLagRing, pbLagPair, pbLag...: the one place that knows the ring's format).
 //
-//   pb_engine.hip    the object, the schedule (stepMany), re-sort / phase update / I/O kernels, the C-ABI
+//   pb_engine.hip    the object, the schedule (stepMany and its table of host events), re-sort / phase update / I/O
+//                    kernels, the C-ABI
 //   pb_force.hip     k_force: the exact per-step force kernel in all its forms + the forms table
 //   pb_stream.hip    k_force_stream: the opt-in streamlined (tolerance) force kernel
 //   pb_resident.hip  k_resident: the multi-step one-workgroup-per-simulation kernel
@@ -12,10 +14,11 @@
 //   pb_structure.hip structure analysis: radial pair counts and the hexatic order (pbSimRadialCounts, pbSimStructureStats)
 //   pb_dynamics.hip  rearrangement analysis: a marked reference, bond survival and displacements (pbSimMarkReference)
 //   pb_moments.hip   time series: integer moment rows per member, now or recorded while stepping (pbSimSetSeries)
-//   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a ring of snapshots (pbSimSetTimeCorrelation)
+//   pb_timecorr.hip  time correlations: MSD, VACF and overlap per lag over a lag ring (pbSimSetTimeCorrelation)
 //   pb_field.hip     field maps: count, dead and integer sums of radius and velocity per grid cell (pbSimFieldMap)
 //   pb_sfactor.hip   structure factor: integer phasor sums per member and wavevector (pbSimStructureFactor)
-//   pb_scatter.hip  self-intermediate scattering: integer phasor sums per member, lag and wavevector (pbSimSetScattering)
+//   pb_scatter.hip   self-intermediate scattering: integer phasor sums per member, lag and wavevector over a lag ring
+//                    (pbSimSetScattering)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 //   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of, and
@@ -47,7 +50,7 @@ std::string &pbLastError();
   } while (0)
 
 // an argument the entry point `fn` refuses: the text behind pbGetLastErrorString is fn + what
-inline int pbFail(const char *fn, const char *what) {
+inline int pbFail(const char *fn, const std::string &what) {
   pbLastError() = std::string(fn) + what;
   return PB_ERR_ARG;
 }
@@ -89,8 +92,18 @@ struct PbSeries {
   std::vector<float> times;               // per slot: start time of the step the record was taken in front of
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
-// The host's book of a ring of records that are paired lag by lag (pb_timecorr.hip, pb_scatter.hip): record r goes into
-// slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1).
+// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip) share -----------------------------------
+// A ring of `lags` snapshots of the whole batch in ORIGINAL order, lags x total entries of Snap.  Record r goes into
+// slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1); all pairs of a record are added
+// into `table` by one launch over pbLagGrid() workgroups of PB_LAG_LANES lanes, which pbLagPair() takes apart again.
+// Everything that knows this format is in this file: the book and the ring value here, pbLagPair (device) and the
+// pbLag... host functions behind pbSim.  An analysis adds its snapshot kernel, its accumulate body and its row writer.
+constexpr int PB_LAG_LANES = 256;
+constexpr unsigned PB_LAG_MAX_LAGS = 64u, PB_LAG_BLOCKS = 256u;  // (the public header states both per analysis)
+static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS, "one bound on the lags");
+static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS, "one bound on the blocks per lag");
+
+// the host's counters of a ring
 struct PbLagBook {
   unsigned lags = 0;
   unsigned long long records = 0;                     // records taken so far
@@ -108,16 +121,48 @@ struct PbLagBook {
     for (uint32_t l = 0; l < n; l++) origins[l]++, sumSteps[l] += stepsNow - steps[(s + lags - l) % lags];
     records++;
   }
+  template <typename Row>  // the book's three columns of a lag's row
+  void columns(unsigned lag, Row &r) const { r.lag = lag, r.origins = origins[lag], r.sum_steps = sumSteps[lag]; }
 };
-// time correlations (pb_timecorr.hip): the ring of snapshots and the table when on (pbSimSetTimeCorrelation)
+// the ring when on (`ring` is set), with the analysis' table behind it
+template <typename Snap>
+struct PbLagRing {
+  PbDevBuf<Snap> ring;                 // lags x total, ORIGINAL order: record r at slot r % lags
+  PbDevBuf<unsigned long long> table;  // the analysis' 64-bit words, zeroed when the ring is made
+  float interval = 0.0f;               // 0: in front of every step; -1: manual records only
+  PbLagBook book;                      // lags (0: off), records, steps per slot, origins and step sums per lag
+  PbSpanClock clock;                   // around the last record's launches
+  // an entry point that needs the analysis on refuses when the `what` ("correlation", "scattering") is off
+  int checkOn(const char *fn, const char *what) const {
+    return ring ? PB_OK : pbFail(fn, std::string(": the ") + what + " is off");
+  }
+};
+// workgroups of a record's accumulate launch: blocksPerLag blocks of bots per member and lag the record is paired with
+inline uint32_t pbLagGrid(uint32_t nsims, uint32_t nLags, uint32_t blocksPerLag) { return nsims * nLags * blocksPerLag; }
+// ... and what workgroup blockIdx.x of that grid works on: block `block` of the bots of `member`, as they are in the
+// record just taken (`now`) and were `lag` records before it (`then`); lag < nLags <= lags
+template <typename Snap>
+struct PbLagPair {
+  uint32_t member, lag, block;
+  const Snap *now, *then;
+};
+template <typename Snap>
+__device__ inline PbLagPair<Snap> pbLagPair(const Snap *ring, uint32_t n, uint32_t total, uint32_t lags,
+                                            uint32_t slotNow, uint32_t nLags, uint32_t blocksPerLag) {
+  const uint32_t perMember = nLags * blocksPerLag;
+  const uint32_t member = blockIdx.x / perMember, rest = blockIdx.x - member * perMember;
+  const uint32_t lag = rest / blocksPerLag, b = rest - lag * blocksPerLag;
+  const uint32_t slotThen = slotNow >= lag ? slotNow - lag : slotNow + lags - lag;
+  return {member, lag, b, ring + (size_t)slotNow * total + (size_t)member * n,
+          ring + (size_t)slotThen * total + (size_t)member * n};
+}
+
+// time correlations (pb_timecorr.hip): float4 (x, y, vx, vy) snapshots and nsims x lags cells of nine words, member-major
+// (pbSimSetTimeCorrelation)
 struct PbTimeCorr {
-  PbDevBuf<float4> ring;                // lags x total, ORIGINAL order: record r at slot r % lags
-  PbDevBuf<unsigned long long> table;   // nsims x lags cells of nine words, member-major
-  float interval = 0.0f;                // 0: in front of every step; -1: manual records only
+  PbLagRing<float4> lag;
   float radius = 0.0f;
-  unsigned long long a2 = 0;            // rint(radius * 2^20) squared
-  PbLagBook book;                       // lags (0: off), records, steps per slot, origins and step sums per lag
-  PbSpanClock clock;                    // around the last record's launches
+  unsigned long long a2 = 0;  // rint(radius * 2^20) squared
 };
 
 // field maps (pb_field.hip): the scratch of the largest map asked for so far, made by the first call (pbSimFieldMap)
@@ -140,18 +185,15 @@ struct PbSfactor {
   unsigned long long analyses = 0;
 };
 
-// self-intermediate scattering (pb_scatter.hip): the ring of quantised snapshots and the table when on (pbSimSetScattering)
+// self-intermediate scattering (pb_scatter.hip): int2 snapshots of the quantised positions ((INT32_MIN, 0): unmeasured)
+// and nsims x lags x nvec cells of (re, im), then nsims x lags sample counters (pbSimSetScattering)
 struct PbScattering {
-  PbDevBuf<int2> ring;                 // lags x total, ORIGINAL order: record r at slot r % lags; (INT32_MIN, 0): unmeasured
-  PbDevBuf<unsigned long long> table;  // nsims x lags x nvec cells of (re, im), then nsims x lags sample counters
-  PbDevBuf<int2> phasors;              // the 4096 (cos, sin) entries of pb_phasor.hpp
-  PbDevBuf<int2> vectors;              // nvec (nx, ny) pairs
-  std::vector<int> list;               // the host's copy of the list, as passed
-  float interval = 0.0f;               // 0: in front of every step; -1: manual records only
+  PbLagRing<int2> lag;
+  PbDevBuf<int2> phasors;  // the 4096 (cos, sin) entries of pb_phasor.hpp
+  PbDevBuf<int2> vectors;  // nvec (nx, ny) pairs
+  std::vector<int> list;   // the host's copy of the list, as passed
   unsigned nvec = 0;
   int boxLog2 = 0;
-  PbLagBook book;                      // lags (0: off), records, steps per slot, origins and step sums per lag
-  PbSpanClock clock;                   // around the last record's launches
 };
 
 // Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
@@ -259,6 +301,101 @@ inline int pbSpanGet(const pbSim *S, const PbSpanClock &K, unsigned long long co
   }
   return PB_OK;
 }
+// The interval of a recorder that stepMany fires: 0 in front of every step, > 0 the schedule's fp32 gate, and, where
+// `manual` allows it, -1 for records by hand only (pbRecordDue in pb_engine.hip reads it by the same rule).
+inline int pbCheckInterval(const char *fn, float interval, bool manual) {
+  if ((manual && interval == -1.0f) || (interval >= 0.0f && interval < __builtin_inff())) return PB_OK;
+  return pbFail(fn, std::string(": interval must be finite and >= 0") + (manual ? ", or -1 for manual records only" : ""));
+}
+
+// ---- the host side of the lag ring (the format is stated at PbLagBook) ------------------------------------------------
+// A setter's checks of interval and lags, which read no handle, ...
+inline int pbLagCheckArgs(const char *fn, float interval, unsigned lags) {
+  if (const int rc = pbCheckInterval(fn, interval, true)) return rc;
+  return lags > PB_LAG_MAX_LAGS ? pbFail(fn, ": lags must be at most 64") : PB_OK;
+}
+// ... and, behind the analysis' own argument checks, those of the batch
+template <typename Snap>
+int pbLagCheckBatch(const char *fn, const pbSim *S, unsigned lags) {
+  if (S->nsims > 65535u) return pbFail(fn, ": the batch must hold at most 65535 members");  // the member is a grid's y
+  if (const int rc = pbCheckBatch(fn, S)) return rc;
+  if ((unsigned long long)lags * S->total * sizeof(Snap) > (1ull << 33))
+    return pbFail(fn, ": the ring (lags x bots x " + std::to_string(sizeof(Snap)) + " bytes) must not exceed 2^33 bytes");
+  return PB_OK;
+}
+// the ring and the zeroed table of `words` words into R; on an error the caller drops R
+template <typename Snap>
+int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words) {
+  PB_TRY(R.ring.alloc((size_t)lags * S->total));
+  PB_TRY(R.table.alloc(words));
+  PB_TRY(hipMemsetAsync(R.table, 0, sizeof(unsigned long long) * words, S->stream));
+  return PB_OK;
+}
+// Switches the analysis `held` (S->tc, S->sc) off and, unless lags is 0, on again: a fresh value with a ring of `lags`
+// snapshots, a zeroed table of wordsPerLag words per member and lag, a book at record 0, and what fill(fresh) sets of
+// the analysis' own.  When any of it fails, what was made goes and the analysis stays off.
+template <typename A, typename Fill>
+int pbLagSwitch(pbSim *S, A &held, float interval, unsigned lags, size_t wordsPerLag, Fill fill) {
+  useDevice(S);
+  PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
+  held = A();
+  if (!lags) return PB_OK;
+  A fresh;
+  int rc = pbLagAllocate(S, fresh.lag, lags, (size_t)S->nsims * lags * wordsPerLag);
+  if (rc == PB_OK) rc = fill(fresh);
+  if (rc != PB_OK) {          // (a ring that took the last free memory, say)
+    (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
+    return rc;
+  }
+  fresh.lag.interval = interval, fresh.lag.book.start(lags);
+  held = std::move(fresh);
+  return PB_OK;
+}
+// One record of the state as it is: snapshot(grid, slot) stores every bot into the ring's next slot, then
+// accumulate(grid, slotNow, nLags, blocksPerLag) adds its pairs with the lags it is paired with.  Both launch on the
+// batch's stream; nothing waits.
+template <typename Snap, typename Shot, typename Acc>
+int pbLagRecord(pbSim *S, PbLagRing<Snap> &R, Shot snapshot, Acc accumulate) {
+  const uint32_t slot = R.book.slot(), nLags = R.book.paired();
+  const uint32_t perMember = cdiv(S->n, PB_LAG_LANES);
+  const uint32_t bpl = perMember < PB_LAG_BLOCKS ? perMember : PB_LAG_BLOCKS;
+  PB_TRY(R.clock.start(S->stream));
+  snapshot(dim3(perMember, S->nsims), R.ring + (size_t)slot * S->total);
+  accumulate(dim3(pbLagGrid(S->nsims, nLags, bpl)), slot, nLags, bpl);
+  PB_TRY(hipGetLastError());
+  PB_TRY(R.clock.stop(S->stream));
+  R.book.recorded(S->stats.steps);
+  return PB_OK;
+}
+// the body of pbSim...Record: one record by hand, of the state as it is
+template <typename A>
+int pbLagManualRecord(const char *fn, pbSim *S, A pbSim::*which, const char *what, int (*record)(pbSim *)) {
+  if (!S) return pbFail(fn, ": null handle");
+  if (const int rc = (S->*which).lag.checkOn(fn, what)) return rc;
+  useDevice(S);
+  return record(S);
+}
+// The table as it stands, read back into acc for the analysis' row writer.  Refused when the analysis is off or any of
+// the nsims x lags sample counters, acc[samplesAt + g * samplesStride], is at its cap.
+template <typename Snap>
+int pbLagFetch(const char *fn, pbSim *S, const PbLagRing<Snap> &R, const char *what,
+               std::vector<unsigned long long> &acc, size_t samplesAt, size_t samplesStride) {
+  if (const int rc = R.checkOn(fn, what)) return rc;
+  useDevice(S);
+  acc.resize(R.table.capacity());
+  PB_TRY(hipMemcpyAsync(acc.data(), R.table, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost, S->stream));
+  PB_TRY(hipStreamSynchronize(S->stream));
+  for (size_t g = 0; g < (size_t)S->nsims * R.book.lags; g++)
+    if (acc[samplesAt + g * samplesStride] >= (1ull << 31))  // the counts are exact whatever the state: the other sums may not be
+      return pbFail(fn, std::string(": a lag holds 2^31 samples or more: restart the ") + what);
+  return PB_OK;
+}
+// the body of pbSimGet...Times
+template <typename A>
+int pbLagTimes(const char *fn, pbSim *S, A pbSim::*which, unsigned long long *records, float *last_device_ms) {
+  if (!S) return pbFail(fn, ": null handle");
+  return pbSpanGet(S, (S->*which).lag.clock, (S->*which).lag.book.records, records, last_device_ms);
+}
 
 // absForce_a has a reader (impl.cuh:167-169) or the caller asked for it (pbSimSetForceSums)
 static inline bool pbStreamWalk(const pbSim *S) { return S->streamWalk >= 0 ? S->streamWalk == 1 : S->streamWalkAuto; }
@@ -306,9 +443,7 @@ bool pbResidentWanted(const pbSim *S);                                          
 void pbLaunchResident(pbSim *S, float dt, float t0, int m, int lightWave);
 // frees the cluster analysis' scratch, if any (~pbSim: PbClusterScratch is incomplete here)              pb_cluster.hip
 void pbClusterFree(pbSim *S);
-// one record of every member into the ring's next slot, in front of the step that starts at t (stepMany)   pb_moments.hip
-int pbSeriesRecord(pbSim *S, float t);
-// one snapshot of every member, as it is now, into the ring's next slot and its lags into the table      pb_timecorr.hip
-int pbTimeCorrRecord(pbSim *S);
-// one quantised snapshot of every member, as it is now, into the ring's next slot and its lags into the table  pb_scatter.hip
-int pbScatteringRecord(pbSim *S);
+// What stepMany's table of host events fires from other files: one record of every member, of the state as it is, ...
+int pbSeriesRecord(pbSim *S, float t);  // ... in front of the step that starts at t                        pb_moments.hip
+int pbTimeCorrRecord(pbSim *S);         // ... a snapshot and its lags (pbLagRecord)                        pb_timecorr.hip
+int pbScatteringRecord(pbSim *S);       // ... a quantised snapshot and its lags (pbLagRecord)              pb_scatter.hip

@@ -177,8 +177,7 @@ int pbSimMoments(pbSim *S, pbMomentsRow *rows) {
 
 int pbSimSetSeries(pbSim *S, float interval, unsigned capacity) {
   if (!S) return pbFail("pbSimSetSeries", ": null handle");
-  if (!(interval >= 0.0f) || !(interval < __builtin_inff()))
-    return pbFail("pbSimSetSeries", ": interval must be finite and >= 0");
+  if (const int rc = pbCheckInterval("pbSimSetSeries", interval, false)) return rc;  // (the series has no manual records)
   if ((unsigned long long)capacity * S->nsims * sizeof(pbMomentsRow) > (1ull << 31))
     return pbFail("pbSimSetSeries", ": capacity x members x 152 bytes must not exceed 2^31 bytes");
   const int rc = pbCheckBatch("pbSimSetSeries", S);

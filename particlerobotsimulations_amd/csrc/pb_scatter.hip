@@ -1,11 +1,11 @@
 // pb_scatter.hip -- the self-intermediate scattering function on gfx950: per member, lag and wavevector of a caller's
 // list, the integer sums  sum C[idx]  and  sum S[idx]  over the measured (bot, origin) pairs, idx being the table step of
 // k . (r(t + tau) - r(t)), averaged over time origins while pbSimStep runs (pbSimSetScattering / pbSimScatteringRecord /
-// pbSimGetScattering; include/particlebot_hip.h has the definitions).  The ring and its pairing are pb_timecorr.hip's,
-// the turn, the index and the table are pb_phasor.hpp's; neither is restated here.
+// pbSimGetScattering; include/particlebot_hip.h has the definitions).  The ring of snapshots, its pairing lag by lag, its
+// book and the shells of the entry points are the lag ring's (pb_engine.hpp, PbLagBook ... pbLagTimes); the turn, the
+// index and the table are pb_phasor.hpp's; neither is restated here.  The table is two 64-bit words per member, lag and
+// wavevector, and one sample counter per member and lag behind them.
 //
-//   k_scat_clear       zeroes the table (two 64-bit words per member, lag and wavevector) and the sample counters (one
-//                      per member and lag) behind it
 //   k_scat_snapshot    one pass over pr[cur] and orig[cur] in SLOT order (coalesced reads); each lane quantises one bot
 //                      and writes one int2 (qx, qy) to ring[slot][member * n + orig]; an out-of-range bot is stored as
 //                      (INT32_MIN, 0), which no measured bot can be.  The scattered 8-byte store is the only uncoalesced
@@ -42,13 +42,8 @@ static_assert(PB_SCATTER_MAX_VECTORS == 256u, "a workgroup of 256 lanes holds th
 
 namespace {
 
-constexpr int SC = 256;
+constexpr int SC = PB_LAG_LANES;
 enum { C_RE, C_IM, C_WORDS };  // the words of a table cell
-
-__global__ __launch_bounds__(SC) void k_scat_clear(unsigned long long *__restrict__ words, uint32_t count) {
-  const uint32_t i = blockIdx.x * SC + threadIdx.x;
-  if (i < count) words[i] = 0ull;
-}
 
 __global__ __launch_bounds__(SC) void k_scat_snapshot(const float4 *__restrict__ pr, const uint32_t *__restrict__ orig,
                                                       uint32_t n, int2 *__restrict__ snap) {
@@ -73,12 +68,7 @@ __global__ __launch_bounds__(SC) void k_scat_accumulate(const int2 *__restrict__
                                                         unsigned long long *__restrict__ samples) {
   __shared__ int2 sTab[PB_PHASOR_STEPS];  // (C[j], S[j])
   __shared__ int4 sPair[SC];              // (dqx << shift, dqy << shift, mask, 0) of the tile's pairs
-  const uint32_t perMember = nLags * blocksPerLag;
-  const uint32_t member = blockIdx.x / perMember, rest = blockIdx.x - member * perMember;
-  const uint32_t lag = rest / blocksPerLag, b = rest - lag * blocksPerLag;  // lag < nLags <= lags
-  const uint32_t slotThen = slotNow >= lag ? slotNow - lag : slotNow + lags - lag;
-  const int2 *now = ring + (size_t)slotNow * total + (size_t)member * n;
-  const int2 *then = ring + (size_t)slotThen * total + (size_t)member * n;
+  const auto [member, lag, b, now, then] = pbLagPair(ring, n, total, lags, slotNow, nLags, blocksPerLag);
   for (uint32_t j = threadIdx.x; j < PB_PHASOR_STEPS; j += SC) sTab[j] = phasors[j];
   // vp is a power of two, nvec <= vp <= 256: lane t is vector t & (vp - 1) of stripe t / vp, 256 / vp stripes
   const uint32_t k = threadIdx.x & (vp - 1u), stripe = threadIdx.x / vp, stripes = (uint32_t)SC / vp;
@@ -146,45 +136,22 @@ const int *phasorTable() {
   return table.data();
 }
 
-size_t cellsOf(const pbSim *S, const PbScattering &K) { return (size_t)S->nsims * K.book.lags * K.nvec; }
-// the table's words and the sample counters behind them
-size_t wordsOf(const pbSim *S, const PbScattering &K) { return cellsOf(S, K) * C_WORDS + (size_t)S->nsims * K.book.lags; }
-
-// the ring, the zeroed table, the phasors and the list of K (book, nvec and list set); on an error the caller drops K
-int allocate(pbSim *S, PbScattering &K) {
-  const size_t words = wordsOf(S, K);  // below 2^28 + 2^22
-  PB_TRY(K.ring.alloc((size_t)K.book.lags * S->total));
-  PB_TRY(K.table.alloc(words));
-  PB_TRY(K.phasors.alloc(PB_PHASOR_STEPS));
-  PB_TRY(K.vectors.alloc(K.nvec));
-  PB_TRY(hipMemcpyAsync(K.phasors, phasorTable(), sizeof(int2) * PB_PHASOR_STEPS, hipMemcpyHostToDevice, S->stream));
-  PB_TRY(hipMemcpyAsync(K.vectors, K.list.data(), sizeof(int2) * K.nvec, hipMemcpyHostToDevice, S->stream));
-  hipLaunchKernelGGL(k_scat_clear, dim3(cdiv((uint32_t)words, SC)), dim3(SC), 0, S->stream, K.table, (uint32_t)words);
-  PB_TRY(hipGetLastError());
-  PB_TRY(hipStreamSynchronize(S->stream));  // (the two copies read host memory that may go with the next switch)
-  return PB_OK;
-}
+size_t cellsOf(const pbSim *S, const PbScattering &K) { return (size_t)S->nsims * K.lag.book.lags * K.nvec; }
 
 }  // namespace
 
 int pbScatteringRecord(pbSim *S) {
   PbScattering &K = S->sc;
-  const uint32_t lags = K.book.lags, slot = K.book.slot(), nLags = K.book.paired();
-  const uint32_t perMember = cdiv(S->n, SC);
-  const uint32_t bpl = perMember < PB_SCATTER_BLOCKS ? perMember : PB_SCATTER_BLOCKS;
   uint32_t vp = 1u;
   while (vp < K.nvec) vp <<= 1;
   const int c = S->cur;
-  PB_TRY(K.clock.start(S->stream));
-  hipLaunchKernelGGL(k_scat_snapshot, dim3(cdiv(S->n, SC), S->nsims), dim3(SC), 0, S->stream, S->pr[c], S->orig[c], S->n,
-                     K.ring + (size_t)slot * S->total);
-  hipLaunchKernelGGL(k_scat_accumulate, dim3(S->nsims * nLags * bpl), dim3(SC), 0, S->stream, K.ring, S->n, S->total,
-                     lags, slot, nLags, bpl, pbPhasorShift(K.boxLog2), K.vectors, K.nvec, vp, K.phasors, K.table,
-                     K.table + cellsOf(S, K) * C_WORDS);
-  PB_TRY(hipGetLastError());
-  PB_TRY(K.clock.stop(S->stream));
-  K.book.recorded(S->stats.steps);
-  return PB_OK;
+  return pbLagRecord(S, K.lag, [&](dim3 grid, int2 *snap) {
+    hipLaunchKernelGGL(k_scat_snapshot, grid, dim3(SC), 0, S->stream, S->pr[c], S->orig[c], S->n, snap);
+  }, [&](dim3 grid, uint32_t slot, uint32_t nLags, uint32_t bpl) {
+    hipLaunchKernelGGL(k_scat_accumulate, grid, dim3(SC), 0, S->stream, K.lag.ring, S->n, S->total, K.lag.book.lags,
+                       slot, nLags, bpl, pbPhasorShift(K.boxLog2), K.vectors, K.nvec, vp, K.phasors, K.lag.table,
+                       K.lag.table + cellsOf(S, K) * C_WORDS);
+  });
 }
 
 extern "C" {
@@ -192,43 +159,30 @@ extern "C" {
 int pbSimSetScattering(pbSim *S, float interval, unsigned lags, int boxLog2, const int *vectors, unsigned nvec) {
   const char *fn = "pbSimSetScattering";
   if (!S) return pbFail(fn, ": null handle");
-  if (!(interval == -1.0f) && (!(interval >= 0.0f) || !(interval < __builtin_inff())))
-    return pbFail(fn, ": interval must be finite and >= 0, or -1 for manual records only");
-  if (lags > PB_SCATTER_MAX_LAGS) return pbFail(fn, ": lags must be at most 64");
+  if (const int rc = pbLagCheckArgs(fn, interval, lags)) return rc;
   if (lags) {  // (lags == 0 switches off: the box and the list are not read)
     if (!vectors) return pbFail(fn, ": null vectors");
     if (boxLog2 < PB_SK_MIN_LOG2 || boxLog2 > PB_SK_MAX_LOG2) return pbFail(fn, ": boxLog2 must be -8 ... 12");
     if (nvec < 1u || nvec > PB_SCATTER_MAX_VECTORS) return pbFail(fn, ": nvec must be 1 ... 256");
   }
-  if (S->nsims > 65535u) return pbFail(fn, ": the batch must hold at most 65535 members");  // the member is a grid's y
-  int rc = pbCheckBatch(fn, S);
-  if (rc != PB_OK) return rc;
-  if ((unsigned long long)lags * S->total * sizeof(int2) > (1ull << 33))
-    return pbFail(fn, ": the ring (lags x bots x 8 bytes) must not exceed 2^33 bytes");
+  if (const int rc = pbLagCheckBatch<int2>(fn, S, lags)) return rc;
   if (lags && (unsigned long long)S->nsims * lags * nvec * (sizeof(unsigned long long) * C_WORDS) > (1ull << 31))
     return pbFail(fn, ": the table (members x lags x nvec x 16 bytes) must not exceed 2^31 bytes");
-  useDevice(S);
-  PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
-  S->sc = PbScattering();
-  if (!lags) return PB_OK;
-  PbScattering K;
-  K.book.start(lags), K.nvec = nvec;
-  K.list.assign(vectors, vectors + 2u * (size_t)nvec);  // the list is copied at the call
-  rc = allocate(S, K);
-  if (rc != PB_OK) {  // (a ring that took the last free memory, say): whatever was made goes, the scattering stays off
-    (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
-    return rc;
-  }
-  K.interval = interval, K.boxLog2 = boxLog2;
-  S->sc = std::move(K);
-  return PB_OK;
+  // per member and lag: the cells of the list and one sample counter (below 2^28 + 2^22 words in all)
+  return pbLagSwitch(S, S->sc, interval, lags, (size_t)nvec * C_WORDS + 1u, [&](PbScattering &K) -> int {
+    K.nvec = nvec, K.boxLog2 = boxLog2;
+    K.list.assign(vectors, vectors + 2u * (size_t)nvec);  // the list is copied at the call
+    PB_TRY(K.phasors.alloc(PB_PHASOR_STEPS));
+    PB_TRY(K.vectors.alloc(nvec));
+    PB_TRY(hipMemcpyAsync(K.phasors, phasorTable(), sizeof(int2) * PB_PHASOR_STEPS, hipMemcpyHostToDevice, S->stream));
+    PB_TRY(hipMemcpyAsync(K.vectors, K.list.data(), sizeof(int2) * nvec, hipMemcpyHostToDevice, S->stream));
+    PB_TRY(hipStreamSynchronize(S->stream));  // (the two copies read host memory that may go with the next switch)
+    return PB_OK;
+  });
 }
 
 int pbSimScatteringRecord(pbSim *S) {
-  if (!S) return pbFail("pbSimScatteringRecord", ": null handle");
-  if (!S->sc.ring) return pbFail("pbSimScatteringRecord", ": the scattering is off");
-  useDevice(S);
-  return pbScatteringRecord(S);
+  return pbLagManualRecord("pbSimScatteringRecord", S, &pbSim::sc, "scattering", pbScatteringRecord);
 }
 
 int pbSimGetScatteringInfo(pbSim *S, float *interval, unsigned *lags, int *boxLog2, unsigned *nvec,
@@ -236,41 +190,33 @@ int pbSimGetScatteringInfo(pbSim *S, float *interval, unsigned *lags, int *boxLo
   if (!S) return pbFail("pbSimGetScatteringInfo", ": null handle");
   if (!interval && !lags && !boxLog2 && !nvec && !records)
     return pbFail("pbSimGetScatteringInfo", ": interval, lags, boxLog2, nvec and records are all null");
-  if (interval) *interval = S->sc.interval;
-  if (lags) *lags = S->sc.book.lags;
+  if (interval) *interval = S->sc.lag.interval;
+  if (lags) *lags = S->sc.lag.book.lags;
   if (boxLog2) *boxLog2 = S->sc.boxLog2;
   if (nvec) *nvec = S->sc.nvec;
-  if (records) *records = S->sc.book.records;
+  if (records) *records = S->sc.lag.book.records;
   return PB_OK;
 }
 
 int pbSimGetScattering(pbSim *S, pbScatteringRow *rows) {
   if (!S || !rows) return pbFail("pbSimGetScattering", ": null handle or rows");
   const PbScattering &K = S->sc;
-  if (!K.ring) return pbFail("pbSimGetScattering", ": the scattering is off");
-  useDevice(S);
-  const size_t cells = cellsOf(S, K), groups = (size_t)S->nsims * K.book.lags;
-  std::vector<unsigned long long> acc(wordsOf(S, K));
-  PB_TRY(hipMemcpyAsync(acc.data(), K.table, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost, S->stream));
-  PB_TRY(hipStreamSynchronize(S->stream));
+  const size_t cells = cellsOf(S, K);
+  std::vector<unsigned long long> acc;
+  if (const int rc = pbLagFetch("pbSimGetScattering", S, K.lag, "scattering", acc, cells * C_WORDS, 1u)) return rc;
   const unsigned long long *count = acc.data() + cells * C_WORDS;
-  for (size_t g = 0; g < groups; g++)
-    if (count[g] >= (1ull << 31))  // the counts are exact whatever the state: the other sums may not be
-      return pbFail("pbSimGetScattering", ": a lag holds 2^31 samples or more: restart the scattering");
   for (size_t c = 0; c < cells; c++) {
     const size_t g = c / K.nvec, k = c - g * K.nvec;
-    const unsigned lag = (unsigned)(g % K.book.lags);
     pbScatteringRow &r = rows[c];
-    r.lag = lag, r.nx = K.list[2u * k], r.ny = K.list[2u * k + 1u], r.reserved = 0u;
-    r.origins = K.book.origins[lag], r.sum_steps = K.book.sumSteps[lag], r.samples = count[g];
+    K.lag.book.columns((unsigned)(g % K.lag.book.lags), r);
+    r.nx = K.list[2u * k], r.ny = K.list[2u * k + 1u], r.reserved = 0u, r.samples = count[g];
     r.re = (long long)acc[c * C_WORDS + C_RE], r.im = (long long)acc[c * C_WORDS + C_IM];
   }
   return PB_OK;
 }
 
 int pbSimGetScatteringTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
-  if (!S) return pbFail("pbSimGetScatteringTimes", ": null handle");
-  return pbSpanGet(S, S->sc.clock, S->sc.book.records, records, last_device_ms);
+  return pbLagTimes("pbSimGetScatteringTimes", S, &pbSim::sc, records, last_device_ms);
 }
 
 }  // extern "C"

@@ -2,7 +2,10 @@
 // overlap function per lag, averaged over time origins while pbSimStep runs (pbSimSetTimeCorrelation /
 // pbSimTimeCorrelationRecord / pbSimGetTimeCorrelation; include/particlebot_hip.h has the definitions).
 //
-//   k_tc_clear       zeroes the table: nine 64-bit words per (member, lag)
+// The ring of snapshots, its pairing lag by lag, its book and the shells of the entry points are the lag ring's
+// (pb_engine.hpp, PbLagBook ... pbLagTimes); here are what the ring stores, what a pair adds and how a row is written.
+// The table is nine 64-bit words per (member, lag).
+//
 //   k_tc_snapshot    one pass over pr[cur], vel[cur] and orig[cur] in SLOT order (coalesced reads); each lane writes one
 //                    float4 (x, y, vx, vy) to ring[slot][member * n + orig]: the scattered 16-byte store is the only
 //                    uncoalesced access
@@ -25,15 +28,10 @@ static_assert(sizeof(pbTimeCorrelationRow) == 96, "a lag's row is 96 bytes");
 
 namespace {
 
-constexpr int TT = 256;
+constexpr int TT = PB_LAG_LANES;
 // the words of a table cell
 enum { T_SAMPLES, T_QX, T_QY, T_MSD_LO, T_MSD_HI, T_VACF_LO, T_VACF_HI, T_OVERLAP, T_SUMS, T_MAX_Q2 = T_SUMS, T_COLS };
 static_assert(T_COLS == 9, "nine accumulators per lane and per cell");
-
-__global__ __launch_bounds__(TT) void k_tc_clear(unsigned long long *__restrict__ table, uint32_t words) {
-  const uint32_t i = blockIdx.x * TT + threadIdx.x;
-  if (i < words) table[i] = 0ull;
-}
 
 __global__ __launch_bounds__(TT) void k_tc_snapshot(const float4 *__restrict__ pr, const float2 *__restrict__ vel,
                                                     const uint32_t *__restrict__ orig, uint32_t n,
@@ -55,12 +53,7 @@ __global__ __launch_bounds__(TT) void k_tc_accumulate(const float4 *__restrict__
                                                       uint32_t blocksPerLag, unsigned long long a2,
                                                       unsigned long long *__restrict__ table) {
   __shared__ unsigned long long sRed[TT / 64][T_COLS];
-  const uint32_t perMember = nLags * blocksPerLag;
-  const uint32_t member = blockIdx.x / perMember, rest = blockIdx.x - member * perMember;
-  const uint32_t lag = rest / blocksPerLag, b = rest - lag * blocksPerLag;  // lag < nLags <= lags
-  const uint32_t slotThen = slotNow >= lag ? slotNow - lag : slotNow + lags - lag;
-  const float4 *now = ring + (size_t)slotNow * total + (size_t)member * n;
-  const float4 *then = ring + (size_t)slotThen * total + (size_t)member * n;
+  const auto [member, lag, b, now, then] = pbLagPair(ring, n, total, lags, slotNow, nLags, blocksPerLag);
   unsigned long long a[T_SUMS];
 #pragma unroll
   for (int c = 0; c < T_SUMS; c++) a[c] = 0ull;
@@ -102,32 +95,17 @@ __global__ __launch_bounds__(TT) void k_tc_accumulate(const float4 *__restrict__
   else atomicAdd(cell + c, v);  // two's complement: a signed word takes its sum modulo 2^64
 }
 
-// the ring and the zeroed table of a correlation of `lags` lags into T; on an error the caller drops T
-int allocate(pbSim *S, PbTimeCorr &T, unsigned lags) {
-  const size_t words = (size_t)S->nsims * lags * T_COLS;
-  PB_TRY(T.ring.alloc((size_t)lags * S->total));
-  PB_TRY(T.table.alloc(words));
-  hipLaunchKernelGGL(k_tc_clear, dim3(cdiv((uint32_t)words, TT)), dim3(TT), 0, S->stream, T.table, (uint32_t)words);
-  PB_TRY(hipGetLastError());
-  return PB_OK;
-}
-
 }  // namespace
 
 int pbTimeCorrRecord(pbSim *S) {
-  const uint32_t lags = S->tc.book.lags, slot = S->tc.book.slot(), nLags = S->tc.book.paired();
-  const uint32_t perMember = cdiv(S->n, TT);
-  const uint32_t bpl = perMember < PB_TCORR_BLOCKS ? perMember : PB_TCORR_BLOCKS;
+  PbTimeCorr &T = S->tc;
   const int c = S->cur;
-  PB_TRY(S->tc.clock.start(S->stream));
-  hipLaunchKernelGGL(k_tc_snapshot, dim3(cdiv(S->n, TT), S->nsims), dim3(TT), 0, S->stream, S->pr[c], S->vel[c],
-                     S->orig[c], S->n, S->tc.ring + (size_t)slot * S->total);
-  hipLaunchKernelGGL(k_tc_accumulate, dim3(S->nsims * nLags * bpl), dim3(TT), 0, S->stream, S->tc.ring, S->n, S->total,
-                     lags, slot, nLags, bpl, S->tc.a2, S->tc.table);
-  PB_TRY(hipGetLastError());
-  PB_TRY(S->tc.clock.stop(S->stream));
-  S->tc.book.recorded(S->stats.steps);
-  return PB_OK;
+  return pbLagRecord(S, T.lag, [&](dim3 grid, float4 *snap) {
+    hipLaunchKernelGGL(k_tc_snapshot, grid, dim3(TT), 0, S->stream, S->pr[c], S->vel[c], S->orig[c], S->n, snap);
+  }, [&](dim3 grid, uint32_t slot, uint32_t nLags, uint32_t bpl) {
+    hipLaunchKernelGGL(k_tc_accumulate, grid, dim3(TT), 0, S->stream, T.lag.ring, S->n, S->total, T.lag.book.lags,
+                       slot, nLags, bpl, T.a2, T.lag.table);
+  });
 }
 
 extern "C" {
@@ -135,37 +113,19 @@ extern "C" {
 int pbSimSetTimeCorrelation(pbSim *S, float interval, unsigned lags, float overlapRadius) {
   const char *fn = "pbSimSetTimeCorrelation";
   if (!S) return pbFail(fn, ": null handle");
-  if (!(interval == -1.0f) && (!(interval >= 0.0f) || !(interval < __builtin_inff())))
-    return pbFail(fn, ": interval must be finite and >= 0, or -1 for manual records only");
-  if (lags > PB_TCORR_MAX_LAGS) return pbFail(fn, ": lags must be at most 64");
+  if (const int rc = pbLagCheckArgs(fn, interval, lags)) return rc;
   if (!(overlapRadius >= 0.0f) || !pbFixedInRange(overlapRadius))
     return pbFail(fn, ": overlapRadius must be in [0, 2048)");
-  if (S->nsims > 65535u) return pbFail(fn, ": the batch must hold at most 65535 members");  // the member is a grid's y
-  int rc = pbCheckBatch(fn, S);
-  if (rc != PB_OK) return rc;
-  if ((unsigned long long)lags * S->total * sizeof(float4) > (1ull << 33))
-    return pbFail(fn, ": the ring (lags x bots x 16 bytes) must not exceed 2^33 bytes");
-  useDevice(S);
-  PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
-  S->tc = PbTimeCorr();
-  if (!lags) return PB_OK;
-  rc = allocate(S, S->tc, lags);
-  if (rc != PB_OK) {  // (a ring that took the last free memory, say): whatever was made goes, the correlation stays off
-    S->tc = PbTimeCorr();
-    (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
-    return rc;
-  }
-  const long long qa = pbFixedQuantise(overlapRadius);
-  S->tc.interval = interval, S->tc.radius = overlapRadius, S->tc.a2 = (unsigned long long)(qa * qa);
-  S->tc.book.start(lags);
-  return PB_OK;
+  if (const int rc = pbLagCheckBatch<float4>(fn, S, lags)) return rc;
+  return pbLagSwitch(S, S->tc, interval, lags, T_COLS, [&](PbTimeCorr &T) {
+    const long long qa = pbFixedQuantise(overlapRadius);
+    T.radius = overlapRadius, T.a2 = (unsigned long long)(qa * qa);
+    return PB_OK;
+  });
 }
 
 int pbSimTimeCorrelationRecord(pbSim *S) {
-  if (!S) return pbFail("pbSimTimeCorrelationRecord", ": null handle");
-  if (!S->tc.ring) return pbFail("pbSimTimeCorrelationRecord", ": the correlation is off");
-  useDevice(S);
-  return pbTimeCorrRecord(S);
+  return pbLagManualRecord("pbSimTimeCorrelationRecord", S, &pbSim::tc, "correlation", pbTimeCorrRecord);
 }
 
 int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float *overlapRadius,
@@ -173,32 +133,24 @@ int pbSimGetTimeCorrelationInfo(pbSim *S, float *interval, unsigned *lags, float
   if (!S) return pbFail("pbSimGetTimeCorrelationInfo", ": null handle");
   if (!interval && !lags && !overlapRadius && !records)
     return pbFail("pbSimGetTimeCorrelationInfo", ": interval, lags, overlapRadius and records are all null");
-  if (interval) *interval = S->tc.interval;
-  if (lags) *lags = S->tc.book.lags;
+  if (interval) *interval = S->tc.lag.interval;
+  if (lags) *lags = S->tc.lag.book.lags;
   if (overlapRadius) *overlapRadius = S->tc.radius;
-  if (records) *records = S->tc.book.records;
+  if (records) *records = S->tc.lag.book.records;
   return PB_OK;
 }
 
 int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
   if (!S || !rows) return pbFail("pbSimGetTimeCorrelation", ": null handle or rows");
-  if (!S->tc.ring) return pbFail("pbSimGetTimeCorrelation", ": the correlation is off");
-  useDevice(S);
-  const size_t cells = (size_t)S->nsims * S->tc.book.lags;
-  std::vector<unsigned long long> acc(cells * T_COLS);
-  PB_TRY(hipMemcpyAsync(acc.data(), S->tc.table, sizeof(unsigned long long) * acc.size(), hipMemcpyDeviceToHost,
-                        S->stream));
-  PB_TRY(hipStreamSynchronize(S->stream));
-  for (size_t k = 0; k < cells; k++)
-    if (acc[k * T_COLS + T_SAMPLES] >= (1ull << 31))  // the counts are exact whatever the state: the other sums may not be
-      return pbFail("pbSimGetTimeCorrelation", ": a lag holds 2^31 samples or more: restart the correlation");
-  for (size_t k = 0; k < cells; k++) {
+  const PbLagBook &book = S->tc.lag.book;
+  std::vector<unsigned long long> acc;
+  if (const int rc = pbLagFetch("pbSimGetTimeCorrelation", S, S->tc.lag, "correlation", acc, T_SAMPLES, T_COLS))
+    return rc;
+  for (size_t k = 0; k < (size_t)S->nsims * book.lags; k++) {
     const unsigned long long *w = &acc[k * T_COLS];
-    const unsigned lag = (unsigned)(k % S->tc.book.lags);
     pbTimeCorrelationRow &r = rows[k];
-    r.lag = lag, r.reserved = 0u;
-    r.origins = S->tc.book.origins[lag], r.sum_steps = S->tc.book.sumSteps[lag];
-    r.samples = w[T_SAMPLES];
+    book.columns((unsigned)(k % book.lags), r);
+    r.reserved = 0u, r.samples = w[T_SAMPLES];
     r.sum_qx = (long long)w[T_QX], r.sum_qy = (long long)w[T_QY];
     r.msd = pbFixedNormalised(pbFixedCompose(w[T_MSD_LO], w[T_MSD_HI]));
     r.vacf = pbFixedNormalised(pbFixedCompose(w[T_VACF_LO], w[T_VACF_HI]));
@@ -208,8 +160,7 @@ int pbSimGetTimeCorrelation(pbSim *S, pbTimeCorrelationRow *rows) {
 }
 
 int pbSimGetTimeCorrelationTimes(pbSim *S, unsigned long long *records, float *last_device_ms) {
-  if (!S) return pbFail("pbSimGetTimeCorrelationTimes", ": null handle");
-  return pbSpanGet(S, S->tc.clock, S->tc.book.records, records, last_device_ms);
+  return pbLagTimes("pbSimGetTimeCorrelationTimes", S, &pbSim::tc, records, last_device_ms);
 }
 
 }  // extern "C"

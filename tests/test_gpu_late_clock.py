@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import display_ref as R
+import scatter_ref as XR
 import series_ref as SR
 import test_late_clock_ref as LC
 import timecorr_ref as TR
@@ -124,6 +125,7 @@ def test_parity_with_a_payload_and_obstacles_from_16383_9(pb, orc, form):
 
 TRAIL = dict(centroid_int=0.2, centroid_steps=8)
 LAGS, OVERLAP = 8, 0.05
+SCAT, SCAT_BOX = 0.07, 3  # the scattering's own interval, no multiple of REC: its gate steps are not the others'
 
 
 def expected_trail(recs, pos_of, slots):
@@ -144,8 +146,12 @@ def test_records_from_a_late_start(pb, orc, t0, resident):
     gates = SR.gate_steps(t0, DT, REC, STEPS, 1e9)
     rec = [k for k, _ in gates]
     trail = LC.trail_slots(t0, TRAIL["centroid_int"], TRAIL["centroid_steps"], STEPS)
+    sgates = SR.gate_steps(t0, DT, SCAT, STEPS, 1e9)
+    srec = [k for k, _ in sgates]
+    vectors = pb.half_plane_vectors(1)[:3]
     assert LC.consecutive(rec) >= 16 and len(rec) > LAGS
-    stops = sorted(set(gates) | {(k, float(t)) for k, t, _ in trail})
+    assert len(srec) > LAGS and set(srec) - set(rec) and set(rec) - set(srec)
+    stops = sorted(set(gates) | set(sgates) | {(k, float(t)) for k, t, _ in trail})
     P = LC.late_params(orc, **TRAIL)
     start = state_from(LC.late_oracle(orc, P, t0))
 
@@ -160,6 +166,7 @@ def test_records_from_a_late_start(pb, orc, t0, resident):
     a, b = make(), make()
     a.set_series(REC, 512)
     a.set_time_correlation(REC, LAGS, OVERLAP)
+    a.set_scattering(SCAT, LAGS, SCAT_BOX, vectors)
     a.set_centroid_trail(True)
     assert a.step(STEPS, dt=DT, sort_interval=SORT) == STEPS  # one call
     # the twin, nothing switched on, stopped in front of every step at which a records something
@@ -177,6 +184,8 @@ def test_records_from_a_late_start(pb, orc, t0, resident):
     assert a.series_info()["records"] == a.time_correlation_info()["records"] == len(rec)
     want = TR.table([(at[k][1]["pos"], at[k][1]["vel"]) for k in rec], rec, LAGS, OVERLAP)
     assert a.time_correlation()[0] == want
+    assert a.scattering_info()["records"] == len(srec)
+    assert a.scattering()[0] == XR.table([at[k][1]["pos"] for k in srec], srec, LAGS, vectors, SCAT_BOX)
     xy, times, records = a.centroid_trail()
     want_xy, want_t, want_n = expected_trail(trail, lambda k: at[k][1]["pos"], TRAIL["centroid_steps"])
     assert records == want_n == len(trail)
@@ -191,6 +200,16 @@ def test_records_from_a_late_start(pb, orc, t0, resident):
         assert (s.stats()["steps"], s.stats()["resorts"], s.stats()["phase_updates"]) == (STEPS, resorts, updates)
     if resident == 2:
         assert a.stats()["resident_launches"] > 0
+    else:
+        # A step in front of which a record is due is not run ahead: the launch before it is plain and it starts with a
+        # state launch of its own, as do the call's first step and (plain only) its last launch.  The trail and the
+        # phase update read positions only and forbid no fusion.
+        due = len((set(rec) | set(srec)) - {0})
+        stats = a.stats()
+        print(t0, "records in front of", due, "steps;", stats)
+        assert stats["fused_launches"] == STEPS - 1 - due
+        assert stats["state_launches"] == stats["plain_launches"] == 1 + due
+        assert stats["resident_launches"] == 0
 
 
 # ---- a batch, the stop, the standing clock, a negative clock ---------------------------------------------------------
