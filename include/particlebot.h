@@ -264,6 +264,19 @@ class Particlebot {
   bool scatteringRecord();
   bool scatteringInfo(float &interval, unsigned &lags, int &boxLog2, unsigned &nvec, unsigned long long &records);
   bool scatteringRows(std::vector<pbScatteringRow> &rows);
+  /* The self van Hove function of the resident state on the device (pbSimSetVanHove / pbSimGetVanHove,
+   * include/particlebot_hip.h has the definitions): setVanHove(interval, lags, binWidth, bins) keeps a device ring of
+   * `lags` position snapshots, one taken in front of every step whose start time passes the schedule's gate at `interval`
+   * (0: every step, -1: only by vanHoveRecord), and a table of exact integer histograms per lag: `bins` radial bins of
+   * binWidth, 2 bins of each signed component, and the sums of the displacement's second and fourth powers; lags 0
+   * switches it off.  vanHoveRecord takes one record now; vanHoveInfo gives interval, lags, binWidth, bins and the
+   * records taken so far; vanHoveRows the `lags` rows and the lags * 5 * bins counters, per lag radial | x | y.  Fused
+   * engine only: Legacy and HostOnly instances return false with a message in lastError(), as do bad arguments, and a
+   * record or a read with the analysis off.  It is not part of a checkpoint. */
+  bool setVanHove(float interval, unsigned lags, float binWidth, unsigned bins);
+  bool vanHoveRecord();
+  bool vanHoveInfo(float &interval, unsigned &lags, float &binWidth, unsigned &bins, unsigned long long &records);
+  bool vanHoveRows(std::vector<pbVanHoveRow> &rows, std::vector<unsigned long long> &counts);
   /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
    * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on

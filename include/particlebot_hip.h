@@ -754,8 +754,8 @@ int pbSimGetCorrelationTimes(pbSim *sim, unsigned long long *analyses, float *la
  * into the ring (the only uncoalesced access), and one launch for all lags that reads two snapshots per lag as coalesced
  * 16-byte loads in original order, at most PB_TCORR_BLOCKS workgroups of 256 lanes per member and lag, each adding its
  * nine sums into the cell with one set of 64-bit integer atomics.
- * Out of scope: logarithmic or multi-tau lag spacing; the non-Gaussian parameter (sum s^2 does not fit the exact
- * scheme); phase correlations (they need a transcendental; the self-intermediate scattering function does not any more:
+ * Out of scope: logarithmic or multi-tau lag spacing; the non-Gaussian parameter here (sum s^2 does not fit a pair of
+ * words; the van Hove function keeps it in four: pbSimSetVanHove, below); phase correlations (they need a transcendental; the self-intermediate scattering function does not any more:
  * pbSimSetScattering, below); per-bot
  * outputs; neighbour-based quantities per lag such as bond lifetime; recording inside the resident kernel without ending
  * the stretch; the ensemble layer's summary rows and its RCCL gather; the legacy engine. */
@@ -996,6 +996,95 @@ int pbSimGetScatteringInfo(pbSim *sim, float *interval, unsigned *lags, int *box
                            unsigned long long *records);
 int pbSimGetScattering(pbSim *sim, pbScatteringRow *rows /* nsims * lags * nvec: member, lag, vector */);
 int pbSimGetScatteringTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
+
+/* Self van Hove function on the device (csrc/pb_vanhove.hip): the distribution whose moments the time correlation gives.
+ *     G_s(r, tau) = < (1/N) sum_i delta(r - (r_i(t + tau) - r_i(t))) >_t
+ * per member and lag as exact integer histograms, averaged over time origins while pbSimStep runs: a histogram of the
+ * displacement's length, one of each signed component (the drift towards the light skews these), and the sums of the
+ * second and fourth powers, from which the non-Gaussian parameter alpha_2 follows.  The ring, the records and the
+ * pairing are the time correlation's (pbSimSetTimeCorrelation, above).  Off by default: a run that does not ask for it
+ * makes the same launches, has the same pbSimStats and the same bits, and nothing is allocated.
+ * pbSimSetVanHove(sim, interval, lags, binWidth, bins).  interval follows the time correlation's rules exactly: > 0 the
+ * schedule's gate, 0 every step, -1.0f manual only.  lags is 1 ... PB_VANHOVE_MAX_LAGS; lags == 0 switches off and
+ * frees everything (binWidth and bins are then not read).  bins is 1 ... PB_VANHOVE_MAX_BINS.  binWidth is finite, > 0
+ * and < 2048, and its quantised value qw = rint(binWidth * 2^20) (pbSimMoments' quantisation) must be >= 1.  Calling
+ * again restarts from record 0 with a zeroed table.
+ * A RECORD is taken at the same instant and describes the same state as a time-correlation record.  It stores, per bot
+ * of every member in ORIGINAL order, the fp32 position (x, y): 8 bytes per bot and ring slot, into slot r % lags.
+ * A PAIR (now, then) of a bot is MEASURED iff dx = x_now - x_then and dy = y_now - y_then, formed in fp32, both satisfy
+ * fabsf(.) < 2048.0f: the time correlation's rule without its velocity terms; a NaN or an infinity fails it.  Then
+ *     qx = rint(dx * 2^20),  qy = rint(dy * 2^20),  s = qx^2 + qy^2 < 2^63
+ * which is the s of the time correlation: the histogram is the distribution whose second moment its msd is.
+ * PAIRING.  Record r is paired with the records r - l for l = 0 ... min(r, lags - 1).  Lag 0 pairs a record with itself:
+ * every measured pair lands in radial bin 0 and in index bins of x and of y.
+ * PER MEMBER AND LAG, over the measured (bot, origin) pairs:
+ *   RADIAL HISTOGRAM, bins counters.  The edges are E_k = min((k qw)^2, 2^63) for k = 0 ... bins, computed by the host
+ *     in 128-bit arithmetic and held as 64-bit words.  A pair goes to bin b = max{k : E_k <= s} iff s < E_bins, else to
+ *     beyond_r.  An edge belongs to the upper bin; a displacement of zero lands in bin 0.
+ *   AXIS HISTOGRAMS, 2 bins counters each for x and y.  bx = floor(qx / qw), floor towards minus infinity, is counted at
+ *     index bx + bins iff -bins <= bx < bins, else in beyond_x; the same for y.  Index j covers
+ *     [(j - bins) qw, (j - bins + 1) qw).
+ *   MOMENTS.  samples; msd = sum s, a 128-bit sum as pbMoment128 (NORMALISED: 0 <= lo < 2^32, hi the floor quotient),
+ *     units of 2^-40; q4 = sum s^2, 192 bits as three little-endian 64-bit limbs, units of 2^-80.
+ * These identities hold whatever the state:
+ *     sum radial + beyond_r = samples,   sum x + beyond_x = samples,   sum y + beyond_y = samples.
+ * The caller forms <r^2> = msd / (2^40 samples), <r^4> = q4 / (2^80 samples) and, in two dimensions,
+ * alpha_2 = <r^4> / (2 <r^2>^2) - 1.
+ * One pbVanHoveRow per member and lag: lag in RECORDS; origins, sum_steps and samples as in pbTimeCorrelationRow.
+ * EXACTNESS.  The bins are found in integers: a binary search in the exact edges and an integer division, no floating
+ * point guess.  s splits into two 64-bit accumulators as the time correlation's msd.  s^2 < 2^126 is the 128-bit
+ * product, added as its four 32-bit pieces to four 64-bit accumulators: each gains less than 2^32 per sample, so with
+ * fewer than 2^31 samples none wraps, and the host composes a0 + a1 2^32 + a2 2^64 + a3 2^96.  Integer adds commute:
+ * results do not depend on slot order, on the kernel form that stepped or on the order in which the device adds.  No
+ * float atomics and no 128-bit atomics.  pbSimGetVanHove checks the counts it is about to return, and if a cell holds
+ * 2^31 samples or more it answers PB_ERR_ARG ("a lag holds 2^31 samples or more: restart the van Hove function") and
+ * writes nothing.
+ * OTHER CALLS.  pbSimVanHoveRecord: one record now, of the state as it is, whatever the interval.
+ * pbSimGetVanHoveInfo: interval, lags (0: off), binWidth, bins and the records taken so far; any pointer may be NULL,
+ * not all.  pbSimGetVanHove: nsims * lags rows, member-major, and nsims * lags * 5 * bins counters, per member and lag
+ * the bins radial counters, then the 2 bins of x, then the 2 bins of y; either pointer may be NULL, not both; a lag
+ * that no record has reached yet has origins == 0 and zeros.  pbSimGetVanHoveTimes: records so far and the span of the
+ * last record's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
+ * When several records are due in front of a step the order is: series, time correlation, scattering, van Hove.  No
+ * launch is fused across the gate and a resident stretch ends in front of it, as for the other three.
+ * The ring is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it alone; pbSimDestroy
+ * frees it.  Recording never waits for the device.  It only reads: the state, slot layout, keys, cell lists,
+ * pbSimStats, time, RNG, the mark, the series, the time correlation, the scattering and every other analysis' scratch
+ * stay as they were.
+ * PB_ERR_ARG, before the device is touched: a NULL handle; rows and counts both NULL; interval NaN, infinite, or
+ * negative other than -1; lags > PB_VANHOVE_MAX_LAGS; bins outside 1 ... PB_VANHOVE_MAX_BINS; binWidth not in (0, 2048)
+ * or below half a quantum; a ring above 2^33 bytes (lags x total x 8); a table above 2^31 bytes (nsims x lags x
+ * (10 + 5 bins) x 8); a batch of 2^28 bots or more or of more than 65535 members; the pointers of pbSimGetVanHoveInfo
+ * all NULL; a record or a read with the analysis off.
+ * Cost: a record is one pass over posrad and original indices in slot order that scatters 8 bytes per bot into the ring,
+ * and one launch for all lags: one workgroup of 256 lanes per (member, lag, bot block), at most PB_VANHOVE_BLOCKS blocks
+ * per member and lag.  A workgroup keeps the edges (8 KiB at most) and a histogram of 5 bins 32-bit counters (20 KiB at
+ * most) in LDS, reads the two snapshots as coalesced 8-byte loads, adds three LDS counters per pair and keeps the
+ * moments in registers; at the end each non-zero counter is one 64-bit integer atomic into the cell.  Device memory:
+ * the ring, (10 + 5 bins) x 8 bytes per member and lag, and (bins + 1) x 8 bytes of edges.
+ * Out of scope: the distinct part G_d; logarithmic bins or lag spacing; a two-dimensional histogram of (dx, dy);
+ * displacements relative to the centroid; the ensemble layer's summary rows; the legacy engine. */
+#define PB_VANHOVE_MAX_LAGS 64u
+#define PB_VANHOVE_MAX_BINS 1024u
+#define PB_VANHOVE_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
+typedef struct pbVanHoveRow {          /* 96 bytes */
+  unsigned lag, reserved;              /* lag in RECORDS: record r against record r - lag; 0 */
+  unsigned long long origins;          /* record pairs added so far (the same for every member) */
+  unsigned long long sum_steps;        /* sum over those pairs of step(r) - step(r - lag) */
+  unsigned long long samples;          /* measured (bot, origin) pairs */
+  unsigned long long beyond_r;         /* measured pairs with s >= E_bins */
+  unsigned long long beyond_x;         /* ... with floor(qx / qw) outside -bins ... bins - 1 */
+  unsigned long long beyond_y;
+  pbMoment128 msd;                     /* sum s; units of 2^-40 */
+  unsigned long long q4[3];            /* sum s^2, 192 bits little-endian; units of 2^-80 */
+} pbVanHoveRow;
+int pbSimSetVanHove(pbSim *sim, float interval, unsigned lags, float binWidth, unsigned bins);
+int pbSimVanHoveRecord(pbSim *sim);   /* one record now, of the state as it is */
+int pbSimGetVanHoveInfo(pbSim *sim, float *interval, unsigned *lags, float *binWidth, unsigned *bins,
+                        unsigned long long *records);
+int pbSimGetVanHove(pbSim *sim, pbVanHoveRow *rows /* nsims * lags, or NULL */,
+                    unsigned long long *counts /* nsims * lags * 5 * bins: radial | x | y, or NULL; not both NULL */);
+int pbSimGetVanHoveTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a

@@ -17,7 +17,7 @@ from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
            "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
-           "half_plane_vectors", "phasor_table", "scattering_summary"]
+           "half_plane_vectors", "phasor_table", "scattering_summary", "van_hove_summary"]
 
 
 def phasor_table():
@@ -125,6 +125,40 @@ def scattering_summary(row):
     return {"fs_re": float(Fraction(int(row["re"]), m << 30)) if m else None,
             "fs_im": float(Fraction(int(row["im"]), m << 30)) if m else None,
             "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else None}
+
+
+def van_hove_summary(row, width):
+    """What one row of van_hove() says, in float64 from the integers (pure Python; every quotient is formed as one exact
+    fraction and converted once): msd = msd / (2^40 samples), the mean squared displacement in world units;
+    msd_in_widths = that over width^2, which says how many bins of `width` the distribution spans;
+    alpha2 = <r^4> / (2 <r^2>^2) - 1 = q4 samples / (2 msd^2) - 1, the non-Gaussian parameter in two dimensions (0 for a
+    Gaussian; nan where msd == 0); mean_lag_steps = sum_steps / origins.  msd and msd_in_widths are nan for a row with
+    no samples, mean_lag_steps for one with no origins."""
+    from fractions import Fraction
+    m, origins, msd, q4 = (int(row[k]) for k in ("samples", "origins", "msd", "q4"))
+    nan = float("nan")
+    mean = Fraction(msd, m << 40) if m else None
+    w2 = Fraction(float(width)) ** 2
+    return {"msd": float(mean) if m else nan,
+            "msd_in_widths": float(mean / w2) if m and w2 else nan,
+            "alpha2": float(Fraction(q4 * m, 2 * msd * msd) - 1) if msd else nan,
+            "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else nan}
+
+
+def van_hove_lists(rows, counts, nsims, lags, bins):
+    """The rows and counters of pbSimGetVanHove as van_hove() returns them: per member a list over lags of dicts, each
+    van_hove_row() plus radial (bins ints), x and y (2 bins ints each)."""
+    out = []
+    for m in range(nsims):
+        member = []
+        for l in range(lags):
+            g = m * lags + l
+            c = [int(v) for v in counts[g * 5 * bins:(g + 1) * 5 * bins]]
+            d = _capi.van_hove_row(rows[g])
+            d["radial"], d["x"], d["y"] = c[:bins], c[bins:3 * bins], c[3 * bins:]
+            member.append(d)
+        out.append(member)
+    return out
 
 
 def field_values(cells):
@@ -941,6 +975,48 @@ class Sim:
         """(records taken so far, device milliseconds of the last record's launches)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetScatteringTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetScatteringTimes")
+        return int(n.value), float(ms.value)
+
+
+    def set_van_hove(self, interval, lags, width, bins):
+        """Keep a device ring of `lags` snapshots of the positions (original order), one taken in front of every step
+        whose start time passes the schedule's gate at `interval` (0: every step, -1: only by van_hove_record()) while
+        step() runs, and add every record against the `lags` latest ones into a table per member and lag
+        (pbSimSetVanHove): the self van Hove function as exact integer histograms of the displacement's length (`bins`
+        bins of `width`) and of its x and y components (2 bins each, from -bins width to bins width), with the sums of
+        its second and fourth powers.  Restarts at record 0; lags 0 switches it off.  Recording changes no state bit."""
+        _capi.check(_capi.lib().pbSimSetVanHove(self._h, float(interval), int(lags), float(width), int(bins)),
+                    "pbSimSetVanHove")
+
+    def van_hove_record(self):
+        """One record now, of the state as it is (pbSimVanHoveRecord)."""
+        _capi.check(_capi.lib().pbSimVanHoveRecord(self._h), "pbSimVanHoveRecord")
+
+    def van_hove_info(self):
+        """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveInfo)."""
+        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
+        _capi.check(_capi.lib().pbSimGetVanHoveInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b),
+                                                    C.byref(r)), "pbSimGetVanHoveInfo")
+        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
+                "records": int(r.value)}
+
+    def van_hove(self):
+        """The table as it stands (pbSimGetVanHove): per member a list over lags (lag 0 first) of dicts of Python ints:
+        lag, origins, sum_steps, samples, beyond_r, beyond_x, beyond_y, msd (units of 2^-40), q4 (units of 2^-80), and
+        the histograms radial (bins ints), x and y (2 bins ints each, index j covering [(j - bins) width,
+        (j - bins + 1) width)) as lists.  van_hove_summary() turns a row into msd and alpha2."""
+        info = self.van_hove_info()
+        lags, bins = info["lags"], info["bins"]
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbVanHoveRow * max(nsims * lags, 1))()
+        counts = (C.c_ulonglong * max(nsims * lags * 5 * bins, 1))()
+        _capi.check(_capi.lib().pbSimGetVanHove(self._h, rows, counts), "pbSimGetVanHove")
+        return van_hove_lists(rows, counts, nsims, lags, bins)
+
+    def van_hove_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetVanHoveTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetVanHoveTimes")
         return int(n.value), float(ms.value)
 
 

@@ -271,6 +271,26 @@ def scattering_row(r):
     return {name: int(getattr(r, name)) for name, _ in pbScatteringRow._fields_ if name != "reserved"}
 
 
+class pbVanHoveRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
+                ("samples", C.c_ulonglong), ("beyond_r", C.c_ulonglong), ("beyond_x", C.c_ulonglong),
+                ("beyond_y", C.c_ulonglong), ("msd", pbMoment128), ("q4", C.c_ulonglong * 3)]
+
+
+VANHOVE_MAX_LAGS = 64
+VANHOVE_MAX_BINS = 1024
+
+
+def van_hove_row(r):
+    """A pbVanHoveRow as a dict of Python ints (reserved left out): msd composed from its 128 bits (hi * 2^32 + lo,
+    units of 2^-40) and q4 from its three little-endian 64-bit limbs (units of 2^-80)."""
+    out = {name: int(getattr(r, name)) for name in ("lag", "origins", "sum_steps", "samples", "beyond_r", "beyond_x",
+                                                    "beyond_y")}
+    out["msd"] = (int(r.msd.hi) << 32) + int(r.msd.lo)
+    out["q4"] = int(r.q4[0]) + (int(r.q4[1]) << 64) + (int(r.q4[2]) << 128)
+    return out
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -372,6 +392,12 @@ SYMBOLS = {
                                     C.POINTER(C.c_ulonglong)]),
     "pbSimGetScattering": (_I, [_VP, C.POINTER(pbScatteringRow)]),
     "pbSimGetScatteringTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimSetVanHove": (_I, [_VP, _F, _U, _F, _U]),
+    "pbSimVanHoveRecord": (_I, [_VP]),
+    "pbSimGetVanHoveInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_F), C.POINTER(_U),
+                                 C.POINTER(C.c_ulonglong)]),
+    "pbSimGetVanHove": (_I, [_VP, C.POINTER(pbVanHoveRow), C.POINTER(C.c_ulonglong)]),
+    "pbSimGetVanHoveTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1559,6 +1559,34 @@ bool Particlebot::scatteringRows(std::vector<pbScatteringRow> &rows) {
   });
 }
 
+bool Particlebot::setVanHove(float interval, unsigned lags, float binWidth, unsigned bins) {
+  auto call = [&] { return pbSimSetVanHove(sim, interval, lags, binWidth, bins); };
+  return onFusedEngine("setVanHove", "van Hove function", call);
+}
+
+bool Particlebot::vanHoveRecord() {
+  return onFusedEngine("vanHoveRecord", "van Hove function", [&] { return pbSimVanHoveRecord(sim); });
+}
+
+bool Particlebot::vanHoveInfo(float &interval, unsigned &lags, float &binWidth, unsigned &bins,
+                              unsigned long long &records) {
+  auto call = [&] { return pbSimGetVanHoveInfo(sim, &interval, &lags, &binWidth, &bins, &records); };
+  return onFusedEngine("vanHoveInfo", "van Hove function", call);
+}
+
+bool Particlebot::vanHoveRows(std::vector<pbVanHoveRow> &rows, std::vector<unsigned long long> &counts) {
+  return onFusedEngine("vanHoveRows", "van Hove function", [&] {
+    unsigned lags = 0, bins = 0;
+    const int rc = pbSimGetVanHoveInfo(sim, nullptr, &lags, nullptr, &bins, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? lags : 1, pbVanHoveRow());  // (with the analysis off the engine refuses)
+    counts.assign(lags ? (size_t)lags * 5u * bins : 1, 0ull);
+    const int got = pbSimGetVanHove(sim, rows.data(), counts.data());
+    if (got != PB_OK) rows.clear(), counts.clear();
+    return got;
+  });
+}
+
 bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
   return onFusedEngine("fieldMap", "field map", [&] {
     const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;

@@ -473,6 +473,43 @@ int pbHostScatteringRows(void *hv, pbScatteringRow *rows, unsigned long long cap
   return 0;
 }
 
+// the self van Hove function of the resident state (Particlebot::setVanHove / vanHoveRecord / vanHoveInfo / vanHoveRows;
+// fused engine only): the recorder's switch, one record now, what it holds, and the 96-byte pbVanHoveRow of every lag
+// with the lag's 5 * bins counters (cap rows and 5 * bins * cap counters of room; *count = how many rows there are).
+// -1 on the other engines, a bad interval, lags, width or bins, a record or a read with the analysis off, or too
+// little room.
+int pbHostSetVanHove(void *hv, float interval, unsigned lags, float binWidth, unsigned bins) {
+  return ((HostSim *)hv)->bot->setVanHove(interval, lags, binWidth, bins) ? 0 : -1;
+}
+
+int pbHostVanHoveRecord(void *hv) { return ((HostSim *)hv)->bot->vanHoveRecord() ? 0 : -1; }
+
+int pbHostVanHoveInfo(void *hv, float *interval, unsigned *lags, float *binWidth, unsigned *bins,
+                      unsigned long long *records) {
+  float i = 0.0f, w = 0.0f;
+  unsigned l = 0, b = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->vanHoveInfo(i, l, w, b, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (binWidth) *binWidth = w;
+  if (bins) *bins = b;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostVanHoveRows(void *hv, pbVanHoveRow *rows, unsigned long long *counts, unsigned long long cap,
+                      unsigned long long *count) {
+  std::vector<pbVanHoveRow> v;
+  std::vector<unsigned long long> c;
+  if (!count || !((HostSim *)hv)->bot->vanHoveRows(v, c)) return -1;
+  *count = v.size();
+  if ((rows || counts) && cap < v.size()) return -1;
+  copyOut(rows, v);
+  copyOut(counts, c);
+  return 0;
+}
+
 // a field map of the resident state (Particlebot::fieldMap; fused engine only): ny * nx 64-byte pbFieldCell entries and,
 // unless NULL, the 16-byte pbFieldTotals row.  -1 on the other engines and on a bad view.
 int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFieldTotals *totals) {

@@ -92,7 +92,7 @@ struct PbSeries {
   std::vector<float> times;               // per slot: start time of the step the record was taken in front of
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
-// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip) share -----------------------------------
+// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip) share -------------------
 // A ring of `lags` snapshots of the whole batch in ORIGINAL order, lags x total entries of Snap.  Record r goes into
 // slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1); all pairs of a record are added
 // into `table` by one launch over pbLagGrid() workgroups of PB_LAG_LANES lanes, which pbLagPair() takes apart again.
@@ -100,8 +100,10 @@ struct PbSeries {
 // pbLag... host functions behind pbSim.  An analysis adds its snapshot kernel, its accumulate body and its row writer.
 constexpr int PB_LAG_LANES = 256;
 constexpr unsigned PB_LAG_MAX_LAGS = 64u, PB_LAG_BLOCKS = 256u;  // (the public header states both per analysis)
-static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS, "one bound on the lags");
-static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS, "one bound on the blocks per lag");
+static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS &&
+                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS, "one bound on the lags");
+static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS &&
+                  PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS, "one bound on the blocks per lag");
 
 // the host's counters of a ring
 struct PbLagBook {
@@ -132,7 +134,7 @@ struct PbLagRing {
   float interval = 0.0f;               // 0: in front of every step; -1: manual records only
   PbLagBook book;                      // lags (0: off), records, steps per slot, origins and step sums per lag
   PbSpanClock clock;                   // around the last record's launches
-  // an entry point that needs the analysis on refuses when the `what` ("correlation", "scattering") is off
+  // an entry point that needs the analysis on refuses when the `what` ("correlation", "scattering", ...) is off
   int checkOn(const char *fn, const char *what) const {
     return ring ? PB_OK : pbFail(fn, std::string(": the ") + what + " is off");
   }
@@ -194,6 +196,15 @@ struct PbScattering {
   std::vector<int> list;   // the host's copy of the list, as passed
   unsigned nvec = 0;
   int boxLog2 = 0;
+};
+
+// self van Hove function (pb_vanhove.hip): float2 (x, y) snapshots and nsims x lags cells of 10 + 5 bins words, member-
+// major: ten moments, then the radial, x and y histograms (pb_vanhove.hpp; pbSimSetVanHove)
+struct PbVanHove {
+  PbLagRing<float2> lag;
+  float width = 0.0f;
+  uint32_t qw = 0, bins = 0;              // rint(width * 2^20); counters per radial histogram
+  PbDevBuf<unsigned long long> edges;  // bins + 1: E_k = min((k qw)^2, 2^63)
 };
 
 // Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
@@ -277,6 +288,7 @@ struct pbSim {
   PbField field;
   PbSfactor sk;
   PbScattering sc;
+  PbVanHove vh;
   pbSimStats stats{};
 };
 
@@ -331,7 +343,7 @@ int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words) {
   PB_TRY(hipMemsetAsync(R.table, 0, sizeof(unsigned long long) * words, S->stream));
   return PB_OK;
 }
-// Switches the analysis `held` (S->tc, S->sc) off and, unless lags is 0, on again: a fresh value with a ring of `lags`
+// Switches the analysis `held` (S->tc, S->sc, S->vh) off and, unless lags is 0, on again: a fresh value with a ring of `lags`
 // snapshots, a zeroed table of wordsPerLag words per member and lag, a book at record 0, and what fill(fresh) sets of
 // the analysis' own.  When any of it fails, what was made goes and the analysis stays off.
 template <typename A, typename Fill>
@@ -447,3 +459,4 @@ void pbClusterFree(pbSim *S);
 int pbSeriesRecord(pbSim *S, float t);  // ... in front of the step that starts at t                        pb_moments.hip
 int pbTimeCorrRecord(pbSim *S);         // ... a snapshot and its lags (pbLagRecord)                        pb_timecorr.hip
 int pbScatteringRecord(pbSim *S);       // ... a quantised snapshot and its lags (pbLagRecord)              pb_scatter.hip
+int pbVanHoveRecord(pbSim *S);          // ... a position snapshot and its lags (pbLagRecord)               pb_vanhove.hip

@@ -1,5 +1,5 @@
 // pb_fixed.hpp -- the fixed-point kit of the analyses that accumulate exact integers on the device (pb_moments.hip,
-// pb_timecorr.hip, pb_field.hip, pb_dynamics.hip, pb_correlate.hip; the wave helpers serve pb_cluster.hip,
+// pb_timecorr.hip, pb_vanhove.hip, pb_field.hip, pb_dynamics.hip, pb_correlate.hip; the wave helpers serve pb_cluster.hip,
 // pb_contacts.hip and pb_structure.hip too): the quantiser and its range, the split of a 64-bit product into two
 // accumulators, the sums over a wave and over a workgroup's four waves, and the host's way back to a pbMoment128.
 // The arithmetic part compiles as plain C++ (tests/pb_fixed_check.cpp); the device part needs hipcc.

@@ -11,6 +11,7 @@
 //                   [--field FILE [--field-cells N] [--field-half H]]
 //                   [--sk FILE [--sk-kind density|radius|velocity] [--sk-box-log2 E] [--sk-nmax M]]
 //                   [--scatter FILE [--scatter-interval T] [--scatter-lags N] [--scatter-box-log2 E] [--scatter-nmax M]]
+//                   [--vanhove FILE [--vanhove-interval T] [--vanhove-lags N] [--vanhove-width W] [--vanhove-bins B]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -100,6 +101,11 @@ struct RunOptions {
   int skKind = PB_SK_DENSITY;
   long skBoxLog2 = PB_SK_MIN_LOG2 - 1, scatterBoxLog2 = PB_SK_MIN_LOG2 - 1;  // below the range: boxLog2() chooses
   long skNmax = 16, scatterNmax = 3;  // 544 and 24 wavevectors
+
+  std::string vanhovePath;
+  float vanhoveInterval = -1.0f;  // below 0: dump_interval
+  float vanhoveWidth = -1.0f;     // below 0: an eighth of min_radius (a default and not a claim)
+  long vanhoveLags = 32, vanhoveBins = 64;
 };
 
 using Choice = std::pair<const char *, int>;  // a word and what it stands for
@@ -195,6 +201,12 @@ const Flag kFlags[] = {
     {"--scatter-lags", &RunOptions::scatterLags, 1, PB_SCATTER_MAX_LAGS},
     {"--scatter-box-log2", &RunOptions::scatterBoxLog2, PB_SK_MIN_LOG2, PB_SK_MAX_LOG2},
     {"--scatter-nmax", &RunOptions::scatterNmax, 1, 10},  // (11: 264 vectors, past PB_SCATTER_MAX_VECTORS)
+
+    {"--vanhove", &RunOptions::vanhovePath, "recorder"},
+    {"--vanhove-interval", &RunOptions::vanhoveInterval, 0.0f, false},
+    {"--vanhove-lags", &RunOptions::vanhoveLags, 1, PB_VANHOVE_MAX_LAGS},
+    {"--vanhove-width", &RunOptions::vanhoveWidth, 0.0f, true, 2048.0f},
+    {"--vanhove-bins", &RunOptions::vanhoveBins, 1, PB_VANHOVE_MAX_BINS},
 };
 
 // a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
@@ -272,6 +284,23 @@ std::string decimal128(const pbMoment128 &m) {
   const __int128 v = (__int128)m.hi * ((__int128)1 << 32) + (__int128)m.lo;
   const unsigned __int128 mag = v < 0 ? -(unsigned __int128)v : (unsigned __int128)v;
   return (v < 0 ? "-" : "") + decimal128((unsigned long long)(mag >> 64), (unsigned long long)mag);
+}
+
+// an unsigned integer of little-endian 64-bit limbs in decimal
+std::string decimalLimbs(std::vector<unsigned long long> v) {
+  std::string s;
+  bool more = true;
+  while (more) {
+    unsigned long long rem = 0;
+    more = false;
+    for (size_t k = v.size(); k-- > 0;) {
+      const unsigned __int128 cur = ((unsigned __int128)rem << 64) | v[k];
+      v[k] = (unsigned long long)(cur / 10), rem = (unsigned long long)(cur % 10);
+      more = more || v[k] != 0;
+    }
+    s.insert(s.begin(), (char)('0' + (int)rem));
+  }
+  return s;
 }
 
 // an analysis output; NULL after saying so
@@ -652,6 +681,58 @@ struct Run {
     }
     return fclose(f) == 0;
   }
+
+  // --vanhove FILE: the device's self van Hove function (Particlebot::setVanHove).  While the engine steps, a snapshot of
+  // the positions is taken in front of every step whose start time passes the schedule's gate at --vanhove-interval, into
+  // a device ring of --vanhove-lags snapshots, and every record is added against the latest ones into the histograms of
+  // every bot's displacement per lag: --vanhove-bins radial bins of --vanhove-width and twice as many of each component.
+  // Switched on behind a resume, like --timecorr (the ring is not part of a checkpoint), and refused by the same count.
+  // At the end of the run, per lag, lag 0 first: the radial bins (Axis r), then those of x, then of y, each axis followed
+  // by one line with Bin -1 for its beyond count.  The lag's columns are repeated on each of its lines: the integers as
+  // they are (SumQ2 in units of 2^-40, SumQ4 of 2^-80, in decimal from their 128 and 192 bits), then
+  // Alpha2 = SumQ4 Samples / (2 SumQ2^2) - 1 as %.9g (nan where SumQ2 is 0).  Lower is the bin's lower edge in world
+  // units as %.9g, a multiple of the quantised width; a beyond line has the radial histogram's end, and nan for an axis,
+  // whose beyond count has two sides.
+  int startVanHove() {
+    if (o.vanhovePath.empty()) return 0;
+    const float every = recordEvery(o.vanhoveInterval, cfg);
+    if (!recordsFit("--vanhove", every)) return 2;
+    const float width = o.vanhoveWidth > 0.0f ? o.vanhoveWidth : 0.125f * sim.getParams().min_radius;
+    return sim.setVanHove(every, (unsigned)o.vanhoveLags, width, (unsigned)o.vanhoveBins) ? 0 : 1;
+  }
+
+  bool writeVanHove() {
+    if (o.vanhovePath.empty()) return true;
+    std::vector<pbVanHoveRow> rows;
+    std::vector<unsigned long long> counts;
+    float interval = 0.0f, width = 0.0f;
+    unsigned lags = 0, bins = 0;
+    unsigned long long records = 0;
+    if (!sim.vanHoveRows(rows, counts) || !sim.vanHoveInfo(interval, lags, width, bins, records)) return false;
+    FILE *f = openWhole(o.vanhovePath, "Lag, Origins, SumSteps, Samples, SumQ2, SumQ4, Alpha2, Axis, Bin, Lower, Count");
+    if (!f) return false;
+    const double qw = (double)std::nearbyint(width * 1048576.0f) / 1048576.0;  // the quantised width, as the engine's
+    for (size_t l = 0; l < rows.size(); l++) {
+      const pbVanHoveRow &v = rows[l];
+      const long double q2 = std::ldexp((long double)v.msd.hi, 32) + (long double)v.msd.lo;
+      const long double q4 = std::ldexp((long double)v.q4[2], 128) + std::ldexp((long double)v.q4[1], 64) + (long double)v.q4[0];
+      const double alpha2 = q2 != 0.0L ? (double)(q4 * (long double)v.samples / (2.0L * q2 * q2) - 1.0L) : std::nan("");
+      char lead[512];
+      snprintf(lead, sizeof lead, "%u, %llu, %llu, %llu, %s, %s, %.9g", v.lag, v.origins, v.sum_steps, v.samples,
+               decimal128(v.msd).c_str(), decimalLimbs({v.q4[0], v.q4[1], v.q4[2]}).c_str(), alpha2);
+      const unsigned long long *c = &counts[l * 5u * bins];
+      // an axis: its counters, where they start, the bin of its first counter, its beyond count and that line's edge
+      const auto axis = [&](char name, size_t at, size_t count, long first, unsigned long long beyond, double end) {
+        for (size_t j = 0; j < count; j++)
+          fprintf(f, "%s, %c, %zu, %.9g, %llu\n", lead, name, j, (double)(first + (long)j) * qw, c[at + j]);
+        fprintf(f, "%s, %c, -1, %.9g, %llu\n", lead, name, end, beyond);
+      };
+      axis('r', 0, bins, 0, v.beyond_r, (double)bins * qw);
+      axis('x', bins, 2u * (size_t)bins, -(long)bins, v.beyond_x, std::nan(""));
+      axis('y', 3u * (size_t)bins, 2u * (size_t)bins, -(long)bins, v.beyond_y, std::nan(""));
+    }
+    return fclose(f) == 0;
+  }
 };
 
 }  // namespace
@@ -786,6 +867,7 @@ int main(int argc, char **argv) {
   if (!run.startSeries()) return 1;
   if (const int refused = run.startTimeCorrelation()) return refused;
   if (const int refused = run.startScattering()) return refused;
+  if (const int refused = run.startVanHove()) return refused;
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!o.ckptPath.empty() && run.stepsDone > lastCkptStep) {
@@ -820,6 +902,6 @@ int main(int argc, char **argv) {
   if (!o.finalCkptPath.empty() && !writeCheckpoint(o.finalCkptPath)) return 1;
   fclose(fp);
   const bool written = run.writeTrail() && run.writeContacts() && run.writeRdf() && run.writeTimeCorrelation() &&
-                       run.writeScattering() && run.writeCorrelation();
+                       run.writeScattering() && run.writeVanHove() && run.writeCorrelation();
   return written ? 0 : 1;
 }

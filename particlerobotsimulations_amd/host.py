@@ -63,6 +63,9 @@ _ANALYSES = {
     "pbHostSetScattering": [_F, C.c_uint, C.c_int, _P, C.c_uint], "pbHostScatteringRecord": [],
     "pbHostScatteringInfo": [_P, _P, _P, _P, _P],
     "pbHostScatteringRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
+    "pbHostSetVanHove": [_F, C.c_uint, _F, C.c_uint], "pbHostVanHoveRecord": [],
+    "pbHostVanHoveInfo": [_P, _P, _P, _P, _P],
+    "pbHostVanHoveRows": [_P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
     "pbHostFieldMap": [_P, _P, _P],
     "pbHostStructureFactor": [C.c_int, C.c_int, _P, C.c_uint, _P],
 }
@@ -482,6 +485,43 @@ class HostSim:
             raise RuntimeError("scattering: the scattering needs the fused engine, the scattering on and fewer than "
                                "2^31 samples per lag")
         return [[[_capi.scattering_row(rows[l * nvec + k]) for k in range(nvec)] for l in range(lags)]]
+
+    def set_van_hove(self, interval, lags, width, bins):
+        """Keep a device ring of `lags` position snapshots, one per step whose start passes the schedule's gate at
+        `interval` (0: every step, -1: only by van_hove_record()), and add every record against the `lags` latest ones
+        into exact integer histograms of the displacement per lag: `bins` radial bins of `width` and 2 bins of each
+        component (pbSimSetVanHove; fused engine only).  Restarts at record 0; lags 0 switches it off."""
+        if lib().pbHostSetVanHove(self._h, float(interval), int(lags), float(width), int(bins)) != 0:
+            raise RuntimeError("set_van_hove: the van Hove function needs the fused engine, a finite interval >= 0 (or "
+                               "-1), lags <= 64, a width in (0, 2048) and 1 ... 1024 bins")
+
+    def van_hove_record(self):
+        """One record now, of the state as it is (pbSimVanHoveRecord; fused engine only)."""
+        if lib().pbHostVanHoveRecord(self._h) != 0:
+            raise RuntimeError("van_hove_record: the van Hove function needs the fused engine and the analysis on")
+
+    def van_hove_info(self):
+        """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveInfo; fused engine
+        only)."""
+        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
+        if lib().pbHostVanHoveInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b), C.byref(r)) != 0:
+            raise RuntimeError("van_hove_info: the van Hove function needs the fused engine")
+        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
+                "records": int(r.value)}
+
+    def van_hove(self):
+        """The table as it stands, as Sim.van_hove gives it: a list with one list over lags of dicts of Python ints, the
+        histograms radial, x and y as lists (Particlebot::vanHoveRows; fused engine only)."""
+        from . import van_hove_lists
+        info = self.van_hove_info()
+        lags, bins = info["lags"], info["bins"]
+        cap = max(lags, 1)
+        rows, counts = (_capi.pbVanHoveRow * cap)(), (C.c_ulonglong * max(cap * 5 * bins, 1))()
+        count = C.c_ulonglong(0)
+        if lib().pbHostVanHoveRows(self._h, rows, counts, cap, C.byref(count)) != 0:
+            raise RuntimeError("van_hove: the van Hove function needs the fused engine, the analysis on and fewer than "
+                               "2^31 samples per lag")
+        return van_hove_lists(rows, counts, 1, lags, bins)
 
     def field_map(self, nx, ny, center, half, member=None):
         """A field map of the state as it is now, on the device (pbSimFieldMap; fused engine only): (cells, totals) as
