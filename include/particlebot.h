@@ -277,6 +277,17 @@ class Particlebot {
   bool vanHoveRecord();
   bool vanHoveInfo(float &interval, unsigned &lags, float &binWidth, unsigned &bins, unsigned long long &records);
   bool vanHoveRows(std::vector<pbVanHoveRow> &rows, std::vector<unsigned long long> &counts);
+  /* The distinct van Hove function of the resident state on the device (pbSimSetVanHoveDistinct /
+   * pbSimGetVanHoveDistinct, include/particlebot_hip.h has the definitions), shaped as the self part above:
+   * setVanHoveDistinct(interval, lags, binWidth, bins) keeps a ring of `lags` position snapshots and, per lag, `bins`
+   * exact counters of the ordered pairs (a bot then, another bot now) by distance; bins * binWidth must stay below 2048.
+   * vanHoveDistinctRows gives the `lags` rows and the lags * bins counters.  Fused engine only; not part of a
+   * checkpoint. */
+  bool setVanHoveDistinct(float interval, unsigned lags, float binWidth, unsigned bins);
+  bool vanHoveDistinctRecord();
+  bool vanHoveDistinctInfo(float &interval, unsigned &lags, float &binWidth, unsigned &bins,
+                           unsigned long long &records);
+  bool vanHoveDistinctRows(std::vector<pbVanHoveDistinctRow> &rows, std::vector<unsigned long long> &counts);
   /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
    * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on

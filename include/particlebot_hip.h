@@ -1062,7 +1062,7 @@ int pbSimGetScatteringTimes(pbSim *sim, unsigned long long *records, float *last
  * most) in LDS, reads the two snapshots as coalesced 8-byte loads, adds three LDS counters per pair and keeps the
  * moments in registers; at the end each non-zero counter is one 64-bit integer atomic into the cell.  Device memory:
  * the ring, (10 + 5 bins) x 8 bytes per member and lag, and (bins + 1) x 8 bytes of edges.
- * Out of scope: the distinct part G_d; logarithmic bins or lag spacing; a two-dimensional histogram of (dx, dy);
+ * Out of scope: logarithmic bins or lag spacing; a two-dimensional histogram of (dx, dy);
  * displacements relative to the centroid; the ensemble layer's summary rows; the legacy engine. */
 #define PB_VANHOVE_MAX_LAGS 64u
 #define PB_VANHOVE_MAX_BINS 1024u
@@ -1085,6 +1085,82 @@ int pbSimGetVanHoveInfo(pbSim *sim, float *interval, unsigned *lags, float *binW
 int pbSimGetVanHove(pbSim *sim, pbVanHoveRow *rows /* nsims * lags, or NULL */,
                     unsigned long long *counts /* nsims * lags * 5 * bins: radial | x | y, or NULL; not both NULL */);
 int pbSimGetVanHoveTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
+
+/* Distinct van Hove function on the device (csrc/pb_vanhove_distinct.hip): the other half of the van Hove function,
+ *     G_d(r, tau) = < (1/N) sum_i sum_{j != i} delta(r - |r_j(t + tau) - r_i(t)|) >_t
+ * per member and lag as an exact integer histogram of ordered pairs, averaged over time origins while pbSimStep runs:
+ * where the OTHER bots are, tau later, relative to where a bot was.  Its tau = 0 limit is the radial pair count behind
+ * g(r); its decay says how long the neighbour shells survive, the filling of the hole at r = 0 when bots take each
+ * other's places.  Off by default: a run that does not ask for it makes the same launches, has the same pbSimStats and
+ * the same bits, and nothing is allocated.
+ * pbSimSetVanHoveDistinct(sim, interval, lags, binWidth, bins).  interval and lags (1 ... PB_VANHOVE_MAX_LAGS) follow
+ * the time correlation's rules exactly: > 0 the schedule's gate, 0 every step, -1.0f manual only; lags == 0 switches off
+ * and frees everything (binWidth and bins are then not read).  bins is 1 ... PB_VANHOVE_MAX_BINS.  binWidth is finite,
+ * > 0, and its quantised value qw = rint(binWidth * 2^20) (pbSimMoments' quantisation) must be >= 1 and satisfy
+ * qw * bins < 2^31: rMax = bins * binWidth < 2048, so no edge saturates and every pair in range is inside the
+ * fixed-point bound.  Calling again restarts from record 0 with a zeroed table.
+ * A RECORD is taken at the same instant and describes the same state as a time-correlation record.  A bot is PRESENT
+ * at a record iff x, y and rad are all finite (the rule by which every analysis files its bots).  The ring stores,
+ * per bot of every member in ORIGINAL order, the fp32 position (x, y), NaN for an absent bot: 8 bytes per bot and ring
+ * slot, into slot r % lags.  Results are guaranteed for |x|, |y| <= 2^20, as for every analysis that files.
+ * PAIRING.  Record r is paired with the records r - l for l = 0 ... min(r, lags - 1).  For a lag every ORDERED pair
+ * (i at the earlier record, j at the later record) of one member takes part whose original indices differ, with i
+ * present then and j present now.  With dx = x_j(now) - x_i(then) and dy = y_j(now) - y_i(then) formed in fp32 without
+ * contraction: if fabsf(dx) < 2048 and fabsf(dy) < 2048,
+ *     qx = rint(dx * 2^20),  qy = rint(dy * 2^20),  s = qx^2 + qy^2
+ * and the pair is counted in radial bin b = max{k : (k qw)^2 <= s} iff s < (bins qw)^2: pbSimSetVanHove's radial edges
+ * and rule.  An edge belongs to the upper bin; coincident bots land in bin 0.  Pairs out of range are counted nowhere.
+ * The self pair i == j is excluded even when another bot sits exactly on i's old position (that other pair is counted).
+ * With the same width and bins, radial_self[k] + radial_distinct[k] is the histogram over all ordered (i, j) pairs.
+ * Lag 0 pairs a record with itself: the ordered pair counts of that state, so every count is even.
+ * One pbVanHoveDistinctRow per member and lag: lag in RECORDS; origins and sum_steps as in pbTimeCorrelationRow; centres,
+ * the sum over the origins of the bots present at the earlier record; partners, the same at the later record; pairs,
+ * the sum of the lag's histogram, formed by the host.  Plus bins 64-bit counters per member and lag.
+ * EXACTNESS.  The bin starts from an fp32 guess and is settled by integer comparisons with the exact 64-bit edges,
+ * E_b <= s < E_(b + 1), which hold whatever the guess was.  Everything added is an integer: results do not
+ * depend on slot order, on the kernel form that stepped or on the order in which the device adds.  No float atomics and
+ * no 128-bit atomics.  pbSimGetVanHoveDistinct checks centres, and if a lag holds 2^31 or more it answers PB_ERR_ARG
+ * ("a lag holds 2^31 samples or more: restart the distinct van Hove function") and writes nothing.
+ * OTHER CALLS, shaped as the self part's.  pbSimVanHoveDistinctRecord: one record now, whatever the interval.
+ * pbSimGetVanHoveDistinctInfo: interval, lags (0: off), binWidth, bins and the records so far; any pointer may be NULL,
+ * not all.  pbSimGetVanHoveDistinct: nsims * lags rows, member-major, and nsims * lags * bins counters; either pointer
+ * may be NULL, not both; a lag that no record has reached yet has origins == 0 and zeros.
+ * pbSimGetVanHoveDistinctTimes: records so far and the span of the last record's launches in milliseconds.
+ * When several records are due in front of a step the order is: series, time correlation, scattering, van Hove,
+ * distinct van Hove.  No launch is fused across the gate and a resident stretch ends in front of it.
+ * The ring is not part of a checkpoint.  Recording never waits for the device and only reads the simulation.  It does
+ * re-file the analysis layer's shared scratch, exactly as any on-demand analysis call does (the setter makes that
+ * scratch, so that no record allocates); it leaves alone the rearrangement mark, every analysis' result buffers, and
+ * every clock and run counter of the on-demand analyses.
+ * PB_ERR_ARG, before the device is touched: a NULL handle; rows and counts both NULL; interval NaN, infinite, or
+ * negative other than -1; lags > PB_VANHOVE_MAX_LAGS; bins outside 1 ... PB_VANHOVE_MAX_BINS; binWidth not in (0, 2048)
+ * or below half a quantum; qw * bins >= 2^31; a ring above 2^33 bytes (lags x total x 8); a table above 2^31 bytes
+ * (nsims x lags x (2 + bins) x 8); a batch of 2^28 bots or more or of more than 65535 members; the pointers of
+ * pbSimGetVanHoveDistinctInfo all NULL; a record or a read with the analysis off.
+ * Cost: a record files the bots on a grid of edge rMax (1 + 2^-10) (the sort of pbSimRadialCounts), copies (x, y) of the
+ * filed bots into the ring, and makes one launch for all lags: grid (blocks of 256 bots, member, lag).  A lane reads its
+ * bot's earlier position (an 8-byte gather) and walks the nine cells around THAT position over the current filing, so
+ * the work per lag is that of one pbSimRadialCounts at rMax counting both ends.  A workgroup keeps the edges (8 KiB at
+ * most) and bins 32-bit counters (4 KiB at most) in LDS; at the end each non-zero counter is one 64-bit integer atomic.
+ * Device memory: the ring, (2 + bins) x 8 bytes per member and lag, (bins + 1) x 8 bytes of edges, the shared scratch.
+ * Out of scope: angle-resolved or two-dimensional (dx, dy) histograms; normalisation to g(r) or a density; one ring for
+ * the self and the distinct part; logarithmic bins or lag spacing; the coherent F(k, tau); chi_4; the ensemble layer's
+ * summary rows; the legacy engine. */
+typedef struct pbVanHoveDistinctRow {  /* 48 bytes */
+  unsigned lag, reserved;              /* lag in RECORDS: record r against record r - lag; 0 */
+  unsigned long long origins;          /* record pairs added so far (the same for every member) */
+  unsigned long long sum_steps;        /* sum over those pairs of step(r) - step(r - lag) */
+  unsigned long long centres;          /* sum over the origins of the bots present at the earlier record */
+  unsigned long long partners;         /* ... at the later record */
+  unsigned long long pairs;            /* ordered pairs counted: the sum of the lag's histogram */
+} pbVanHoveDistinctRow;
+int pbSimSetVanHoveDistinct(pbSim *sim, float interval, unsigned lags, float binWidth, unsigned bins);
+int pbSimVanHoveDistinctRecord(pbSim *sim);   /* one record now, of the state as it is */
+int pbSimGetVanHoveDistinctInfo(pbSim *sim, float *interval, unsigned *lags, float *binWidth, unsigned *bins,
+                                unsigned long long *records);
+int pbSimGetVanHoveDistinct(pbSim *sim, pbVanHoveDistinctRow *rows /* nsims * lags, or NULL */,
+                            unsigned long long *counts /* nsims * lags * bins, or NULL; not both NULL */);
+int pbSimGetVanHoveDistinctTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a

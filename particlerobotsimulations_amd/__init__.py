@@ -161,6 +161,21 @@ def van_hove_lists(rows, counts, nsims, lags, bins):
     return out
 
 
+def van_hove_distinct_lists(rows, counts, nsims, lags, bins):
+    """The rows and counters of pbSimGetVanHoveDistinct as van_hove_distinct() returns them: per member a list over lags
+    of dicts, each van_hove_distinct_row() plus counts (bins ints)."""
+    out = []
+    for m in range(nsims):
+        member = []
+        for l in range(lags):
+            g = m * lags + l
+            d = _capi.van_hove_distinct_row(rows[g])
+            d["counts"] = [int(v) for v in counts[g * bins:(g + 1) * bins]]
+            member.append(d)
+        out.append(member)
+    return out
+
+
 def field_values(cells):
     """The cells of field_map() as a dict of arrays of the cells' shape: count, dead, sum_qr, sum_wx, sum_wy as they are,
     and rr, vv as object arrays of Python ints composed from their 128 bits (hi * 2^32 + lo).  The sums are in units of
@@ -1017,6 +1032,46 @@ class Sim:
         """(records taken so far, device milliseconds of the last record's launches)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
         _capi.check(_capi.lib().pbSimGetVanHoveTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetVanHoveTimes")
+        return int(n.value), float(ms.value)
+
+    def set_van_hove_distinct(self, interval, lags, width, bins):
+        """Keep a device ring of `lags` snapshots of the positions, taken as set_van_hove() takes them, and add every
+        record against the `lags` latest ones into a table per member and lag (pbSimSetVanHoveDistinct): the distinct van
+        Hove function as exact integer counts of the ordered pairs (a bot then, ANOTHER bot now) by distance, `bins` bins
+        of `width` with bins * width below 2048.  Restarts at record 0; lags 0 switches it off.  Recording changes no
+        state bit."""
+        _capi.check(_capi.lib().pbSimSetVanHoveDistinct(self._h, float(interval), int(lags), float(width), int(bins)),
+                    "pbSimSetVanHoveDistinct")
+
+    def van_hove_distinct_record(self):
+        """One record now, of the state as it is (pbSimVanHoveDistinctRecord)."""
+        _capi.check(_capi.lib().pbSimVanHoveDistinctRecord(self._h), "pbSimVanHoveDistinctRecord")
+
+    def van_hove_distinct_info(self):
+        """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveDistinctInfo)."""
+        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
+        _capi.check(_capi.lib().pbSimGetVanHoveDistinctInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b),
+                                                            C.byref(r)), "pbSimGetVanHoveDistinctInfo")
+        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
+                "records": int(r.value)}
+
+    def van_hove_distinct(self):
+        """The table as it stands (pbSimGetVanHoveDistinct): per member a list over lags (lag 0 first) of dicts of Python
+        ints: lag, origins, sum_steps, centres, partners, pairs, and counts (bins ints; bin k covers
+        [k width, (k + 1) width))."""
+        info = self.van_hove_distinct_info()
+        lags, bins = info["lags"], info["bins"]
+        nsims = int(getattr(self, "nsims", 1))
+        rows = (_capi.pbVanHoveDistinctRow * max(nsims * lags, 1))()
+        counts = (C.c_ulonglong * max(nsims * lags * bins, 1))()
+        _capi.check(_capi.lib().pbSimGetVanHoveDistinct(self._h, rows, counts), "pbSimGetVanHoveDistinct")
+        return van_hove_distinct_lists(rows, counts, nsims, lags, bins)
+
+    def van_hove_distinct_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetVanHoveDistinctTimes(self._h, C.byref(n), C.byref(ms)),
+                    "pbSimGetVanHoveDistinctTimes")
         return int(n.value), float(ms.value)
 
 

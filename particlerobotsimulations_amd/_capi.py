@@ -291,6 +291,16 @@ def van_hove_row(r):
     return out
 
 
+class pbVanHoveDistinctRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
+                ("centres", C.c_ulonglong), ("partners", C.c_ulonglong), ("pairs", C.c_ulonglong)]
+
+
+def van_hove_distinct_row(r):
+    """A pbVanHoveDistinctRow as a dict of Python ints (reserved left out)."""
+    return {name: int(getattr(r, name)) for name, _ in pbVanHoveDistinctRow._fields_ if name != "reserved"}
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -398,6 +408,12 @@ SYMBOLS = {
                                  C.POINTER(C.c_ulonglong)]),
     "pbSimGetVanHove": (_I, [_VP, C.POINTER(pbVanHoveRow), C.POINTER(C.c_ulonglong)]),
     "pbSimGetVanHoveTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimSetVanHoveDistinct": (_I, [_VP, _F, _U, _F, _U]),
+    "pbSimVanHoveDistinctRecord": (_I, [_VP]),
+    "pbSimGetVanHoveDistinctInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_F), C.POINTER(_U),
+                                         C.POINTER(C.c_ulonglong)]),
+    "pbSimGetVanHoveDistinct": (_I, [_VP, C.POINTER(pbVanHoveDistinctRow), C.POINTER(C.c_ulonglong)]),
+    "pbSimGetVanHoveDistinctTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1587,6 +1587,36 @@ bool Particlebot::vanHoveRows(std::vector<pbVanHoveRow> &rows, std::vector<unsig
   });
 }
 
+bool Particlebot::setVanHoveDistinct(float interval, unsigned lags, float binWidth, unsigned bins) {
+  auto call = [&] { return pbSimSetVanHoveDistinct(sim, interval, lags, binWidth, bins); };
+  return onFusedEngine("setVanHoveDistinct", "distinct van Hove function", call);
+}
+
+bool Particlebot::vanHoveDistinctRecord() {
+  return onFusedEngine("vanHoveDistinctRecord", "distinct van Hove function",
+                       [&] { return pbSimVanHoveDistinctRecord(sim); });
+}
+
+bool Particlebot::vanHoveDistinctInfo(float &interval, unsigned &lags, float &binWidth, unsigned &bins,
+                                      unsigned long long &records) {
+  auto call = [&] { return pbSimGetVanHoveDistinctInfo(sim, &interval, &lags, &binWidth, &bins, &records); };
+  return onFusedEngine("vanHoveDistinctInfo", "distinct van Hove function", call);
+}
+
+bool Particlebot::vanHoveDistinctRows(std::vector<pbVanHoveDistinctRow> &rows,
+                                      std::vector<unsigned long long> &counts) {
+  return onFusedEngine("vanHoveDistinctRows", "distinct van Hove function", [&] {
+    unsigned lags = 0, bins = 0;
+    const int rc = pbSimGetVanHoveDistinctInfo(sim, nullptr, &lags, nullptr, &bins, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? lags : 1, pbVanHoveDistinctRow());  // (with the analysis off the engine refuses)
+    counts.assign(lags ? (size_t)lags * bins : 1, 0ull);
+    const int got = pbSimGetVanHoveDistinct(sim, rows.data(), counts.data());
+    if (got != PB_OK) rows.clear(), counts.clear();
+    return got;
+  });
+}
+
 bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
   return onFusedEngine("fieldMap", "field map", [&] {
     const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;

@@ -510,6 +510,42 @@ int pbHostVanHoveRows(void *hv, pbVanHoveRow *rows, unsigned long long *counts, 
   return 0;
 }
 
+// the distinct van Hove function of the resident state (Particlebot::setVanHoveDistinct / vanHoveDistinctRecord /
+// vanHoveDistinctInfo / vanHoveDistinctRows; fused engine only), shaped as the self part's: the 48-byte
+// pbVanHoveDistinctRow of every lag with the lag's bins counters (cap rows and bins * cap counters of room).  -1 on the
+// other engines, a bad interval, lags, width or bins, a record or a read with the analysis off, or too little room.
+int pbHostSetVanHoveDistinct(void *hv, float interval, unsigned lags, float binWidth, unsigned bins) {
+  return ((HostSim *)hv)->bot->setVanHoveDistinct(interval, lags, binWidth, bins) ? 0 : -1;
+}
+
+int pbHostVanHoveDistinctRecord(void *hv) { return ((HostSim *)hv)->bot->vanHoveDistinctRecord() ? 0 : -1; }
+
+int pbHostVanHoveDistinctInfo(void *hv, float *interval, unsigned *lags, float *binWidth, unsigned *bins,
+                              unsigned long long *records) {
+  float i = 0.0f, w = 0.0f;
+  unsigned l = 0, b = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->vanHoveDistinctInfo(i, l, w, b, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (binWidth) *binWidth = w;
+  if (bins) *bins = b;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostVanHoveDistinctRows(void *hv, pbVanHoveDistinctRow *rows, unsigned long long *counts, unsigned long long cap,
+                              unsigned long long *count) {
+  std::vector<pbVanHoveDistinctRow> v;
+  std::vector<unsigned long long> c;
+  if (!count || !((HostSim *)hv)->bot->vanHoveDistinctRows(v, c)) return -1;
+  *count = v.size();
+  if ((rows || counts) && cap < v.size()) return -1;
+  copyOut(rows, v);
+  copyOut(counts, c);
+  return 0;
+}
+
 // a field map of the resident state (Particlebot::fieldMap; fused engine only): ny * nx 64-byte pbFieldCell entries and,
 // unless NULL, the 16-byte pbFieldTotals row.  -1 on the other engines and on a bad view.
 int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFieldTotals *totals) {

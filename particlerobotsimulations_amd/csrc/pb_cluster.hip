@@ -285,14 +285,25 @@ int ensureScratch(pbSim *S, uint32_t numKeys) {
   return PB_OK;
 }
 
+// the grid's shape depends on the batch alone: cells = max(16, n rounded up to a power of two) per member
+uint32_t gridBits(const pbSim *S) {
+  uint32_t bits = 4;
+  while (bits < 31 && (1u << bits) < S->n) bits++;
+  return bits;
+}
+
 }  // namespace
+
+// The scratch of the filing front end, for a caller that must not allocate later (pb_cluster.hpp).
+int pbClusterEnsureScratch(pbSim *S) {
+  useDevice(S);
+  return ensureScratch(S, S->nsims << gridBits(S));
+}
 
 // The filing front end (pb_cluster.hpp): everything up to, but not including, the link pass.
 int pbClusterFile(pbSim *S, double reach, double perRmax) {
   useDevice(S);
-  // the grid's shape depends on the batch alone: cells = max(16, n rounded up to a power of two) per member
-  uint32_t bits = 4;
-  while (bits < 31 && (1u << bits) < S->n) bits++;
+  const uint32_t bits = gridBits(S);
   const uint32_t gxLog2 = (bits + 1) / 2, gyLog2 = bits / 2;
   const uint32_t cells = 1u << bits, numKeys = S->nsims * cells;
   const int rc = ensureScratch(S, numKeys);

@@ -1,6 +1,6 @@
 // pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip, pb_dynamics.hip and
-// pb_correlate.hip: the scratch object with its five clocks, the fresh grid, the workgroup scan (the wave helpers are
-// pb_fixed.hpp's), the walk over a bot's nine cells (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour
+// pb_correlate.hip and pb_vanhove_distinct.hip: the scratch object with its five clocks, the fresh grid, the workgroup
+// scan (the wave helpers are pb_fixed.hpp's), the walk over a bot's nine cells (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour
 // sweep of the analysis layer is built on, the front end that files the bots (rmax, hash, sort, gather, cell starts) and
 // the argument checks of the entry points.
 #pragma once
@@ -236,6 +236,9 @@ inline int pbClockGet(const char *fn, const pbSim *S, PbAnalysisClock PbClusterS
 // vals[sortedIn], parent[o] = o and size[o] = 0 on the device, the grid (invCell, gxLog2, gyLog2) in the scratch object.
 // Allocates the scratch on first use.  Launches are queued on the batch's stream, not waited for.       pb_cluster.hip
 int pbClusterFile(pbSim *S, double reach, double perRmax);
+// Makes the scratch pbClusterFile would make on first use, and nothing else: for a recorder that files inside the
+// schedule, where nothing may allocate (pb_vanhove_distinct.hip).                                       pb_cluster.hip
+int pbClusterEnsureScratch(pbSim *S);
 // The whole cluster pipeline (the front end with reach = gap, perRmax = 2); leaves cpr, the cell starts, parent (roots),
 // degree and the rows on the device and the stream drained.                                             pb_cluster.hip
 int pbClusterAnalyse(pbSim *S, float gap);

@@ -635,9 +635,10 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   bool ahead = false;  // true: radius+integration of the coming step are already applied
   const bool resident = pbResidentWanted(S);
   // The host events that are on, in firing order: the records of the time series (pb_moments.hip), the time
-  // correlations (pb_timecorr.hip), the scattering (pb_scatter.hip) and the van Hove function (pb_vanhove.hip), the
-  // centroid trail, the phase update.  A new recorder is one more entry; the loop below does not name them.
-  PbHostEvent events[6];
+  // correlations (pb_timecorr.hip), the scattering (pb_scatter.hip), the van Hove function (pb_vanhove.hip) and its
+  // distinct part (pb_vanhove_distinct.hip), the centroid trail, the phase update.  A new recorder is one more entry;
+  // the loop below does not name them.
+  PbHostEvent events[7];
   int nEvents = 0;
   if (S->series.ring) events[nEvents++] = {true, true, S->series.interval, pbSeriesRecord};
   if (S->tc.lag.ring)
@@ -646,6 +647,8 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     events[nEvents++] = {true, true, S->sc.lag.interval, [](pbSim *B, float) { return pbScatteringRecord(B); }};
   if (S->vh.lag.ring)
     events[nEvents++] = {true, true, S->vh.lag.interval, [](pbSim *B, float) { return pbVanHoveRecord(B); }};
+  if (S->vd.lag.ring)
+    events[nEvents++] = {true, true, S->vd.lag.interval, [](pbSim *B, float) { return pbVanHoveDistinctRecord(B); }};
   if (S->trail.ring) events[nEvents++] = {false, false, S->trail.interval, trailRecord};
   if (lightWave)
     events[nEvents++] = {false, false, S->host.phase_update_interval, [](pbSim *B, float) { return phaseUpdate(B); }};

@@ -19,6 +19,9 @@
 //   pb_sfactor.hip   structure factor: integer phasor sums per member and wavevector (pbSimStructureFactor)
 //   pb_scatter.hip   self-intermediate scattering: integer phasor sums per member, lag and wavevector over a lag ring
 //                    (pbSimSetScattering)
+//   pb_vanhove.hip   self van Hove function: displacement histograms per lag over a lag ring (pbSimSetVanHove)
+//   pb_vanhove_distinct.hip  distinct van Hove function: pair histograms per lag, a neighbour sweep around every bot's
+//                    earlier position (pbSimSetVanHoveDistinct)
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 //   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of, and
@@ -92,7 +95,8 @@ struct PbSeries {
   std::vector<float> times;               // per slot: start time of the step the record was taken in front of
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
-// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip) share -------------------
+// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip, pb_vanhove_distinct.hip)
+// share ------------------------------------------------------------------------------------------------------------------
 // A ring of `lags` snapshots of the whole batch in ORIGINAL order, lags x total entries of Snap.  Record r goes into
 // slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1); all pairs of a record are added
 // into `table` by one launch over pbLagGrid() workgroups of PB_LAG_LANES lanes, which pbLagPair() takes apart again.
@@ -101,7 +105,7 @@ struct PbSeries {
 constexpr int PB_LAG_LANES = 256;
 constexpr unsigned PB_LAG_MAX_LAGS = 64u, PB_LAG_BLOCKS = 256u;  // (the public header states both per analysis)
 static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS &&
-                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS, "one bound on the lags");
+                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS, "one bound on the lags");  // (the distinct part uses the self part's)
 static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS &&
                   PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS, "one bound on the blocks per lag");
 
@@ -207,6 +211,16 @@ struct PbVanHove {
   PbDevBuf<unsigned long long> edges;  // bins + 1: E_k = min((k qw)^2, 2^63)
 };
 
+// distinct van Hove function (pb_vanhove_distinct.hip): float2 (x, y) snapshots, NaN for an absent bot, and nsims x lags
+// cells of 2 + bins words, member-major: centres, partners, then the radial histogram of ordered pairs (pb_vanhove.hpp;
+// pbSimSetVanHoveDistinct)
+struct PbVanHoveDistinct {
+  PbLagRing<float2> lag;
+  float width = 0.0f;
+  uint32_t qw = 0, bins = 0;           // rint(width * 2^20) with qw bins < 2^31; counters per histogram
+  PbDevBuf<unsigned long long> edges;  // bins + 1: E_k = (k qw)^2
+};
+
 // Members release in reverse declaration order behind ~pbSim's body: the stream and the events are declared first
 // and go last.
 struct pbSim {
@@ -289,6 +303,7 @@ struct pbSim {
   PbSfactor sk;
   PbScattering sc;
   PbVanHove vh;
+  PbVanHoveDistinct vd;
   pbSimStats stats{};
 };
 
@@ -343,7 +358,7 @@ int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words) {
   PB_TRY(hipMemsetAsync(R.table, 0, sizeof(unsigned long long) * words, S->stream));
   return PB_OK;
 }
-// Switches the analysis `held` (S->tc, S->sc, S->vh) off and, unless lags is 0, on again: a fresh value with a ring of `lags`
+// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd) off and, unless lags is 0, on again: a fresh value with a ring of `lags`
 // snapshots, a zeroed table of wordsPerLag words per member and lag, a book at record 0, and what fill(fresh) sets of
 // the analysis' own.  When any of it fails, what was made goes and the analysis stays off.
 template <typename A, typename Fill>
@@ -460,3 +475,4 @@ int pbSeriesRecord(pbSim *S, float t);  // ... in front of the step that starts 
 int pbTimeCorrRecord(pbSim *S);         // ... a snapshot and its lags (pbLagRecord)                        pb_timecorr.hip
 int pbScatteringRecord(pbSim *S);       // ... a quantised snapshot and its lags (pbLagRecord)              pb_scatter.hip
 int pbVanHoveRecord(pbSim *S);          // ... a position snapshot and its lags (pbLagRecord)               pb_vanhove.hip
+int pbVanHoveDistinctRecord(pbSim *S);  // ... a filing, a snapshot and its lags (pbLagRecord)     pb_vanhove_distinct.hip

@@ -12,6 +12,8 @@
 //                   [--sk FILE [--sk-kind density|radius|velocity] [--sk-box-log2 E] [--sk-nmax M]]
 //                   [--scatter FILE [--scatter-interval T] [--scatter-lags N] [--scatter-box-log2 E] [--scatter-nmax M]]
 //                   [--vanhove FILE [--vanhove-interval T] [--vanhove-lags N] [--vanhove-width W] [--vanhove-bins B]]
+//                   [--vanhove-distinct FILE [--vanhove-distinct-interval T] [--vanhove-distinct-lags N]
+//                    [--vanhove-distinct-width W] [--vanhove-distinct-bins B]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -106,6 +108,11 @@ struct RunOptions {
   float vanhoveInterval = -1.0f;  // below 0: dump_interval
   float vanhoveWidth = -1.0f;     // below 0: an eighth of min_radius (a default and not a claim)
   long vanhoveLags = 32, vanhoveBins = 64;
+
+  std::string vanhoveDistinctPath;
+  float vanhoveDistinctInterval = -1.0f;  // below 0: dump_interval
+  float vanhoveDistinctWidth = -1.0f;     // below 0: an eighth of min_radius, at most 2047 / bins
+  long vanhoveDistinctLags = 32, vanhoveDistinctBins = 64;
 };
 
 using Choice = std::pair<const char *, int>;  // a word and what it stands for
@@ -207,6 +214,12 @@ const Flag kFlags[] = {
     {"--vanhove-lags", &RunOptions::vanhoveLags, 1, PB_VANHOVE_MAX_LAGS},
     {"--vanhove-width", &RunOptions::vanhoveWidth, 0.0f, true, 2048.0f},
     {"--vanhove-bins", &RunOptions::vanhoveBins, 1, PB_VANHOVE_MAX_BINS},
+
+    {"--vanhove-distinct", &RunOptions::vanhoveDistinctPath, "recorder"},
+    {"--vanhove-distinct-interval", &RunOptions::vanhoveDistinctInterval, 0.0f, false},
+    {"--vanhove-distinct-lags", &RunOptions::vanhoveDistinctLags, 1, PB_VANHOVE_MAX_LAGS},
+    {"--vanhove-distinct-width", &RunOptions::vanhoveDistinctWidth, 0.0f, true, 2048.0f},
+    {"--vanhove-distinct-bins", &RunOptions::vanhoveDistinctBins, 1, PB_VANHOVE_MAX_BINS},
 };
 
 // a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
@@ -733,6 +746,44 @@ struct Run {
     }
     return fclose(f) == 0;
   }
+
+  // --vanhove-distinct FILE: the device's distinct van Hove function (Particlebot::setVanHoveDistinct).  Records are
+  // taken as --vanhove takes them, at --vanhove-distinct-interval into a ring of --vanhove-distinct-lags snapshots, and
+  // every record is added against the latest ones into --vanhove-distinct-bins counters of --vanhove-distinct-width per
+  // lag: the ordered pairs (a bot then, another bot now) by distance.  The default width is --vanhove's, an eighth of
+  // min_radius, cut so that bins x width stays below 2048 as the engine asks.  Switched on behind a resume and refused by
+  // the same count as --timecorr.  At the end of the run one line per lag and bin, lag 0 first; the lag's columns are
+  // repeated on each of its lines, the integers as they are, and Lower is the bin's lower edge in world units as %.9g.
+  int startVanHoveDistinct() {
+    if (o.vanhoveDistinctPath.empty()) return 0;
+    const float every = recordEvery(o.vanhoveDistinctInterval, cfg);
+    if (!recordsFit("--vanhove-distinct", every)) return 2;
+    const float most = 2047.0f / (float)o.vanhoveDistinctBins;
+    const float width = o.vanhoveDistinctWidth > 0.0f ? o.vanhoveDistinctWidth
+                                                      : std::min(0.125f * sim.getParams().min_radius, most);
+    return sim.setVanHoveDistinct(every, (unsigned)o.vanhoveDistinctLags, width, (unsigned)o.vanhoveDistinctBins) ? 0 : 1;
+  }
+
+  bool writeVanHoveDistinct() {
+    if (o.vanhoveDistinctPath.empty()) return true;
+    std::vector<pbVanHoveDistinctRow> rows;
+    std::vector<unsigned long long> counts;
+    float interval = 0.0f, width = 0.0f;
+    unsigned lags = 0, bins = 0;
+    unsigned long long records = 0;
+    if (!sim.vanHoveDistinctRows(rows, counts) || !sim.vanHoveDistinctInfo(interval, lags, width, bins, records))
+      return false;
+    FILE *f = openWhole(o.vanhoveDistinctPath, "Lag, Origins, SumSteps, Centres, Partners, Pairs, Bin, Lower, Count");
+    if (!f) return false;
+    const double qw = (double)std::nearbyint(width * 1048576.0f) / 1048576.0;  // the quantised width, as the engine's
+    for (size_t l = 0; l < rows.size(); l++) {
+      const pbVanHoveDistinctRow &v = rows[l];
+      for (size_t j = 0; j < bins; j++)
+        fprintf(f, "%u, %llu, %llu, %llu, %llu, %llu, %zu, %.9g, %llu\n", v.lag, v.origins, v.sum_steps, v.centres,
+                v.partners, v.pairs, j, (double)j * qw, counts[l * bins + j]);
+    }
+    return fclose(f) == 0;
+  }
 };
 
 }  // namespace
@@ -868,6 +919,7 @@ int main(int argc, char **argv) {
   if (const int refused = run.startTimeCorrelation()) return refused;
   if (const int refused = run.startScattering()) return refused;
   if (const int refused = run.startVanHove()) return refused;
+  if (const int refused = run.startVanHoveDistinct()) return refused;
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!o.ckptPath.empty() && run.stepsDone > lastCkptStep) {
@@ -902,6 +954,7 @@ int main(int argc, char **argv) {
   if (!o.finalCkptPath.empty() && !writeCheckpoint(o.finalCkptPath)) return 1;
   fclose(fp);
   const bool written = run.writeTrail() && run.writeContacts() && run.writeRdf() && run.writeTimeCorrelation() &&
-                       run.writeScattering() && run.writeVanHove() && run.writeCorrelation();
+                       run.writeScattering() && run.writeVanHove() && run.writeVanHoveDistinct() &&
+                       run.writeCorrelation();
   return written ? 0 : 1;
 }

@@ -1,13 +1,15 @@
 // pb_vanhove.hpp -- the arithmetic of the self van Hove function that has no device in it (pb_vanhove.hip holds the
 // kernels and the entry points; include/particlebot_hip.h has the definitions): the words of a table cell, the table of
-// radial edges, the two bin rules and the 192-bit sum of fourth powers.  Compiles as plain C++
-// (tests/pb_vanhove_check.cpp); the kernel and the host's row writer both use what is here, so there is one statement of
+// radial edges, the two bin rules and the 192-bit sum of fourth powers, and behind them the cell and the radial rules of
+// the distinct part (pb_vanhove_distinct.hip).  Compiles as plain C++ (tests/pb_vanhove_check.cpp,
+// tests/pb_vanhove_distinct_check.cpp); the kernel and the host's row writer both use what is here, so there is one statement of
 // each rule.
 //
 // All of it is integer arithmetic on pb_fixed.hpp's quantities: |qx|, |qy| <= 2^31 - 128, s = qx^2 + qy^2 < 2^63, the bin
-// width qw = pbFixedQuantise(binWidth) in 1 ... 2^31 - 128 and bins in 1 ... PB_VANHOVE_MAX_BINS.  No rule here guesses in
-// floating point: the radial bin is a binary search in the exact edges and the axis bin an integer division, so there
-// is no correction step whose reach would have to be proven.
+// width qw = pbFixedQuantise(binWidth) in 1 ... 2^31 - 128 and bins in 1 ... PB_VANHOVE_MAX_BINS.  The self part guesses
+// nowhere in floating point: the radial bin is a binary search in the exact edges and the axis bin an integer division.
+// The distinct part's two further radial rules (at the end) start from a floating-point guess and end in exact integer
+// comparisons that hold whatever the guess was, so there is no correction step whose reach would have to be proven.
 #pragma once
 
 #include <stddef.h>
@@ -79,3 +81,37 @@ inline void pbVhQ4Compose(unsigned long long a0, unsigned long long a1, unsigned
   const unsigned __int128 high = (low >> 64) + (unsigned __int128)a2 + ((unsigned __int128)a3 << 32);  // below 2^96
   limbs[0] = (unsigned long long)low, limbs[1] = (unsigned long long)high, limbs[2] = (unsigned long long)(high >> 64);
 }
+
+// ---- the distinct part (pb_vanhove_distinct.hip) -------------------------------------------------------------------------
+// The words of a table cell: the bots present at the earlier record, the bots present at the later one, both summed over
+// the origins, then bins radial counters of ordered pairs.
+enum { PB_VHD_CENTRES, PB_VHD_PARTNERS, PB_VHD_HEAD };
+PB_FIXED_HD size_t pbVhdCellWords(uint32_t bins) { return (size_t)PB_VHD_HEAD + bins; }
+
+// The distinct part asks qw bins < 2^31 on top of the self part's bounds: rMax = bins binWidth < 2048, no edge
+// saturates, E_bins = (qw bins)^2 < 2^62, and a pair is counted iff s < E_bins.  For such an s there are two more ways
+// to the radial bin max{k : (k qw)^2 <= s}; both end in exact integer comparisons, so neither needs a proof of how good
+// its first guess is: the guess only decides how many comparisons are made.
+//
+// (b) from a guess (the kernel's is (uint32_t)(sqrtf(d2) / binWidth) in fp32): clamped into 0 ... bins - 1, then moved
+// down while E_g > s and up while E_(g + 1) <= s.  E_0 = 0 <= s ends the first loop and E_bins > s the second, and
+// between them E_g <= s < E_(g + 1) holds: that is the rule.  edgeAt(k) gives E_k for k = 1 ... bins, as above.
+template <typename EdgeAt>
+PB_FIXED_HD uint32_t pbVhRadialBinFrom(const EdgeAt &edgeAt, uint32_t bins, unsigned long long s, uint32_t guess) {
+  uint32_t g = guess < bins ? guess : bins - 1u;
+  while (g > 0u && edgeAt(g) > s) g--;
+  while (g + 1u < bins && edgeAt(g + 1u) <= s) g++;  // (E_bins > s is the caller's: the edge is not read)
+  return g;
+}
+
+// (c) by the integer square root: k qw <= sqrt(s) iff k qw <= floor(sqrt(s)) for integers, so the bin is
+// floor(sqrt(s)) / qw, one 32-bit division.  The root of s < 2^62 starts from the fp64 root (within one of the truth:
+// the conversion and the root each err by 2^-53 relative, the root is below 2^31) and is corrected by comparing squares,
+// which do not overflow: (r + 1)^2 <= 2^62.
+PB_FIXED_HD uint32_t pbVhIsqrt(unsigned long long s) {
+  unsigned long long r = (unsigned long long)__builtin_sqrt((double)s);
+  while (r * r > s) r--;
+  while ((r + 1ull) * (r + 1ull) <= s) r++;
+  return (uint32_t)r;
+}
+PB_FIXED_HD uint32_t pbVhRadialBinRoot(uint32_t qw, unsigned long long s) { return pbVhIsqrt(s) / qw; }

@@ -66,6 +66,9 @@ _ANALYSES = {
     "pbHostSetVanHove": [_F, C.c_uint, _F, C.c_uint], "pbHostVanHoveRecord": [],
     "pbHostVanHoveInfo": [_P, _P, _P, _P, _P],
     "pbHostVanHoveRows": [_P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
+    "pbHostSetVanHoveDistinct": [_F, C.c_uint, _F, C.c_uint], "pbHostVanHoveDistinctRecord": [],
+    "pbHostVanHoveDistinctInfo": [_P, _P, _P, _P, _P],
+    "pbHostVanHoveDistinctRows": [_P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
     "pbHostFieldMap": [_P, _P, _P],
     "pbHostStructureFactor": [C.c_int, C.c_int, _P, C.c_uint, _P],
 }
@@ -522,6 +525,44 @@ class HostSim:
             raise RuntimeError("van_hove: the van Hove function needs the fused engine, the analysis on and fewer than "
                                "2^31 samples per lag")
         return van_hove_lists(rows, counts, 1, lags, bins)
+
+    def set_van_hove_distinct(self, interval, lags, width, bins):
+        """Keep a device ring of `lags` position snapshots, taken as set_van_hove() takes them, and add every record
+        against the `lags` latest ones into exact integer counts per lag of the ordered pairs (a bot then, another bot
+        now) by distance: `bins` bins of `width` (pbSimSetVanHoveDistinct; fused engine only).  Restarts at record 0;
+        lags 0 switches it off."""
+        if lib().pbHostSetVanHoveDistinct(self._h, float(interval), int(lags), float(width), int(bins)) != 0:
+            raise RuntimeError("set_van_hove_distinct: the distinct van Hove function needs the fused engine, a finite "
+                               "interval >= 0 (or -1), lags <= 64, 1 ... 1024 bins and a width with bins * width < 2048")
+
+    def van_hove_distinct_record(self):
+        """One record now, of the state as it is (pbSimVanHoveDistinctRecord; fused engine only)."""
+        if lib().pbHostVanHoveDistinctRecord(self._h) != 0:
+            raise RuntimeError("van_hove_distinct_record: the distinct van Hove function needs the fused engine and the "
+                               "analysis on")
+
+    def van_hove_distinct_info(self):
+        """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveDistinctInfo; fused
+        engine only)."""
+        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
+        if lib().pbHostVanHoveDistinctInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b), C.byref(r)) != 0:
+            raise RuntimeError("van_hove_distinct_info: the distinct van Hove function needs the fused engine")
+        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
+                "records": int(r.value)}
+
+    def van_hove_distinct(self):
+        """The table as it stands, as Sim.van_hove_distinct gives it: a list with one list over lags of dicts of Python
+        ints with `counts` as a list (Particlebot::vanHoveDistinctRows; fused engine only)."""
+        from . import van_hove_distinct_lists
+        info = self.van_hove_distinct_info()
+        lags, bins = info["lags"], info["bins"]
+        cap = max(lags, 1)
+        rows, counts = (_capi.pbVanHoveDistinctRow * cap)(), (C.c_ulonglong * max(cap * bins, 1))()
+        count = C.c_ulonglong(0)
+        if lib().pbHostVanHoveDistinctRows(self._h, rows, counts, cap, C.byref(count)) != 0:
+            raise RuntimeError("van_hove_distinct: the distinct van Hove function needs the fused engine, the analysis "
+                               "on and fewer than 2^31 centres per lag")
+        return van_hove_distinct_lists(rows, counts, 1, lags, bins)
 
     def field_map(self, nx, ny, center, half, member=None):
         """A field map of the state as it is now, on the device (pbSimFieldMap; fused engine only): (cells, totals) as
