@@ -219,6 +219,14 @@ class Particlebot {
   bool rearrangementStats(pbRearrangementStats &out);
   bool rearrangement(std::vector<float> &disp, std::vector<unsigned> &marked, std::vector<unsigned> &now,
                      std::vector<unsigned> &kept);
+  /* Local strain and D2min of the resident state against the mark, on the device (pbSimStrainStats / pbSimStrainOf,
+   * include/particlebot_hip.h has the definitions): strainStats gives the member's row of integers (fitted and unfitted
+   * bots, bots with D2min above d2Threshold, used and dropped bonds, the sums of the moments and of D2min); strain
+   * every bot's nine integer moments (9 nCells), its local deformation gradient (4 nCells: Jxx Jxy Jyx Jyy) and its
+   * D2min (nCells, units of 2^-40) in ORIGINAL order.  Fused engine only: Legacy and HostOnly instances return false
+   * with a message on stderr.  Also false on a bad d2Threshold, and with no mark held. */
+  bool strainStats(float d2Threshold, pbStrainStats &out);
+  bool strain(std::vector<long long> &moments, std::vector<double> &gradient, std::vector<double> &d2min);
   /* Time series of the resident state on the device (pbSimMoments / pbSimSetSeries / pbSimGetSeriesOf,
    * include/particlebot_hip.h has the definitions): moments gives the row of integer moments of the state as it is now;
    * setSeries(interval, capacity) starts a device ring that takes such a row in front of every step whose start time

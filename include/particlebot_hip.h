@@ -1162,6 +1162,72 @@ int pbSimGetVanHoveDistinct(pbSim *sim, pbVanHoveDistinctRow *rows /* nsims * la
                             unsigned long long *counts /* nsims * lags * bins, or NULL; not both NULL */);
 int pbSimGetVanHoveDistinctTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
+/* Local strain and non-affine displacement D2min on the device (csrc/pb_strain.hip; the fit itself is
+ * csrc/pb_strain.hpp): the Falk-Langer fit against the mark of the rearrangement analysis.  For every bot, the best
+ * local affine map that carries its MARKED bond vectors onto its present ones (the local deformation gradient: strain
+ * and rotation), and the residual D2min, the non-affine part.  A blob that translates, rotates or breathes has large
+ * displacements and D2min = 0; a neighbourhood that rearranges has not.  Summed over a member the same moments give the
+ * macroscopic deformation gradient of the whole collective.  A mark must be held (pbSimMarkReference).  Read-only: the
+ * simulation, the mark, and every other analysis' buffers and answers stay bit for bit as they were.  No spatial filing:
+ * the bots are not filed afresh, the walk is over the marked CSR.
+ * N0(i) is bot i's marked list, p0 the marked positions, p1 the positions as they are now, raw from the state arrays
+ * (not a filing's copy, which holds NaN for a bot with a non-finite radius).
+ * BOND VECTORS.  For j in N0(i), all in fp32 without contraction:
+ *     d0x = x0_j - x0_i;   d0y = y0_j - y0_i;   dx = x1_j - x1_i;   dy = y1_j - y1_i
+ * The bond is USED iff all four values are finite and each has fabsf(.) < PB_STRAIN_REACH (8.0f); otherwise it is
+ * DROPPED: counted, and it contributes nothing.  For a used bond q = (long long)rint(v * 1048576.0f) (the scaling is
+ * exact, the conversion rounds to nearest even), so |q| <= 2^23 and a product of two is at most 2^46.
+ * PER-BOT INTEGER MOMENTS over the used bonds, nine 64-bit words in this order:
+ *     k    number of used bonds
+ *     Yxx = sum q0x*q0x;   Yxy = sum q0x*q0y;   Yyy = sum q0y*q0y
+ *     Xxx = sum qx*q0x;    Xxy = sum qx*q0y;    Xyx = sum qy*q0x;    Xyy = sum qy*q0y
+ *     W   = sum (qx*qx + qy*qy)
+ * All exact while the bot has fewer than 2^16 marked entries (every sum stays below 2^63).  A bot with more is
+ * unfitted, all its bonds are counted as dropped and its moments are zero.
+ * THE FIT, in binary64: every operation rounded once, no contraction, the order of operations exactly as written,
+ * integers converted with round-to-nearest:
+ *     a = Yxx, b = Yxy, c = Yyy;   det = a*c - b*b
+ *     FITTED iff k >= 3 and det > 0
+ *     Jxx = (Xxx*c - Xxy*b)/det;   Jxy = (Xxy*a - Xxx*b)/det
+ *     Jyx = (Xyx*c - Xyy*b)/det;   Jyy = (Xyy*a - Xyx*b)/det
+ *     d2  = W - ((Jxx*Xxx + Jxy*Xxy) + (Jyx*Xyx + Jyy*Xyy));   d2 = d2 > 0 ? d2 : 0              (units of 2^-40)
+ * J maps marked bond vectors onto present ones (d ~ J d0): the identity for an unmoved neighbourhood, a rotation matrix
+ * for a rotated one.  An unfitted bot has J = 0 and d2 = 0.  The device and the host (pbSimStrainOf's gradient) evaluate
+ * the same function, so the device's d2 is the value the host derives from the device's moments, bit for bit.
+ * PER MEMBER one pbStrainStats row; everything in it is an integer, so nothing depends on the order of the adds:
+ *     fitted, unfitted (fitted + unfitted = nCells);  above: fitted bots with d2 > (double)d2Threshold * 2^40
+ *     bonds_used, bonds_dropped (their sum is the member's marked directed entries)
+ *     Yxx ... W   the eight sums over all used bonds of the member (fitted bots or not), pbMoment128 NORMALISED by the
+ *                 host to 0 <= lo < 2^32 with hi the floor quotient; the device adds low 32 bits and the rest apart
+ *     sum_d2      over fitted bots the sum of e = (unsigned long long)rint(d2); an e of 2^63 or more, which only the
+ *                 rounding of an ill-conditioned fit can produce, counts as 2^63.  max_d2: the largest e
+ * With F = X Y^-1 formed from the member's sums the caller has the macroscopic deformation gradient.
+ * pbSimStrainStats: one row per member.  pbSimStrainOf: one member's per-bot results in ORIGINAL order: moments, 9 words
+ * per bot in the order above; gradient, Jxx Jxy Jyx Jyy per bot, derived on the host from the moments with the shared
+ * function; d2min, the device's value.  Any pointer may be NULL, not all three.  pbSimGetStrainTimes: calls so far and
+ * the span of the last one's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
+ * PB_ERR_ARG, before the device is touched: NULL handle; NULL rows; all three per-bot pointers NULL; member out of
+ * range; d2Threshold negative, NaN or infinite; a batch of 2^28 bots or more, or of more than 65535 members; no mark held
+ * ("no reference marked").
+ * Cost: one pass that puts the present positions into ORIGINAL order (the mark's own scatter kernel) and one kernel with
+ * a lane per bot that walks the bot's marked list and gathers two positions per entry.  No float atomics, no scratch
+ * memory.  Scratch on top of the mark: 8 + 80 bytes per bot of the batch (present positions; nine moments and d2) and
+ * 184 per member (the rows), allocated by the first call, kept, freed by pbSimDestroy. */
+#define PB_STRAIN_REACH 8.0f
+enum { PB_STRAIN_K, PB_STRAIN_YXX, PB_STRAIN_YXY, PB_STRAIN_YYY, PB_STRAIN_XXX, PB_STRAIN_XXY, PB_STRAIN_XYX,
+       PB_STRAIN_XYY, PB_STRAIN_W, PB_STRAIN_MOMENTS };
+typedef struct pbStrainStats {         /* 184 bytes */
+  unsigned fitted, unfitted, above, reserved;        /* reserved: 0 */
+  unsigned long long bonds_used, bonds_dropped;
+  pbMoment128 yxx, yxy, yyy, xxx, xxy, xyx, xyy, w;  /* units of 2^-40 */
+  pbMoment128 sum_d2;                                /* units of 2^-40 */
+  unsigned long long max_d2;                         /* 0 with no fitted bot */
+} pbStrainStats;
+int pbSimStrainStats(pbSim *sim, float d2Threshold, pbStrainStats *rows /* nsims entries */);
+int pbSimStrainOf(pbSim *sim, unsigned member, long long *moments /* 9 n */,
+                  double *gradient /* 4 n: Jxx Jxy Jyx Jyy */, double *d2min /* n; ORIGINAL order; NULL skipped */);
+int pbSimGetStrainTimes(pbSim *sim, unsigned long long *analyses, float *last_device_ms);
+
 /* Phase-noise generator of a batch (PB_RNG_*; default PB_RNG_COUNTER).  Selecting an XORWOW kind builds
  * one 48-byte state per bot -- curand_init(member's seed, bot, 0): the 2^67-step subsequence skip is a
  * 160x160 GF(2) jump per set bit of the bot index -- and restarts the draw counter.

@@ -17,7 +17,8 @@ from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
            "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
-           "half_plane_vectors", "phasor_table", "scattering_summary", "van_hove_summary"]
+           "half_plane_vectors", "phasor_table", "scattering_summary", "van_hove_summary",
+           "deformation_gradient", "mean_d2min"]
 
 
 def phasor_table():
@@ -83,6 +84,29 @@ def mean_squared_displacement(row, subtract_drift=False):
     if subtract_drift:
         num -= int(row["sum_qx"]) ** 2 + int(row["sum_qy"]) ** 2
     return float(Fraction(num, m * m << 40))
+
+
+def deformation_gradient(row):
+    """The macroscopic deformation gradient of a member from one row of strain() (pure Python): F = X Y^-1 with the
+    row's sums over all used bonds, the affine map that carries the marked bond vectors onto the present ones in the
+    least-squares sense.  A 2 x 2 float64 array, every entry formed from the integers as one exact fraction and
+    converted once; NaN where the marked bonds do not span the plane (det Y <= 0)."""
+    from fractions import Fraction
+    a, b, c = int(row["yxx"]), int(row["yxy"]), int(row["yyy"])
+    det = a * c - b * b
+    if det <= 0:
+        return np.full((2, 2), np.nan)
+    xxx, xxy, xyx, xyy = (int(row[k]) for k in ("xxx", "xxy", "xyx", "xyy"))
+    return np.array([[float(Fraction(xxx * c - xxy * b, det)), float(Fraction(xxy * a - xxx * b, det))],
+                     [float(Fraction(xyx * c - xyy * b, det)), float(Fraction(xyy * a - xyx * b, det))]], np.float64)
+
+
+def mean_d2min(row):
+    """The mean non-affine displacement D2min per fitted bot from one row of strain() (pure Python), in world units
+    squared: sum_d2 / 2^40 / fitted as one exact fraction converted once; NaN when no bot was fitted."""
+    from fractions import Fraction
+    m = int(row["fitted"])
+    return float(Fraction(int(row["sum_d2"]), m << 40)) if m else float("nan")
 
 
 def time_correlation_summary(row, lag0=None):
@@ -787,6 +811,33 @@ class Sim:
                     "pbSimGetRearrangementTimes")
         return int(n.value), float(ms.value)
 
+    def strain(self, threshold=0.0):
+        """Every member's local strain and non-affine displacement against the mark, on the device (pbSimStrainStats):
+        a list of dicts of Python ints, one per member: fitted / unfitted (bots with and without a Falk-Langer fit),
+        above (fitted bots with D2min > threshold, in world units squared), bonds_used / bonds_dropped, the sums yxx,
+        yxy, yyy, xxx, xxy, xyx, xyy, w of the moments over all used bonds, sum_d2 and max_d2 (all in units of 2^-40).
+        deformation_gradient() and mean_d2min() turn a row into floats."""
+        rows = (_capi.pbStrainStats * int(getattr(self, "nsims", 1)))()
+        _capi.check(_capi.lib().pbSimStrainStats(self._h, float(threshold), rows), "pbSimStrainStats")
+        return [_capi.strain_row(r) for r in rows]
+
+    def strain_of(self, member=0):
+        """One member per bot, original order (pbSimStrainOf): a dict of moments (int64, n x 9: k, Yxx, Yxy, Yyy, Xxx,
+        Xxy, Xyx, Xyy, W), gradient (float64, n x 2 x 2: the local deformation gradient J, zero for an unfitted bot) and
+        d2min (float64, units of 2^-40: the device's value)."""
+        n = self.n
+        out = {"moments": np.empty((n, 9), np.int64), "gradient": np.empty((n, 2, 2), np.float64),
+               "d2min": np.empty(n, np.float64)}
+        _capi.check(_capi.lib().pbSimStrainOf(self._h, int(member), *[_capi.np_ptr(out[k]) for k in
+                                                                     ("moments", "gradient", "d2min")]),
+                    "pbSimStrainOf")
+        return out
+
+    def strain_times(self):
+        """(strain analyses run so far, device milliseconds of the last one)."""
+        n, ms = C.c_ulonglong(0), C.c_float(0.0)
+        _capi.check(_capi.lib().pbSimGetStrainTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetStrainTimes")
+        return int(n.value), float(ms.value)
 
     def moments(self):
         """Every member's row of integer moments of the state as it is now, from the device (pbSimMoments): a list of

@@ -144,6 +144,28 @@ def moments_row(r):
     return d
 
 
+class pbStrainStats(C.Structure):
+    _fields_ = [("fitted", C.c_uint), ("unfitted", C.c_uint), ("above", C.c_uint), ("reserved", C.c_uint),
+                ("bonds_used", C.c_ulonglong), ("bonds_dropped", C.c_ulonglong),
+                ("yxx", pbMoment128), ("yxy", pbMoment128), ("yyy", pbMoment128), ("xxx", pbMoment128),
+                ("xxy", pbMoment128), ("xyx", pbMoment128), ("xyy", pbMoment128), ("w", pbMoment128),
+                ("sum_d2", pbMoment128), ("max_d2", C.c_ulonglong)]
+
+
+PB_STRAIN_MOMENTS = ("k", "yxx", "yxy", "yyy", "xxx", "xxy", "xyx", "xyy", "w")  # a bot's nine words, in order
+
+
+def strain_row(r):
+    """A pbStrainStats row as a dict of Python ints (without `reserved`); each of yxx ... w and sum_d2 is the 128-bit sum
+    hi * 2^32 + lo as one int, units of 2^-40, as is max_d2."""
+    d = {}
+    for name, kind in pbStrainStats._fields_:
+        if name != "reserved":
+            v = getattr(r, name)
+            d[name] = (int(v.hi) << 32) + int(v.lo) if kind is pbMoment128 else int(v)
+    return d
+
+
 class pbCorrelationBin(C.Structure):
     _fields_ = [("pairs", C.c_ulonglong), ("dot", pbMoment128), ("ax", pbMoment128), ("ay", pbMoment128)]
 
@@ -377,6 +399,9 @@ SYMBOLS = {
     "pbSimRearrangementStats": (_I, [_VP, C.POINTER(pbRearrangementStats)]),
     "pbSimRearrangementOf": (_I, [_VP, _U, _VP, _VP, _VP, _VP]),
     "pbSimGetRearrangementTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimStrainStats": (_I, [_VP, _F, C.POINTER(pbStrainStats)]),
+    "pbSimStrainOf": (_I, [_VP, _U, _VP, _VP, _VP]),
+    "pbSimGetStrainTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimMoments": (_I, [_VP, C.POINTER(pbMomentsRow)]),
     "pbSimSetSeries": (_I, [_VP, _F, _U]),
     "pbSimGetSeriesInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(C.c_ulonglong)]),

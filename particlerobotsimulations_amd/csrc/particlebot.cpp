@@ -1468,6 +1468,19 @@ bool Particlebot::rearrangement(std::vector<float> &disp, std::vector<unsigned> 
   });
 }
 
+bool Particlebot::strainStats(float d2Threshold, pbStrainStats &out) {
+  return onFusedEngine("strainStats", "strain analysis", [&] { return pbSimStrainStats(sim, d2Threshold, &out); });
+}
+
+bool Particlebot::strain(std::vector<long long> &moments, std::vector<double> &gradient, std::vector<double> &d2min) {
+  return onFusedEngine("strain", "strain analysis", [&] {
+    moments.resize((size_t)PB_STRAIN_MOMENTS * params.nCells);
+    gradient.resize(4 * (size_t)params.nCells);
+    d2min.resize(params.nCells);
+    return pbSimStrainOf(sim, 0, moments.data(), gradient.data(), d2min.data());
+  });
+}
+
 bool Particlebot::moments(pbMomentsRow &out) {
   return onFusedEngine("moments", "time series", [&] { return pbSimMoments(sim, &out); });
 }

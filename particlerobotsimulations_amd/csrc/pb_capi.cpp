@@ -360,6 +360,23 @@ int pbHostRearrangementOf(void *hv, float *disp, unsigned *marked, unsigned *now
   return 0;
 }
 
+// strain analysis of the resident state against the mark (Particlebot::strainStats / strain; fused engine only): the
+// 184-byte pbStrainStats row at `threshold`, or the per-bot moments (9 nCells), deformation gradient (4 nCells) and
+// D2min (nCells), original order, any of which may be NULL.  -1 on the other engines, a bad threshold, or with no mark.
+int pbHostStrainStats(void *hv, float threshold, pbStrainStats *out) {
+  return out && ((HostSim *)hv)->bot->strainStats(threshold, *out) ? 0 : -1;
+}
+
+int pbHostStrainOf(void *hv, long long *moments, double *gradient, double *d2min) {
+  std::vector<long long> m;
+  std::vector<double> g, d;
+  if (!((HostSim *)hv)->bot->strain(m, g, d)) return -1;
+  copyOut(moments, m);
+  copyOut(gradient, g);
+  copyOut(d2min, d);
+  return 0;
+}
+
 // time series of the resident state (Particlebot::moments / setSeries / seriesInfo / seriesRows; fused engine only): the
 // 152-byte pbMomentsRow of the state as it is, the recorder's switch, what it holds, and the records from `first` on
 // (cap entries of room; *count = how many there are).  -1 on the other engines, a bad interval or capacity, a read

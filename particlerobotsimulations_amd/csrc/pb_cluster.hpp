@@ -1,4 +1,4 @@
-// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip, pb_dynamics.hip and
+// pb_cluster.hpp -- what pb_cluster.hip shares with pb_contacts.hip, pb_structure.hip, pb_dynamics.hip, pb_strain.hip and
 // pb_correlate.hip and pb_vanhove_distinct.hip: the scratch object with its five clocks, the fresh grid, the workgroup
 // scan (the wave helpers are pb_fixed.hpp's), the walk over a bot's nine cells (pbWalkNine) and the link rule (pbWhenLinked) that every neighbour
 // sweep of the analysis layer is built on, the front end that files the bots (rmax, hash, sort, gather, cell starts) and
@@ -64,6 +64,14 @@ struct PbClusterScratch {
   PbDevBuf<unsigned long long> kAcc;      // nsims * the most bins so far * 9: per bin the count and eight partial sums
   PbDevBuf<unsigned long long> kTotals;   // nsims * 5: measured, sum ax, sum ay, the two partial sums of a^2
   PbAnalysisClock correlateClock;
+  // strain analysis (pb_strain.hip): allocated by the first call, kept
+  PbDevBuf<float2> tPos1;                 // total, ORIGINAL order: the present positions, raw from the state arrays
+  PbDevBuf<long long> tMoments;           // 9 per bot, ORIGINAL order
+  PbDevBuf<double> tD2;                   // total, ORIGINAL order: D2min
+  PbDevBuf<pbStrainStats> tRows;          // nsims; every pbMoment128 holds the two partial sums until the host composes them
+  PbSpanClock strainSpan;                 // no filing, so no ev0: the span is the analysis' own
+  unsigned long long strainRuns = 0;
+  float strainMs = 0.0f;
 };
 
 namespace {
@@ -219,6 +227,10 @@ inline int pbClockStop(pbSim *S, PbAnalysisClock &K) {
   const int rc = pbClockMark(S, K);
   return rc != PB_OK ? rc : pbClockRead(S, K);
 }
+// "no reference marked" is known without the device (pb_dynamics.hip holds the mark)
+inline int pbNeedMark(const char *fn, const pbSim *S) {
+  return S->cluster && S->cluster->dMarked ? PB_OK : pbFail(fn, ": no reference marked");
+}
 // the body of pbSimGet{Cluster,Contact,Structure,Rearrangement}Times; K points into S's scratch object
 inline int pbClockGet(const char *fn, const pbSim *S, PbAnalysisClock PbClusterScratch::*K, unsigned long long *runs,
                       float *last_device_ms) {
@@ -248,6 +260,10 @@ int pbClusterAnalyse(pbSim *S, float gap);
 // Nothing here touches the device; the gap check needs no look at the handle, the other two read the host-side batch
 // object, so they need a real one.                                                                       pb_cluster.hip
 int pbClusterCheckArgs(const char *fn, const pbSim *S, const float *gap, const unsigned *member);
+// k_dyn_scatter's launch, queued on the batch's stream: the positions of the whole batch as they are now, raw from the
+// state arrays, into ORIGINAL order at pos (total entries).  The mark's own pass, shared with the strain analysis.
+//                                                                                                        pb_dynamics.hip
+int pbDynamicsScatter(pbSim *S, float2 *pos);
 // k_contact_scan's three launches, queued on the batch's stream: offsets[0 .. n] = the exclusive prefix sum of
 // degree[0 .. n), parts (ceil(n / 256) + 1 words at the least) the scan's block sums with the 64-bit total in
 // parts[ceil(n / 256)].  Offsets are 32-bit: the caller reads the total before it trusts them.         pb_contacts.hip

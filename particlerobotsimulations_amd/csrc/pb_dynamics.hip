@@ -221,11 +221,6 @@ void freeMark(PbClusterScratch *C) {
   dropMark(C);
 }
 
-// "no reference marked" is known without the device
-int needMark(const char *fn, const pbSim *S) {
-  return S->cluster && S->cluster->dMarked ? PB_OK : pbFail(fn, ": no reference marked");
-}
-
 // files the bots at the mark's gap and leaves now, kept, disp and the rows (partial sums in sum_q2_*) on the device
 int compareSweep(pbSim *S) {
   const float gap = S->cluster->dGap;
@@ -247,6 +242,13 @@ int compareSweep(pbSim *S) {
 }
 
 }  // namespace
+
+int pbDynamicsScatter(pbSim *S, float2 *pos) {
+  hipLaunchKernelGGL(k_dyn_scatter, dim3(cdiv(S->n, CT), S->nsims), dim3(CT), 0, S->stream, S->pr[S->cur],
+                     S->orig[S->cur], S->n, pos);
+  PB_TRY(hipGetLastError());
+  return PB_OK;
+}
 
 int pbSimMarkReference(pbSim *S, float linkGap) {
   if (!S) return pbFail("pbSimMarkReference", ": null handle");
@@ -276,8 +278,9 @@ int pbSimMarkReference(pbSim *S, float linkGap) {
   PB_TRY(C->dOther.ensure(count ? count : 1ull));
   hipLaunchKernelGGL(k_dyn_fill, gBots, b, 0, S->stream, C->cpr, C->start, n, G, linkGap, C->dOffsets, C->dOther, flag);
   hipLaunchKernelGGL(k_dyn_order, dim3(blocks), b, 0, S->stream, C->dOffsets, C->dOther, total);
-  hipLaunchKernelGGL(k_dyn_scatter, gBots, b, 0, S->stream, S->pr[S->cur], S->orig[S->cur], n, C->dPos0);
   PB_TRY(hipGetLastError());
+  rc = pbDynamicsScatter(S, C->dPos0);
+  if (rc != PB_OK) return rc;
   rc = pbClockMark(S, C->dynamicsClock);  // the mark ends here: the flag's way back is not part of its device time
   if (rc != PB_OK) return rc;
   unsigned long long raised = 0ull;
@@ -317,7 +320,7 @@ int pbSimGetReferenceInfo(pbSim *S, int *marked, float *linkGap, float *time, un
 int pbSimRearrangementStats(pbSim *S, pbRearrangementStats *rows) {
   if (!S || !rows) return pbFail("pbSimRearrangementStats", ": null handle or rows");
   int rc = pbClusterCheckArgs("pbSimRearrangementStats", S, nullptr, nullptr);
-  if (rc == PB_OK) rc = needMark("pbSimRearrangementStats", S);
+  if (rc == PB_OK) rc = pbNeedMark("pbSimRearrangementStats", S);
   if (rc == PB_OK) rc = compareSweep(S);
   if (rc != PB_OK) return rc;
   PB_TRY(hipMemcpy(rows, S->cluster->dRows, sizeof(pbRearrangementStats) * S->nsims, hipMemcpyDeviceToHost));
@@ -334,7 +337,7 @@ int pbSimRearrangementOf(pbSim *S, unsigned member, float *disp, unsigned *marke
   if (!disp && !marked && !now && !kept)
     return pbFail("pbSimRearrangementOf", ": disp, marked, now and kept are all null");
   int rc = pbClusterCheckArgs("pbSimRearrangementOf", S, nullptr, &member);
-  if (rc == PB_OK) rc = needMark("pbSimRearrangementOf", S);
+  if (rc == PB_OK) rc = pbNeedMark("pbSimRearrangementOf", S);
   if (rc == PB_OK) rc = compareSweep(S);
   if (rc != PB_OK) return rc;
   PbClusterScratch *C = S->cluster;

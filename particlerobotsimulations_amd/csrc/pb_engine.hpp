@@ -22,6 +22,8 @@
 //   pb_vanhove.hip   self van Hove function: displacement histograms per lag over a lag ring (pbSimSetVanHove)
 //   pb_vanhove_distinct.hip  distinct van Hove function: pair histograms per lag, a neighbour sweep around every bot's
 //                    earlier position (pbSimSetVanHoveDistinct)
+//   pb_strain.hip    local strain and D2min: the Falk-Langer fit of every bot's marked bonds onto its present ones, a
+//                    gather over the rearrangement analysis' mark (pbSimStrainStats); pb_strain.hpp holds the fit
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
 //   pb_sweep.hpp     the neighbour sweep (device code shared by k_force and k_resident)
 //   pb_memory.hpp    the owners of device memory, pinned memory, events and streams the batch object is made of, and

@@ -5,6 +5,7 @@
 //                   [--trail FILE] [--clusters FILE [--cluster-gap G]] [--contacts FILE [--contact-gap G]]
 //                   [--structure FILE [--structure-gap G]] [--rdf FILE [--rdf-rmax R] [--rdf-bins B]]
 //                   [--rearrange FILE [--rearrange-gap G] [--rearrange-window]]
+//                   [--strain FILE [--strain-threshold T] [--rearrange-gap G] [--rearrange-window]]
 //                   [--series FILE [--series-interval T] [--series-capacity N]]
 //                   [--correlate FILE [--correlate-kind velocity|radius] [--correlate-rmax R] [--correlate-bins B]]
 //                   [--timecorr FILE [--timecorr-interval T] [--timecorr-lags N] [--timecorr-overlap A]]
@@ -84,6 +85,8 @@ struct RunOptions {
   std::string clustersPath, contactsPath, structurePath, rearrangePath;
   float clusterGap = 0.0f, contactGap = 0.0f, structureGap = 0.0f, rearrangeGap = 0.0f;
   bool rearrangeWindow = false;
+  std::string strainPath;  // measured against --rearrange's mark, with or without --rearrange itself
+  float strainThreshold = 0.0f;
 
   std::string rdfPath, correlatePath;
   float rdfRmax = 0.0f, correlateRmax = 0.0f;  // 0: 10 * max_radius
@@ -176,6 +179,8 @@ const Flag kFlags[] = {
     {"--rearrange", &RunOptions::rearrangePath, "analysis"},
     {"--rearrange-gap", &RunOptions::rearrangeGap, 0.0f, false},
     {"--rearrange-window", &RunOptions::rearrangeWindow},
+    {"--strain", &RunOptions::strainPath, "analysis"},
+    {"--strain-threshold", &RunOptions::strainThreshold, 0.0f, false},
 
     // an interval of 0: a record in front of every step
     {"--series", &RunOptions::seriesPath, "recorder"},
@@ -378,7 +383,7 @@ struct Run {
   const RunOptions &o;
   long stepsDone = 0, frames = 0;
   unsigned long long seriesWritten = 0;  // --series: the records drained so far
-  bool referenceMarked = false;          // --rearrange: the mark and its time
+  bool referenceMarked = false;          // --rearrange and --strain: the mark and its time
   float markTime = 0.0f;
 
   // A lag's sums are exact only below 2^31 samples, and the engine refuses a table that holds more.  The tables stay on
@@ -508,13 +513,44 @@ struct Run {
   // first included, one row compares the state with it (Particlebot::rearrangementStats).  Every number is the integer
   // it is: bonds directed, SumQx / SumQy in units of 2^-20, SumQ2 / MaxQ2 of 2^-40, SumQ2 in decimal from its 128 bits.
   // --rearrange-window marks again after each row, so that every row describes one dump interval.
+  // --strain FILE [--strain-threshold T]: against the same mark (it is taken, at --rearrange-gap, and with
+  // --rearrange-window renewed, whether --rearrange is given or not), one row of the strain analysis' integers at every
+  // dump time (Particlebot::strainStats): fitted and unfitted bots, fitted bots whose D2min is above T, used and
+  // dropped bonds, the eight sums of the moments, SumD2 and MaxD2, all of 2^-40 and the 128-bit ones in decimal.  Both
+  // rows of a dump time are written before a window's re-mark.
   bool dumpRearrangement() {
-    if (o.rearrangePath.empty()) return true;
+    if (o.rearrangePath.empty() && o.strainPath.empty()) return true;
     if (!referenceMarked) {  // the run's first dump time
       if (!sim.markReference(o.rearrangeGap)) return false;
       referenceMarked = true;
       markTime = sim.getTime();
     }
+    if (!writeRearrangementRow() || !writeStrainRow()) return false;
+    if (o.rearrangeWindow) {  // the next row describes the interval that starts here
+      if (!sim.markReference(o.rearrangeGap)) return false;
+      markTime = sim.getTime();
+    }
+    return true;
+  }
+
+  bool writeStrainRow() {
+    if (o.strainPath.empty()) return true;
+    pbStrainStats ss;
+    if (!sim.strainStats(o.strainThreshold, ss)) return false;
+    FILE *f = openForDump(o.strainPath, Header::WhenEmpty,
+                          "Time, MarkTime, Fitted, Unfitted, Above, BondsUsed, BondsDropped, Yxx, Yxy, Yyy, Xxx, Xxy, Xyx, "
+                          "Xyy, W, SumD2, MaxD2");
+    if (!f) return false;
+    fprintf(f, "%f, %f, %u, %u, %u, %llu, %llu, %s, %s, %s, %s, %s, %s, %s, %s, %s, %llu\n", sim.getTime(), markTime,
+            ss.fitted, ss.unfitted, ss.above, ss.bonds_used, ss.bonds_dropped, decimal128(ss.yxx).c_str(),
+            decimal128(ss.yxy).c_str(), decimal128(ss.yyy).c_str(), decimal128(ss.xxx).c_str(),
+            decimal128(ss.xxy).c_str(), decimal128(ss.xyx).c_str(), decimal128(ss.xyy).c_str(), decimal128(ss.w).c_str(),
+            decimal128(ss.sum_d2).c_str(), ss.max_d2);
+    return fclose(f) == 0;
+  }
+
+  bool writeRearrangementRow() {
+    if (o.rearrangePath.empty()) return true;
     pbRearrangementStats rs;
     if (!sim.rearrangementStats(rs)) return false;
     FILE *f = openForDump(o.rearrangePath, Header::WhenEmpty,
@@ -524,12 +560,7 @@ struct Run {
     fprintf(f, "%f, %f, %llu, %llu, %llu, %u, %u, %u, %u, %lld, %lld, %s, %llu\n", sim.getTime(), markTime,
             rs.bonds_marked, rs.bonds_now, rs.bonds_kept, rs.bots_unchanged, rs.bots_lost, rs.bots_gained, rs.measured,
             rs.sum_qx, rs.sum_qy, decimal128(rs.sum_q2_hi, rs.sum_q2_lo).c_str(), rs.max_q2);
-    if (fclose(f) != 0) return false;
-    if (o.rearrangeWindow) {  // the next row describes the interval that starts here
-      if (!sim.markReference(o.rearrangeGap)) return false;
-      markTime = sim.getTime();
-    }
-    return true;
+    return fclose(f) == 0;
   }
 
   // --series FILE: the device's time-series recorder (Particlebot::setSeries).  While the engine steps, one row of

@@ -54,6 +54,7 @@ _ANALYSES = {
     "pbHostContacts": [_F, _P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)], "pbHostContactVirial": [_F, _P],
     "pbHostRadialCounts": [_F, C.c_uint, _P], "pbHostStructureStats": [_F, _P], "pbHostHexatic": [_F, _P, _P],
     "pbHostMarkReference": [_F], "pbHostRearrangementStats": [_P], "pbHostRearrangementOf": [_P, _P, _P, _P],
+    "pbHostStrainStats": [_F, _P], "pbHostStrainOf": [_P, _P, _P],
     "pbHostMoments": [_P], "pbHostSetSeries": [_F, C.c_uint], "pbHostSeriesInfo": [_P, _P, _P],
     "pbHostSeriesRows": [C.c_ulonglong, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
     "pbHostPairCorrelation": [C.c_int, _F, C.c_uint, _P, _P],
@@ -369,6 +370,28 @@ class HostSim:
                "kept": np.empty(n, np.uint32)}
         if lib().pbHostRearrangementOf(self._h, *[_ptr(out[k]) for k in ("disp", "marked", "now", "kept")]) != 0:
             raise RuntimeError("rearrangement_of: the rearrangement analysis needs the fused engine and a marked reference")
+        return out
+
+    def strain(self, threshold=0.0):
+        """Local strain and D2min against the mark, on the device (pbSimStrainStats; fused engine only): a list with one
+        dict of Python ints: fitted / unfitted / above (fitted bots with D2min > threshold), bonds_used / bonds_dropped,
+        the sums yxx ... w of the moments, sum_d2 and max_d2 (units of 2^-40)."""
+        row = _capi.pbStrainStats()
+        if lib().pbHostStrainStats(self._h, float(threshold), C.byref(row)) != 0:
+            raise RuntimeError("strain: the strain analysis needs the fused engine, a marked reference and a finite "
+                               "threshold >= 0")
+        return [_capi.strain_row(row)]
+
+    def strain_of(self, member=0):
+        """Per bot, original order (pbSimStrainOf; fused engine only): a dict of moments (int64, n x 9), gradient
+        (float64, n x 2 x 2: the local deformation gradient J) and d2min (float64, units of 2^-40)."""
+        if int(member) != 0:
+            raise IndexError(member)
+        n = self.n
+        out = {"moments": np.empty((n, 9), np.int64), "gradient": np.empty((n, 2, 2), np.float64),
+               "d2min": np.empty(n, np.float64)}
+        if lib().pbHostStrainOf(self._h, *[_ptr(out[k]) for k in ("moments", "gradient", "d2min")]) != 0:
+            raise RuntimeError("strain_of: the strain analysis needs the fused engine and a marked reference")
         return out
 
     def moments(self):
