@@ -20,6 +20,19 @@ fold, and differ from call to call with the gap.
 Pair correlations take at most 1024 bins (PB_CORR_MAX_BINS), radial counts 4096: "the largest bin count the call takes"
 is 1024 for the one and 4096 for the other.
 
+The strain family (strain() at three thresholds, strain_of() per member) files nothing: it reads the CSR and the
+positions of whichever mark is in place, shares pbDynamicsScatter with the rearrangement compare and keeps its rows in
+the shared scratch.  Its expectations come from tests/strain_ref.py on the marked network restated once per mark; the
+mark is the earlier state for A and the state itself for B and C, where every fitted bot's gradient is the identity and
+its d2min exactly 0 (check_strain_not_trivial says what the rows hold there).  check_orders asks for a strain call
+directly behind every family that re-files, behind an entry that replaces the mark, behind a compare and behind a
+displacement correlation, and for a compare directly behind a strain call.
+
+The recorders' shapes are here as well: RECORD_BETWEEN, the distinct van Hove records the GPU file takes between every
+two calls (a filing at rMax = 1 with no radius term: check_record_grid shows that no call of the catalogue files on that
+grid), and the two van Hove functions of the interleaving test, the self part's width chosen from the oracle's
+displacements over one lag (van_hove_self_width, check_van_hove_self_width).
+
 A result is compared with its expectation the way the owning test file compares it (Entry.check), and with the result
 of the same call on a fresh session bit for bit (same_bits)."""
 import collections
@@ -37,7 +50,10 @@ import field_ref as FR
 import render_ref as RR
 import series_ref as MR
 import sfactor_ref as QR
+import strain_ref as ER
 import structure_ref as SR
+import vanhove_distinct_ref as GR
+import vanhove_ref as VR
 from helpers import jittered_blob, simparams_from_orc
 
 f32 = np.float32
@@ -55,7 +71,8 @@ SK_BOX = 4
 MARKS = {"A": 0.0019, "B": 0.05, "C": 0.0}
 STATES = ("batch3x300", "single17")         # the two every test runs on
 ALL_STATES = STATES + ("batch3x300_small_radii",)   # and the one more the call orders run on
-ORDERS = ("catalogue", "reversed", "shuffle0", "shuffle1", "shuffle2", "shuffle3")
+SHUFFLES = 4
+ORDERS = ("catalogue", "reversed") + tuple(f"shuffle{k}" for k in range(SHUFFLES))
 FILING = ("clusters", "contacts", "hexatic", "radial", "correlation")  # the families that re-file the bots, the mark aside
 UNMEASURED = {10: "nan x", 40: "inf y", 77: "x -2048", 123: "vy 2048", 200: "nan radius", 290: "radius 2048"}
 
@@ -300,6 +317,41 @@ def _rearrangement(st, key):
                    lambda: [YR.analyse(pos0[m], rad0[m], s["pos"], s["rad"], gap) for m, s in enumerate(st.final)])
 
 
+def _marked_network(st, key, m):
+    pos0, rad0, gap, _ = mark_of(st, key)
+    return _cached((st.name, "marked network", key, m), lambda: NR.topology(pos0[m], rad0[m], gap))
+
+
+def _strain(st, key, threshold):
+    """strain_ref's (row, per-bot arrays) of every member: the mark `key` against the state as it is."""
+    pos0 = mark_of(st, key)[0]
+
+    def one(m):
+        off, _, oth = _marked_network(st, key, m)
+        return ER.analyse_csr(off, oth, pos0[m], st.final[m]["pos"], threshold)
+
+    return _cached((st.name, "strain", key, threshold), lambda: [one(m) for m in range(st.nsims)])
+
+
+@functools.lru_cache(maxsize=None)
+def strain_thresholds():
+    """(0, the median of the reference's d2min over the fitted bots of batch3x300 under mark A in world units, rounded to
+    fp32 as the call takes it, 1e30 that no bot exceeds): the same three on every state."""
+    bots = [b for _, b in _strain(state("batch3x300"), "A", 0.0)]
+    d2 = np.concatenate([b["d2min"][b["fitted"]] for b in bots])
+    return 0.0, float(f32(np.median(d2) / 2.0 ** 40)), 1.0e30
+
+
+def nan_aware_bits64(got, want):
+    """float64 arrays as test_gpu_strain compares them, by their bits; a NaN of the reference asks for a NaN."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype == np.float64 and got.shape == want.shape, (got.dtype, got.shape, want.shape)
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan)
+    bad = np.flatnonzero(got.view(np.uint64)[~nan] != want.view(np.uint64)[~nan])
+    assert bad.size == 0, (bad.size, bad[:8])
+
+
 def catalogue(st):
     """The named calls, in the order `catalogue` runs them.  call(sim) makes the call; expected(mark) is what the
     restatement gives for the state under the mark named (only entries with reads_mark look at it); check(got, want)
@@ -466,6 +518,28 @@ def catalogue(st):
             lambda sim, shape=shape: sim.render(*render_view(st, shape), light_radius=0.25, member=odd),
             lambda mark, shape=shape: want_frame(shape), check_frame)
 
+    # the strain analysis files nothing: it reads the CSR and the positions of whichever mark the order has put in place
+    def check_strain(got, want):
+        assert len(got) == st.nsims and all(tuple(row) == ER.FIELDS for row in got)
+        assert got == want, [{k: (g[k], w[k]) for k in g if g[k] != w[k]} for g, w in zip(got, want)]
+
+    def check_strain_of(got, want):
+        assert got["moments"].dtype == np.int64 and got["moments"].shape == (st.n, 9)
+        assert got["gradient"].shape == (st.n, 2, 2) and got["d2min"].shape == (st.n,)
+        ints_equal(got["moments"], want["moments"])
+        nan_aware_bits64(got["d2min"], want["d2min"])
+        nan_aware_bits64(got["gradient"], want["gradient"])
+        _, grad, d2 = ER.fit_all(got["moments"])  # the device's d2min is the fit of the device's own moments
+        nan_aware_bits64(got["d2min"], d2)
+        nan_aware_bits64(got["gradient"], grad)
+
+    for threshold in strain_thresholds():
+        add(f"strain({threshold!r})", "strain", lambda sim, t=threshold: sim.strain(t),
+            lambda mark, t=threshold: [r[0] for r in _strain(st, mark, t)], check_strain, reads_mark=True)
+    for m in (first, last, odd):
+        add(f"strain_of(member {m})", "strain", lambda sim, m=m: sim.strain_of(m),
+            lambda mark, m=m: _strain(st, mark, 0.0)[m][1], check_strain_of, reads_mark=True)
+
     # the mark: three reads of whichever mark the order has put in place, and two compound entries that replace it
     def check_rearrangement_of(got, want):
         assert got["disp"].dtype == f32
@@ -511,11 +585,11 @@ def _renamed(entries):
 # ---- the orders ------------------------------------------------------------------------------------------------------
 
 def orders(st):
-    """name -> list of catalogue indices: the catalogue as written, reversed, and four shuffles in each of which every
-    entry appears twice."""
+    """name -> list of catalogue indices: the catalogue as written, reversed, and SHUFFLES shuffles in each of which
+    every entry appears twice."""
     count = len(catalogue(st))
     out = {"catalogue": list(range(count)), "reversed": list(range(count))[::-1]}
-    for k in range(4):
+    for k in range(SHUFFLES):
         out[f"shuffle{k}"] = [int(i) for i in np.random.default_rng(7000 + k).permutation(list(range(count)) * 2)]
     assert tuple(out) == ORDERS
     return out
@@ -577,7 +651,7 @@ def check_orders(st):
     assert len(set(names)) == len(names)
     all_orders = orders(st)
     assert all_orders["reversed"] == all_orders["catalogue"][::-1]
-    for k in range(4):
+    for k in range(SHUFFLES):
         assert sorted(all_orders[f"shuffle{k}"]) == sorted(all_orders["catalogue"] * 2)
     assert len({tuple(o) for o in all_orders.values()}) == len(ORDERS)
     placed = [[names[i] for i in order] for order in all_orders.values()]
@@ -592,18 +666,38 @@ def check_orders(st):
     assert any(a in plain and b in linked for a, b in pairs), "no link-rule call directly behind a plain filing"
     assert any(a in linked and b in plain for a, b in pairs), "no plain filing directly behind a link-rule call"
     # a read of the mark behind five other families' re-filings since the mark was put in place
-    best = 0
+    # (by the link rule's readers and the displacement correlation, and by the strain analysis, each on its own)
+    best = {False: 0, True: 0}
     for order in all_orders.values():
         since = set()
         for e, _ in walk(st, order):
             if e.sets_mark:
                 since = set()
             elif e.reads_mark:
-                best = max(best, len(since))
+                best[e.family == "strain"] = max(best[e.family == "strain"], len(since))
             if e.family in FILING:
                 since.add(e.family)
-    assert best >= 5, f"the mark is never read behind more than {best} other families"
+    assert best[False] >= 5, f"the mark is never read behind more than {best[False]} other families"
+    assert best[True] >= 5, f"no strain call reads the mark behind more than {best[True]} other families"
+    # the strain analysis reads the mark's buffers and shares a kernel and the scratch with the rest: a strain call
+    # directly behind every family that re-files, behind an entry that replaces the mark (and may move dOther), behind a
+    # rearrangement compare and behind a correlation that reads the marked positions; and a compare behind a strain call
+    by_name = {e.name: e for e in entries}
+    behind = {(by_name[a], by_name[b]) for p in placed for a, b in zip(p, p[1:])}
+    strain_behind = [a for a, b in behind if b.family == "strain"]
+    for fam in FILING:
+        assert any(a.family == fam for a in strain_behind), f"no strain call directly behind a call of {fam}"
+    assert any(a.sets_mark for a in strain_behind), "no strain call directly behind an entry that replaces the mark"
+    assert any(is_compare(a) for a in strain_behind), "no strain call directly behind a rearrangement read"
+    assert any(a.family == "correlation" and a.reads_mark for a in strain_behind), \
+        "no strain call directly behind a correlation that reads the mark"
+    assert any(a.family == "strain" and is_compare(b) for a, b in behind), "no rearrangement read directly behind a strain call"
     return len(entries)
+
+
+def is_compare(entry):
+    """rearrangement() or rearrangement_of() on the mark in place (not reference_info(), which asks the host alone)."""
+    return entry.family == "mark" and not entry.sets_mark and entry.name.startswith("rearrangement")
 
 
 def check_not_trivial(st):
@@ -626,3 +720,103 @@ def check_not_trivial(st):
         # the link rule's grid edge, (2 rmax + gap) (1 + 2^-10): one cell for everything, or cells of a bot's diameter
         rmax = max(float(np.nanmax(np.where(np.isfinite(f["rad"]), f["rad"], 0.0))) for f in st.final)
         assert rmax == 2048.0 if st.name == "batch3x300" else rmax < 0.12
+        check_strain_not_trivial(st)
+
+
+def check_strain_not_trivial(st):
+    """The strain rows of a batch state, from strain_ref alone.  Under mark A (90 steps against 120) bots are fitted and
+    their d2min is positive; under marks B and C the marked state IS the present one, so every fitted bot has the
+    identity for a gradient and a d2min of exactly 0 (test_gpu_strain asserts the same of a state against itself): there
+    the moments, the fitted bots and the bonds are what the rows say.  single17 (17 bots moved by noise of 0.03, no pure
+    translation) has 13 fitted bots under mark A; nothing is asserted of it here."""
+    _, middle, huge = strain_thresholds()
+    for key in MARKS:
+        for m, (row, bots) in enumerate(_strain(st, key, 0.0)):
+            assert row["fitted"] > 0 and row["unfitted"] > 0 and row["bonds_used"] > 0 and row["w"] > 0, (key, m, row)
+            assert (row["max_d2"] > 0 and row["sum_d2"] > row["max_d2"]) if key == "A" else row["max_d2"] == 0, (key, m, row)
+            assert (bots["gradient"][bots["fitted"]] == np.eye(2)).all() == (key != "A"), (key, m)
+    for m, (row, _) in enumerate(_strain(st, "A", middle)):
+        assert 0 < row["above"] < row["fitted"], (m, row)
+    assert all(row["above"] == 0 for row, _ in _strain(st, "A", huge))
+    # the planted bots had bonds at step 90; a NaN, an infinite or a far-away component now fails pbStrainInReach
+    odd = _strain(st, "A", 0.0)[1]
+    assert odd[0]["unfitted"] > 0 and odd[0]["bonds_dropped"] > 0
+    length = np.diff(np.asarray(_marked_network(st, "A", 1)[0]).astype(np.int64))
+    # (bot 10 had no bond at step 90; the bots at inf y and at x = -2048 had five and four, dropped at both ends)
+    gone = (10, 40, 77)
+    for bot in gone:
+        assert odd[1]["dropped"][bot] == length[bot] and not odd[1]["fitted"][bot], bot
+    assert length[40] > 0 and length[77] > 0 and odd[0]["bonds_dropped"] == 2 * sum(int(length[b]) for b in gone)
+
+
+# ---- the recorders that run between and beside the calls -------------------------------------------------------------
+
+RECORD_BETWEEN = (2, 1.0 / 32, 32)  # (lags, width, bins) of the distinct van Hove records taken between two calls
+VAN_HOVE_LAGS, VAN_HOVE_INTERVAL, VAN_HOVE_BINS = 4, 0.05, 16  # the two recorders of the interleaving test
+VAN_HOVE_DISTINCT = (1.0 / 32, 32)
+
+
+def filing_edges(st):
+    """The edge of every grid a call of the catalogue files the state on (pbClusterFile): (2 rmax + gap) (1 + 2^-10)
+    for the link rule's callers, rmax the largest finite radius of the batch as it is; rMax (1 + 2^-10) for the radial
+    counts and the pair correlations."""
+    rmax = max(float(np.max(np.where(np.isfinite(s["rad"]), s["rad"], f32(0.0)))) for s in st.final)
+    grow = 1.0 + 1.0 / 1024.0
+    gaps = sorted(set(GAPS) | set(MARKS.values()))
+    return ([(2.0 * rmax + float(f32(gap))) * grow for gap in gaps]
+            + [max(float(f32(r)) * grow, 1.0 / 256.0) for r, _ in RADIAL + CORRELATION])
+
+
+def check_record_grid(st):
+    """The records between the calls file on a grid no call of the catalogue files on: rMax = 1, an edge a tenth away
+    from every other at the least, so that a sweep which kept the grid of the record in front of it walks other cells."""
+    lags, width, bins = RECORD_BETWEEN
+    edge, gx, gy = GR.grid_of(st.n, width, bins)
+    assert VR.qw_of(width) * bins == 1 << 20 and edge == 1.0 + 1.0 / 1024.0
+    assert (gx, gy) == ((32, 16) if st.n == 300 else (8, 4))
+    others = filing_edges(st)
+    assert len(others) == len(set(GAPS) | set(MARKS.values())) + len(RADIAL) + len(CORRELATION)
+    assert all(abs(e / edge - 1.0) > 0.1 for e in others), (edge, others)
+    return edge, others
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_lagged_positions():
+    """batch3x300's members run on by the oracle (nothing planted), their positions at 0, 5, 10 and 15 steps behind the
+    state: records 0.05 s apart as the interleaving test's gate takes them."""
+    from oracle import orclib as orc
+    st = state("batch3x300")
+    out = []
+    for P, start in zip(st.params, st.start):
+        osim = orc.Sim(P, reset=False)
+        for key in ("pos", "vel", "rad", "phase", "dead"):
+            osim.set(key, start[key])
+        assert osim.run(STEPS, dt=DT, sort_interval=SORT_INTERVAL)
+        pos = [osim.get("pos")]
+        for _ in range(VAN_HOVE_LAGS - 1):
+            assert osim.run(5, dt=DT, sort_interval=SORT_INTERVAL)
+            pos.append(osim.get("pos"))
+        osim.close()
+        out.append(pos)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def van_hove_self_width():
+    """The self part's bin width in the interleaving test: static friction holds most bots where they are, so the width
+    comes from those that move: the largest power of two not above the 90th percentile of the displacement over one
+    lag of 0.05 s, all members of batch3x300 together."""
+    moved = np.concatenate([np.linalg.norm((p[1] - p[0]).astype(np.float64), axis=1) for p in oracle_lagged_positions()])
+    return float(2.0 ** np.floor(np.log2(np.percentile(moved, 90))))
+
+
+def check_van_hove_self_width():
+    """With that width lag 1 fills more than one bin and lag 3 does not fall beyond the last edge as a whole."""
+    width = van_hove_self_width()
+    assert 2.0 ** -12 <= width <= 2.0 ** -8, width
+    for m, pos in enumerate(oracle_lagged_positions()):
+        rows = VR.table(pos, [0, 5, 10, 15], VAN_HOVE_LAGS, width, VAN_HOVE_BINS)
+        assert all(VR.identities_hold(r) for r in rows)
+        assert sum(1 for c in rows[1]["radial"] if c) > 1 and sum(rows[1]["radial"][1:]) > 0, (m, rows[1])
+        assert 0 < sum(rows[3]["radial"][1:]) and rows[3]["beyond_r"] < rows[3]["samples"], (m, rows[3])
+    return width

@@ -1,7 +1,10 @@
 """The analysis-session tests without a GPU: the states of tests/analysis_session_cases.py are reproducible from
 their recipe bit for bit (the device's state is later required to equal them), the six orders of each hold every
-grow-then-shrink, both switches of the filing kind and the long-lived mark (check_orders), the expectations say something
-on these states (check_not_trivial), and the comparisons and the restatement the cases file adds behave."""
+grow-then-shrink, both switches of the filing kind, the long-lived mark and a strain call directly behind everything
+that could disturb it (check_orders), the expectations say something on these states (check_not_trivial, the strain
+rows among them), the distinct van Hove records taken between the calls file on a grid no call files on and leave a
+table that says something, the van Hove shapes of the interleaving test fill their bins, and the comparisons and the
+restatement the cases file adds behave."""
 import numpy as np
 import pytest
 
@@ -15,11 +18,22 @@ f32 = np.float32
 def test_orders_hold_every_precondition(orc, name):
     st = AC.state(name)
     count = AC.check_orders(st)
-    assert 40 <= count <= 60
+    assert count == 60
     all_orders = AC.orders(st)
     assert tuple(all_orders) == AC.ORDERS and len(all_orders["shuffle3"]) == 2 * count
-    families = {e.family for e in AC.catalogue(st)}
-    assert families == set(AC.FILING) | {"mark", "field", "sfactor", "moments", "display", "render"}
+    entries = AC.catalogue(st)
+    families = {e.family for e in entries}
+    assert families == set(AC.FILING) | {"mark", "strain", "field", "sfactor", "moments", "display", "render"}
+    # the strain family: three thresholds and three members, every one a reader of the mark and none a taker
+    strain = [e for e in entries if e.family == "strain"]
+    assert len(strain) == 6 and all(e.reads_mark and not e.sets_mark for e in strain)
+    low, middle, high = AC.strain_thresholds()
+    assert low == 0.0 and high == 1.0e30 and 0.0 < middle < 1.0e-3 and middle == float(f32(middle))
+    assert [e.name for e in strain[:3]] == [f"strain({t!r})" for t in (low, middle, high)]
+    # every strain entry is wanted under every mark, by an order or by the session that lost its mark
+    index = {e.name: i for i, e in enumerate(entries)}
+    wanted = set(AC.needed(st))
+    assert all((index[e.name], key) in wanted for e in strain for key in AC.MARKS)
     # the marks an order puts in place: the recipe's until an entry takes another, then that one
     marks = [mark for _, mark in AC.walk(st, all_orders["catalogue"])]
     assert marks[0] == "A" and marks[-2:] == ["B", "C"] and set(marks) == {"A", "B", "C"}
@@ -29,6 +43,57 @@ def test_orders_hold_every_precondition(orc, name):
 @pytest.mark.parametrize("name", AC.ALL_STATES)
 def test_expectations_are_not_trivial(orc, name):
     AC.check_not_trivial(AC.state(name))
+
+
+def test_strain_expectations_are_the_references_own(orc):
+    """The catalogue restates the marked network once per mark and feeds strain_ref.analyse_csr: the same rows and the
+    same bits as strain_ref.analyse; and the middle threshold is the median it is said to be."""
+    import strain_ref as ER
+    st = AC.state("batch3x300")
+    _, middle, _ = AC.strain_thresholds()
+    for key in AC.MARKS:
+        pos0, rad0, gap, _ = AC.mark_of(st, key)
+        for m in range(st.nsims):
+            row, bots = ER.analyse(pos0[m], rad0[m], st.final[m]["pos"], gap, middle)
+            got_row, got_bots = AC._strain(st, key, middle)[m]
+            assert got_row == row and tuple(row) == ER.FIELDS
+            for k in ("moments", "gradient", "d2min"):
+                assert got_bots[k].tobytes() == bots[k].tobytes(), (key, m, k)
+    bots = [b for _, b in AC._strain(st, "A", 0.0)]
+    d2 = np.concatenate([b["d2min"][b["fitted"]] for b in bots]) / 2.0 ** 40
+    assert abs(int((d2 > middle).sum()) - int((d2 < middle).sum())) <= 2 and d2.size > 400
+    single = AC._strain(AC.state("single17"), "A", 0.0)[0][0]
+    assert single["fitted"] == 13 and single["max_d2"] > 0  # what check_strain_not_trivial's docstring says of it
+
+
+@pytest.mark.parametrize("name", AC.ALL_STATES)
+def test_records_between_the_calls_file_on_a_grid_of_their_own(orc, name):
+    st = AC.state(name)
+    edge, others = AC.check_record_grid(st)
+    # the link rule's edges are those check_not_trivial describes: one cell for everything, or cells of a bot's diameter
+    assert (max(others) > 4096.0) == (name == "batch3x300")
+    lags, width, bins = AC.RECORD_BETWEEN
+    assert lags == 2 and width * bins == 1.0 and all(width * bins != r for r, _ in AC.RADIAL + AC.CORRELATION)
+    # and the table they leave says something: pairs at lag 1 in every member, in more than one bin
+    import vanhove_distinct_ref as GR
+    for m, s in enumerate(st.final):
+        rows = GR.table([(s["pos"], s["rad"])] * 3, [0] * 3, lags, width, bins)
+        assert rows[1]["pairs"] > 0 and sum(1 for c in rows[1]["counts"] if c) > 1, (m, rows[1])
+        assert rows[1]["origins"] == 2 and rows[0]["origins"] == 3
+
+
+def test_the_interleaving_tests_van_hove_shapes_say_something(orc):
+    width = AC.check_van_hove_self_width()
+    print("self width", width)
+    # the distinct part: rMax 1 inside blobs a few units across, counts in most bins at lag 1 and at lag 3
+    import vanhove_distinct_ref as GR
+    st = AC.state("batch3x300")
+    dw, dbins = AC.VAN_HOVE_DISTINCT
+    for m, pos in enumerate(AC.oracle_lagged_positions()):
+        rad = st.final[m]["rad"] if m != 1 else st.at_mark[m]["rad"]  # (any finite radii: presence is all they decide)
+        rows = GR.table([(p, rad) for p in pos], [0, 5, 10, 15], AC.VAN_HOVE_LAGS, dw, dbins)
+        for lag in (1, 3):
+            assert sum(1 for c in rows[lag]["counts"] if c) >= dbins // 2 and rows[lag]["pairs"] > 0, (m, lag)
 
 
 def test_the_limits_the_catalogue_names_are_the_librarys():

@@ -1,34 +1,54 @@
 """GPU: the analysis layer as one session.  A batch handle serves every analysis from one scratch object
 (PbClusterScratch, csrc/pb_cluster.hpp) and a few private buffers, and every entry point re-files the bots on a grid of
 its own; the other GPU test files call each analysis on a fresh session, in one order.  Here the catalogue of
-tests/analysis_session_cases.py (54 named calls: every gap, bin count, map, vector list and frame shape at its largest
-and then at its smallest, three reads of the rearrangement mark and two entries that replace it) runs on ONE handle in
-six orders on each of three states, and every result must equal both the restatement's expectation and the result of
-the same call made alone on a fresh session brought to the state by the same recipe, bit for bit.  Around the calls
-nothing of the engine's state moves, the recorders' rings stay what a run without analyses leaves, the run counters and
-the device memory held depend on the calls made and not on their order, and a refused call leaves the session usable.
+tests/analysis_session_cases.py (60 named calls: every gap, bin count, map, vector list and frame shape at its largest
+and then at its smallest, three reads of the rearrangement mark, two entries that replace it, and the strain analysis,
+which files nothing and reads the mark's buffers, at three thresholds and per member) runs on ONE handle in six orders
+on each of three states, and every result must equal both the restatement's expectation and the result of the same call
+made alone on a fresh session brought to the state by the same recipe, bit for bit.  The same holds with a record of
+the distinct van Hove function between every two calls: the recorder files the bots itself, on a grid no call of the
+catalogue uses, and its table is that of a twin which made no analysis call.  Around the calls nothing of the engine's
+state moves, the six recorders' rings and tables stay what a run without analyses leaves, the run counters and the
+device memory held depend on the calls made and not on their order, and a refused call leaves the session usable.
 
 tests/test_analysis_session_cases_ref.py proves without a device that the orders hold every grow-then-shrink, both
-switches of the filing kind and a mark read behind five other families' re-filings.
+switches of the filing kind, a mark read behind five other families' re-filings (by a compare and by a strain call), a
+strain call directly behind every family that re-files, behind a re-mark, a compare and a displacement correlation, and
+a compare directly behind a strain call; and that the records' grid is no call's.
 
-Measured on one MI355X, this file run alone: 24 tests in 12.9 s, of which 5.8 s are the first test's setup (the process's
-first use of the device and the session's libm gate, which whichever GPU module runs first pays).  The slowest case is
-batch3x300-catalogue with 1.6 s: it computes the state's expectations and makes its 66 fresh sessions; the next state's
-first case takes 1.2 s, single17's 0.5 s, every other case and test 0.03 ... 0.35 s (a doubled shuffle of 108 calls with
-both comparisons: 0.2 s).
+Measured on one MI355X, this file run alone: 30 tests in 9.2 s.  The slowest case is batch3x300-catalogue with 1.7 s: it
+computes the state's expectations and makes its 84 fresh sessions; the next state's first case takes 1.2 s, single17's
+0.6 s.  A case with records takes 0.3 s (catalogue: 59 records) or 0.5 s (a doubled shuffle: 119 records, and the
+reference's table of 119 records of one member), every other case and test 0.03 ... 0.35 s (a doubled shuffle of 120
+calls with both comparisons: 0.2 s).
 
-The two changes the issue names were tried on a copy of the tree, and one more.  Without the memset of sCounts in
+Changes tried on a copy of the tree.  Earlier, on the catalogue of 54 calls: without the memset of sCounts in
 pbSimRadialCounts all 18 cases of test_every_order fail (a fresh buffer holds no zeros), and so do 18 tests of the
 per-analysis files, which call radial_counts twice on one handle.  With pbSimPairCorrelation skipping its filing at an
 unchanged rMax, catalogue and reversed pass and 9 shuffles fail (batch3x300-shuffle1, every shuffle of the two other
 states: a link grid of one cell hides it, which is what batch3x300_small_radii is there for); one per-analysis test
 notices too (test_gpu_correlation's shared-scratch test).  With the rearrangement compare filing on the grid edge of
-the analysis before it, batch3x300-catalogue, -shuffle0 and -shuffle1 fail and the per-analysis files stay green."""
+the analysis before it, batch3x300-catalogue, -shuffle0 and -shuffle1 fail and the per-analysis files stay green.
+On this catalogue, each run on one MI355X:
+  1. The hexatic sweep skips its filing when its gap is the one it last filed with.  The record test fails at
+     batch3x300-shuffle1 (structure(0.0019) and structure(0.05) sweep the record's grid), and so do batch3x300-shuffle1
+     and -shuffle2 of test_every_order; 27 of 30 pass, and test_gpu_structure, test_gpu_link_consumers and
+     test_gpu_vanhove_distinct stay green.  Only batch3x300 can see it: there the link grid is one cell of edge 4100
+     and the record's cells of edge 1 are too fine for it, whereas on the two other states the record's grid is coarser
+     than the link rule needs and a sweep of it still meets every neighbour.  The catalogue order never repeats a gap
+     in two consecutive hexatic calls, so it cannot take the skip at all.
+  2. strainSweep without the memset of tRows.  All 18 cases of test_every_order, all 6 cases with records and the
+     refused-call test fail, from the second strain call of a session on; 17 of 20 tests of test_gpu_strain fail too.
+  3. pbSimMarkReference leaves the old entries of dOther in place when the new mark needs no more of them.  17 cases of
+     test_every_order (all but batch3x300-reversed), all 6 cases with records and the refused-call test fail: the
+     compare of the replacing entry and the strain reads under mark C, the one directly behind the re-mark among them
+     (batch3x300-shuffle2 #48).  test_gpu_strain and test_gpu_dynamics stay green."""
 import numpy as np
 import pytest
 
 import analysis_session_cases as AC
 import geometry_cases as gc
+import vanhove_distinct_ref as GR
 from helpers import assert_bit_equal
 from test_gpu_field import live_memory
 from test_gpu_series import layout_of
@@ -39,7 +59,7 @@ f32 = np.float32
 STATE_KEYS = ("pos", "vel", "rad", "phase", "dead")
 COUNTERS = ("cluster_times", "contact_times", "structure_times", "rearrangement_times", "correlation_times",
             "field_times", "structure_factor_times", "series_times", "time_correlation_times", "scattering_times",
-            "render_stats")
+            "render_stats", "strain_times", "van_hove_times", "van_hove_distinct_times")
 VEC3 = [[1, 0], [-3, 2], [7, 5]]
 
 
@@ -98,11 +118,14 @@ def fresh(pb):
     return answers
 
 
-def run_checked(st, sim, order, answers, what, mark="A"):
-    """Every call of the order on `sim`: the failures, each naming the call, its place and the call in front of it."""
+def run_checked(st, sim, order, answers, what, mark="A", between=None):
+    """Every call of the order on `sim`: the failures, each naming the call, its place and the call in front of it.
+    between() is called between every two calls."""
     index = {e.name: i for i, e in enumerate(AC.catalogue(st))}
     failures, previous = [], "the recipe"
     for place, (e, mark_now) in enumerate(AC.walk(st, order, mark)):
+        if between and place:
+            between()
         got = e.norm(e.call(sim))
         where = f"{what} #{place} {e.name} [mark {mark_now}] behind {previous}"
         try:
@@ -135,6 +158,57 @@ def test_every_order_gives_the_answers_of_a_fresh_session(pb, fresh, name, order
         assert_is_the_state(sim, st)
     finally:
         sim.close()
+
+
+# ---- 1b. a record of the distinct van Hove function between any two calls ------------------------------------------------
+
+_REPEATED = {}
+
+
+def repeated_table(st, member, records):
+    """vanhove_distinct_ref's table of `records` records of the member's state as it is, computed once."""
+    key = (st.name, member, records)
+    if key not in _REPEATED:
+        s = st.final[member]
+        steps = AC.STEPS if st.nsims == 3 else 0
+        _REPEATED[key] = GR.table([(s["pos"], s["rad"])] * records, [steps] * records, *AC.RECORD_BETWEEN)
+    return _REPEATED[key]
+
+
+@pytest.mark.parametrize("order", ["catalogue", "shuffle1"])
+@pytest.mark.parametrize("name", AC.ALL_STATES)
+def test_a_distinct_record_between_any_two_calls_changes_no_answer(pb, fresh, name, order):
+    """The recorder files the bots itself, at rMax = 1 with perRmax = 0, on the scratch the analyses share: a call that
+    trusted the grid, the cell starts or the filed copies of the call in front of it would meet the record's."""
+    st = AC.state(name)
+    answers = fresh(name)
+    calls = AC.orders(st)[order]
+    lags, width, bins = AC.RECORD_BETWEEN
+    _, _, odd = AC.members_of(st)
+    sim, twin = AC.bring(pb, st), AC.bring(pb, st, mark=False)
+    try:
+        for s in (sim, twin):
+            s.set_van_hove_distinct(-1.0, lags, width, bins)  # manual records only
+        assert_is_the_state(sim, st)
+        failures = run_checked(st, sim, calls, answers, f"{name} {order} with records", between=sim.van_hove_distinct_record)
+        assert not failures, (len(failures), failures[:12])
+        assert_is_the_state(sim, st)
+        records = len(calls) - 1
+        for _ in range(records):  # the twin: the same records, no analysis call, not even the recipe's mark
+            twin.van_hove_distinct_record()
+        assert sim.van_hove_distinct_info() == twin.van_hove_distinct_info()
+        assert sim.van_hove_distinct_info() == {"interval": -1.0, "lags": lags, "width": width, "bins": bins,
+                                                "records": records}
+        assert sim.van_hove_distinct_times()[0] == records and twin.strain_times()[0] == twin.cluster_times()[0] == 0
+        got, alone = sim.van_hove_distinct(), twin.van_hove_distinct()
+        assert AC.same_bits(got, alone)
+        assert got[odd] == repeated_table(st, odd, records)
+        for m, rows in enumerate(got):
+            assert [r["origins"] for r in rows] == [records, records - 1], m
+            assert rows[1]["pairs"] > 0 and sum(1 for c in rows[1]["counts"] if c) > 1, (m, rows[1])
+    finally:
+        sim.close()
+        twin.close()
 
 
 # ---- 2. nothing changes ------------------------------------------------------------------------------------------------
@@ -183,6 +257,8 @@ def test_recorders_run_through_interleaved_analyses(pb):
             sim.set_series(0.05, 16)
             sim.set_time_correlation(0.05, 4, 0.5)
             sim.set_scattering(0.05, 4, AC.SK_BOX, VEC3)
+            sim.set_van_hove(AC.VAN_HOVE_INTERVAL, AC.VAN_HOVE_LAGS, AC.van_hove_self_width(), AC.VAN_HOVE_BINS)
+            sim.set_van_hove_distinct(AC.VAN_HOVE_INTERVAL, AC.VAN_HOVE_LAGS, *AC.VAN_HOVE_DISTINCT)
             sim.set_centroid_trail(True)
             for chunk in range(4):
                 assert sim.step(10, dt=AC.DT, sort_interval=AC.SORT_INTERVAL) == 10
@@ -191,9 +267,13 @@ def test_recorders_run_through_interleaved_analyses(pb):
                 if chunk == 1:
                     sim.time_correlation_record()
                     sim.scattering_record()
+                    sim.van_hove_record()
+                    sim.van_hove_distinct_record()
             return {"series": [sim.series_of(m) for m in range(st.nsims)], "series_info": sim.series_info(),
                     "time_correlation": sim.time_correlation(), "time_correlation_info": sim.time_correlation_info(),
                     "scattering": sim.scattering(), "scattering_info": sim.scattering_info(),
+                    "van_hove": sim.van_hove(), "van_hove_info": sim.van_hove_info(),
+                    "van_hove_distinct": sim.van_hove_distinct(), "van_hove_distinct_info": sim.van_hove_distinct_info(),
                     "trail": [sim.centroid_trail(m) for m in range(st.nsims)],
                     "states": [sim.get_state_of(m) for m in range(st.nsims)], "stats": sim.stats(), "time": sim.time,
                     "phase_draws": sim.phase_draws}, counters(sim)
@@ -203,15 +283,21 @@ def test_recorders_run_through_interleaved_analyses(pb):
     (got, ran), (want, idle) = run(True), run(False)
     # the analyses ran in between, three doubled shuffles of them; the twin made none beyond the recipe's mark
     assert ran["correlation_times"] == 3 * 2 * 9 and ran["field_times"] == 3 * 2 * 6 and ran["render_stats"] == 3 * 2 * 3
-    assert ran["cluster_times"] > 0 and ran["rearrangement_times"] > 1
+    assert ran["cluster_times"] > 0 and ran["rearrangement_times"] > 1 and ran["strain_times"] == 3 * 2 * 6
     assert [idle[k] for k in COUNTERS[:7]] == [0, 0, 0, 1, 0, 0, 0] and idle["render_stats"] == 0
+    assert idle["strain_times"] == 0
     assert ran["series_times"] == idle["series_times"] and ran["scattering_times"] == idle["scattering_times"]
     assert ran["time_correlation_times"] == idle["time_correlation_times"]
+    assert ran["van_hove_times"] == idle["van_hove_times"] >= 5
+    assert ran["van_hove_distinct_times"] == idle["van_hove_distinct_times"] == idle["van_hove_times"]
     # the twin recorded something: rows while stepping, both manual records, a trail slot per member
     assert want["series_info"]["records"] >= 4 and len(want["series"][1]) == want["series_info"]["records"]
     assert want["time_correlation_info"]["records"] >= 5 and want["scattering_info"]["records"] >= 5
     assert all(rec >= 1 for _, _, rec in want["trail"])
     assert want["time_correlation"][0][1]["samples"] > 0 and want["scattering"][2][1][1]["samples"] > 0
+    assert want["van_hove_info"]["records"] == want["van_hove_distinct_info"]["records"] >= 5
+    for m in (0, 2):  # (nothing planted there) the ring of four lags wrapped, and both tables hold counts at its last lag
+        assert sum(want["van_hove"][m][3]["radial"]) > 0 and want["van_hove_distinct"][m][3]["pairs"] > 0, m
     for key in want:
         assert AC.same_bits(got[key], want[key]), key
 
@@ -247,9 +333,11 @@ def test_counters_and_memory_do_not_depend_on_the_order(pb, name):
     assert once["cluster_times"] > 0 and once["contact_times"] > 0 and once["structure_times"] > 0
     assert once["rearrangement_times"] > 0 and once["correlation_times"] == 9 and once["field_times"] == 6
     assert once["structure_factor_times"] == 6 and once["render_stats"] == 3
+    assert once["strain_times"] == sum(1 for e in AC.catalogue(st) if e.family == "strain") == 6
     assert once["series_times"] == once["time_correlation_times"] == once["scattering_times"] == 0
+    assert once["van_hove_times"] == once["van_hove_distinct_times"] == 0
     assert runs["reversed"] == once
-    for k in range(4):
+    for k in range(AC.SHUFFLES):
         assert runs[f"shuffle{k}"] == {key: 2 * v for key, v in once.items()}, k
     assert held["catalogue"][0] > start[0] and held["catalogue"][1] > start[1]
     for order_name in AC.ORDERS:
@@ -305,6 +393,8 @@ def test_a_refused_call_in_the_middle_leaves_the_session_usable(pb, fresh):
                                                         lambda: sim.structure_factor(VEC3, AC.SK_BOX, member=3))]),
             ("rearrangement()", [("code 2.*pbSimRearrangementOf.*member out of range", lambda: sim.rearrangement_of(3)),
                                  ("code 2.*pbSimMarkReference.*linkGap", lambda: sim.mark_reference(-1.0))]),
+            ("strain(0.0)", [("code 2.*pbSimStrainStats.*d2Threshold", lambda: sim.strain(-1.0)),
+                             ("code 2.*pbSimStrainOf.*member out of range", lambda: sim.strain_of(3))]),
         ):
             good(name)
             refused(*refusals[0])
@@ -314,12 +404,13 @@ def test_a_refused_call_in_the_middle_leaves_the_session_usable(pb, fresh):
         # a refused mark is refused before it touches the one held
         assert sim.reference_info()["marked"] and sim.reference_info()["gap"] == float(f32(AC.MARKS["A"]))
         sim.clear_reference()
-        for call in (sim.rearrangement, sim.rearrangement_of, lambda: sim.pair_correlation("displacement", 0.4, 7)):
+        for call in (sim.rearrangement, sim.rearrangement_of, lambda: sim.pair_correlation("displacement", 0.4, 7),
+                     sim.strain, sim.strain_of):
             refused("code 2.*no reference marked", call)
         refused("code 2.*pbSimGetColorsOf", lambda: sim.colors(3))
         # nothing refused was counted; every good call was
         after = counters(sim)
-        for name in ("rearrangement_times", "correlation_times", "field_times", "structure_factor_times"):
+        for name in ("rearrangement_times", "correlation_times", "field_times", "structure_factor_times", "strain_times"):
             assert after[name] == before[name] + 3, (name, before, after)
         # the whole catalogue behind all that: every family still gives its fresh-session answer; the mark is gone until
         # an entry takes a new one, so the three reads and the displacement correlations come behind the two that do

@@ -13,6 +13,8 @@ import scatter_ref as XR
 import series_ref as SR
 import test_late_clock_ref as LC
 import timecorr_ref as TR
+import vanhove_distinct_ref as DR
+import vanhove_ref as VR
 from helpers import assert_bit_equal, simparams_from_orc
 from test_gpu_series import reference_rows
 from test_late_clock_ref import DT, LATE, MARKS, NEGATIVE, PUI, REC, SORT, STANDING, STEPS, bits, clock, firing
@@ -123,9 +125,20 @@ def test_parity_with_a_payload_and_obstacles_from_16383_9(pb, orc, form):
 
 # ---- records late ----------------------------------------------------------------------------------------------------
 
-TRAIL = dict(centroid_int=0.2, centroid_steps=8)
-LAGS, OVERLAP = 8, 0.05
-SCAT, SCAT_BOX = 0.07, 3  # the scattering's own interval, no multiple of REC: its gate steps are not the others'
+TRAIL = LC.RECORD_TRAIL
+LAGS, OVERLAP = LC.RECORD_LAGS, 0.05
+SCAT, SCAT_BOX = LC.SCAT, 3  # the scattering's own interval, no multiple of REC: its gate steps are not the others'
+_VAN_HOVE = {}
+
+
+def expected_van_hove(t0, at, rec, srec):
+    """(self table on the REC gate, distinct table on the SCAT gate) from the twin's states; both stepping paths leave
+    the same states, so the second path at a start time reuses the first one's tables."""
+    states = b"".join(at[k][1][key].tobytes() for k in sorted(set(rec) | set(srec)) for key in ("pos", "rad"))
+    if _VAN_HOVE.get(t0, (None,))[0] != states:
+        _VAN_HOVE[t0] = (states, VR.table([at[k][1]["pos"] for k in rec], rec, LAGS, *LC.VAN_HOVE_SELF),
+                         DR.table([(at[k][1]["pos"], at[k][1]["rad"]) for k in srec], srec, LAGS, *LC.VAN_HOVE_DISTINCT))
+    return _VAN_HOVE[t0][1:]
 
 
 def expected_trail(recs, pos_of, slots):
@@ -141,7 +154,7 @@ def expected_trail(recs, pos_of, slots):
 
 
 @pytest.mark.parametrize("resident", [1, 2], ids=["per_step", "resident"])
-@pytest.mark.parametrize("t0", [16383.9, 65535.9])
+@pytest.mark.parametrize("t0", LC.RECORD_T0)
 def test_records_from_a_late_start(pb, orc, t0, resident):
     gates = SR.gate_steps(t0, DT, REC, STEPS, 1e9)
     rec = [k for k, _ in gates]
@@ -167,6 +180,8 @@ def test_records_from_a_late_start(pb, orc, t0, resident):
     a.set_series(REC, 512)
     a.set_time_correlation(REC, LAGS, OVERLAP)
     a.set_scattering(SCAT, LAGS, SCAT_BOX, vectors)
+    a.set_van_hove(REC, LAGS, *LC.VAN_HOVE_SELF)
+    a.set_van_hove_distinct(SCAT, LAGS, *LC.VAN_HOVE_DISTINCT)
     a.set_centroid_trail(True)
     assert a.step(STEPS, dt=DT, sort_interval=SORT) == STEPS  # one call
     # the twin, nothing switched on, stopped in front of every step at which a records something
@@ -186,6 +201,11 @@ def test_records_from_a_late_start(pb, orc, t0, resident):
     assert a.time_correlation()[0] == want
     assert a.scattering_info()["records"] == len(srec)
     assert a.scattering()[0] == XR.table([at[k][1]["pos"] for k in srec], srec, LAGS, vectors, SCAT_BOX)
+    want_self, want_distinct = expected_van_hove(t0, at, rec, srec)
+    assert a.van_hove_info()["records"] == len(rec) and a.van_hove_distinct_info()["records"] == len(srec)
+    assert a.van_hove()[0] == want_self
+    assert a.van_hove_distinct()[0] == want_distinct
+    assert sum(want_self[LAGS - 1]["radial"][1:]) > 0 and want_distinct[LAGS - 1]["pairs"] > 0
     xy, times, records = a.centroid_trail()
     want_xy, want_t, want_n = expected_trail(trail, lambda k: at[k][1]["pos"], TRAIL["centroid_steps"])
     assert records == want_n == len(trail)

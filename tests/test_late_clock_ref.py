@@ -70,6 +70,16 @@ def dump_due(t, interval):
     return not bool(f32(t - f32(interval * np.floor(f32(t / interval)))) > f32(0.01))
 
 
+# the lagged recorders of the late records test: the lags, the scattering's own interval (no multiple of REC: its gate
+# steps are not the others'), the trail, and the shapes of the two van Hove functions, picked from the oracle's states
+# (test_van_hove_shapes_hold_counts_late asserts what they are picked for).  Static friction holds most of the 300 bots
+# between two records; those that move cover 0.0004 (the 90th percentile) to 0.02 in one record and up to 0.033 in seven,
+# so 16 bins of 2^-9 reach 0.031.  The nearest bots are 0.11 apart, a tenth of the pairs within 0.6: 8 bins of 1/16.
+RECORD_LAGS, SCAT = 8, 0.07
+RECORD_TRAIL = dict(centroid_int=0.2, centroid_steps=8)
+RECORD_T0 = (16383.9, 65535.9)
+VAN_HOVE_SELF = (2.0 ** -9, 16)       # (width, bins), on the REC gate
+VAN_HOVE_DISTINCT = (1.0 / 16, 8)     # on the SCAT gate
 NEG_TRAIL = dict(centroid_int=0.02, centroid_steps=8)  # the trail of the negative clock's case
 DEAD_AT = 16384.5                                      # time_to_dead of the case whose bots die late
 
@@ -210,3 +220,40 @@ def test_oracle_stops_where_the_replay_says(orc):
         done += 1
     assert done == steps_run(STOP_T0, STEPS, STOP_MAX_TIME)
     assert bits(osim.time) == bits(clock(STOP_T0, STEPS, STOP_MAX_TIME)[-1])
+
+
+# ---- the van Hove shapes of the late records test -------------------------------------------------------------------
+
+def oracle_records(orc, t0, steps_wanted):
+    """The oracle's (pos, rad) in front of each of the steps named, from t0 with the late records test's parameters."""
+    osim = late_oracle(orc, late_params(orc, **RECORD_TRAIL), t0)
+    wanted, at = set(steps_wanted), {}
+    for k in range(STEPS):
+        if k in wanted:
+            at[k] = (osim.get("pos"), osim.get("rad"))
+        assert osim.update(DT, SORT) == 0
+    osim.close()
+    return at
+
+
+@pytest.mark.parametrize("t0", RECORD_T0)
+def test_van_hove_shapes_hold_counts_late(orc, t0):
+    """Both tables of the late records test, from the oracle's states at the gates' steps: counts in at least two bins
+    at lag 1 and at the last lag, displacements and pairs beyond the last edge as well, and radii that stay finite (the
+    distinct part counts a bot as present by them)."""
+    import vanhove_distinct_ref as DR
+    import vanhove_ref as VR
+    rec, srec = firing(t0, REC), firing(t0, SCAT)
+    assert len(rec) > RECORD_LAGS and len(srec) > RECORD_LAGS and consecutive(rec) >= 16
+    at = oracle_records(orc, t0, rec + srec)
+    assert all(np.isfinite(p).all() and np.isfinite(r).all() for p, r in at.values())
+    self_rows = VR.table([at[k][0] for k in rec], rec, RECORD_LAGS, *VAN_HOVE_SELF)
+    pair_rows = DR.table([at[k] for k in srec], srec, RECORD_LAGS, *VAN_HOVE_DISTINCT)
+    for lag in (1, RECORD_LAGS - 1):
+        row, pairs = self_rows[lag], pair_rows[lag]
+        print(t0, lag, row["radial"], row["beyond_r"], pairs["counts"], pairs["pairs"])
+        assert VR.identities_hold(row) and row["origins"] == len(rec) - lag and row["samples"] == 300 * row["origins"]
+        assert sum(1 for c in row["radial"] if c) >= 2 and sum(row["radial"][1:]) > 0, (t0, lag, row)
+        assert sum(1 for c in pairs["counts"] if c) >= 2 and pairs["origins"] == len(srec) - lag, (t0, lag, pairs)
+        assert 0 < pairs["pairs"] < pairs["centres"] * 299  # the range leaves most pairs out
+    assert self_rows[RECORD_LAGS - 1]["beyond_r"] > 0
