@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
+from . import _analysis, _capi
+from ._analysis import van_hove_distinct_lists, van_hove_lists  # noqa: F401
 from ._capi import SimParams, make_params, pbSimConfig, pbSimStats  # noqa: F401
 
 __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params", "library_paths", "self_test",
@@ -49,10 +50,7 @@ def structure_factor_values(rows):
     rows = np.asarray(rows)
     out = {name: rows[name] for name in ("nx", "ny", "measured")}
     for name in ("re", "im", "re2", "im2"):
-        flat = [(int(h) << 32) + int(l) for h, l in zip(rows[name + "_hi"].reshape(-1), rows[name + "_lo"].reshape(-1))]
-        big = np.empty(len(flat), object)
-        big[:] = flat
-        out[name] = big.reshape(rows.shape)
+        out[name] = _capi.compose_128(rows, name)
     s = [float(Fraction(re * re + im * im, int(m) << 60)) if m else float("nan")
          for re, im, m in zip(out["re"].reshape(-1), out["im"].reshape(-1), rows["measured"].reshape(-1))]
     out["s"] = np.array(s, np.float64).reshape(rows.shape)
@@ -169,37 +167,6 @@ def van_hove_summary(row, width):
             "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else nan}
 
 
-def van_hove_lists(rows, counts, nsims, lags, bins):
-    """The rows and counters of pbSimGetVanHove as van_hove() returns them: per member a list over lags of dicts, each
-    van_hove_row() plus radial (bins ints), x and y (2 bins ints each)."""
-    out = []
-    for m in range(nsims):
-        member = []
-        for l in range(lags):
-            g = m * lags + l
-            c = [int(v) for v in counts[g * 5 * bins:(g + 1) * 5 * bins]]
-            d = _capi.van_hove_row(rows[g])
-            d["radial"], d["x"], d["y"] = c[:bins], c[bins:3 * bins], c[3 * bins:]
-            member.append(d)
-        out.append(member)
-    return out
-
-
-def van_hove_distinct_lists(rows, counts, nsims, lags, bins):
-    """The rows and counters of pbSimGetVanHoveDistinct as van_hove_distinct() returns them: per member a list over lags
-    of dicts, each van_hove_distinct_row() plus counts (bins ints)."""
-    out = []
-    for m in range(nsims):
-        member = []
-        for l in range(lags):
-            g = m * lags + l
-            d = _capi.van_hove_distinct_row(rows[g])
-            d["counts"] = [int(v) for v in counts[g * bins:(g + 1) * bins]]
-            member.append(d)
-        out.append(member)
-    return out
-
-
 def field_values(cells):
     """The cells of field_map() as a dict of arrays of the cells' shape: count, dead, sum_qr, sum_wx, sum_wy as they are,
     and rr, vv as object arrays of Python ints composed from their 128 bits (hi * 2^32 + lo).  The sums are in units of
@@ -207,10 +174,7 @@ def field_values(cells):
     cells = np.asarray(cells)
     out = {name: cells[name] for name in ("count", "dead", "sum_qr", "sum_wx", "sum_wy")}
     for name in ("rr", "vv"):
-        flat = [(int(h) << 32) + int(l) for h, l in zip(cells[name + "_hi"].reshape(-1), cells[name + "_lo"].reshape(-1))]
-        big = np.empty(len(flat), object)
-        big[:] = flat
-        out[name] = big.reshape(cells.shape)
+        out[name] = _capi.compose_128(cells, name)
     return out
 
 
@@ -222,7 +186,7 @@ def correlation_values(rows):
         raise ValueError("correlation_values: the rows of one member, shaped (bins,)")
     out = {"pairs": [int(v) for v in rows["pairs"]]}
     for name in ("dot", "ax", "ay"):
-        out[name] = [(int(h) << 32) + int(l) for h, l in zip(rows[name + "_hi"], rows[name + "_lo"])]
+        out[name] = list(_capi.compose_128(rows, name))
     return out
 
 
@@ -291,45 +255,40 @@ def self_test(div_samples=1 << 32):
     return {k: int(v.value) for k, v in zip(keys, vals)}
 
 
+def _self_test(symbol, *args):
+    """A self test of the (checked, mismatches) kind: the counts `symbol` writes after `args`, as a dict."""
+    checked, bad = C.c_ulonglong(), C.c_ulonglong()
+    _capi.check(getattr(_capi.lib(), symbol)(*args, C.byref(checked), C.byref(bad)), symbol)
+    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+
+
 def self_test_hold_threshold(c):
     """pbSelfTestHoldThreshold: `sqrtf(x) < c` against `x < T(c)` on the GPU for every non-negative float x."""
-    checked, bad = C.c_ulonglong(), C.c_ulonglong()
-    _capi.check(_capi.lib().pbSelfTestHoldThreshold(float(c), C.byref(checked), C.byref(bad)), "pbSelfTestHoldThreshold")
-    return {"checked": checked.value, "mismatches": bad.value}
+    return _self_test("pbSelfTestHoldThreshold", float(c))
 
 
 def self_test_magnitude_root():
     """pbSelfTestMagnitudeRoot: the unclamped one-Newton-step root of the both-sums form's attraction magnitude
     against sqrtf on the GPU for every float of [2^-96, FLT_MAX)."""
-    checked, bad = C.c_ulonglong(), C.c_ulonglong()
-    _capi.check(_capi.lib().pbSelfTestMagnitudeRoot(C.byref(checked), C.byref(bad)), "pbSelfTestMagnitudeRoot")
-    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+    return _self_test("pbSelfTestMagnitudeRoot")
 
 
 def self_test_term_root():
     """pbSelfTestTermRoot: the both-sums form's in-trip root of a pair term's squared magnitude (contact terms
     included) on the GPU for all 2^32 bit patterns: guarded to sqrtf, or bit-equal to sqrtf."""
-    checked, bad = C.c_ulonglong(), C.c_ulonglong()
-    _capi.check(_capi.lib().pbSelfTestTermRoot(C.byref(checked), C.byref(bad)), "pbSelfTestTermRoot")
-    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+    return _self_test("pbSelfTestTermRoot")
 
 
 def self_test_pair_geometry(first_slice=0, slices=64):
     """pbSelfTestPairGeometry: pbDistUnitFast against sqrtf and IEEE division on EVERY (d2, numerator)
     mantissa pair of `slices` of the 64 slices of d2 in [1, 4) (all 64: 2^47 pairs, ~90 s of one MI355X)."""
-    checked, bad = C.c_ulonglong(), C.c_ulonglong()
-    _capi.check(_capi.lib().pbSelfTestPairGeometry(int(first_slice), int(slices), C.byref(checked), C.byref(bad)),
-                "pbSelfTestPairGeometry")
-    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+    return _self_test("pbSelfTestPairGeometry", int(first_slice), int(slices))
 
 
 def self_test_division(first_slice=0, slices=64):
     """pbSelfTestDivision: pbDiv2Fast against IEEE division on EVERY (denominator, numerator) mantissa pair of
     `slices` of the 64 slices of the denominator range (all 64: 2^46 quotients)."""
-    checked, bad = C.c_ulonglong(), C.c_ulonglong()
-    _capi.check(_capi.lib().pbSelfTestDivision(int(first_slice), int(slices), C.byref(checked), C.byref(bad)),
-                "pbSelfTestDivision")
-    return {"checked": int(checked.value), "mismatches": int(bad.value)}
+    return _self_test("pbSelfTestDivision", int(first_slice), int(slices))
 
 
 def force_forms():
@@ -340,7 +299,7 @@ def force_forms():
     for i in range(L.pbForceFormCount()):
         f = _capi.pbForceForm()
         _capi.check(L.pbForceFormGet(i, C.byref(f)), "pbForceFormGet")
-        out.append({k: int(getattr(f, k)) for k, _ in _capi.pbForceForm._fields_})
+        out.append(_capi.row_dict(f))
     return out
 
 
@@ -468,6 +427,11 @@ class ClockSample:
 class Sim:
     """One resident simulation on the current GPU (pbSim* in include/particlebot_hip.h)."""
 
+    nsims = 1  # members in the batch (an Ensemble has its own count)
+    # a member's state, in pbSimGetStateOf's order: name -> (dtype, values per bot)
+    _STATE = {"pos": (np.float32, 2), "vel": (np.float32, 2), "rad": (np.float32, 1), "phase": (np.float32, 1),
+              "dead": (np.int32, 1), "absForce_a": (np.float32, 1), "absForce_r": (np.float32, 1)}
+
     def __init__(self, params, wall_half=0.0, keepalive=None):
         self._keep = keepalive
         self.params = params
@@ -495,43 +459,44 @@ class Sim:
         assert a.size == count, (a.size, count)
         return a
 
+    def _put(self, symbol, member, what, **arrays):
+        """Upload arrays of one member's state (original bot order; None leaves an array as it is) through `symbol`,
+        which takes them in the order given; `what` names the call in an error."""
+        held = [self._in(a, self._STATE[k][0], self._STATE[k][1] * self.n) for k, a in arrays.items()]
+        _capi.check(getattr(_capi.lib(), symbol)(self._h, int(member), *[_capi.np_ptr(a) for a in held]), what)
+
+    def _get_state_of(self, member, out, what):
+        """One member's state into `out` (None: a new dict); an array `out` lacks is made."""
+        out = {} if out is None else out
+        for k, (dtype, width) in self._STATE.items():
+            if out.get(k) is None:
+                out[k] = np.empty((self.n, width) if width > 1 else self.n, dtype)
+        _capi.check(_capi.lib().pbSimGetStateOf(self._h, int(member), *[_capi.np_ptr(out[k]) for k in self._STATE]),
+                    what)
+        if not self.config()["attraction_sums"]:
+            out["absForce_a"] = None  # a dead value in this batch: not maintained (set_force_sums)
+        return out
+
     def set_state(self, pos=None, vel=None, rad=None, phase=None, dead=None):
-        n = self.n
-        pos = self._in(pos, np.float32, 2 * n)
-        vel = self._in(vel, np.float32, 2 * n)
-        rad = self._in(rad, np.float32, n)
-        phase = self._in(phase, np.float32, n)
-        dead = self._in(dead, np.int32, n)
-        _capi.check(_capi.lib().pbSimSetState(self._h, _capi.np_ptr(pos), _capi.np_ptr(vel), _capi.np_ptr(rad),
-                                              _capi.np_ptr(phase), _capi.np_ptr(dead)), "pbSimSetState")
+        self._put("pbSimSetStateOf", 0, "pbSimSetState", pos=pos, vel=vel, rad=rad, phase=phase, dead=dead)
 
     def set_forces(self, absForce_a, absForce_r):
         """Overwrite absForce_a / absForce_r (original bot order): the two arrays the next step's
         radius actuation reads.  With set_state this restores a complete mid-run state."""
-        n = self.n
-        a, r = self._in(absForce_a, np.float32, n), self._in(absForce_r, np.float32, n)
-        _capi.check(_capi.lib().pbSimSetForcesOf(self._h, 0, _capi.np_ptr(a), _capi.np_ptr(r)), "pbSimSetForcesOf")
+        self._put("pbSimSetForcesOf", 0, "pbSimSetForcesOf", absForce_a=absForce_a, absForce_r=absForce_r)
 
     def get_state(self, out=None):
         """The state in original bot order.  `out`: a dict returned by an earlier call, whose arrays are then
         written in place (a caller that reads back often keeps its host buffers: fresh pages cost more than
         the copy)."""
-        n = self.n
-        if out is None:
-            out = {
-                "pos": np.empty((n, 2), np.float32), "vel": np.empty((n, 2), np.float32),
-                "rad": np.empty(n, np.float32), "phase": np.empty(n, np.float32),
-                "dead": np.empty(n, np.int32), "absForce_a": np.empty(n, np.float32),
-                "absForce_r": np.empty(n, np.float32),
-            }
-        elif out.get("absForce_a") is None:
-            out["absForce_a"] = np.empty(n, np.float32)
-        _capi.check(_capi.lib().pbSimGetState(self._h, *[_capi.np_ptr(out[k]) for k in
-                                                         ("pos", "vel", "rad", "phase", "dead",
-                                                          "absForce_a", "absForce_r")]), "pbSimGetState")
-        if not self.config()["attraction_sums"]:
-            out["absForce_a"] = None  # a dead value in this batch: not maintained (set_force_sums)
-        return out
+        return self._get_state_of(0, out, "pbSimGetState")
+
+    # (per member, as every analysis takes `member`: a Sim is a batch of one, so anything that has nsims has these)
+    def set_state_of(self, member, pos=None, vel=None, rad=None, phase=None, dead=None):
+        self._put("pbSimSetStateOf", member, "pbSimSetStateOf", pos=pos, vel=vel, rad=rad, phase=phase, dead=dead)
+
+    def get_state_of(self, member):
+        return self._get_state_of(member, None, "pbSimGetStateOf")
 
     @property
     def time(self):
@@ -584,14 +549,14 @@ class Sim:
     def stats(self):
         s = pbSimStats()
         _capi.check(_capi.lib().pbSimGetStats(self._h, C.byref(s)))
-        return {k: int(getattr(s, k)) for k, _ in pbSimStats._fields_}
+        return _capi.row_dict(s)
 
     def config(self):
         """What the next step() launches: force_variant / force_kind / lanes_per_bot / resident /
         fast_math_ok / payload / rng (pbSimGetConfig)."""
         c = pbSimConfig()
         _capi.check(_capi.lib().pbSimGetConfig(self._h, C.byref(c)))
-        return {k: int(getattr(c, k)) for k, _ in pbSimConfig._fields_}
+        return _capi.row_dict(c)
 
     def force_kernel_name(self):
         """The per-step force kernel the next step() launches, as rocprofv3 names it (pbSimForceKernelName)."""
@@ -673,49 +638,40 @@ class Sim:
         _capi.check(_capi.lib().pbSimRenderOf(self._h, int(member), C.byref(view), _capi.np_ptr(out)), "pbSimRenderOf")
         return out
 
-    def render_stats(self):
-        """(frames rendered, device milliseconds of the last frame's launches)."""
+    def _span(self, symbol):
+        """(count so far, device milliseconds of the last one) as the span clock behind `symbol` holds them."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetRenderStats(self._h, C.byref(n), C.byref(ms)), "pbSimGetRenderStats")
+        _capi.check(getattr(_capi.lib(), symbol)(self._h, C.byref(n), C.byref(ms)), symbol)
         return int(n.value), float(ms.value)
 
+    def render_stats(self):
+        """(frames rendered, device milliseconds of the last frame's launches)."""
+        return self._span("pbSimGetRenderStats")
 
     def clusters(self, gap=0.0):
         """Cluster analysis of every member's state as it is now, on the device (pbSimClusterStats): a list of dicts
         (clusters, largest, largest_label, isolated, links, max_degree, rounds), one per member."""
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbClusterStats * nsims)()
+        rows = (_capi.pbClusterStats * self.nsims)()
         _capi.check(_capi.lib().pbSimClusterStats(self._h, float(gap), rows), "pbSimClusterStats")
-        return [{name: int(getattr(r, name)) for name, _ in _capi.pbClusterStats._fields_} for r in rows]
+        return [_capi.row_dict(r) for r in rows]
 
     def cluster_labels(self, gap=0.0, member=0):
         """(labels, degree) of one member: uint32 arrays in original bot order (pbSimClusterLabelsOf)."""
-        labels, degree = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
-        _capi.check(_capi.lib().pbSimClusterLabelsOf(self._h, int(member), float(gap), _capi.np_ptr(labels),
-                                                     _capi.np_ptr(degree)), "pbSimClusterLabelsOf")
-        return labels, degree
+        out = _analysis.per_bot(_analysis.CLUSTER_LABELS, self.n, lambda *p: _capi.check(
+            _capi.lib().pbSimClusterLabelsOf(self._h, int(member), float(gap), *p), "pbSimClusterLabelsOf"))
+        return out["labels"], out["degree"]
 
     def cluster_times(self):
         """(analyses run so far, device milliseconds of the last one)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetClusterTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetClusterTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetClusterTimes")
 
     def contacts(self, gap=0.0, member=0):
         """The contact network of one member's state as it is now, from the device (pbSimContactsOf): a dict with
         offsets (uint32, n + 1: a CSR adjacency in original bot order, ascending `other` per bot), other (uint32, E),
         gap (float32, E: dist - (ri + rj), negative in contact) and force (float32, E x 2: the pair law's force ON the
         owning bot FROM other).  Every undirected link appears twice, once under each end."""
-        L = _capi.lib()
-        count = C.c_ulonglong(0)
-        _capi.check(L.pbSimContactsOf(self._h, int(member), float(gap), None, None, 0, C.byref(count)),
-                    "pbSimContactsOf")
-        offsets = np.empty(self.n + 1, np.uint32)
-        links = np.empty(int(count.value), _capi.CONTACT_LINK_DTYPE)
-        _capi.check(L.pbSimContactsOf(self._h, int(member), float(gap), _capi.np_ptr(offsets), _capi.np_ptr(links),
-                                      links.size, C.byref(count)), "pbSimContactsOf")
-        return {"offsets": offsets, "other": links["other"].copy(), "gap": links["gap"].copy(),
-                "force": np.stack([links["fx"], links["fy"]], axis=1)}
+        return _analysis.contacts(self.n, lambda *a: _capi.check(
+            _capi.lib().pbSimContactsOf(self._h, int(member), float(gap), *a), "pbSimContactsOf"))
 
     def contact_virial(self, gap=0.0, member=0):
         """Per-bot virial of one member's contact network (pbSimContactVirialOf): float64, n x 4, the columns
@@ -727,16 +683,13 @@ class Sim:
 
     def contact_times(self):
         """(exports run so far, device milliseconds of the last one)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetContactTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetContactTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetContactTimes")
 
     def radial_counts(self, r_max, bins, member=None):
         """Radial pair counts of every member's state as it is now, on the device (pbSimRadialCounts): uint64,
         (nsims, bins), or (bins,) for one member.  The ordered pair (i, j) is in bin int(dist * (float32(bins) / r_max))
         in fp32; every count is even.  radial_distribution() turns them into g(r)."""
-        nsims = int(getattr(self, "nsims", 1))
-        out = np.zeros((nsims, int(bins)), np.uint64)
+        out = np.zeros((self.nsims, int(bins)), np.uint64)
         _capi.check(_capi.lib().pbSimRadialCounts(self._h, float(r_max), int(bins), _capi.np_ptr(out)),
                     "pbSimRadialCounts")
         return out if member is None else out[int(member)]
@@ -745,24 +698,20 @@ class Sim:
         """Hexatic order of every member's state as it is now, on the device (pbSimStructureStats): a list of dicts, one
         per member: bonds (directed), psi6_re / psi6_im (sums in units of 2^-30), coordination (bots with 0..6 and 7 or
         more neighbours) and psi6, the complex mean over the bonds.  Bonds are the cluster analysis' links for `gap`."""
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbStructureStats * nsims)()
+        rows = (_capi.pbStructureStats * self.nsims)()
         _capi.check(_capi.lib().pbSimStructureStats(self._h, float(gap), rows), "pbSimStructureStats")
         return [_capi.structure_row(r) for r in rows]
 
     def hexatic(self, gap=0.0, member=0):
         """(psi6, neighbours) of one member: complex128[n] and uint32[n] in original bot order (pbSimHexaticOf); psi6 of
         a bot is the mean of e^(6 i theta) over its bonds, 0 without neighbours."""
-        psi, nb = np.empty(self.n, np.complex128), np.empty(self.n, np.uint32)
-        _capi.check(_capi.lib().pbSimHexaticOf(self._h, int(member), float(gap), _capi.np_ptr(psi), _capi.np_ptr(nb)),
-                    "pbSimHexaticOf")
-        return psi, nb
+        out = _analysis.per_bot(_analysis.HEXATIC, self.n, lambda *p: _capi.check(
+            _capi.lib().pbSimHexaticOf(self._h, int(member), float(gap), *p), "pbSimHexaticOf"))
+        return out["psi6"], out["neighbours"]
 
     def structure_times(self):
         """(structure analyses run so far, device milliseconds of the last one)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetStructureTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetStructureTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetStructureTimes")
 
     def mark_reference(self, gap=0.0):
         """Keep every member's positions and link network at `gap` on the device as the reference that rearrangement()
@@ -788,28 +737,19 @@ class Sim:
         bots_unchanged / bots_lost / bots_gained, measured, sum_qx / sum_qy (displacement sums, units of 2^-20), sum_q2
         (the sum of squared displacements as one Python int, units of 2^-40) and max_q2.  mean_squared_displacement()
         turns a row into the MSD."""
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbRearrangementStats * nsims)()
+        rows = (_capi.pbRearrangementStats * self.nsims)()
         _capi.check(_capi.lib().pbSimRearrangementStats(self._h, rows), "pbSimRearrangementStats")
         return [_capi.rearrangement_row(r) for r in rows]
 
     def rearrangement_of(self, member=0):
         """One member per bot, original order (pbSimRearrangementOf): a dict of disp (float32, n x 2: dx, dy since the
         mark, verbatim) and marked, now, kept (uint32: the bot's links at the mark, now, and in both)."""
-        n = self.n
-        out = {"disp": np.empty((n, 2), np.float32), "marked": np.empty(n, np.uint32), "now": np.empty(n, np.uint32),
-               "kept": np.empty(n, np.uint32)}
-        _capi.check(_capi.lib().pbSimRearrangementOf(self._h, int(member), *[_capi.np_ptr(out[k]) for k in
-                                                                            ("disp", "marked", "now", "kept")]),
-                    "pbSimRearrangementOf")
-        return out
+        return _analysis.per_bot(_analysis.REARRANGEMENT_OF, self.n, lambda *p: _capi.check(
+            _capi.lib().pbSimRearrangementOf(self._h, int(member), *p), "pbSimRearrangementOf"))
 
     def rearrangement_times(self):
         """(marks and compares run so far, device milliseconds of the last one)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetRearrangementTimes(self._h, C.byref(n), C.byref(ms)),
-                    "pbSimGetRearrangementTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetRearrangementTimes")
 
     def strain(self, threshold=0.0):
         """Every member's local strain and non-affine displacement against the mark, on the device (pbSimStrainStats):
@@ -817,36 +757,29 @@ class Sim:
         above (fitted bots with D2min > threshold, in world units squared), bonds_used / bonds_dropped, the sums yxx,
         yxy, yyy, xxx, xxy, xyx, xyy, w of the moments over all used bonds, sum_d2 and max_d2 (all in units of 2^-40).
         deformation_gradient() and mean_d2min() turn a row into floats."""
-        rows = (_capi.pbStrainStats * int(getattr(self, "nsims", 1)))()
+        rows = (_capi.pbStrainStats * self.nsims)()
         _capi.check(_capi.lib().pbSimStrainStats(self._h, float(threshold), rows), "pbSimStrainStats")
-        return [_capi.strain_row(r) for r in rows]
+        return [_capi.row_dict(r) for r in rows]
 
     def strain_of(self, member=0):
         """One member per bot, original order (pbSimStrainOf): a dict of moments (int64, n x 9: k, Yxx, Yxy, Yyy, Xxx,
         Xxy, Xyx, Xyy, W), gradient (float64, n x 2 x 2: the local deformation gradient J, zero for an unfitted bot) and
         d2min (float64, units of 2^-40: the device's value)."""
-        n = self.n
-        out = {"moments": np.empty((n, 9), np.int64), "gradient": np.empty((n, 2, 2), np.float64),
-               "d2min": np.empty(n, np.float64)}
-        _capi.check(_capi.lib().pbSimStrainOf(self._h, int(member), *[_capi.np_ptr(out[k]) for k in
-                                                                     ("moments", "gradient", "d2min")]),
-                    "pbSimStrainOf")
-        return out
+        return _analysis.per_bot(_analysis.STRAIN_OF, self.n, lambda *p: _capi.check(
+            _capi.lib().pbSimStrainOf(self._h, int(member), *p), "pbSimStrainOf"))
 
     def strain_times(self):
         """(strain analyses run so far, device milliseconds of the last one)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetStrainTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetStrainTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetStrainTimes")
 
     def moments(self):
         """Every member's row of integer moments of the state as it is now, from the device (pbSimMoments): a list of
         dicts of Python ints, one per member: time, step, measured, sum_qx / sum_qy / sum_qr / sum_wx / sum_wy (units of
         2^-20), the box min_qx / max_qx / min_qy / max_qy, and xx, yy, xy, rr, vv (the 128-bit sums composed, units of
         2^-40).  moments_summary() turns a row into centroid, gyration tensor, radii and velocities."""
-        rows = (_capi.pbMomentsRow * int(getattr(self, "nsims", 1)))()
+        rows = (_capi.pbMomentsRow * self.nsims)()
         _capi.check(_capi.lib().pbSimMoments(self._h, rows), "pbSimMoments")
-        return [_capi.moments_row(r) for r in rows]
+        return [_capi.row_dict(r) for r in rows]
 
     def set_series(self, interval, capacity):
         """Record such a row per member into a device ring of `capacity` rows in front of every step whose start time
@@ -856,9 +789,8 @@ class Sim:
 
     def series_info(self):
         """A dict of interval, capacity (0: off) and records taken so far (pbSimGetSeriesInfo)."""
-        i, c, r = C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
-        _capi.check(_capi.lib().pbSimGetSeriesInfo(self._h, C.byref(i), C.byref(c), C.byref(r)), "pbSimGetSeriesInfo")
-        return {"interval": float(i.value), "capacity": int(c.value), "records": int(r.value)}
+        return _analysis.read_info(_analysis.SERIES_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetSeriesInfo(self._h, *p), "pbSimGetSeriesInfo"))
 
     def series_of(self, member=0, first=None, count=None):
         """Records first .. first + count of one member in the order taken, as moments() gives rows (pbSimGetSeriesOf).
@@ -870,13 +802,11 @@ class Sim:
             count = max(info["records"] - int(first), 0)
         rows = (_capi.pbMomentsRow * max(int(count), 1))()
         _capi.check(_capi.lib().pbSimGetSeriesOf(self._h, int(member), int(first), int(count), rows), "pbSimGetSeriesOf")
-        return [_capi.moments_row(r) for r in rows[:int(count)]]
+        return [_capi.row_dict(r) for r in rows[:int(count)]]
 
     def series_times(self):
         """(records taken so far, device milliseconds of the last row's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetSeriesTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetSeriesTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetSeriesTimes")
 
     def pair_correlation(self, kind, r_max, bins, member=None):
         """Pair correlations of every member's state as it is now, on the device (pbSimPairCorrelation): all pairs binned
@@ -886,19 +816,16 @@ class Sim:
         ax_lo / ax_hi, ay_lo / ay_hi (each 128-bit value is hi * 2^32 + lo with 0 <= lo < 2^32; correlation_values()
         composes them), totals a list of dicts (measured, sum_ax, sum_ay, sum_a2, pairs), one per member; with member=k
         that member's (bins,) rows and its dict.  connected_correlation() turns both into C(r)."""
-        nsims = int(getattr(self, "nsims", 1))
-        rows = np.zeros((nsims, max(int(bins), 1)), _capi.CORRELATION_BIN_DTYPE)
-        tot = (_capi.pbCorrelationTotals * nsims)()
+        rows = np.zeros((self.nsims, max(int(bins), 1)), _capi.CORRELATION_BIN_DTYPE)
+        tot = (_capi.pbCorrelationTotals * self.nsims)()
         _capi.check(_capi.lib().pbSimPairCorrelation(self._h, _capi.correlation_kind(kind), float(r_max), int(bins),
                                                      _capi.np_ptr(rows), tot), "pbSimPairCorrelation")
-        totals = [_capi.correlation_totals(t) for t in tot]
+        totals = [_capi.row_dict(t) for t in tot]
         return (rows, totals) if member is None else (rows[int(member)], totals[int(member)])
 
     def correlation_times(self):
         """(pair correlations run so far, device milliseconds of the last one)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetCorrelationTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetCorrelationTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetCorrelationTimes")
 
     def set_time_correlation(self, interval, lags, overlap_radius):
         """Keep a device ring of `lags` snapshots (x, y, vx, vy of every bot, original order), one taken in front of
@@ -915,28 +842,21 @@ class Sim:
 
     def time_correlation_info(self):
         """A dict of interval, lags (0: off), overlap_radius and records taken so far (pbSimGetTimeCorrelationInfo)."""
-        i, l, a, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_ulonglong(0)
-        _capi.check(_capi.lib().pbSimGetTimeCorrelationInfo(self._h, C.byref(i), C.byref(l), C.byref(a), C.byref(r)),
-                    "pbSimGetTimeCorrelationInfo")
-        return {"interval": float(i.value), "lags": int(l.value), "overlap_radius": float(a.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.TIME_CORRELATION_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetTimeCorrelationInfo(self._h, *p), "pbSimGetTimeCorrelationInfo"))
 
     def time_correlation(self):
         """The table as it stands (pbSimGetTimeCorrelation): per member a list of `lags` dicts of Python ints, lag 0
         first: lag, origins, sum_steps, samples, sum_qx / sum_qy (units of 2^-20), msd and vacf (the 128-bit sums
         composed, units of 2^-40), overlap, max_q2.  time_correlation_summary() turns a row into MSD, VACF and Q."""
         lags = self.time_correlation_info()["lags"]
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbTimeCorrelationRow * max(nsims * lags, 1))()
+        rows = (_capi.pbTimeCorrelationRow * max(self.nsims * lags, 1))()
         _capi.check(_capi.lib().pbSimGetTimeCorrelation(self._h, rows), "pbSimGetTimeCorrelation")
-        return [[_capi.time_correlation_row(rows[m * lags + l]) for l in range(lags)] for m in range(nsims)]
+        return _analysis.lag_table(self.nsims, lags, lambda g: _capi.row_dict(rows[g]))
 
     def time_correlation_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetTimeCorrelationTimes(self._h, C.byref(n), C.byref(ms)),
-                    "pbSimGetTimeCorrelationTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetTimeCorrelationTimes")
 
     def field_map(self, nx, ny, center, half, member=None):
         """A field map of every member's state as it is now, on the device (pbSimFieldMap): nx x ny cells over the view
@@ -947,23 +867,18 @@ class Sim:
         unmeasured), one per member.  With member=k only that member is mapped (pbSimFieldMapOf): its (ny, nx) cells and
         its dict."""
         view = _capi.field_view(nx, ny, center, half)
-        nsims = int(getattr(self, "nsims", 1)) if member is None else 1
-        fits = 1 <= int(nx) <= 1024 and 1 <= int(ny) <= 1024 and nsims * int(nx) * int(ny) * 64 <= 1 << 31
-        shape = (int(ny), int(nx)) if fits else (1, 1)  # (a call that the engine refuses gets no buffer to speak of)
         if member is not None:
-            cells, tot = np.zeros(shape, _capi.FIELD_CELL_DTYPE), _capi.pbFieldTotals()
+            cells, tot = _analysis.field_cells(1, nx, ny)[0], _capi.pbFieldTotals()
             _capi.check(_capi.lib().pbSimFieldMapOf(self._h, int(member), C.byref(view), _capi.np_ptr(cells),
                                                     C.byref(tot)), "pbSimFieldMapOf")
-            return cells, _capi.field_totals(tot)
-        cells, tot = np.zeros((nsims,) + shape, _capi.FIELD_CELL_DTYPE), (_capi.pbFieldTotals * nsims)()
+            return cells, _capi.row_dict(tot)
+        cells, tot = _analysis.field_cells(self.nsims, nx, ny), (_capi.pbFieldTotals * self.nsims)()
         _capi.check(_capi.lib().pbSimFieldMap(self._h, C.byref(view), _capi.np_ptr(cells), tot), "pbSimFieldMap")
-        return cells, [_capi.field_totals(t) for t in tot]
+        return cells, [_capi.row_dict(t) for t in tot]
 
     def field_times(self):
         """(field maps computed so far, device milliseconds of the last one's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetFieldTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetFieldTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetFieldTimes")
 
     def structure_factor(self, vectors, box_log2, kind="density", member=None):
         """The structure factor of every member's state as it is now, on the device (pbSimStructureFactor): per member
@@ -974,29 +889,21 @@ class Sim:
         im2_hi (each 128-bit value is hi * 2^32 + lo with 0 <= lo < 2^32; units of 2^-30 for the density, 2^-50
         otherwise; structure_factor_values() composes them and S(k)).  With member=k only that member's (nvec,) rows
         (pbSimStructureFactorOf)."""
-        vec, code = _capi.sk_vectors(vectors), _capi.sk_kind(kind)
-        nvec = vec.shape[0]
-        nsims = int(getattr(self, "nsims", 1)) if member is None else 1
-        fits = 1 <= nvec <= _capi.SK_MAX_VECTORS and nsims * nvec * 80 <= 1 << 31
-        shape = (nvec,) if fits else (1,)  # (a call that the engine refuses gets no buffer to speak of)
-        held = vec if nvec else np.zeros((1, 2), np.int32)  # (an empty list still has an address; the engine refuses it)
+        (held, nvec), code = _analysis.held_vectors(vectors), _capi.sk_kind(kind)
         ptr = _capi.np_ptr(held)
         if member is not None:
-            rows = np.zeros(shape, _capi.SK_ROW_DTYPE)
+            rows = _analysis.structure_factor_rows(1, nvec)[0]
             _capi.check(_capi.lib().pbSimStructureFactorOf(self._h, int(member), code, int(box_log2), ptr, nvec,
                                                            _capi.np_ptr(rows)), "pbSimStructureFactorOf")
             return rows
-        rows = np.zeros((nsims,) + shape, _capi.SK_ROW_DTYPE)
+        rows = _analysis.structure_factor_rows(self.nsims, nvec)
         _capi.check(_capi.lib().pbSimStructureFactor(self._h, code, int(box_log2), ptr, nvec, _capi.np_ptr(rows)),
                     "pbSimStructureFactor")
         return rows
 
     def structure_factor_times(self):
         """(structure factors computed so far, device milliseconds of the last one's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetStructureFactorTimes(self._h, C.byref(n), C.byref(ms)),
-                    "pbSimGetStructureFactorTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetStructureFactorTimes")
 
     def set_scattering(self, interval, lags, box_log2, vectors):
         """Keep a device ring of `lags` snapshots of the quantised positions (original order), one taken in front of
@@ -1006,12 +913,10 @@ class Sim:
         1 ... 256 (pbSimSetScattering): the self-intermediate scattering function as exact integer phasor sums.
         Restarts at record 0; lags 0 switches it off (vectors may then be None).  Recording changes no state bit."""
         if int(lags) == 0 and vectors is None:
-            vec = np.zeros((0, 2), np.int32)
-        else:
-            vec = _capi.sk_vectors(vectors)
-        held = vec if vec.shape[0] else np.zeros((1, 2), np.int32)  # (an empty list still has an address)
+            vectors = np.zeros((0, 2), np.int32)
+        held, nvec = _analysis.held_vectors(vectors)
         _capi.check(_capi.lib().pbSimSetScattering(self._h, float(interval), int(lags), int(box_log2),
-                                                   _capi.np_ptr(held), vec.shape[0]), "pbSimSetScattering")
+                                                   _capi.np_ptr(held), nvec), "pbSimSetScattering")
 
     def scattering_record(self):
         """One record now, of the state as it is (pbSimScatteringRecord)."""
@@ -1019,11 +924,8 @@ class Sim:
 
     def scattering_info(self):
         """A dict of interval, lags (0: off), box_log2, nvec and records taken so far (pbSimGetScatteringInfo)."""
-        i, l, e, k, r = C.c_float(0.0), C.c_uint(0), C.c_int(0), C.c_uint(0), C.c_ulonglong(0)
-        _capi.check(_capi.lib().pbSimGetScatteringInfo(self._h, C.byref(i), C.byref(l), C.byref(e), C.byref(k),
-                                                       C.byref(r)), "pbSimGetScatteringInfo")
-        return {"interval": float(i.value), "lags": int(l.value), "box_log2": int(e.value), "nvec": int(k.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.SCATTERING_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetScatteringInfo(self._h, *p), "pbSimGetScatteringInfo"))
 
     def scattering(self):
         """The table as it stands (pbSimGetScattering): per member a list over lags (lag 0 first) of lists over the
@@ -1031,18 +933,13 @@ class Sim:
         scattering_summary() turns a row into F_s."""
         info = self.scattering_info()
         lags, nvec = info["lags"], info["nvec"]
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbScatteringRow * max(nsims * lags * nvec, 1))()
+        rows = (_capi.pbScatteringRow * max(self.nsims * lags * nvec, 1))()
         _capi.check(_capi.lib().pbSimGetScattering(self._h, rows), "pbSimGetScattering")
-        return [[[_capi.scattering_row(rows[(m * lags + l) * nvec + k]) for k in range(nvec)] for l in range(lags)]
-                for m in range(nsims)]
+        return _analysis.lag_table(self.nsims, lags, lambda g: _capi.row_dict(rows[g]), nvec)
 
     def scattering_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetScatteringTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetScatteringTimes")
-        return int(n.value), float(ms.value)
-
+        return self._span("pbSimGetScatteringTimes")
 
     def set_van_hove(self, interval, lags, width, bins):
         """Keep a device ring of `lags` snapshots of the positions (original order), one taken in front of every step
@@ -1060,11 +957,8 @@ class Sim:
 
     def van_hove_info(self):
         """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveInfo)."""
-        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
-        _capi.check(_capi.lib().pbSimGetVanHoveInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b),
-                                                    C.byref(r)), "pbSimGetVanHoveInfo")
-        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.VAN_HOVE_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetVanHoveInfo(self._h, *p), "pbSimGetVanHoveInfo"))
 
     def van_hove(self):
         """The table as it stands (pbSimGetVanHove): per member a list over lags (lag 0 first) of dicts of Python ints:
@@ -1073,17 +967,14 @@ class Sim:
         (j - bins + 1) width)) as lists.  van_hove_summary() turns a row into msd and alpha2."""
         info = self.van_hove_info()
         lags, bins = info["lags"], info["bins"]
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbVanHoveRow * max(nsims * lags, 1))()
-        counts = (C.c_ulonglong * max(nsims * lags * 5 * bins, 1))()
+        rows = (_capi.pbVanHoveRow * max(self.nsims * lags, 1))()
+        counts = (C.c_ulonglong * max(self.nsims * lags * 5 * bins, 1))()
         _capi.check(_capi.lib().pbSimGetVanHove(self._h, rows, counts), "pbSimGetVanHove")
-        return van_hove_lists(rows, counts, nsims, lags, bins)
+        return van_hove_lists(rows, counts, self.nsims, lags, bins)
 
     def van_hove_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetVanHoveTimes(self._h, C.byref(n), C.byref(ms)), "pbSimGetVanHoveTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetVanHoveTimes")
 
     def set_van_hove_distinct(self, interval, lags, width, bins):
         """Keep a device ring of `lags` snapshots of the positions, taken as set_van_hove() takes them, and add every
@@ -1100,11 +991,8 @@ class Sim:
 
     def van_hove_distinct_info(self):
         """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveDistinctInfo)."""
-        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
-        _capi.check(_capi.lib().pbSimGetVanHoveDistinctInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b),
-                                                            C.byref(r)), "pbSimGetVanHoveDistinctInfo")
-        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.VAN_HOVE_DISTINCT_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetVanHoveDistinctInfo(self._h, *p), "pbSimGetVanHoveDistinctInfo"))
 
     def van_hove_distinct(self):
         """The table as it stands (pbSimGetVanHoveDistinct): per member a list over lags (lag 0 first) of dicts of Python
@@ -1112,18 +1000,14 @@ class Sim:
         [k width, (k + 1) width))."""
         info = self.van_hove_distinct_info()
         lags, bins = info["lags"], info["bins"]
-        nsims = int(getattr(self, "nsims", 1))
-        rows = (_capi.pbVanHoveDistinctRow * max(nsims * lags, 1))()
-        counts = (C.c_ulonglong * max(nsims * lags * bins, 1))()
+        rows = (_capi.pbVanHoveDistinctRow * max(self.nsims * lags, 1))()
+        counts = (C.c_ulonglong * max(self.nsims * lags * bins, 1))()
         _capi.check(_capi.lib().pbSimGetVanHoveDistinct(self._h, rows, counts), "pbSimGetVanHoveDistinct")
-        return van_hove_distinct_lists(rows, counts, nsims, lags, bins)
+        return van_hove_distinct_lists(rows, counts, self.nsims, lags, bins)
 
     def van_hove_distinct_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
-        n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        _capi.check(_capi.lib().pbSimGetVanHoveDistinctTimes(self._h, C.byref(n), C.byref(ms)),
-                    "pbSimGetVanHoveDistinctTimes")
-        return int(n.value), float(ms.value)
+        return self._span("pbSimGetVanHoveDistinctTimes")
 
 
 class Ensemble(Sim):
@@ -1139,33 +1023,6 @@ class Ensemble(Sim):
         h = C.c_void_p()
         _capi.check(_capi.lib().pbSimCreateBatch(C.byref(h), arr, self.nsims, float(wall_half)), "pbSimCreateBatch")
         self._h = h
-
-    def set_state_of(self, member, pos=None, vel=None, rad=None, phase=None, dead=None):
-        n = self.n
-        pos = self._in(pos, np.float32, 2 * n)
-        vel = self._in(vel, np.float32, 2 * n)
-        rad = self._in(rad, np.float32, n)
-        phase = self._in(phase, np.float32, n)
-        dead = self._in(dead, np.int32, n)
-        _capi.check(_capi.lib().pbSimSetStateOf(self._h, int(member), _capi.np_ptr(pos), _capi.np_ptr(vel),
-                                                _capi.np_ptr(rad), _capi.np_ptr(phase), _capi.np_ptr(dead)),
-                    "pbSimSetStateOf")
-
-    def get_state_of(self, member):
-        n = self.n
-        out = {
-            "pos": np.empty((n, 2), np.float32), "vel": np.empty((n, 2), np.float32),
-            "rad": np.empty(n, np.float32), "phase": np.empty(n, np.float32),
-            "dead": np.empty(n, np.int32), "absForce_a": np.empty(n, np.float32),
-            "absForce_r": np.empty(n, np.float32),
-        }
-        _capi.check(_capi.lib().pbSimGetStateOf(self._h, int(member), *[_capi.np_ptr(out[k]) for k in
-                                                                        ("pos", "vel", "rad", "phase", "dead",
-                                                                         "absForce_a", "absForce_r")]),
-                    "pbSimGetStateOf")
-        if not self.config()["attraction_sums"]:
-            out["absForce_a"] = None
-        return out
 
     def centroids(self):
         out = np.empty((self.nsims, 2), np.float64)

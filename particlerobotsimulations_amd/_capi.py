@@ -83,6 +83,37 @@ class pbRenderView(C.Structure):
                 ("halfExtent", C.c_float), ("lightRadius", C.c_float), ("style", C.c_int)]
 
 
+class pbMoment128(C.Structure):
+    _fields_ = [("lo", C.c_ulonglong), ("hi", C.c_longlong)]
+
+
+def row_dict(row):
+    """A C row as a dict, by one rule for every structure here: `reserved` is left out; a pbMoment128 becomes the 128-bit
+    sum hi * 2^32 + lo as one Python int; an array field a list of ints; a c_float a float; anything else an int."""
+    d = {}
+    for name, kind in row._fields_:
+        if name == "reserved":
+            continue
+        v = getattr(row, name)
+        if kind is pbMoment128:
+            d[name] = (int(v.hi) << 32) + int(v.lo)
+        elif issubclass(kind, C.Array):
+            d[name] = [int(x) for x in v]
+        else:
+            d[name] = float(v) if kind is C.c_float else int(v)
+    return d
+
+
+def compose_128(records, name):
+    """The 128-bit column `name` of a numpy record array (one of the *_DTYPEs): records[name + "_hi"] * 2^32 +
+    records[name + "_lo"] as an object array of Python ints, shaped like `records`."""
+    flat = [(int(h) << 32) + int(l)
+            for h, l in zip(records[name + "_hi"].reshape(-1), records[name + "_lo"].reshape(-1))]
+    big = np.empty(len(flat), object)
+    big[:] = flat
+    return big.reshape(records.shape)
+
+
 class pbClusterStats(C.Structure):
     _fields_ = [("clusters", C.c_uint), ("largest", C.c_uint), ("largest_label", C.c_uint), ("isolated", C.c_uint),
                 ("links", C.c_ulonglong), ("max_degree", C.c_uint), ("rounds", C.c_uint)]
@@ -98,12 +129,12 @@ class pbStructureStats(C.Structure):
 
 
 def structure_row(r):
-    """A pbStructureStats row as a dict: the integers as they are, and psi6 = (psi6_re + i psi6_im) / 2^30 / bonds as a
-    Python complex (0 without bonds): the mean of e^(6 i theta) over the member's directed bonds."""
-    bonds, re, im = int(r.bonds), int(r.psi6_re), int(r.psi6_im)
-    psi = complex(re / 1073741824.0, im / 1073741824.0) / bonds if bonds else 0j
-    return {"bonds": bonds, "psi6_re": re, "psi6_im": im, "coordination": [int(c) for c in r.coordination],
-            "psi6": psi}
+    """A pbStructureStats row as a dict: row_dict(r), and psi6 = (psi6_re + i psi6_im) / 2^30 / bonds as a Python complex
+    (0 without bonds): the mean of e^(6 i theta) over the member's directed bonds."""
+    d = row_dict(r)
+    bonds = d["bonds"]
+    d["psi6"] = complex(d["psi6_re"] / 1073741824.0, d["psi6_im"] / 1073741824.0) / bonds if bonds else 0j
+    return d
 
 
 class pbRearrangementStats(C.Structure):
@@ -114,16 +145,13 @@ class pbRearrangementStats(C.Structure):
 
 
 def rearrangement_row(r):
-    """A pbRearrangementStats row as a dict of Python ints; sum_q2 is the 128-bit sum (sum_q2_hi * 2^64 + sum_q2_lo) as
-    one int.  Bond counts are directed; sum_qx / sum_qy are in units of 2^-20, sum_q2 and max_q2 in units of 2^-40."""
-    d = {name: int(getattr(r, name)) for name, _ in pbRearrangementStats._fields_
-         if name not in ("sum_q2_lo", "sum_q2_hi")}
-    d["sum_q2"] = (int(r.sum_q2_hi) << 64) | int(r.sum_q2_lo)
+    """A pbRearrangementStats row as a dict of Python ints: row_dict(r) with sum_q2, the 128-bit sum of two 64-bit halves
+    (sum_q2_hi * 2^64 + sum_q2_lo), as one int.  Bond counts are directed; sum_qx / sum_qy are in units of 2^-20, sum_q2
+    and max_q2 in units of 2^-40."""
+    d = row_dict(r)
+    lo, hi = d.pop("sum_q2_lo"), d.pop("sum_q2_hi")
+    d["sum_q2"] = (hi << 64) | lo
     return d
-
-
-class pbMoment128(C.Structure):
-    _fields_ = [("lo", C.c_ulonglong), ("hi", C.c_longlong)]
 
 
 class pbMomentsRow(C.Structure):
@@ -132,16 +160,6 @@ class pbMomentsRow(C.Structure):
                 ("sum_wx", C.c_longlong), ("sum_wy", C.c_longlong),
                 ("min_qx", C.c_int), ("max_qx", C.c_int), ("min_qy", C.c_int), ("max_qy", C.c_int),
                 ("xx", pbMoment128), ("yy", pbMoment128), ("xy", pbMoment128), ("rr", pbMoment128), ("vv", pbMoment128)]
-
-
-def moments_row(r):
-    """A pbMomentsRow as a dict of Python ints (time: the fp32 value as a float); each of xx, yy, xy, rr, vv is the
-    128-bit sum hi * 2^32 + lo as one int.  Sums of q are in units of 2^-20, sums of products in units of 2^-40."""
-    d = {}
-    for name, kind in pbMomentsRow._fields_:
-        v = getattr(r, name)
-        d[name] = (int(v.hi) << 32) + int(v.lo) if kind is pbMoment128 else float(v) if name == "time" else int(v)
-    return d
 
 
 class pbStrainStats(C.Structure):
@@ -153,17 +171,6 @@ class pbStrainStats(C.Structure):
 
 
 PB_STRAIN_MOMENTS = ("k", "yxx", "yxy", "yyy", "xxx", "xxy", "xyx", "xyy", "w")  # a bot's nine words, in order
-
-
-def strain_row(r):
-    """A pbStrainStats row as a dict of Python ints (without `reserved`); each of yxx ... w and sum_d2 is the 128-bit sum
-    hi * 2^32 + lo as one int, units of 2^-40, as is max_d2."""
-    d = {}
-    for name, kind in pbStrainStats._fields_:
-        if name != "reserved":
-            v = getattr(r, name)
-            d[name] = (int(v.hi) << 32) + int(v.lo) if kind is pbMoment128 else int(v)
-    return d
 
 
 class pbCorrelationBin(C.Structure):
@@ -190,28 +197,10 @@ def correlation_kind(kind):
     return int(kind)
 
 
-def correlation_totals(t):
-    """A pbCorrelationTotals row as a dict of Python ints, sum_a2 composed from its 128 bits."""
-    return {"measured": int(t.measured), "sum_ax": int(t.sum_ax), "sum_ay": int(t.sum_ay),
-            "sum_a2": (int(t.sum_a2.hi) << 32) + int(t.sum_a2.lo), "pairs": int(t.pairs)}
-
-
 class pbTimeCorrelationRow(C.Structure):
     _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
                 ("samples", C.c_ulonglong), ("sum_qx", C.c_longlong), ("sum_qy", C.c_longlong),
                 ("msd", pbMoment128), ("vacf", pbMoment128), ("overlap", C.c_ulonglong), ("max_q2", C.c_ulonglong)]
-
-
-def time_correlation_row(r):
-    """A pbTimeCorrelationRow as a dict of Python ints (reserved left out); msd and vacf are the 128-bit sums
-    hi * 2^32 + lo as one int.  sum_qx / sum_qy are in units of 2^-20, msd, vacf and max_q2 in units of 2^-40."""
-    d = {}
-    for name, kind in pbTimeCorrelationRow._fields_:
-        if name == "reserved":
-            continue
-        v = getattr(r, name)
-        d[name] = (int(v.hi) << 32) + int(v.lo) if kind is pbMoment128 else int(v)
-    return d
 
 
 class pbFieldView(C.Structure):
@@ -238,11 +227,6 @@ def field_view(nx, ny, center, half):
     """A pbFieldView of nx x ny cells centred on `center` = (x, y); `half` is one half extent or (halfX, halfY)."""
     hx, hy = (half, half) if np.isscalar(half) else half
     return pbFieldView(int(nx), int(ny), float(center[0]), float(center[1]), float(hx), float(hy))
-
-
-def field_totals(t):
-    """A pbFieldTotals row as a dict of Python ints."""
-    return {name: int(getattr(t, name)) for name, _ in pbFieldTotals._fields_}
 
 
 class pbStructureFactorRow(C.Structure):
@@ -288,11 +272,6 @@ SCATTER_MAX_LAGS = 64
 SCATTER_MAX_VECTORS = 256
 
 
-def scattering_row(r):
-    """A pbScatteringRow as a dict of Python ints (reserved left out); re and im are in units of 2^-30."""
-    return {name: int(getattr(r, name)) for name, _ in pbScatteringRow._fields_ if name != "reserved"}
-
-
 class pbVanHoveRow(C.Structure):
     _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
                 ("samples", C.c_ulonglong), ("beyond_r", C.c_ulonglong), ("beyond_x", C.c_ulonglong),
@@ -304,23 +283,16 @@ VANHOVE_MAX_BINS = 1024
 
 
 def van_hove_row(r):
-    """A pbVanHoveRow as a dict of Python ints (reserved left out): msd composed from its 128 bits (hi * 2^32 + lo,
-    units of 2^-40) and q4 from its three little-endian 64-bit limbs (units of 2^-80)."""
-    out = {name: int(getattr(r, name)) for name in ("lag", "origins", "sum_steps", "samples", "beyond_r", "beyond_x",
-                                                    "beyond_y")}
-    out["msd"] = (int(r.msd.hi) << 32) + int(r.msd.lo)
-    out["q4"] = int(r.q4[0]) + (int(r.q4[1]) << 64) + (int(r.q4[2]) << 128)
-    return out
+    """A pbVanHoveRow as a dict of Python ints: row_dict(r) (msd in units of 2^-40) with q4 composed from its three
+    little-endian 64-bit limbs (units of 2^-80)."""
+    d = row_dict(r)
+    d["q4"] = d["q4"][0] + (d["q4"][1] << 64) + (d["q4"][2] << 128)
+    return d
 
 
 class pbVanHoveDistinctRow(C.Structure):
     _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
                 ("centres", C.c_ulonglong), ("partners", C.c_ulonglong), ("pairs", C.c_ulonglong)]
-
-
-def van_hove_distinct_row(r):
-    """A pbVanHoveDistinctRow as a dict of Python ints (reserved left out)."""
-    return {name: int(getattr(r, name)) for name, _ in pbVanHoveDistinctRow._fields_ if name != "reserved"}
 
 
 # pbContactLink as a numpy record

@@ -2,10 +2,11 @@
 behind a handful of C wrappers (csrc/pb_capi.cpp)."""
 import ctypes as C
 import os
+from functools import partial
 
 import numpy as np
 
-from . import _capi
+from . import _analysis, _capi
 
 PB_MAX_OBSTACLES = 10
 
@@ -47,35 +48,85 @@ class FlatConfig(C.Structure):
 
 _lib = None
 _ptr = _capi.np_ptr  # an array's address, for a void * argument
-_P, _F = C.c_void_p, C.c_float
-# the analysis wrappers of csrc/pb_capi.cpp: what each takes after the handle (all return 0 or -1)
-_ANALYSES = {
-    "pbHostClusterStats": [_F, _P], "pbHostClusterLabels": [_F, _P, _P],
-    "pbHostContacts": [_F, _P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)], "pbHostContactVirial": [_F, _P],
-    "pbHostRadialCounts": [_F, C.c_uint, _P], "pbHostStructureStats": [_F, _P], "pbHostHexatic": [_F, _P, _P],
-    "pbHostMarkReference": [_F], "pbHostRearrangementStats": [_P], "pbHostRearrangementOf": [_P, _P, _P, _P],
-    "pbHostStrainStats": [_F, _P], "pbHostStrainOf": [_P, _P, _P],
-    "pbHostMoments": [_P], "pbHostSetSeries": [_F, C.c_uint], "pbHostSeriesInfo": [_P, _P, _P],
-    "pbHostSeriesRows": [C.c_ulonglong, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
-    "pbHostPairCorrelation": [C.c_int, _F, C.c_uint, _P, _P],
-    "pbHostSetTimeCorrelation": [_F, C.c_uint, _F], "pbHostTimeCorrelationRecord": [],
-    "pbHostTimeCorrelationInfo": [_P, _P, _P, _P],
-    "pbHostTimeCorrelationRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
-    "pbHostSetScattering": [_F, C.c_uint, C.c_int, _P, C.c_uint], "pbHostScatteringRecord": [],
-    "pbHostScatteringInfo": [_P, _P, _P, _P, _P],
-    "pbHostScatteringRows": [_P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
-    "pbHostSetVanHove": [_F, C.c_uint, _F, C.c_uint], "pbHostVanHoveRecord": [],
-    "pbHostVanHoveInfo": [_P, _P, _P, _P, _P],
-    "pbHostVanHoveRows": [_P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
-    "pbHostSetVanHoveDistinct": [_F, C.c_uint, _F, C.c_uint], "pbHostVanHoveDistinctRecord": [],
-    "pbHostVanHoveDistinctInfo": [_P, _P, _P, _P, _P],
-    "pbHostVanHoveDistinctRows": [_P, _P, C.c_ulonglong, C.POINTER(C.c_ulonglong)],
-    "pbHostFieldMap": [_P, _P, _P],
-    "pbHostStructureFactor": [C.c_int, C.c_int, _P, C.c_uint, _P],
+_P, _F, _I, _U, _S = C.c_void_p, C.c_float, C.c_int, C.c_uint, C.c_char_p
+_ULL, _PULL = C.c_ulonglong, C.POINTER(C.c_ulonglong)
+# every pbHost* function libparticlebot_host.so exports (csrc/pb_capi.cpp, csrc/pb_host_resources.cpp):
+# name -> (restype, argtypes).  An analysis wrapper takes the handle first and returns 0 or -1.
+SYMBOLS = {
+    "pbHostLoadConfig": (_I, [_S, _S, C.POINTER(FlatConfig)]),
+    "pbHostCreate": (_P, [_S, _S, _I]),
+    "pbHostDestroy": (None, [_P]),
+    "pbHostReset": (None, [_P]),
+    "pbHostUpdate": (None, [_P]),
+    "pbHostAdvance": (_I, [_P, _I]),
+    "pbHostStepsUntilDump": (_I, [_P, _I]),
+    "pbHostTime": (_F, [_P]),
+    "pbHostSetTime": (None, [_P, _F]),
+    "pbHostFinished": (_I, [_P]),
+    "pbHostDump": (_I, [_P, _S, _S]),
+    "pbHostLoadFromFile": (_I, [_P, _S]),
+    "pbHostWriteFrame": (_I, [_P, _S, _I, _I, _F, _F, _F]),
+    "pbHostWriteFrameStyle": (_I, [_P, _S, _I, _I, _F, _F, _F, _I]),
+    "pbHostRenderFrame": (_I, [_P, _S, _P, _I, _I, _F, _F, _F, _I]),
+    "pbHostRenderStats": (_I, [_P, _PULL, C.POINTER(_F)]),
+    "pbHostClusterStats": (_I, [_P, _F, _P]),
+    "pbHostClusterLabels": (_I, [_P, _F, _P, _P]),
+    "pbHostContacts": (_I, [_P, _F, _P, _P, _ULL, _PULL]),
+    "pbHostContactVirial": (_I, [_P, _F, _P]),
+    "pbHostRadialCounts": (_I, [_P, _F, _U, _P]),
+    "pbHostStructureStats": (_I, [_P, _F, _P]),
+    "pbHostHexatic": (_I, [_P, _F, _P, _P]),
+    "pbHostMarkReference": (_I, [_P, _F]),
+    "pbHostRearrangementStats": (_I, [_P, _P]),
+    "pbHostRearrangementOf": (_I, [_P, _P, _P, _P, _P]),
+    "pbHostStrainStats": (_I, [_P, _F, _P]),
+    "pbHostStrainOf": (_I, [_P, _P, _P, _P]),
+    "pbHostMoments": (_I, [_P, _P]),
+    "pbHostSetSeries": (_I, [_P, _F, _U]),
+    "pbHostSeriesInfo": (_I, [_P, _P, _P, _P]),
+    "pbHostSeriesRows": (_I, [_P, _ULL, _P, _ULL, _PULL]),
+    "pbHostPairCorrelation": (_I, [_P, _I, _F, _U, _P, _P]),
+    "pbHostSetTimeCorrelation": (_I, [_P, _F, _U, _F]),
+    "pbHostTimeCorrelationRecord": (_I, [_P]),
+    "pbHostTimeCorrelationInfo": (_I, [_P, _P, _P, _P, _P]),
+    "pbHostTimeCorrelationRows": (_I, [_P, _P, _ULL, _PULL]),
+    "pbHostSetScattering": (_I, [_P, _F, _U, _I, _P, _U]),
+    "pbHostScatteringRecord": (_I, [_P]),
+    "pbHostScatteringInfo": (_I, [_P, _P, _P, _P, _P, _P]),
+    "pbHostScatteringRows": (_I, [_P, _P, _ULL, _PULL]),
+    "pbHostSetVanHove": (_I, [_P, _F, _U, _F, _U]),
+    "pbHostVanHoveRecord": (_I, [_P]),
+    "pbHostVanHoveInfo": (_I, [_P, _P, _P, _P, _P, _P]),
+    "pbHostVanHoveRows": (_I, [_P, _P, _P, _ULL, _PULL]),
+    "pbHostSetVanHoveDistinct": (_I, [_P, _F, _U, _F, _U]),
+    "pbHostVanHoveDistinctRecord": (_I, [_P]),
+    "pbHostVanHoveDistinctInfo": (_I, [_P, _P, _P, _P, _P, _P]),
+    "pbHostVanHoveDistinctRows": (_I, [_P, _P, _P, _ULL, _PULL]),
+    "pbHostFieldMap": (_I, [_P, _P, _P, _P]),
+    "pbHostStructureFactor": (_I, [_P, _I, _I, _P, _U, _P]),
+    "pbHostSetDisplay": (None, [_P, _I]),
+    "pbHostCentroidTrail": (_I, [_P, _P, _P, C.POINTER(_U)]),
+    "pbHostSaveCheckpoint": (_I, [_P, _S]),
+    "pbHostLoadCheckpoint": (_I, [_P, _S]),
+    "pbHostDrawDead": (_I, [_P, _P]),
+    "pbHostGetArray": (_I, [_P, _I, _P]),
+    "pbHostSetArray": (_I, [_P, _I, _P, _I, _I]),
+    "pbHostLibcRandDraws": (None, [_U, _I, _P]),
+    "pbHostLibmCheck": (_I, [_I, _U, _PULL, _PULL, _PULL]),
+    "pbHostLibcVersion": (_S, []),
+    "pbHostXorwowOutputs": (None, [_I, _ULL, _U, _U, _P]),
+    "pbHostXorwowNormals": (None, [_I, _U, _U, _U, _P]),
+    "pbHostXorwowJumpMatrix": (None, [_U, _P]),
+    "pbHostEngineHandle": (_P, [_P]),
+    "pbHostNumBots": (_U, [_P]),
+    "pbHostCentroidSteps": (_I, [_P]),
+    "pbHostGetResources": (_I, [_P]),
+    "pbHostParseCpuList": (_I, [_S, C.POINTER(_I), _I]),
 }
 
 
 def lib():
+    """Load libparticlebot_host.so and bind every symbol of SYMBOLS.  Raises if the library or a symbol is missing."""
     global _lib
     if _lib is not None:
         return _lib
@@ -83,55 +134,10 @@ def lib():
     if not os.path.exists(_capi.HOST_SO):
         raise RuntimeError(f"{_capi.HOST_SO} not found: run __graft_entry__.build()")
     L = C.CDLL(_capi.HOST_SO)
-    L.pbHostLoadConfig.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(FlatConfig)]
-    L.pbHostLoadConfig.restype = C.c_int
-    L.pbHostCreate.argtypes = [C.c_char_p, C.c_char_p, C.c_int]
-    L.pbHostCreate.restype = C.c_void_p
-    L.pbHostDestroy.argtypes = [C.c_void_p]
-    L.pbHostReset.argtypes = [C.c_void_p]
-    L.pbHostUpdate.argtypes = [C.c_void_p]
-    L.pbHostAdvance.argtypes = [C.c_void_p, C.c_int]
-    L.pbHostAdvance.restype = C.c_int
-    L.pbHostStepsUntilDump.argtypes = [C.c_void_p, C.c_int]
-    L.pbHostStepsUntilDump.restype = C.c_int
-    L.pbHostTime.argtypes = [C.c_void_p]
-    L.pbHostTime.restype = C.c_float
-    L.pbHostSetTime.argtypes = [C.c_void_p, C.c_float]
-    L.pbHostSetTime.restype = None
-    L.pbHostFinished.argtypes = [C.c_void_p]
-    L.pbHostFinished.restype = C.c_int
-    L.pbHostDump.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
-    L.pbHostDump.restype = C.c_int
-    L.pbHostLoadFromFile.argtypes = [C.c_void_p, C.c_char_p]
-    L.pbHostLoadFromFile.restype = C.c_int
-    L.pbHostDrawDead.argtypes = [C.c_void_p, C.c_void_p]
-    L.pbHostSaveCheckpoint.argtypes = [C.c_void_p, C.c_char_p]
-    L.pbHostSaveCheckpoint.restype = C.c_int
-    L.pbHostLoadCheckpoint.argtypes = [C.c_void_p, C.c_char_p]
-    L.pbHostLoadCheckpoint.restype = C.c_int
-    L.pbHostGetArray.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.pbHostGetArray.restype = C.c_int
-    L.pbHostSetArray.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
-    L.pbHostSetArray.restype = C.c_int
-    L.pbHostLibcRandDraws.argtypes = [C.c_uint, C.c_int, C.c_void_p]
-    L.pbHostNumBots.argtypes = [C.c_void_p]
-    L.pbHostNumBots.restype = C.c_uint
-    L.pbHostCentroidSteps.argtypes = [C.c_void_p]
-    L.pbHostCentroidSteps.restype = C.c_int
-    L.pbHostSetDisplay.argtypes = [C.c_void_p, C.c_int]
-    L.pbHostCentroidTrail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint)]
-    L.pbHostCentroidTrail.restype = C.c_int
-    L.pbHostWriteFrameStyle.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
-                                        C.c_int]
-    L.pbHostWriteFrameStyle.restype = C.c_int
-    L.pbHostRenderFrame.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float,
-                                    C.c_float, C.c_int]
-    L.pbHostRenderFrame.restype = C.c_int
-    L.pbHostRenderStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong), C.POINTER(C.c_float)]
-    L.pbHostRenderStats.restype = C.c_int
-    for name, args in _ANALYSES.items():
-        fn = getattr(L, name)
-        fn.argtypes, fn.restype = [C.c_void_p] + args, C.c_int
+    for name, (res, args) in SYMBOLS.items():
+        fn = getattr(L, name)  # AttributeError if the symbol is not exported
+        fn.restype = res
+        fn.argtypes = args
     _lib = L
     return L
 
@@ -180,6 +186,11 @@ class HostSim:
             self.close()
         except Exception:
             pass
+
+    def _call(self, symbol, refused, *args):
+        """One wrapper call on this handle; a non-zero return raises RuntimeError(refused)."""
+        if getattr(lib(), symbol)(self._h, *args) != 0:
+            raise RuntimeError(refused)
 
     def update(self):
         lib().pbHostUpdate(self._h)
@@ -231,8 +242,7 @@ class HostSim:
         xy = np.empty((steps, 2), np.float32)
         times = np.empty(steps, np.float32)
         rec = C.c_uint(0)
-        if lib().pbHostCentroidTrail(self._h, _ptr(xy), _ptr(times), C.byref(rec)) != 0:
-            raise RuntimeError("centroid_trail: set_display(True) first")
+        self._call("pbHostCentroidTrail", "centroid_trail: set_display(True) first", _ptr(xy), _ptr(times), C.byref(rec))
         return xy, times, int(rec.value)
 
     def write_frame(self, path, size=800, center=(0.0, 0.0), half_extent=0.0, style="plain", renderer="host"):
@@ -257,7 +267,6 @@ class HostSim:
                                        half_extent, 1) != 0:
                 raise OSError(f"writeFramePPMReference({path}) failed")
             return
-        L.pbHostWriteFrame.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float]
         if L.pbHostWriteFrame(self._h, os.fsencode(path), width, height, center[0], center[1],
                               half_extent) != 0:
             raise OSError(f"writeFramePPM({path}) failed")
@@ -268,16 +277,16 @@ class HostSim:
         if style not in ("plain", "reference"):
             raise ValueError(style)
         out = np.empty((int(height), int(width), 3), np.uint8)
-        if lib().pbHostRenderFrame(self._h, None, _ptr(out), int(width), int(height), center[0], center[1],
-                                   half_extent, 1 if style == "reference" else 0) != 0:
-            raise RuntimeError("renderFrame failed (the device rasteriser needs the fused engine and a valid view)")
+        self._call("pbHostRenderFrame",
+                   "renderFrame failed (the device rasteriser needs the fused engine and a valid view)", None, _ptr(out),
+                   int(width), int(height), center[0], center[1], half_extent, 1 if style == "reference" else 0)
         return out
 
     def render_stats(self):
         """(frames rendered on the device, device milliseconds of the last frame's launches)."""
         n, ms = C.c_ulonglong(0), C.c_float(0.0)
-        if lib().pbHostRenderStats(self._h, C.byref(n), C.byref(ms)) != 0:
-            raise RuntimeError("render_stats: the device rasteriser needs the fused engine")
+        self._call("pbHostRenderStats", "render_stats: the device rasteriser needs the fused engine", C.byref(n),
+                   C.byref(ms))
         return int(n.value), float(ms.value)
 
     def clusters(self, gap=0.0):
@@ -285,79 +294,74 @@ class HostSim:
         clusters, largest, largest_label, isolated, links, max_degree and rounds.  Bots are linked when
         dist - (ri + rj) < gap in fp32; a label is the smallest original index of a component."""
         row = _capi.pbClusterStats()
-        if lib().pbHostClusterStats(self._h, float(gap), C.byref(row)) != 0:
-            raise RuntimeError("clusters: the cluster analysis needs the fused engine and a finite gap >= 0")
-        return {name: int(getattr(row, name)) for name, _ in _capi.pbClusterStats._fields_}
+        self._call("pbHostClusterStats", "clusters: the cluster analysis needs the fused engine and a finite gap >= 0",
+                   float(gap), C.byref(row))
+        return _capi.row_dict(row)
 
     def cluster_labels(self, gap=0.0):
         """(labels, degree): two uint32 arrays in original bot order (pbSimClusterLabelsOf; fused engine only)."""
-        labels, degree = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
-        if lib().pbHostClusterLabels(self._h, float(gap), _ptr(labels), _ptr(degree)) != 0:
-            raise RuntimeError("cluster_labels: the cluster analysis needs the fused engine and a finite gap >= 0")
-        return labels, degree
+        out = _analysis.per_bot(_analysis.CLUSTER_LABELS, self.n, partial(
+            self._call, "pbHostClusterLabels",
+            "cluster_labels: the cluster analysis needs the fused engine and a finite gap >= 0", float(gap)))
+        return out["labels"], out["degree"]
 
     def contacts(self, gap=0.0):
         """The contact network of the state as it is now, from the device (pbSimContactsOf; fused engine only): a dict
         with offsets (uint32, n + 1: CSR in original bot order, ascending `other`), other (uint32, E), gap (float32, E)
         and force (float32, E x 2: the pair law's force on the owning bot from other)."""
-        count = C.c_ulonglong(0)
-        bad = "contacts: the contact export needs the fused engine and a finite gap >= 0"
-        if lib().pbHostContacts(self._h, float(gap), None, None, 0, C.byref(count)) != 0:
-            raise RuntimeError(bad)
-        offsets = np.empty(self.n + 1, np.uint32)
-        links = np.empty(int(count.value), _capi.CONTACT_LINK_DTYPE)
-        if lib().pbHostContacts(self._h, float(gap), _ptr(offsets), _ptr(links), links.size, C.byref(count)) != 0:
-            raise RuntimeError(bad)
-        return {"offsets": offsets, "other": links["other"].copy(), "gap": links["gap"].copy(),
-                "force": np.stack([links["fx"], links["fy"]], axis=1)}
+        return _analysis.contacts(self.n, partial(
+            self._call, "pbHostContacts", "contacts: the contact export needs the fused engine and a finite gap >= 0",
+            float(gap)))
 
     def contact_virial(self, gap=0.0):
         """Per-bot virial of the contact network (pbSimContactVirialOf; fused engine only): float64, n x 4, the columns
         sxx, sxy, syx, syy summed over each bot's entries in CSR order."""
         out = np.empty((self.n, 4), np.float64)
-        if lib().pbHostContactVirial(self._h, float(gap), _ptr(out)) != 0:
-            raise RuntimeError("contact_virial: the contact export needs the fused engine and a finite gap >= 0")
+        self._call("pbHostContactVirial",
+                   "contact_virial: the contact export needs the fused engine and a finite gap >= 0", float(gap),
+                   _ptr(out))
         return out
 
     def radial_counts(self, r_max, bins, member=None):
         """Radial pair counts of the state as it is now, on the device (pbSimRadialCounts; fused engine only): uint64,
         (1, bins), or (bins,) with member=0.  Ordered pairs, bin int(dist * (float32(bins) / r_max)) in fp32."""
         out = np.zeros((1, int(bins)), np.uint64)
-        if lib().pbHostRadialCounts(self._h, float(r_max), int(bins), _ptr(out)) != 0:
-            raise RuntimeError("radial_counts: the structure analysis needs the fused engine, a finite r_max > 0 and "
-                               "1 ... 4096 bins")
+        self._call("pbHostRadialCounts", "radial_counts: the structure analysis needs the fused engine, a finite r_max "
+                   "> 0 and 1 ... 4096 bins", float(r_max), int(bins), _ptr(out))
         return out if member is None else out[int(member)]
 
     def structure(self, gap=0.0):
         """Hexatic order of the state as it is now, on the device (pbSimStructureStats; fused engine only): a list with
         one dict: bonds, psi6_re, psi6_im, coordination and psi6, the complex mean over the directed bonds."""
         row = _capi.pbStructureStats()
-        if lib().pbHostStructureStats(self._h, float(gap), C.byref(row)) != 0:
-            raise RuntimeError("structure: the structure analysis needs the fused engine and a finite gap >= 0")
+        self._call("pbHostStructureStats",
+                   "structure: the structure analysis needs the fused engine and a finite gap >= 0", float(gap),
+                   C.byref(row))
         return [_capi.structure_row(row)]
 
     def hexatic(self, gap=0.0, member=0):
         """(psi6, neighbours): complex128[n] and uint32[n] in original bot order (pbSimHexaticOf; fused engine only)."""
         if int(member) != 0:
             raise IndexError(member)
-        psi, nb = np.empty(self.n, np.complex128), np.empty(self.n, np.uint32)
-        if lib().pbHostHexatic(self._h, float(gap), _ptr(psi), _ptr(nb)) != 0:
-            raise RuntimeError("hexatic: the structure analysis needs the fused engine and a finite gap >= 0")
-        return psi, nb
+        out = _analysis.per_bot(_analysis.HEXATIC, self.n, partial(
+            self._call, "pbHostHexatic", "hexatic: the structure analysis needs the fused engine and a finite gap >= 0",
+            float(gap)))
+        return out["psi6"], out["neighbours"]
 
     def mark_reference(self, gap=0.0):
         """Keep the positions and the link network at `gap` on the device as the reference of rearrangement()
         (pbSimMarkReference; fused engine only).  A new mark replaces the old one."""
-        if lib().pbHostMarkReference(self._h, float(gap)) != 0:
-            raise RuntimeError("mark_reference: the rearrangement analysis needs the fused engine and a finite gap >= 0")
+        self._call("pbHostMarkReference",
+                   "mark_reference: the rearrangement analysis needs the fused engine and a finite gap >= 0", float(gap))
 
     def rearrangement(self):
         """The state as it is now against the mark, on the device (pbSimRearrangementStats; fused engine only): a list
         with one dict: bonds_marked / bonds_now / bonds_kept (directed), bots_unchanged / bots_lost / bots_gained,
         measured, sum_qx / sum_qy (units of 2^-20), sum_q2 (a Python int, units of 2^-40) and max_q2."""
         row = _capi.pbRearrangementStats()
-        if lib().pbHostRearrangementStats(self._h, C.byref(row)) != 0:
-            raise RuntimeError("rearrangement: the rearrangement analysis needs the fused engine and a marked reference")
+        self._call("pbHostRearrangementStats",
+                   "rearrangement: the rearrangement analysis needs the fused engine and a marked reference",
+                   C.byref(row))
         return [_capi.rearrangement_row(row)]
 
     def rearrangement_of(self, member=0):
@@ -365,57 +369,45 @@ class HostSim:
         the mark) and marked, now, kept (uint32: bonds at the mark, now, and in both)."""
         if int(member) != 0:
             raise IndexError(member)
-        n = self.n
-        out = {"disp": np.empty((n, 2), np.float32), "marked": np.empty(n, np.uint32), "now": np.empty(n, np.uint32),
-               "kept": np.empty(n, np.uint32)}
-        if lib().pbHostRearrangementOf(self._h, *[_ptr(out[k]) for k in ("disp", "marked", "now", "kept")]) != 0:
-            raise RuntimeError("rearrangement_of: the rearrangement analysis needs the fused engine and a marked reference")
-        return out
+        return _analysis.per_bot(_analysis.REARRANGEMENT_OF, self.n, partial(
+            self._call, "pbHostRearrangementOf",
+            "rearrangement_of: the rearrangement analysis needs the fused engine and a marked reference"))
 
     def strain(self, threshold=0.0):
         """Local strain and D2min against the mark, on the device (pbSimStrainStats; fused engine only): a list with one
         dict of Python ints: fitted / unfitted / above (fitted bots with D2min > threshold), bonds_used / bonds_dropped,
         the sums yxx ... w of the moments, sum_d2 and max_d2 (units of 2^-40)."""
         row = _capi.pbStrainStats()
-        if lib().pbHostStrainStats(self._h, float(threshold), C.byref(row)) != 0:
-            raise RuntimeError("strain: the strain analysis needs the fused engine, a marked reference and a finite "
-                               "threshold >= 0")
-        return [_capi.strain_row(row)]
+        self._call("pbHostStrainStats", "strain: the strain analysis needs the fused engine, a marked reference and a "
+                   "finite threshold >= 0", float(threshold), C.byref(row))
+        return [_capi.row_dict(row)]
 
     def strain_of(self, member=0):
         """Per bot, original order (pbSimStrainOf; fused engine only): a dict of moments (int64, n x 9), gradient
         (float64, n x 2 x 2: the local deformation gradient J) and d2min (float64, units of 2^-40)."""
         if int(member) != 0:
             raise IndexError(member)
-        n = self.n
-        out = {"moments": np.empty((n, 9), np.int64), "gradient": np.empty((n, 2, 2), np.float64),
-               "d2min": np.empty(n, np.float64)}
-        if lib().pbHostStrainOf(self._h, *[_ptr(out[k]) for k in ("moments", "gradient", "d2min")]) != 0:
-            raise RuntimeError("strain_of: the strain analysis needs the fused engine and a marked reference")
-        return out
+        return _analysis.per_bot(_analysis.STRAIN_OF, self.n, partial(
+            self._call, "pbHostStrainOf", "strain_of: the strain analysis needs the fused engine and a marked reference"))
 
     def moments(self):
         """The row of integer moments of the state as it is now, on the device (pbSimMoments; fused engine only): a list
         with one dict of Python ints, the 128-bit sums xx, yy, xy, rr, vv composed."""
         row = _capi.pbMomentsRow()
-        if lib().pbHostMoments(self._h, C.byref(row)) != 0:
-            raise RuntimeError("moments: the time series needs the fused engine")
-        return [_capi.moments_row(row)]
+        self._call("pbHostMoments", "moments: the time series needs the fused engine", C.byref(row))
+        return [_capi.row_dict(row)]
 
     def set_series(self, interval, capacity):
         """Record such a row into a device ring of `capacity` rows in front of every step whose start time passes the
         schedule's gate at `interval` (0: every step) while the simulation advances (pbSimSetSeries; fused engine only).
         Restarts at record 0; capacity 0 switches the series off."""
-        if lib().pbHostSetSeries(self._h, float(interval), int(capacity)) != 0:
-            raise RuntimeError("set_series: the time series needs the fused engine, a finite interval >= 0 and a ring "
-                               "of at most 2^31 bytes")
+        self._call("pbHostSetSeries", "set_series: the time series needs the fused engine, a finite interval >= 0 and a "
+                   "ring of at most 2^31 bytes", float(interval), int(capacity))
 
     def series_info(self):
         """A dict of interval, capacity (0: off) and records taken so far (pbSimGetSeriesInfo; fused engine only)."""
-        i, c, r = C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
-        if lib().pbHostSeriesInfo(self._h, C.byref(i), C.byref(c), C.byref(r)) != 0:
-            raise RuntimeError("series_info: the time series needs the fused engine")
-        return {"interval": float(i.value), "capacity": int(c.value), "records": int(r.value)}
+        return _analysis.read_info(_analysis.SERIES_INFO, partial(
+            self._call, "pbHostSeriesInfo", "series_info: the time series needs the fused engine"))
 
     def series_rows(self, first=0):
         """The records from number `first` up to the last one taken, in order, as moments() gives rows
@@ -423,10 +415,9 @@ class HostSim:
         info = self.series_info()
         cap = max(info["records"] - int(first), 1)
         rows, count = (_capi.pbMomentsRow * cap)(), C.c_ulonglong(0)
-        if lib().pbHostSeriesRows(self._h, int(first), rows, cap, C.byref(count)) != 0:
-            raise RuntimeError("series_rows: the time series needs the fused engine, the series on and records that the "
-                               "ring still holds")
-        return [_capi.moments_row(r) for r in rows[:int(count.value)]]
+        self._call("pbHostSeriesRows", "series_rows: the time series needs the fused engine, the series on and records "
+                   "that the ring still holds", int(first), rows, cap, C.byref(count))
+        return [_capi.row_dict(r) for r in rows[:int(count.value)]]
 
     def pair_correlation(self, kind, r_max, bins, member=None):
         """Pair correlations of the state as it is now, on the device (pbSimPairCorrelation; fused engine only): (rows,
@@ -434,11 +425,10 @@ class HostSim:
         member=0."""
         rows = np.zeros((1, max(int(bins), 1)), _capi.CORRELATION_BIN_DTYPE)
         tot = _capi.pbCorrelationTotals()
-        if lib().pbHostPairCorrelation(self._h, _capi.correlation_kind(kind), float(r_max), int(bins), _ptr(rows),
-                                       C.byref(tot)) != 0:
-            raise RuntimeError("pair_correlation: the correlation analysis needs the fused engine, a known kind, a "
-                               "finite r_max > 0 and 1 ... 1024 bins")
-        totals = [_capi.correlation_totals(tot)]
+        self._call("pbHostPairCorrelation", "pair_correlation: the correlation analysis needs the fused engine, a known "
+                   "kind, a finite r_max > 0 and 1 ... 1024 bins", _capi.correlation_kind(kind), float(r_max), int(bins),
+                   _ptr(rows), C.byref(tot))
+        totals = [_capi.row_dict(tot)]
         return (rows, totals) if member is None else (rows[int(member)], totals[int(member)])
 
     def set_time_correlation(self, interval, lags, overlap_radius):
@@ -446,59 +436,52 @@ class HostSim:
         schedule's gate at `interval` (0: every step, -1: only by time_correlation_record()) while the simulation
         advances, and sum MSD, VACF and the overlap count per lag over all time origins (pbSimSetTimeCorrelation; fused
         engine only).  Restarts at record 0; lags 0 switches it off."""
-        if lib().pbHostSetTimeCorrelation(self._h, float(interval), int(lags), float(overlap_radius)) != 0:
-            raise RuntimeError("set_time_correlation: the time correlation needs the fused engine, a finite interval "
-                               ">= 0 (or -1), at most 64 lags and an overlap radius in [0, 2048)")
+        self._call("pbHostSetTimeCorrelation", "set_time_correlation: the time correlation needs the fused engine, a "
+                   "finite interval >= 0 (or -1), at most 64 lags and an overlap radius in [0, 2048)", float(interval),
+                   int(lags), float(overlap_radius))
 
     def time_correlation_record(self):
         """One record now, of the state as it is (pbSimTimeCorrelationRecord; fused engine only)."""
-        if lib().pbHostTimeCorrelationRecord(self._h) != 0:
-            raise RuntimeError("time_correlation_record: the time correlation needs the fused engine and the "
-                               "correlation on")
+        self._call("pbHostTimeCorrelationRecord", "time_correlation_record: the time correlation needs the fused engine "
+                   "and the correlation on")
 
     def time_correlation_info(self):
         """A dict of interval, lags (0: off), overlap_radius and records taken so far (pbSimGetTimeCorrelationInfo;
         fused engine only)."""
-        i, l, a, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_ulonglong(0)
-        if lib().pbHostTimeCorrelationInfo(self._h, C.byref(i), C.byref(l), C.byref(a), C.byref(r)) != 0:
-            raise RuntimeError("time_correlation_info: the time correlation needs the fused engine")
-        return {"interval": float(i.value), "lags": int(l.value), "overlap_radius": float(a.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.TIME_CORRELATION_INFO, partial(
+            self._call, "pbHostTimeCorrelationInfo",
+            "time_correlation_info: the time correlation needs the fused engine"))
 
     def time_correlation(self):
         """The table as it stands, as Sim.time_correlation gives it: a list with one list of `lags` dicts of Python
         ints, lag 0 first (Particlebot::timeCorrelationRows; fused engine only)."""
-        cap = max(self.time_correlation_info()["lags"], 1)
+        lags = self.time_correlation_info()["lags"]
+        cap = max(lags, 1)
         rows, count = (_capi.pbTimeCorrelationRow * cap)(), C.c_ulonglong(0)
-        if lib().pbHostTimeCorrelationRows(self._h, rows, cap, C.byref(count)) != 0:
-            raise RuntimeError("time_correlation: the time correlation needs the fused engine, the correlation on and "
-                               "fewer than 2^31 samples per lag")
-        return [[_capi.time_correlation_row(r) for r in rows[:int(count.value)]]]
+        self._call("pbHostTimeCorrelationRows", "time_correlation: the time correlation needs the fused engine, the "
+                   "correlation on and fewer than 2^31 samples per lag", rows, cap, C.byref(count))
+        return _analysis.lag_table(1, lags, lambda g: _capi.row_dict(rows[g]))
 
     def set_scattering(self, interval, lags, box_log2, vectors):
         """Keep a device ring of `lags` snapshots of the quantised positions, taken as the time correlation takes its
         own, and sum the integer phasors of every bot's displacement per lag and wavevector
         (2 pi / 2^box_log2)(nx, ny) of `vectors` over all time origins (pbSimSetScattering; fused engine only).
         Restarts at record 0; lags 0 switches it off."""
-        vec = _capi.sk_vectors(vectors if vectors is not None else np.zeros((0, 2), np.int32))
-        held = vec if vec.shape[0] else np.zeros((1, 2), np.int32)
-        if lib().pbHostSetScattering(self._h, float(interval), int(lags), int(box_log2), _ptr(held), vec.shape[0]) != 0:
-            raise RuntimeError("set_scattering: the scattering needs the fused engine, a finite interval >= 0 (or -1), "
-                               "at most 64 lags, box_log2 in -8 ... 12 and 1 ... 256 vectors")
+        held, nvec = _analysis.held_vectors(vectors if vectors is not None else np.zeros((0, 2), np.int32))
+        self._call("pbHostSetScattering", "set_scattering: the scattering needs the fused engine, a finite interval >= 0 "
+                   "(or -1), at most 64 lags, box_log2 in -8 ... 12 and 1 ... 256 vectors", float(interval), int(lags),
+                   int(box_log2), _ptr(held), nvec)
 
     def scattering_record(self):
         """One record now, of the state as it is (pbSimScatteringRecord; fused engine only)."""
-        if lib().pbHostScatteringRecord(self._h) != 0:
-            raise RuntimeError("scattering_record: the scattering needs the fused engine and the scattering on")
+        self._call("pbHostScatteringRecord",
+                   "scattering_record: the scattering needs the fused engine and the scattering on")
 
     def scattering_info(self):
         """A dict of interval, lags (0: off), box_log2, nvec and records taken so far (pbSimGetScatteringInfo; fused
         engine only)."""
-        i, l, e, k, r = C.c_float(0.0), C.c_uint(0), C.c_int(0), C.c_uint(0), C.c_ulonglong(0)
-        if lib().pbHostScatteringInfo(self._h, C.byref(i), C.byref(l), C.byref(e), C.byref(k), C.byref(r)) != 0:
-            raise RuntimeError("scattering_info: the scattering needs the fused engine")
-        return {"interval": float(i.value), "lags": int(l.value), "box_log2": int(e.value), "nvec": int(k.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.SCATTERING_INFO, partial(
+            self._call, "pbHostScatteringInfo", "scattering_info: the scattering needs the fused engine"))
 
     def scattering(self):
         """The table as it stands, as Sim.scattering gives it: a list with one list over lags of lists over the vectors
@@ -507,110 +490,92 @@ class HostSim:
         lags, nvec = info["lags"], info["nvec"]
         cap = max(lags * nvec, 1)
         rows, count = (_capi.pbScatteringRow * cap)(), C.c_ulonglong(0)
-        if lib().pbHostScatteringRows(self._h, rows, cap, C.byref(count)) != 0:
-            raise RuntimeError("scattering: the scattering needs the fused engine, the scattering on and fewer than "
-                               "2^31 samples per lag")
-        return [[[_capi.scattering_row(rows[l * nvec + k]) for k in range(nvec)] for l in range(lags)]]
+        self._call("pbHostScatteringRows", "scattering: the scattering needs the fused engine, the scattering on and "
+                   "fewer than 2^31 samples per lag", rows, cap, C.byref(count))
+        return _analysis.lag_table(1, lags, lambda g: _capi.row_dict(rows[g]), nvec)
 
     def set_van_hove(self, interval, lags, width, bins):
         """Keep a device ring of `lags` position snapshots, one per step whose start passes the schedule's gate at
         `interval` (0: every step, -1: only by van_hove_record()), and add every record against the `lags` latest ones
         into exact integer histograms of the displacement per lag: `bins` radial bins of `width` and 2 bins of each
         component (pbSimSetVanHove; fused engine only).  Restarts at record 0; lags 0 switches it off."""
-        if lib().pbHostSetVanHove(self._h, float(interval), int(lags), float(width), int(bins)) != 0:
-            raise RuntimeError("set_van_hove: the van Hove function needs the fused engine, a finite interval >= 0 (or "
-                               "-1), lags <= 64, a width in (0, 2048) and 1 ... 1024 bins")
+        self._call("pbHostSetVanHove", "set_van_hove: the van Hove function needs the fused engine, a finite interval "
+                   ">= 0 (or -1), lags <= 64, a width in (0, 2048) and 1 ... 1024 bins", float(interval), int(lags),
+                   float(width), int(bins))
 
     def van_hove_record(self):
         """One record now, of the state as it is (pbSimVanHoveRecord; fused engine only)."""
-        if lib().pbHostVanHoveRecord(self._h) != 0:
-            raise RuntimeError("van_hove_record: the van Hove function needs the fused engine and the analysis on")
+        self._call("pbHostVanHoveRecord",
+                   "van_hove_record: the van Hove function needs the fused engine and the analysis on")
 
     def van_hove_info(self):
         """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveInfo; fused engine
         only)."""
-        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
-        if lib().pbHostVanHoveInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b), C.byref(r)) != 0:
-            raise RuntimeError("van_hove_info: the van Hove function needs the fused engine")
-        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.VAN_HOVE_INFO, partial(
+            self._call, "pbHostVanHoveInfo", "van_hove_info: the van Hove function needs the fused engine"))
 
     def van_hove(self):
         """The table as it stands, as Sim.van_hove gives it: a list with one list over lags of dicts of Python ints, the
         histograms radial, x and y as lists (Particlebot::vanHoveRows; fused engine only)."""
-        from . import van_hove_lists
         info = self.van_hove_info()
         lags, bins = info["lags"], info["bins"]
         cap = max(lags, 1)
         rows, counts = (_capi.pbVanHoveRow * cap)(), (C.c_ulonglong * max(cap * 5 * bins, 1))()
         count = C.c_ulonglong(0)
-        if lib().pbHostVanHoveRows(self._h, rows, counts, cap, C.byref(count)) != 0:
-            raise RuntimeError("van_hove: the van Hove function needs the fused engine, the analysis on and fewer than "
-                               "2^31 samples per lag")
-        return van_hove_lists(rows, counts, 1, lags, bins)
+        self._call("pbHostVanHoveRows", "van_hove: the van Hove function needs the fused engine, the analysis on and "
+                   "fewer than 2^31 samples per lag", rows, counts, cap, C.byref(count))
+        return _analysis.van_hove_lists(rows, counts, 1, lags, bins)
 
     def set_van_hove_distinct(self, interval, lags, width, bins):
         """Keep a device ring of `lags` position snapshots, taken as set_van_hove() takes them, and add every record
         against the `lags` latest ones into exact integer counts per lag of the ordered pairs (a bot then, another bot
         now) by distance: `bins` bins of `width` (pbSimSetVanHoveDistinct; fused engine only).  Restarts at record 0;
         lags 0 switches it off."""
-        if lib().pbHostSetVanHoveDistinct(self._h, float(interval), int(lags), float(width), int(bins)) != 0:
-            raise RuntimeError("set_van_hove_distinct: the distinct van Hove function needs the fused engine, a finite "
-                               "interval >= 0 (or -1), lags <= 64, 1 ... 1024 bins and a width with bins * width < 2048")
+        self._call("pbHostSetVanHoveDistinct", "set_van_hove_distinct: the distinct van Hove function needs the fused "
+                   "engine, a finite interval >= 0 (or -1), lags <= 64, 1 ... 1024 bins and a width with bins * width < "
+                   "2048", float(interval), int(lags), float(width), int(bins))
 
     def van_hove_distinct_record(self):
         """One record now, of the state as it is (pbSimVanHoveDistinctRecord; fused engine only)."""
-        if lib().pbHostVanHoveDistinctRecord(self._h) != 0:
-            raise RuntimeError("van_hove_distinct_record: the distinct van Hove function needs the fused engine and the "
-                               "analysis on")
+        self._call("pbHostVanHoveDistinctRecord", "van_hove_distinct_record: the distinct van Hove function needs the "
+                   "fused engine and the analysis on")
 
     def van_hove_distinct_info(self):
         """A dict of interval, lags (0: off), width, bins and records taken so far (pbSimGetVanHoveDistinctInfo; fused
         engine only)."""
-        i, l, w, b, r = C.c_float(0.0), C.c_uint(0), C.c_float(0.0), C.c_uint(0), C.c_ulonglong(0)
-        if lib().pbHostVanHoveDistinctInfo(self._h, C.byref(i), C.byref(l), C.byref(w), C.byref(b), C.byref(r)) != 0:
-            raise RuntimeError("van_hove_distinct_info: the distinct van Hove function needs the fused engine")
-        return {"interval": float(i.value), "lags": int(l.value), "width": float(w.value), "bins": int(b.value),
-                "records": int(r.value)}
+        return _analysis.read_info(_analysis.VAN_HOVE_DISTINCT_INFO, partial(
+            self._call, "pbHostVanHoveDistinctInfo",
+            "van_hove_distinct_info: the distinct van Hove function needs the fused engine"))
 
     def van_hove_distinct(self):
         """The table as it stands, as Sim.van_hove_distinct gives it: a list with one list over lags of dicts of Python
         ints with `counts` as a list (Particlebot::vanHoveDistinctRows; fused engine only)."""
-        from . import van_hove_distinct_lists
         info = self.van_hove_distinct_info()
         lags, bins = info["lags"], info["bins"]
         cap = max(lags, 1)
         rows, counts = (_capi.pbVanHoveDistinctRow * cap)(), (C.c_ulonglong * max(cap * bins, 1))()
         count = C.c_ulonglong(0)
-        if lib().pbHostVanHoveDistinctRows(self._h, rows, counts, cap, C.byref(count)) != 0:
-            raise RuntimeError("van_hove_distinct: the distinct van Hove function needs the fused engine, the analysis "
-                               "on and fewer than 2^31 centres per lag")
-        return van_hove_distinct_lists(rows, counts, 1, lags, bins)
+        self._call("pbHostVanHoveDistinctRows", "van_hove_distinct: the distinct van Hove function needs the fused "
+                   "engine, the analysis on and fewer than 2^31 centres per lag", rows, counts, cap, C.byref(count))
+        return _analysis.van_hove_distinct_lists(rows, counts, 1, lags, bins)
 
     def field_map(self, nx, ny, center, half, member=None):
         """A field map of the state as it is now, on the device (pbSimFieldMap; fused engine only): (cells, totals) as
         Sim.field_map gives them, cells shaped (1, ny, nx), or (ny, nx) with a single totals dict for member=0."""
         view = _capi.field_view(nx, ny, center, half)
-        fits = 1 <= int(nx) <= 1024 and 1 <= int(ny) <= 1024
-        cells = np.zeros((1, int(ny), int(nx)) if fits else (1, 1, 1), _capi.FIELD_CELL_DTYPE)
-        tot = _capi.pbFieldTotals()
-        if lib().pbHostFieldMap(self._h, C.byref(view), _ptr(cells), C.byref(tot)) != 0:
-            raise RuntimeError("field_map: the field map needs the fused engine, 1 ... 1024 cells per axis and finite "
-                               "half extents > 0")
-        totals = [_capi.field_totals(tot)]
+        cells, tot = _analysis.field_cells(1, nx, ny), _capi.pbFieldTotals()
+        self._call("pbHostFieldMap", "field_map: the field map needs the fused engine, 1 ... 1024 cells per axis and "
+                   "finite half extents > 0", C.byref(view), _ptr(cells), C.byref(tot))
+        totals = [_capi.row_dict(tot)]
         return (cells, totals) if member is None else (cells[int(member)], totals[int(member)])
 
     def structure_factor(self, vectors, box_log2, kind="density", member=None):
         """The structure factor of the state as it is now, on the device (pbSimStructureFactor; fused engine only): the
         rows as Sim.structure_factor gives them, shaped (1, nvec), or (nvec,) for member=0."""
-        vec, code = _capi.sk_vectors(vectors), _capi.sk_kind(kind)
-        nvec = vec.shape[0]
-        fits = 1 <= nvec <= _capi.SK_MAX_VECTORS
-        rows = np.zeros((1, nvec if fits else 1), _capi.SK_ROW_DTYPE)
-        held = vec if nvec else np.zeros((1, 2), np.int32)
-        if lib().pbHostStructureFactor(self._h, code, int(box_log2), _ptr(held), nvec, _ptr(rows)) != 0:
-            raise RuntimeError("structure_factor: the structure factor needs the fused engine, a known kind, box_log2 "
-                               "in -8 ... 12 and 1 ... 4096 vectors")
+        (held, nvec), code = _analysis.held_vectors(vectors), _capi.sk_kind(kind)
+        rows = _analysis.structure_factor_rows(1, nvec)
+        self._call("pbHostStructureFactor", "structure_factor: the structure factor needs the fused engine, a known "
+                   "kind, box_log2 in -8 ... 12 and 1 ... 4096 vectors", code, int(box_log2), _ptr(held), nvec, _ptr(rows))
         return rows if member is None else rows[int(member)]
 
     def save_checkpoint(self, path):

@@ -429,7 +429,7 @@ def test_scattering_row_and_summary_on_known_integers():
     import particlerobotsimulations_amd as pb
     from particlerobotsimulations_amd import _capi
     r = _capi.pbScatteringRow(lag=3, nx=-2, ny=5, reserved=0, origins=5, sum_steps=60, samples=16, re=-(3 << 30), im=1 << 29)
-    d = _capi.scattering_row(r)
+    d = _capi.row_dict(r)
     assert d == {"lag": 3, "nx": -2, "ny": 5, "origins": 5, "sum_steps": 60, "samples": 16, "re": -(3 << 30), "im": 1 << 29}
     assert tuple(d) == XR.FIELDS
     assert pb.scattering_summary(d) == {"fs_re": -3 / 16, "fs_im": 1 / 32, "mean_lag_steps": 12.0}

@@ -317,7 +317,7 @@ def test_moments_row_composes_the_128_bit_sums():
     r.xx.lo, r.xx.hi = (1 << 33) + 5, 3         # a low accumulator beyond 2^32
     r.xy.lo, r.xy.hi = 6, -2                    # a negative signed sum
     r.vv.lo, r.vv.hi = (1 << 60) - 1, (1 << 59)
-    d = _capi.moments_row(r)
+    d = _capi.row_dict(r)
     assert d["xx"] == (3 << 32) + (1 << 33) + 5 and d["xy"] == -(2 << 32) + 6 and d["yy"] == d["rr"] == 0
     assert d["vv"] == (1 << 91) + (1 << 60) - 1
     assert (d["step"], d["time"], d["measured"], d["sum_qx"], d["sum_wx"], d["min_qx"]) == (9, 1.25, 3, -5, -13, -4)

@@ -333,6 +333,6 @@ def test_deformation_gradient_and_mean_d2min_on_known_integers():
     r = _capi.pbStrainStats(fitted=5, unfitted=2, above=1, reserved=0, bonds_used=30, bonds_dropped=3, max_d2=11)
     r.xxy.lo, r.xxy.hi = 7, -1
     r.w.lo, r.w.hi = 9, 1 << 40
-    d = _capi.strain_row(r)
+    d = _capi.row_dict(r)
     assert d["xxy"] == 7 - (1 << 32) and d["w"] == (1 << 72) + 9 and d["fitted"] == 5 and d["bonds_dropped"] == 3
     assert tuple(d) == SR.FIELDS

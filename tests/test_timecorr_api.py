@@ -464,7 +464,7 @@ def test_time_correlation_row_composes_the_128_bit_sums():
                                    max_q2=1 << 62)
     r.msd.lo, r.msd.hi = 5, 3
     r.vacf.lo, r.vacf.hi = 6, -2  # a negative signed sum, normalised: 0 <= lo < 2^32, hi the floor quotient
-    d = _capi.time_correlation_row(r)
+    d = _capi.row_dict(r)
     assert d == {"lag": 3, "origins": 5, "sum_steps": 60, "samples": 15, "sum_qx": -5, "sum_qy": 7, "msd": (3 << 32) + 5,
                  "vacf": -(2 << 32) + 6, "overlap": 4, "max_q2": 1 << 62}
     assert tuple(d) == TR.FIELDS

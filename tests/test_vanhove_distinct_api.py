@@ -5,7 +5,7 @@ pbSimGetVanHoveDistinct, csrc/pb_vanhove_distinct.hip).
    as a stand-alone program, built plainly and under AddressSanitizer and UBSan.
 2. The C-ABI entries are declared, exported and reject bad arguments before they touch the device.
 3. The runner knows --vanhove-distinct and its options; the placement-only host engine has no such analysis.
-4. van_hove_distinct_row and van_hove_distinct_lists on known integers.
+4. row_dict on a pbVanHoveDistinctRow and van_hove_distinct_lists on known integers.
 (tests/test_vanhove_distinct_ref.py holds the reference's own tests.)"""
 import ctypes as C
 import os
@@ -215,7 +215,7 @@ def test_rows_and_lists_on_known_integers():
         rows[g] = _capi.pbVanHoveDistinctRow(lag=g % 2, reserved=0, origins=5 - g % 2, sum_steps=60 * (g % 2),
                                              centres=(1 << 40) + g, partners=(1 << 33) + g, pairs=9 * g + 3)
     counts = (C.c_ulonglong * 12)(*range(12))
-    d = _capi.van_hove_distinct_row(rows[3])
+    d = _capi.row_dict(rows[3])
     assert d == {"lag": 1, "origins": 4, "sum_steps": 60, "centres": (1 << 40) + 3, "partners": (1 << 33) + 3, "pairs": 30}
     assert tuple(d) == DR.FIELDS
     out = pb.van_hove_distinct_lists(rows, counts, 2, 2, 3)
