@@ -296,6 +296,17 @@ class Particlebot {
   bool vanHoveDistinctInfo(float &interval, unsigned &lags, float &binWidth, unsigned &bins,
                            unsigned long long &records);
   bool vanHoveDistinctRows(std::vector<pbVanHoveDistinctRow> &rows, std::vector<unsigned long long> &counts);
+  /* The coherent intermediate scattering function of the resident state on the device (pbSimSetCoherent /
+   * pbSimGetCoherent, include/particlebot_hip.h has the definitions), shaped as the scattering above:
+   * setCoherent(interval, lags, boxLog2, vectors) keeps a device ring of `lags` records of the density modes
+   * rho(k) of `vectors` and, per lag and wavevector, the exact 192-bit integer sums of rho_now conj(rho_then) over all
+   * time origins; lags 0 switches it off.  coherentRecord takes one record now; coherentInfo gives interval, lags,
+   * boxLog2, the vectors' count and the records taken so far; coherentRows the lags * nvec rows, lag-major.  Fused engine
+   * only: Legacy and HostOnly instances return false with a message on stderr.  Not part of a checkpoint. */
+  bool setCoherent(float interval, unsigned lags, int boxLog2, const std::vector<int> &vectors);
+  bool coherentRecord();
+  bool coherentInfo(float &interval, unsigned &lags, int &boxLog2, unsigned &nvec, unsigned long long &records);
+  bool coherentRows(std::vector<pbCoherentRow> &rows);
   /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
    * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on

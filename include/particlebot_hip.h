@@ -890,7 +890,7 @@ int pbSimGetFieldTimes(pbSim *sim, unsigned long long *maps, float *last_device_
  * per member, and 16 / 32 / 64 bytes per member and wavevector (density / radius / velocity) of the largest call so
  * far, allocated by the first call, grown when a call needs more, freed by pbSimDestroy.
  * Out of scope: per-lag k-space quantities other than the self-intermediate scattering function (pbSimSetScattering,
- * below); phase moments, phase
+ * below) and the coherent one (pbSimSetCoherent, further below); phase moments, phase
  * correlations and phase fields on the table; a finer table or an angle-addition refinement; radial averaging of S(k)
  * and normalisations; records inside the series ring; the ensemble layer's summary rows; the legacy engine. */
 #define PB_SK_MAX_VECTORS 4096u
@@ -974,9 +974,9 @@ int pbPhasorTable(int *cosSin /* 2 * 4096, interleaved */, unsigned cap);
  * busy.  A lane owns one vector and keeps re and im in registers; at the end the stripes of a wave are folded with
  * shuffles and one lane per wave and vector adds into the cell with 64-bit integer atomics.  Read back: 16 bytes per
  * (member, lag, vector) and 8 per (member, lag).
- * Out of scope: the coherent F(k, tau) (a product of two rho(k) sums does not fit the exact scheme; a caller can form it
- * from pbSimStructureFactor per record); chi_4; weights other than 1; logarithmic lag spacing; the ensemble layer's
- * summary rows; the legacy engine. */
+ * Out of scope: chi_4; weights other than 1; logarithmic lag spacing; the ensemble layer's summary rows;
+ * the legacy engine.  (The coherent F(k, tau), a product of two rho(k) sums, has a recorder of its own:
+ * pbSimSetCoherent, below.) */
 #define PB_SCATTER_MAX_LAGS 64u
 #define PB_SCATTER_MAX_VECTORS 256u
 #define PB_SCATTER_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
@@ -1144,8 +1144,8 @@ int pbSimGetVanHoveTimes(pbSim *sim, unsigned long long *records, float *last_de
  * most) and bins 32-bit counters (4 KiB at most) in LDS; at the end each non-zero counter is one 64-bit integer atomic.
  * Device memory: the ring, (2 + bins) x 8 bytes per member and lag, (bins + 1) x 8 bytes of edges, the shared scratch.
  * Out of scope: angle-resolved or two-dimensional (dx, dy) histograms; normalisation to g(r) or a density; one ring for
- * the self and the distinct part; logarithmic bins or lag spacing; the coherent F(k, tau); chi_4; the ensemble layer's
- * summary rows; the legacy engine. */
+ * the self and the distinct part; logarithmic bins or lag spacing; chi_4; the ensemble layer's summary rows; the legacy
+ * engine.  (The reciprocal-space companion is pbSimSetCoherent, below.) */
 typedef struct pbVanHoveDistinctRow {  /* 48 bytes */
   unsigned lag, reserved;              /* lag in RECORDS: record r against record r - lag; 0 */
   unsigned long long origins;          /* record pairs added so far (the same for every member) */
@@ -1161,6 +1161,113 @@ int pbSimGetVanHoveDistinctInfo(pbSim *sim, float *interval, unsigned *lags, flo
 int pbSimGetVanHoveDistinct(pbSim *sim, pbVanHoveDistinctRow *rows /* nsims * lags, or NULL */,
                             unsigned long long *counts /* nsims * lags * bins, or NULL; not both NULL */);
 int pbSimGetVanHoveDistinctTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
+
+/* Coherent intermediate scattering on the device (csrc/pb_coherent.hip; the arithmetic is csrc/pb_coherent.hpp): the
+ * collective companion of pbSimSetScattering in reciprocal space, as the distinct van Hove function is in real space.
+ *     F(k, tau) = < (1/N) rho_k(t + tau) conj(rho_k(t)) >_t ,    rho_k(t) = sum_i exp(i k . r_i(t))
+ * per member, lag and wavevector of a caller's list, averaged over time origins while pbSimStep runs, as exact integers:
+ * how a density fluctuation of a given wavelength decays (the real part) or travels (the imaginary part).  With the same
+ * list given to both recorders F - F_s is the distinct part in k-space, and lag 0 is the time-averaged S(k).  The book,
+ * the records and the pairing are the time correlation's (pbSimSetTimeCorrelation, above); the nodes, the measured rule,
+ * the turn, the index and the table are the structure factor's.  Off by default: a run that does not ask for it makes
+ * the same launches, has the same pbSimStats and the same bits, and nothing is allocated.
+ * pbSimSetCoherent(sim, interval, lags, boxLog2, vectors, nvec).  interval, lags, boxLog2 and the list follow
+ * pbSimSetScattering exactly: interval > 0 the schedule's gate, 0 every step, -1.0f manual only.  lags is
+ * 1 ... PB_COHERENT_MAX_LAGS; lags == 0 switches off and frees everything (boxLog2, vectors and nvec are then not read).
+ * boxLog2 is e of the box L = 2^e, PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2.  vectors holds nvec int pairs (nx, ny), nvec
+ * 1 ... PB_COHERENT_MAX_VECTORS, each any int; k = (2 pi / L)(nx, ny).  The list is copied at the call.  Calling again
+ * restarts from record 0 with a zeroed table.
+ * A RECORD is taken at the same instant and describes the same state as the other recorders' records.  Nodes, the
+ * measured rule and the quantisation are PB_SK_DENSITY's: every bot of a member is a node, and a bot is MEASURED iff x
+ * and y are in range.  Per member and wavevector the record computes the MODE
+ *     (C, S) = (sum C[idx], sum S[idx])   over the measured bots, units of 2^-30
+ * with the turn, the index and the table of pbSimStructureFactor, and the member's measured count.  By definition these
+ * are the re, im and measured of pbSimStructureFactor(PB_SK_DENSITY) for the same state, list and box.  They go into
+ * slot r % lags of a ring of modes: 16 bytes per (slot, member, vector) and 4 per (slot, member).  No per-bot snapshot
+ * is kept, and the N x nvec table look-ups are done once per record, not once per lag.
+ * PAIRING.  Record r is paired with the records r - l for l = 0 ... min(r, lags - 1).  Per member, lag and vector, on
+ * exact integers:
+ *     re += C_now * C_then + S_now * S_then
+ *     im += S_now * C_then - C_now * S_then
+ *     bots_now += measured_now
+ *     bots_then += measured_then
+ * which is rho_now conj(rho_then) in units of 2^-60.  Lag 0 pairs a record with itself: im == 0 and
+ * re = sum (C^2 + S^2), the summed numerators of S(k).
+ * EXACTNESS.  |C|, |S| <= measured * 2^30 < 2^58 (a batch has fewer than 2^28 bots).  So each product is below 2^116 in
+ * magnitude and each of re's and im's increments, a sum or a difference of two products, below 2^117.  With fewer than
+ * 2^31 origins a sum stays below 2^148: a signed 192-bit two's-complement word in three little-endian 64-bit limbs holds
+ * it, whatever the state.  A (member, lag, vector) cell has one owner on the device, which adds with carries through
+ * the limbs: no atomic wider than 64 bits and no float atomics.  Integer adds commute: results do not depend on slot
+ * order, on the kernel form that stepped or on the order in which the device adds.  pbSimGetCoherent answers PB_ERR_ARG
+ * ("a lag holds 2^31 origins or more: restart the coherent scattering") and writes nothing if a lag has 2^31 origins
+ * or more; the count is the host's own, so nothing is read back first.
+ * PER MEMBER, LAG AND WAVEVECTOR one pbCoherentRow: lag in RECORDS; nx, ny as passed; origins and sum_steps as in
+ * pbScatteringRow; bots_now and bots_then, the measured counts of the later and of the earlier record summed over the
+ * origins (the same for every vector of a member and lag); re and im, each value = limb[0] + limb[1] 2^64 + limb[2] 2^128
+ * read as a signed 192-bit two's-complement word, units of 2^-60.  The caller forms F = re / (2^60 * bots_then) and the
+ * imaginary part likewise.
+ * ERROR AGAINST THE CONTINUOUS DEFINITION (derived, not measured).  Let eps be the per-bot bound of pbSimStructureFactor,
+ *     eps = pi / 4096 + 2 pi (|nx| + |ny|) 2^-21 / L + 2^-30.
+ * As a complex number a bot's table entry is within eps of exp(i k.r): the chord is no longer than the phase error, and
+ * the two roundings of at most 2^-31 each move the entry by less than 2^-30.  So each mode is within measured * eps of
+ * its float64 value, in magnitude, and a float64 mode is at most measured in magnitude.  With
+ * (a + da) conj(b + db) - a conj(b) = a conj(db) + da conj(b) + da conj(db), each origin's product is within
+ *     measured_now * measured_then * (2 eps + eps^2)
+ * of the float64 product in magnitude, hence in re and in im, when u does not wrap; a sum over origins adds the bounds.
+ * OTHER CALLS.  pbSimCoherentRecord: one record now, of the state as it is, whatever the interval.
+ * pbSimGetCoherentInfo: interval, lags (0: off), boxLog2, nvec and the records taken so far; any pointer may be NULL,
+ * not all.  pbSimGetCoherent: nsims * lags * nvec rows, member-major, then the lag, then the vector in list order; a lag
+ * that no record has reached yet has origins == 0 and zeros.  pbSimGetCoherentTimes: records so far and the span of the
+ * last record's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
+ * When several records are due in front of a step the order is: series, time correlation, scattering, van Hove,
+ * distinct van Hove, coherent scattering; then the centroid trail and the phase update.  No launch is fused across the
+ * gate and a resident stretch ends in front of it.
+ * The ring is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it alone; pbSimDestroy
+ * frees it.  Recording never waits for the device.  It only reads: the state, slot layout, keys, cell lists,
+ * pbSimStats, time, RNG, the mark and every other recorder's and analysis' memory stay as they were.
+ * PB_ERR_ARG, before the device is touched: a NULL handle, vectors or rows; interval NaN, infinite, or negative other
+ * than -1; lags > PB_COHERENT_MAX_LAGS; boxLog2 outside PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2; nvec outside
+ * 1 ... PB_COHERENT_MAX_VECTORS; a ring plus sums above 2^31 bytes (nsims x lags x nvec x (16 + 48): the modes and the
+ * sums; with the cell's two counts the footprint at that bound is 2.5 GiB, see Device memory below); a batch of more
+ * than 65535 members or of 2^28 bots or more (neither is asked when lags == 0: any batch may switch off); the pointers of
+ * pbSimGetCoherentInfo all NULL; a record or a read with the coherent scattering off.
+ * Cost: a record zeroes its slot, makes one pass over posrad in slot order (the original indices are never read) with
+ * measured * nvec table look-ups, and one small launch for all lags.  The first grid is (bot block, member), at most
+ * PB_COHERENT_BLOCKS blocks per member: a workgroup of 256 lanes keeps the table in LDS (32 KiB), stages 256 quantised
+ * bots at a time and walks them with its lanes laid out as (stripe, vector), nvec rounded up to a power of two Vp and
+ * 256 / Vp stripes, so that 8 ... 64 vectors keep every lane busy; the stripes of a wave are folded with shuffles and
+ * one lane per wave and vector adds into the mode with 64-bit integer atomics.  The second has one lane per (member, lag,
+ * vector): four 64 x 64 -> 128-bit products and a cell of eight 64-bit words updated with plain loads and stores.
+ * Device memory: 80 bytes per (member, lag, vector), 16 of the ring's mode and 64 of the cell (48 of sums, 16 of counts);
+ * 4 bytes per (member, lag) of measured counts; the phasor table and the list.  Read back: the cells.
+ * Measured on one MI355X, medians of 20 records into a full ring (profiles/coherent_scattering.txt): the 10^6-bot arena
+ * 0.048 / 0.080 / 0.179 ms with 8 / 24 / 256 vectors at 16 lags and the same at 64; a scattering record with the same
+ * list 0.23 / 0.34 / 1.80 ms at 16 lags and 0.64 / 1.15 / 6.84 ms at 64; one pbSimStructureFactor(PB_SK_DENSITY) call
+ * with its read-back, the route a caller had per sample before, 0.23 / 0.23 / 0.24 ms.  256 members of 1000 bots:
+ * 0.021 / 0.025 / 0.075 ms at 16 lags and 0.024 / 0.035 / 0.182 ms at 64 (at 256 vectors the per-lag launch shows).
+ * Out of scope: current correlations, that is weights other than 1 (the radius and velocity kinds have 128-bit modes and
+ * would need 256-bit products); chi_4; logarithmic lag spacing; radial averaging; the ensemble layer's summary rows; the
+ * legacy engine. */
+#define PB_COHERENT_MAX_LAGS 64u
+#define PB_COHERENT_MAX_VECTORS 256u
+#define PB_COHERENT_BLOCKS 256u /* bot blocks per member: one pass covers 65536 bots of a member */
+typedef struct pbCoherentRow {         /* 96 bytes */
+  unsigned lag;                        /* lag in RECORDS: record r against record r - lag */
+  int nx, ny;                          /* the wavevector's integers, as passed */
+  unsigned reserved;                   /* 0 */
+  unsigned long long origins;          /* record pairs added so far (the same for every member and vector) */
+  unsigned long long sum_steps;        /* sum over those pairs of step(r) - step(r - lag) */
+  unsigned long long bots_now;         /* sum over the origins of the bots measured at the later record */
+  unsigned long long bots_then;        /* ... at the earlier record */
+  unsigned long long re[3], im[3];     /* signed 192-bit sums, little-endian limbs; units of 2^-60 */
+} pbCoherentRow;
+int pbSimSetCoherent(pbSim *sim, float interval, unsigned lags, int boxLog2, const int *vectors /* 2 * nvec */,
+                     unsigned nvec);
+int pbSimCoherentRecord(pbSim *sim);   /* one record now, of the state as it is */
+int pbSimGetCoherentInfo(pbSim *sim, float *interval, unsigned *lags, int *boxLog2, unsigned *nvec,
+                         unsigned long long *records);
+int pbSimGetCoherent(pbSim *sim, pbCoherentRow *rows /* nsims * lags * nvec: member, lag, vector */);
+int pbSimGetCoherentTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
 /* Local strain and non-affine displacement D2min on the device (csrc/pb_strain.hip; the fit itself is
  * csrc/pb_strain.hpp): the Falk-Langer fit against the mark of the rearrangement analysis.  For every bot, the best

@@ -19,7 +19,7 @@ __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
            "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
            "half_plane_vectors", "phasor_table", "scattering_summary", "van_hove_summary",
-           "deformation_gradient", "mean_d2min"]
+           "deformation_gradient", "mean_d2min", "coherent_scattering_summary"]
 
 
 def phasor_table():
@@ -146,6 +146,19 @@ def scattering_summary(row):
     m, origins = int(row["samples"]), int(row["origins"])
     return {"fs_re": float(Fraction(int(row["re"]), m << 30)) if m else None,
             "fs_im": float(Fraction(int(row["im"]), m << 30)) if m else None,
+            "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else None}
+
+
+def coherent_scattering_summary(row):
+    """What one row of coherent_scattering() says, in float64 from the integers (pure Python; every quotient is formed
+    as one exact fraction and converted once): f_re = re / (2^60 bots_then), the coherent intermediate scattering
+    function F(k, lag), at lag 0 the time-averaged S(k); f_im = im / (2^60 bots_then), its imaginary part (a density
+    wave that travels along k); mean_lag_steps = sum_steps / origins.  The first two are None for a row with no
+    measured bot, the last for one with no origins."""
+    from fractions import Fraction
+    m, origins = int(row["bots_then"]), int(row["origins"])
+    return {"f_re": float(Fraction(int(row["re"]), m << 60)) if m else None,
+            "f_im": float(Fraction(int(row["im"]), m << 60)) if m else None,
             "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else None}
 
 
@@ -1008,6 +1021,43 @@ class Sim:
     def van_hove_distinct_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
         return self._span("pbSimGetVanHoveDistinctTimes")
+
+    def set_coherent_scattering(self, interval, lags, box_log2, vectors):
+        """Keep a device ring of `lags` records of the density modes rho(k) = sum exp(i k.r) of every member, one taken
+        in front of every step whose start time passes the schedule's gate at `interval` (0: every step, -1: only by
+        coherent_scattering_record()) while step() runs, and add the product of every record's modes with those of
+        the `lags` latest ones into a table per member, lag and wavevector k = (2 pi / 2^box_log2)(nx, ny) of
+        `vectors`, an (nvec, 2) array of ints, nvec 1 ... 256 (pbSimSetCoherent): the coherent intermediate scattering
+        function as exact 192-bit integer sums.  Restarts at record 0; lags 0 switches it off (vectors may then be
+        None).  Recording changes no state bit."""
+        if int(lags) == 0 and vectors is None:
+            vectors = np.zeros((0, 2), np.int32)
+        held, nvec = _analysis.held_vectors(vectors)
+        _capi.check(_capi.lib().pbSimSetCoherent(self._h, float(interval), int(lags), int(box_log2),
+                                                 _capi.np_ptr(held), nvec), "pbSimSetCoherent")
+
+    def coherent_scattering_record(self):
+        """One record now, of the state as it is (pbSimCoherentRecord)."""
+        _capi.check(_capi.lib().pbSimCoherentRecord(self._h), "pbSimCoherentRecord")
+
+    def coherent_scattering_info(self):
+        """A dict of interval, lags (0: off), box_log2, nvec and records taken so far (pbSimGetCoherentInfo)."""
+        return _analysis.read_info(_analysis.COHERENT_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetCoherentInfo(self._h, *p), "pbSimGetCoherentInfo"))
+
+    def coherent_scattering(self):
+        """The table as it stands (pbSimGetCoherent): per member a list over lags (lag 0 first) of lists over the
+        vectors (list order) of dicts of Python ints: lag, nx, ny, origins, sum_steps, bots_now, bots_then, re, im
+        (units of 2^-60).  coherent_scattering_summary() turns a row into F."""
+        info = self.coherent_scattering_info()
+        lags, nvec = info["lags"], info["nvec"]
+        rows = (_capi.pbCoherentRow * max(self.nsims * lags * nvec, 1))()
+        _capi.check(_capi.lib().pbSimGetCoherent(self._h, rows), "pbSimGetCoherent")
+        return _analysis.lag_table(self.nsims, lags, lambda g: _capi.coherent_row(rows[g]), nvec)
+
+    def coherent_scattering_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        return self._span("pbSimGetCoherentTimes")
 
 
 class Ensemble(Sim):

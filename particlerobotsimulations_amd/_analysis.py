@@ -17,6 +17,7 @@ SCATTERING_INFO = (("interval", C.c_float), ("lags", C.c_uint), ("box_log2", C.c
 VAN_HOVE_INFO = (("interval", C.c_float), ("lags", C.c_uint), ("width", C.c_float), ("bins", C.c_uint),
                  ("records", C.c_ulonglong))
 VAN_HOVE_DISTINCT_INFO = VAN_HOVE_INFO
+COHERENT_INFO = SCATTERING_INFO
 
 
 def read_info(spec, call):

@@ -295,6 +295,29 @@ class pbVanHoveDistinctRow(C.Structure):
                 ("centres", C.c_ulonglong), ("partners", C.c_ulonglong), ("pairs", C.c_ulonglong)]
 
 
+class pbCoherentRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("nx", C.c_int), ("ny", C.c_int), ("reserved", C.c_uint),
+                ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong), ("bots_now", C.c_ulonglong),
+                ("bots_then", C.c_ulonglong), ("re", C.c_ulonglong * 3), ("im", C.c_ulonglong * 3)]
+
+
+COHERENT_MAX_LAGS = 64
+COHERENT_MAX_VECTORS = 256
+
+
+def signed_192(limbs):
+    """The signed 192-bit two's-complement value of three little-endian 64-bit limbs as one Python int."""
+    v = int(limbs[0]) + (int(limbs[1]) << 64) + (int(limbs[2]) << 128)
+    return v - (1 << 192) if v >> 191 else v
+
+
+def coherent_row(r):
+    """A pbCoherentRow as a dict of Python ints: row_dict(r) with re and im composed from their limbs (units of 2^-60)."""
+    d = row_dict(r)
+    d["re"], d["im"] = signed_192(d["re"]), signed_192(d["im"])
+    return d
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -411,6 +434,12 @@ SYMBOLS = {
                                          C.POINTER(C.c_ulonglong)]),
     "pbSimGetVanHoveDistinct": (_I, [_VP, C.POINTER(pbVanHoveDistinctRow), C.POINTER(C.c_ulonglong)]),
     "pbSimGetVanHoveDistinctTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimSetCoherent": (_I, [_VP, _F, _U, _I, _VP, _U]),
+    "pbSimCoherentRecord": (_I, [_VP]),
+    "pbSimGetCoherentInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_I), C.POINTER(_U),
+                                  C.POINTER(C.c_ulonglong)]),
+    "pbSimGetCoherent": (_I, [_VP, C.POINTER(pbCoherentRow)]),
+    "pbSimGetCoherentTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1630,6 +1630,37 @@ bool Particlebot::vanHoveDistinctRows(std::vector<pbVanHoveDistinctRow> &rows,
   });
 }
 
+bool Particlebot::setCoherent(float interval, unsigned lags, int boxLog2, const std::vector<int> &vectors) {
+  return onFusedEngine("setCoherent", "coherent scattering", [&] {
+    const size_t nvec = vectors.size() / 2;
+    const int none[2] = {0, 0};  // (the engine takes no NULL; it refuses an empty list and one that is too long)
+    const unsigned count = (unsigned)(nvec <= PB_COHERENT_MAX_VECTORS ? nvec : PB_COHERENT_MAX_VECTORS + 1u);
+    return pbSimSetCoherent(sim, interval, lags, boxLog2, nvec ? vectors.data() : none, count);
+  });
+}
+
+bool Particlebot::coherentRecord() {
+  return onFusedEngine("coherentRecord", "coherent scattering", [&] { return pbSimCoherentRecord(sim); });
+}
+
+bool Particlebot::coherentInfo(float &interval, unsigned &lags, int &boxLog2, unsigned &nvec,
+                               unsigned long long &records) {
+  auto call = [&] { return pbSimGetCoherentInfo(sim, &interval, &lags, &boxLog2, &nvec, &records); };
+  return onFusedEngine("coherentInfo", "coherent scattering", call);
+}
+
+bool Particlebot::coherentRows(std::vector<pbCoherentRow> &rows) {
+  return onFusedEngine("coherentRows", "coherent scattering", [&] {
+    unsigned lags = 0, nvec = 0;
+    const int rc = pbSimGetCoherentInfo(sim, nullptr, &lags, nullptr, &nvec, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? (size_t)lags * nvec : 1, pbCoherentRow());  // (the engine takes no NULL; with the recorder off it refuses)
+    const int got = pbSimGetCoherent(sim, rows.data());
+    if (got != PB_OK) rows.clear();
+    return got;
+  });
+}
+
 bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
   return onFusedEngine("fieldMap", "field map", [&] {
     const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;

@@ -459,6 +459,7 @@ int pbHostTimeCorrelationRows(void *hv, pbTimeCorrelationRow *rows, unsigned lon
 // engines, a bad interval, lags, box or list, a record or a read with the scattering off, or too little room.
 int pbHostSetScattering(void *hv, float interval, unsigned lags, int boxLog2, const int *vectors, unsigned nvec) {
   if (!vectors && nvec) return -1;
+  if (nvec > PB_SCATTER_MAX_VECTORS) nvec = PB_SCATTER_MAX_VECTORS + 1u;  // (refused below all the same; a huge count is not read)
   return ((HostSim *)hv)->bot->setScattering(interval, lags, boxLog2, std::vector<int>(vectors, vectors + 2 * (size_t)nvec))
              ? 0
              : -1;
@@ -560,6 +561,44 @@ int pbHostVanHoveDistinctRows(void *hv, pbVanHoveDistinctRow *rows, unsigned lon
   if ((rows || counts) && cap < v.size()) return -1;
   copyOut(rows, v);
   copyOut(counts, c);
+  return 0;
+}
+
+// the coherent intermediate scattering function of the resident state (Particlebot::setCoherent / coherentRecord /
+// coherentInfo / coherentRows; fused engine only), shaped as the self part's: the 96-byte pbCoherentRow of every lag and
+// vector (cap entries of room; *count = how many there are).  -1 on the other engines, a bad interval, lags, box or
+// list, a record or a read with the recorder off, or too little room.
+int pbHostSetCoherent(void *hv, float interval, unsigned lags, int boxLog2, const int *vectors, unsigned nvec) {
+  if (!vectors && nvec) return -1;
+  if (nvec > PB_COHERENT_MAX_VECTORS) nvec = PB_COHERENT_MAX_VECTORS + 1u;  // (refused below all the same; a huge count is not read)
+  return ((HostSim *)hv)->bot->setCoherent(interval, lags, boxLog2, std::vector<int>(vectors, vectors + 2 * (size_t)nvec))
+             ? 0
+             : -1;
+}
+
+int pbHostCoherentRecord(void *hv) { return ((HostSim *)hv)->bot->coherentRecord() ? 0 : -1; }
+
+int pbHostCoherentInfo(void *hv, float *interval, unsigned *lags, int *boxLog2, unsigned *nvec,
+                       unsigned long long *records) {
+  float i = 0.0f;
+  unsigned l = 0, k = 0;
+  int e = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->coherentInfo(i, l, e, k, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (boxLog2) *boxLog2 = e;
+  if (nvec) *nvec = k;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostCoherentRows(void *hv, pbCoherentRow *rows, unsigned long long cap, unsigned long long *count) {
+  std::vector<pbCoherentRow> v;
+  if (!count || !((HostSim *)hv)->bot->coherentRows(v)) return -1;
+  *count = v.size();
+  if (rows && cap < v.size()) return -1;
+  copyOut(rows, v);
   return 0;
 }
 

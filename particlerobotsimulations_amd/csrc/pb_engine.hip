@@ -636,9 +636,9 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   const bool resident = pbResidentWanted(S);
   // The host events that are on, in firing order: the records of the time series (pb_moments.hip), the time
   // correlations (pb_timecorr.hip), the scattering (pb_scatter.hip), the van Hove function (pb_vanhove.hip) and its
-  // distinct part (pb_vanhove_distinct.hip), the centroid trail, the phase update.  A new recorder is one more entry;
-  // the loop below does not name them.
-  PbHostEvent events[7];
+  // distinct part (pb_vanhove_distinct.hip), the coherent scattering (pb_coherent.hip), the centroid trail, the phase
+  // update.  A new recorder is one more entry; the loop below does not name them.
+  PbHostEvent events[8];
   int nEvents = 0;
   if (S->series.ring) events[nEvents++] = {true, true, S->series.interval, pbSeriesRecord};
   if (S->tc.lag.ring)
@@ -649,6 +649,8 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     events[nEvents++] = {true, true, S->vh.lag.interval, [](pbSim *B, float) { return pbVanHoveRecord(B); }};
   if (S->vd.lag.ring)
     events[nEvents++] = {true, true, S->vd.lag.interval, [](pbSim *B, float) { return pbVanHoveDistinctRecord(B); }};
+  if (S->co.lag.ring)
+    events[nEvents++] = {true, true, S->co.lag.interval, [](pbSim *B, float) { return pbCoherentRecord(B); }};
   if (S->trail.ring) events[nEvents++] = {false, false, S->trail.interval, trailRecord};
   if (lightWave)
     events[nEvents++] = {false, false, S->host.phase_update_interval, [](pbSim *B, float) { return phaseUpdate(B); }};
@@ -825,6 +827,7 @@ int pbSimCreateBatch(pbSim **out, const SimParams *params, int nsims, float wall
     if (const char *v = getenv("PB_XCD_MEMBERS")) S->xcdMembers = atoi(v) != 0;
     if (const char *v = getenv("PB_XCD_TILES_ALL")) S->xcdTilesAll = atoi(v) != 0;
     if (const char *v = getenv("PB_STREAM_WALK")) rc |= pbSimSetStreamWalk(S, atoi(v));
+    if (const char *v = getenv("PB_COHERENT_STRIPES")) S->coherentStripes = atoi(v) != 0;  // (tools/coherent_cost.py)
     if (rc != PB_OK) {
       pbLastError() = "pbSimCreateBatch: PB_FORCE_VARIANT / PB_LANES_PER_BOT / PB_RESIDENT out of range";
       return PB_ERR_ARG;

@@ -22,6 +22,8 @@
 //   pb_vanhove.hip   self van Hove function: displacement histograms per lag over a lag ring (pbSimSetVanHove)
 //   pb_vanhove_distinct.hip  distinct van Hove function: pair histograms per lag, a neighbour sweep around every bot's
 //                    earlier position (pbSimSetVanHoveDistinct)
+//   pb_coherent.hip  coherent intermediate scattering: a ring of density modes per member and wavevector, and 192-bit
+//                    sums of their products per lag (pbSimSetCoherent); pb_coherent.hpp holds the arithmetic
 //   pb_strain.hip    local strain and D2min: the Falk-Langer fit of every bot's marked bonds onto its present ones, a
 //                    gather over the rearrangement analysis' mark (pbSimStrainStats); pb_strain.hpp holds the fit
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
@@ -97,17 +99,19 @@ struct PbSeries {
   std::vector<float> times;               // per slot: start time of the step the record was taken in front of
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
-// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip, pb_vanhove_distinct.hip)
-// share ------------------------------------------------------------------------------------------------------------------
+// ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip,
+// pb_vanhove_distinct.hip, pb_coherent.hip) share ------------------------------------------------------------------------
 // A ring of `lags` snapshots of the whole batch in ORIGINAL order, lags x total entries of Snap.  Record r goes into
 // slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1); all pairs of a record are added
 // into `table` by one launch over pbLagGrid() workgroups of PB_LAG_LANES lanes, which pbLagPair() takes apart again.
+// (The coherent scattering keeps modes, not bots: lags x nsims x nvec entries, which a kernel of its own pairs.)
 // Everything that knows this format is in this file: the book and the ring value here, pbLagPair (device) and the
 // pbLag... host functions behind pbSim.  An analysis adds its snapshot kernel, its accumulate body and its row writer.
 constexpr int PB_LAG_LANES = 256;
 constexpr unsigned PB_LAG_MAX_LAGS = 64u, PB_LAG_BLOCKS = 256u;  // (the public header states both per analysis)
 static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS &&
-                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS, "one bound on the lags");  // (the distinct part uses the self part's)
+                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS && PB_COHERENT_MAX_LAGS == PB_LAG_MAX_LAGS,
+              "one bound on the lags");  // (the distinct part uses the self part's)
 static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS &&
                   PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS, "one bound on the blocks per lag");
 
@@ -213,6 +217,18 @@ struct PbVanHove {
   PbDevBuf<unsigned long long> edges;  // bins + 1: E_k = min((k qw)^2, 2^63)
 };
 
+// coherent intermediate scattering (pb_coherent.hip): a ring of lags x nsims x nvec modes (C, S) with lags x nsims
+// measured counts beside it, and nsims x lags x nvec cells of eight words (pb_coherent.hpp; pbSimSetCoherent)
+struct PbCoherent {
+  PbLagRing<ulonglong2> lag;    // the modes; the book, the interval, the clock and the table are the lag ring's
+  PbDevBuf<uint32_t> measured;  // lags x nsims: the measured bots of each mode's record
+  PbDevBuf<int2> phasors;       // the 4096 (cos, sin) entries of pb_phasor.hpp
+  PbDevBuf<int2> vectors;       // nvec (nx, ny) pairs
+  std::vector<int> list;        // the host's copy of the list, as passed
+  unsigned nvec = 0;
+  int boxLog2 = 0;
+};
+
 // distinct van Hove function (pb_vanhove_distinct.hip): float2 (x, y) snapshots, NaN for an absent bot, and nsims x lags
 // cells of 2 + bins words, member-major: centres, partners, then the radial histogram of ordered pairs (pb_vanhove.hpp;
 // pbSimSetVanHoveDistinct)
@@ -306,6 +322,10 @@ struct pbSim {
   PbScattering sc;
   PbVanHove vh;
   PbVanHoveDistinct vd;
+  PbCoherent co;
+  // k_coh_modes' lanes as (stripe, vector); false: one lane per vector, for A/B (PB_COHERENT_STRIPES=0 under
+  // PB_ALLOW_ENV_OVERRIDES)
+  bool coherentStripes = true;
   pbSimStats stats{};
 };
 
@@ -352,25 +372,26 @@ int pbLagCheckBatch(const char *fn, const pbSim *S, unsigned lags) {
     return pbFail(fn, ": the ring (lags x bots x " + std::to_string(sizeof(Snap)) + " bytes) must not exceed 2^33 bytes");
   return PB_OK;
 }
-// the ring and the zeroed table of `words` words into R; on an error the caller drops R
+// the ring of perSlot entries per slot and the zeroed table of `words` words into R; on an error the caller drops R
 template <typename Snap>
-int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words) {
-  PB_TRY(R.ring.alloc((size_t)lags * S->total));
+int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words, size_t perSlot) {
+  PB_TRY(R.ring.alloc((size_t)lags * perSlot));
   PB_TRY(R.table.alloc(words));
   PB_TRY(hipMemsetAsync(R.table, 0, sizeof(unsigned long long) * words, S->stream));
   return PB_OK;
 }
-// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd) off and, unless lags is 0, on again: a fresh value with a ring of `lags`
-// snapshots, a zeroed table of wordsPerLag words per member and lag, a book at record 0, and what fill(fresh) sets of
-// the analysis' own.  When any of it fails, what was made goes and the analysis stays off.
+// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd, S->co) off and, unless lags is 0, on again: a fresh value
+// with a ring of `lags` snapshots (of perSlot entries each; 0: one per bot of the batch), a zeroed table of wordsPerLag
+// words per member and lag, a book at record 0, and what fill(fresh) sets of the analysis' own.  When any of it fails,
+// what was made goes and the analysis stays off.
 template <typename A, typename Fill>
-int pbLagSwitch(pbSim *S, A &held, float interval, unsigned lags, size_t wordsPerLag, Fill fill) {
+int pbLagSwitch(pbSim *S, A &held, float interval, unsigned lags, size_t wordsPerLag, Fill fill, size_t perSlot = 0) {
   useDevice(S);
   PB_TRY(hipStreamSynchronize(S->stream));  // a record of the old ring may still be in flight
   held = A();
   if (!lags) return PB_OK;
   A fresh;
-  int rc = pbLagAllocate(S, fresh.lag, lags, (size_t)S->nsims * lags * wordsPerLag);
+  int rc = pbLagAllocate(S, fresh.lag, lags, (size_t)S->nsims * lags * wordsPerLag, perSlot ? perSlot : S->total);
   if (rc == PB_OK) rc = fill(fresh);
   if (rc != PB_OK) {          // (a ring that took the last free memory, say)
     (void)hipGetLastError();  // (the failure is reported here, not by the next launch check of the schedule)
@@ -478,3 +499,4 @@ int pbTimeCorrRecord(pbSim *S);         // ... a snapshot and its lags (pbLagRec
 int pbScatteringRecord(pbSim *S);       // ... a quantised snapshot and its lags (pbLagRecord)              pb_scatter.hip
 int pbVanHoveRecord(pbSim *S);          // ... a position snapshot and its lags (pbLagRecord)               pb_vanhove.hip
 int pbVanHoveDistinctRecord(pbSim *S);  // ... a filing, a snapshot and its lags (pbLagRecord)     pb_vanhove_distinct.hip
+int pbCoherentRecord(pbSim *S);         // ... the density modes and their products with the ring's         pb_coherent.hip

@@ -15,6 +15,7 @@
 //                   [--vanhove FILE [--vanhove-interval T] [--vanhove-lags N] [--vanhove-width W] [--vanhove-bins B]]
 //                   [--vanhove-distinct FILE [--vanhove-distinct-interval T] [--vanhove-distinct-lags N]
 //                    [--vanhove-distinct-width W] [--vanhove-distinct-bins B]]
+//                   [--coherent FILE [--coherent-interval T] [--coherent-lags N] [--coherent-box-log2 E] [--coherent-nmax M]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -116,6 +117,11 @@ struct RunOptions {
   float vanhoveDistinctInterval = -1.0f;  // below 0: dump_interval
   float vanhoveDistinctWidth = -1.0f;     // below 0: an eighth of min_radius, at most 2047 / bins
   long vanhoveDistinctLags = 32, vanhoveDistinctBins = 64;
+
+  std::string coherentPath;
+  float coherentInterval = -1.0f;                // below 0: dump_interval
+  long coherentLags = 32, coherentNmax = 3;      // 24 wavevectors, as --scatter
+  long coherentBoxLog2 = PB_SK_MIN_LOG2 - 1;     // below the range: boxLog2() chooses
 };
 
 using Choice = std::pair<const char *, int>;  // a word and what it stands for
@@ -225,6 +231,12 @@ const Flag kFlags[] = {
     {"--vanhove-distinct-lags", &RunOptions::vanhoveDistinctLags, 1, PB_VANHOVE_MAX_LAGS},
     {"--vanhove-distinct-width", &RunOptions::vanhoveDistinctWidth, 0.0f, true, 2048.0f},
     {"--vanhove-distinct-bins", &RunOptions::vanhoveDistinctBins, 1, PB_VANHOVE_MAX_BINS},
+
+    {"--coherent", &RunOptions::coherentPath, "recorder"},
+    {"--coherent-interval", &RunOptions::coherentInterval, 0.0f, false},
+    {"--coherent-lags", &RunOptions::coherentLags, 1, PB_COHERENT_MAX_LAGS},
+    {"--coherent-box-log2", &RunOptions::coherentBoxLog2, PB_SK_MIN_LOG2, PB_SK_MAX_LOG2},
+    {"--coherent-nmax", &RunOptions::coherentNmax, 1, 10},  // (11: 264 vectors, past PB_COHERENT_MAX_VECTORS)
 };
 
 // a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
@@ -321,6 +333,29 @@ std::string decimalLimbs(std::vector<unsigned long long> v) {
   return s;
 }
 
+// a signed integer of three little-endian 64-bit limbs, two's complement, in decimal
+std::string decimalSigned192(const unsigned long long (&w)[3]) {
+  std::vector<unsigned long long> v(w, w + 3);
+  const bool negative = (w[2] >> 63) != 0;
+  if (negative) {  // the magnitude: every limb inverted, plus one
+    unsigned long long carry = 1;
+    for (unsigned long long &limb : v) limb = ~limb + carry, carry = carry && limb == 0 ? 1 : 0;
+  }
+  return (negative ? "-" : "") + decimalLimbs(v);
+}
+
+// such an integer as a long double (for a quotient that is printed to 9 digits)
+long double real192(const unsigned long long (&w)[3]) {
+  const bool negative = (w[2] >> 63) != 0;
+  unsigned long long v[3] = {w[0], w[1], w[2]};
+  if (negative) {
+    unsigned long long carry = 1;
+    for (unsigned long long &limb : v) limb = ~limb + carry, carry = carry && limb == 0 ? 1 : 0;
+  }
+  const long double mag = ((long double)v[2] * 18446744073709551616.0L + (long double)v[1]) * 18446744073709551616.0L + (long double)v[0];
+  return negative ? -mag : mag;
+}
+
 // an analysis output; NULL after saying so
 FILE *openOutput(const std::string &path, const char *mode) {
   FILE *f = fopen(path.c_str(), mode);
@@ -390,11 +425,15 @@ struct Run {
   // the device until the run ends, so a run whose records (from max_time, the start time and the interval) times nCells
   // would reach 2^31 (10^6 bots: 2147 records) is refused when it starts, not after its last step.  False after saying
   // so.
+  // the records a run from here to max_time takes at this interval (+ 2: the gate's rounding takes at most one more)
+  double recordsAhead(float every) {
+    const double left = std::max(0.0, (double)sim.getParams().max_time - (double)sim.getTime());
+    return left / (double)(every > 0.0f ? every : cfg.timestep) + 2.0;
+  }
+
   bool recordsFit(const char *flag, float every) {
     const SimParams &p = sim.getParams();
-    const double left = std::max(0.0, (double)p.max_time - (double)sim.getTime());
-    // (+ 2: the gate's rounding takes at most one more)
-    const double records = left / (double)(every > 0.0f ? every : cfg.timestep) + 2.0;
+    const double records = recordsAhead(every);
     if (records * (double)p.nCells < 2147483648.0) return true;
     fprintf(stderr, "%s: about %.0f records of %u bots would pass 2^31 samples per lag: raise %s-interval "
                     "or lower max_time\n", flag, records, (unsigned)p.nCells, flag);
@@ -815,6 +854,42 @@ struct Run {
     }
     return fclose(f) == 0;
   }
+
+  // --coherent FILE: the device's coherent intermediate scattering function (Particlebot::setCoherent).  Records are taken
+  // as --scatter takes them, at --coherent-interval into a ring of --coherent-lags records of the density modes rho(k)
+  // over halfPlaneVectors(--coherent-nmax) in the box boxLog2(--coherent-box-log2), and every record's modes are
+  // multiplied with the latest ones' into one row per lag and wavevector.  Switched on behind a resume.  Its sums hold
+  // whatever the bots: the one cap is 2^31 origins per lag, so a run is refused by its record count alone.  At the end
+  // of the run one line per lag and vector, lag 0 first, the vectors in list order:
+  // the integers as they are (Re and Im as exact signed decimals from their 192 bits, units of 2^-60), then
+  // FRe = Re / (2^60 BotsThen) and FIm likewise as %.9g (nan with no bot).
+  int startCoherent() {
+    if (o.coherentPath.empty()) return 0;
+    const float every = recordEvery(o.coherentInterval, cfg);
+    if (const double records = recordsAhead(every); records >= 2147483648.0) {
+      fprintf(stderr, "--coherent: about %.0f records would pass 2^31 origins per lag: raise --coherent-interval or "
+                      "lower max_time\n", records);
+      return 2;
+    }
+    return sim.setCoherent(every, (unsigned)o.coherentLags, boxLog2(o.coherentBoxLog2, cfg),
+                           halfPlaneVectors((int)o.coherentNmax)) ? 0 : 1;
+  }
+
+  bool writeCoherent() {
+    if (o.coherentPath.empty()) return true;
+    std::vector<pbCoherentRow> rows;
+    if (!sim.coherentRows(rows)) return false;
+    FILE *f = openWhole(o.coherentPath, "Lag, Nx, Ny, Origins, SumSteps, BotsNow, BotsThen, Re, Im, FRe, FIm");
+    if (!f) return false;
+    for (const pbCoherentRow &c : rows) {
+      const long double unit = 1152921504606846976.0L * (long double)c.bots_then;  // 2^60 BotsThen
+      const double fRe = c.bots_then ? (double)(real192(c.re) / unit) : std::nan("");
+      const double fIm = c.bots_then ? (double)(real192(c.im) / unit) : std::nan("");
+      fprintf(f, "%u, %d, %d, %llu, %llu, %llu, %llu, %s, %s, %.9g, %.9g\n", c.lag, c.nx, c.ny, c.origins, c.sum_steps,
+              c.bots_now, c.bots_then, decimalSigned192(c.re).c_str(), decimalSigned192(c.im).c_str(), fRe, fIm);
+    }
+    return fclose(f) == 0;
+  }
 };
 
 }  // namespace
@@ -951,6 +1026,7 @@ int main(int argc, char **argv) {
   if (const int refused = run.startScattering()) return refused;
   if (const int refused = run.startVanHove()) return refused;
   if (const int refused = run.startVanHoveDistinct()) return refused;
+  if (const int refused = run.startCoherent()) return refused;
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!o.ckptPath.empty() && run.stepsDone > lastCkptStep) {
@@ -986,6 +1062,6 @@ int main(int argc, char **argv) {
   fclose(fp);
   const bool written = run.writeTrail() && run.writeContacts() && run.writeRdf() && run.writeTimeCorrelation() &&
                        run.writeScattering() && run.writeVanHove() && run.writeVanHoveDistinct() &&
-                       run.writeCorrelation();
+                       run.writeCoherent() && run.writeCorrelation();
   return written ? 0 : 1;
 }

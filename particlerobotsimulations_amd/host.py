@@ -102,6 +102,10 @@ SYMBOLS = {
     "pbHostVanHoveDistinctRecord": (_I, [_P]),
     "pbHostVanHoveDistinctInfo": (_I, [_P, _P, _P, _P, _P, _P]),
     "pbHostVanHoveDistinctRows": (_I, [_P, _P, _P, _ULL, _PULL]),
+    "pbHostSetCoherent": (_I, [_P, _F, _U, _I, _P, _U]),
+    "pbHostCoherentRecord": (_I, [_P]),
+    "pbHostCoherentInfo": (_I, [_P, _P, _P, _P, _P, _P]),
+    "pbHostCoherentRows": (_I, [_P, _P, _ULL, _PULL]),
     "pbHostFieldMap": (_I, [_P, _P, _P, _P]),
     "pbHostStructureFactor": (_I, [_P, _I, _I, _P, _U, _P]),
     "pbHostSetDisplay": (None, [_P, _I]),
