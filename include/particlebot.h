@@ -307,6 +307,19 @@ class Particlebot {
   bool coherentRecord();
   bool coherentInfo(float &interval, unsigned &lags, int &boxLog2, unsigned &nvec, unsigned long long &records);
   bool coherentRows(std::vector<pbCoherentRow> &rows);
+  /* Four-point dynamics of the resident state on the device (pbSimSetFourPoint / pbSimGetFourPoint,
+   * include/particlebot_hip.h has the definitions), shaped as the scattering above:
+   * setFourPoint(interval, lags, overlapRadius, boxLog2, vectors) keeps a device ring of `lags` records of the quantised
+   * positions and, per lag, the exact integer sums over all time origins of the overlap count Q and of Q^2, and per
+   * wavevector those of the density mode of the overlapping bots and of its squared magnitude: chi_4 and S_4(k, lag);
+   * lags 0 switches it off.  fourPointRecord takes one record now; fourPointInfo gives interval, lags, overlapRadius,
+   * boxLog2, the vectors' count and the records taken so far; fourPointRows the lags * nvec rows, lag-major.  Fused
+   * engine only: Legacy and HostOnly instances return false with a message on stderr.  Not part of a checkpoint. */
+  bool setFourPoint(float interval, unsigned lags, float overlapRadius, int boxLog2, const std::vector<int> &vectors);
+  bool fourPointRecord();
+  bool fourPointInfo(float &interval, unsigned &lags, float &overlapRadius, int &boxLog2, unsigned &nvec,
+                     unsigned long long &records);
+  bool fourPointRows(std::vector<pbFourPointRow> &rows);
   /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
    * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on

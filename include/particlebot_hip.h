@@ -974,9 +974,10 @@ int pbPhasorTable(int *cosSin /* 2 * 4096, interleaved */, unsigned cap);
  * busy.  A lane owns one vector and keeps re and im in registers; at the end the stripes of a wave are folded with
  * shuffles and one lane per wave and vector adds into the cell with 64-bit integer atomics.  Read back: 16 bytes per
  * (member, lag, vector) and 8 per (member, lag).
- * Out of scope: chi_4; weights other than 1; logarithmic lag spacing; the ensemble layer's summary rows;
+ * Out of scope: weights other than 1; logarithmic lag spacing; the ensemble layer's summary rows;
  * the legacy engine.  (The coherent F(k, tau), a product of two rho(k) sums, has a recorder of its own:
- * pbSimSetCoherent, below.) */
+ * pbSimSetCoherent, below.  So has chi_4, whose phasor sum is squared once per origin: pbSimSetFourPoint, further
+ * below.) */
 #define PB_SCATTER_MAX_LAGS 64u
 #define PB_SCATTER_MAX_VECTORS 256u
 #define PB_SCATTER_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
@@ -1220,8 +1221,8 @@ int pbSimGetVanHoveDistinctTimes(pbSim *sim, unsigned long long *records, float 
  * that no record has reached yet has origins == 0 and zeros.  pbSimGetCoherentTimes: records so far and the span of the
  * last record's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
  * When several records are due in front of a step the order is: series, time correlation, scattering, van Hove,
- * distinct van Hove, coherent scattering; then the centroid trail and the phase update.  No launch is fused across the
- * gate and a resident stretch ends in front of it.
+ * distinct van Hove, coherent scattering, four-point; then the centroid trail and the phase update.  No launch is fused
+ * across the gate and a resident stretch ends in front of it.
  * The ring is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it alone; pbSimDestroy
  * frees it.  Recording never waits for the device.  It only reads: the state, slot layout, keys, cell lists,
  * pbSimStats, time, RNG, the mark and every other recorder's and analysis' memory stay as they were.
@@ -1246,8 +1247,9 @@ int pbSimGetVanHoveDistinctTimes(pbSim *sim, unsigned long long *records, float 
  * with its read-back, the route a caller had per sample before, 0.23 / 0.23 / 0.24 ms.  256 members of 1000 bots:
  * 0.021 / 0.025 / 0.075 ms at 16 lags and 0.024 / 0.035 / 0.182 ms at 64 (at 256 vectors the per-lag launch shows).
  * Out of scope: current correlations, that is weights other than 1 (the radius and velocity kinds have 128-bit modes and
- * would need 256-bit products); chi_4; logarithmic lag spacing; radial averaging; the ensemble layer's summary rows; the
- * legacy engine. */
+ * would need 256-bit products); logarithmic lag spacing; radial averaging; the ensemble layer's summary rows; the
+ * legacy engine.  (chi_4 and S_4(k, tau), which square a lag-dependent masked mode per origin, are pbSimSetFourPoint's,
+ * next.) */
 #define PB_COHERENT_MAX_LAGS 64u
 #define PB_COHERENT_MAX_VECTORS 256u
 #define PB_COHERENT_BLOCKS 256u /* bot blocks per member: one pass covers 65536 bots of a member */
@@ -1268,6 +1270,128 @@ int pbSimGetCoherentInfo(pbSim *sim, float *interval, unsigned *lags, int *boxLo
                          unsigned long long *records);
 int pbSimGetCoherent(pbSim *sim, pbCoherentRow *rows /* nsims * lags * nvec: member, lag, vector */);
 int pbSimGetCoherentTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
+
+/* Four-point dynamics on the device (csrc/pb_fourpoint.hip; the arithmetic is csrc/pb_fourpoint.hpp): how the overlap of
+ * the time correlation FLUCTUATES, and whether the bots that stayed put form domains.
+ *     Q(t, tau) = sum_i w_i ,   w_i = 1 iff bot i is within overlapRadius of where it was tau earlier
+ *     W_k(t, tau) = sum_i w_i exp(i k . r_i(t))          (r_i(t) the EARLIER position of the pair)
+ *     chi_4(tau) = (<Q^2> - <Q>^2) / N ,   S_4(k, tau) = (<|W_k|^2> - |<W_k>|^2) / N
+ * per member, lag and wavevector of a caller's list, the averages over time origins while pbSimStep runs, as exact
+ * integers: the four-point susceptibility and the structure factor of the slow bots, the standard measure of dynamic
+ * heterogeneity.  The scattering recorder cannot give it (it sums phasors over origins before anything is squared) and
+ * neither can the coherent one (it squares modes that do not depend on the lag): here a MASKED phasor sum is formed per
+ * (origin pair, member, wavevector) and squared exactly once per origin.  The book, the records and the pairing are the
+ * time correlation's (pbSimSetTimeCorrelation, above); the ring is the scattering's; the turn, the index and the table
+ * are the structure factor's.  Off by default: a run that does not ask for it makes the same launches, has the same
+ * pbSimStats and the same bits, and nothing is allocated.
+ * pbSimSetFourPoint(sim, interval, lags, overlapRadius, boxLog2, vectors, nvec).  interval and lags follow the other
+ * lagged recorders exactly: interval > 0 the schedule's gate, 0 every step, -1.0f manual only; lags is
+ * 1 ... PB_FOURPOINT_MAX_LAGS; lags == 0 switches off and frees everything (the radius, boxLog2, vectors and nvec are then
+ * not read).  overlapRadius is in [0, 2048), as for the time correlation.  boxLog2, vectors and nvec are the
+ * scattering's: e of the box L = 2^e, PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2; nvec int pairs (nx, ny), nvec
+ * 1 ... PB_FOURPOINT_MAX_VECTORS, each any int; k = (2 pi / L)(nx, ny).  The list is copied at the call.  Calling again
+ * restarts from record 0 with a zeroed table.
+ * A RECORD is the scattering's: per bot in ORIGINAL order the quantised position (qx, qy), or (INT32_MIN, 0) for an
+ * unmeasured bot (x or y out of range), 8 bytes per bot and slot, into slot r % lags of a ring of its own.  It is taken
+ * at the same instant and describes the same state as the other recorders' records.
+ * A PAIR (now, then) of a bot is MEASURED iff both instants are.
+ * OVERLAP.  qa = (long long)rint(overlapRadius * 1048576.0f) and a2 = qa * qa, both computed once on the host
+ * (qa < 2^31).  With dqx = qx_now - qx_then and dqy likewise, as 64-bit integers: w = 1 iff the pair is measured and
+ * dqx^2 + dqy^2 < a2.  The device tests |dqx| < qa && |dqy| < qa first: the sum of squares implies both, and they keep
+ * every square below 2^62.  The displacement is the difference of the QUANTISED positions, the scattering's choice, not
+ * the time correlation's quantised fp32 difference: the two agree wherever the fp32 difference is exact.
+ * overlapRadius == 0 overlaps nothing; equality dqx^2 + dqy^2 == a2 does not overlap.
+ * MODE of an origin pair.  Per member and wavevector, with the turn, the index and the table of pbSimStructureFactor
+ * taken at the EARLIER position, u = nx * qx_then + ny * qy_then mod 2^32:
+ *     A = sum_i w_i C[idx_i]     B = sum_i w_i S[idx_i]     Q = sum_i w_i     m = the measured pairs
+ * in units of 2^-30.
+ * PAIRING.  Record r is paired with the records r - l for l = 0 ... min(r, lags - 1).  On exact integers, per (member,
+ * lag):
+ *     samples += m     overlap += Q     overlap2 += Q^2
+ * and per (member, lag, vector):
+ *     re += A     im += B     power += A^2 + B^2
+ * At lag 0 every measured bot overlaps itself when qa >= 1: power is then the coherent recorder's lag-0 re.
+ * EXACTNESS.  A batch has fewer than 2^28 bots and a read is refused at 2^31 origins, so:
+ *     Q < 2^28                       sum Q < 2^59             one 64-bit word
+ *     Q^2 < 2^56                     sum Q^2 < 2^87           two little-endian limbs
+ *     |A|, |B| < 2^58                sums below 2^89          signed 128-bit two's complement, two limbs
+ *     A^2 + B^2 < 2^117              sum < 2^148              three limbs, as pbCoherentRow.re
+ * A cell has one owner on the device, which adds with plain loads and stores and carries through the limbs: no atomic
+ * wider than 64 bits and no float atomics.  Integer adds commute: results do not depend on slot order, on the kernel form
+ * that stepped or on the order in which the device adds.  pbSimGetFourPoint answers PB_ERR_ARG ("a lag holds 2^31
+ * origins or more: restart the four-point recorder") and writes nothing if a lag has 2^31 origins or more; the count is
+ * the host's own, so nothing is read back first.
+ * PER MEMBER, LAG AND WAVEVECTOR one pbFourPointRow: lag in RECORDS; nx, ny as passed; origins and sum_steps as in
+ * pbScatteringRow; samples, overlap and overlap2 (the same in every vector's row of a member and lag); re, im and power.
+ * The caller forms, with Nbar = samples / origins and <.> = (.) / origins,
+ *     chi_4 = (<Q^2> - <Q>^2) / Nbar          S_4 = (<|W|^2> - |<W>|^2) / (2^60 Nbar).
+ * ERROR AGAINST THE CONTINUOUS DEFINITION (derived, not measured).  Let eps be the per-bot bound of pbSimStructureFactor,
+ *     eps = pi / 4096 + 2 pi (|nx| + |ny|) 2^-21 / L + 2^-30.
+ * For a given w each mode is within Q * eps of its float64 value, in magnitude.  w itself can differ from a float64 rule
+ * |r_now - r_then| < overlapRadius only for a pair whose displacement length is within two position quanta (2^-20) of
+ * the radius: quantising moves each instant's position by at most half a quantum per axis, hence the displacement by
+ * at most one per axis and its length by at most sqrt 2, and the radius by at most half a quantum.
+ * OTHER CALLS.  pbSimFourPointRecord: one record now, of the state as it is, whatever the interval.
+ * pbSimGetFourPointInfo: interval, lags (0: off), overlapRadius, boxLog2, nvec and the records taken so far; any pointer
+ * may be NULL, not all.  pbSimGetFourPoint: nsims * lags * nvec rows, member-major, then the lag, then the vector in list
+ * order; a lag that no record has reached yet has origins == 0 and zeros.  pbSimGetFourPointTimes: records so far and the
+ * span of the last record's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
+ * When several records are due in front of a step the order is: series, time correlation, scattering, van Hove,
+ * distinct van Hove, coherent scattering, four-point; then the centroid trail and the phase update.  No launch is fused
+ * across the gate and a resident stretch ends in front of it.
+ * The ring is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it alone; pbSimDestroy
+ * frees it.  Recording never waits for the device.  It only reads: the state, slot layout, keys, cell lists,
+ * pbSimStats, time, RNG, the mark and every other recorder's and analysis' memory stay as they were.
+ * PB_ERR_ARG, before the device is touched: a NULL handle, vectors or rows; interval NaN, infinite, or negative other
+ * than -1; lags > PB_FOURPOINT_MAX_LAGS; overlapRadius NaN or outside [0, 2048); boxLog2 outside
+ * PB_SK_MIN_LOG2 ... PB_SK_MAX_LOG2; nvec outside 1 ... PB_FOURPOINT_MAX_VECTORS; a ring above 2^33 bytes
+ * (lags x total x 8); a table above 2^31 bytes (nsims x lags x nvec x (64 + 16): the cells and the per-record modes); a
+ * batch of more than 65535 members or of 2^28 bots or more; the pointers of pbSimGetFourPointInfo all NULL; a record or
+ * a read with the four-point recorder off.
+ * Cost: a record makes one pass over posrad and the original indices, zeroes its scratch, and does
+ * N x lags x nvec table look-ups in one launch for all lags: one workgroup of 256 lanes per (member, lag, bot block), at
+ * most PB_FOURPOINT_BLOCKS blocks per member and lag, keeps the table in LDS (32 KiB), stages 256 pairs at a time from
+ * coalesced 8-byte loads of both snapshots as (qx_then << shift, qy_then << shift, mask), moves the tile's overlapping
+ * entries to its front (a ballot prefix; the waves' counts through LDS) and walks them with its lanes laid out as
+ * (stripe, vector), up to the tile's last overlapping entry: the tile's count sets the trip count, the same in every
+ * lane; the stripes of a wave are folded with shuffles and one lane per wave and vector adds into the record's scratch
+ * with 64-bit integer atomics; m and Q are the staging ballots' popcounts.  One more launch, a lane per (member, lag,
+ * vector), folds the scratch into the cells: two 128-bit adds, two 64 x 64 -> 128-bit products and a 192-bit add.  This
+ * compacted staging ships; the masked form, in which every lane walks the whole tile, is a build-time switch
+ * (PB_FOURPOINT_COMPACT=0) and was measured beside it.
+ * Device memory: the ring, 8 bytes per bot and lag; 80 bytes per (member, lag, vector), 64 of the cell and 16 of the
+ * scratch mode; 48 bytes per (member, lag); the phasor table and the list.  Read back: the cells.
+ * Measured on one MI355X, medians of 20 records into a full ring under a walk that lets 0.47 of the pairs overlap at
+ * lag 1 and 0.014 at lag 63 (profiles/four_point.txt): the 10^6-bot arena 0.356 / 0.358 / 0.541 ms with 8 / 24 / 256
+ * vectors at 16 lags and 0.715 / 0.790 / 1.040 ms at 64 (the masked form: 0.308 / 0.350 / 1.501 and 0.780 / 1.067 /
+ * 5.442 ms); a scattering record with the same list 0.236 / 0.338 / 1.794 ms at 16 lags and 0.645 / 1.155 / 6.825 ms at
+ * 64: cheaper at 8 vectors, and at 24 vectors and 16 lags; the bare pos copy of a host route 0.19 ms: cheaper than any
+ * record.  256 members of 1000 bots: 0.107 / 0.119 / 0.327 ms at 16 lags and 0.352 / 0.375 / 0.707 ms at 64.
+ * Out of scope: the phasor at the later position; weights other than the overlap; a mobility (fast-bot) variant;
+ * logarithmic lags; radial averaging; the ensemble layer's summary rows; the legacy engine. */
+#define PB_FOURPOINT_MAX_LAGS 64u
+#define PB_FOURPOINT_MAX_VECTORS 256u
+#define PB_FOURPOINT_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
+typedef struct pbFourPointRow {        /* 128 bytes */
+  unsigned lag;                        /* lag in RECORDS: record r against record r - lag */
+  int nx, ny;                          /* the wavevector's integers, as passed */
+  unsigned reserved;                   /* 0 */
+  unsigned long long origins;          /* record pairs added so far (the same for every member and vector) */
+  unsigned long long sum_steps;        /* sum over those pairs of step(r) - step(r - lag) */
+  unsigned long long samples;          /* sum over the origins of the measured pairs m */
+  unsigned long long overlap;          /* ... of the overlapping pairs Q */
+  unsigned long long overlap2[2];      /* ... of Q^2: little-endian limbs */
+  unsigned long long re[2], im[2];     /* sums of A and of B: signed 128-bit, little-endian limbs; units of 2^-30 */
+  unsigned long long power[3];         /* sum of A^2 + B^2: 192-bit, little-endian limbs; units of 2^-60 */
+  unsigned long long reserved2;        /* 0 */
+} pbFourPointRow;
+int pbSimSetFourPoint(pbSim *sim, float interval, unsigned lags, float overlapRadius, int boxLog2,
+                      const int *vectors /* 2 * nvec */, unsigned nvec);
+int pbSimFourPointRecord(pbSim *sim);  /* one record now, of the state as it is */
+int pbSimGetFourPointInfo(pbSim *sim, float *interval, unsigned *lags, float *overlapRadius, int *boxLog2,
+                          unsigned *nvec, unsigned long long *records);
+int pbSimGetFourPoint(pbSim *sim, pbFourPointRow *rows /* nsims * lags * nvec: member, lag, vector */);
+int pbSimGetFourPointTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
 /* Local strain and non-affine displacement D2min on the device (csrc/pb_strain.hip; the fit itself is
  * csrc/pb_strain.hpp): the Falk-Langer fit against the mark of the rearrangement analysis.  For every bot, the best

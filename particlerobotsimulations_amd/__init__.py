@@ -19,7 +19,7 @@ __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
            "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
            "half_plane_vectors", "phasor_table", "scattering_summary", "van_hove_summary",
-           "deformation_gradient", "mean_d2min", "coherent_scattering_summary"]
+           "deformation_gradient", "mean_d2min", "coherent_scattering_summary", "four_point_summary"]
 
 
 def phasor_table():
@@ -160,6 +160,28 @@ def coherent_scattering_summary(row):
     return {"f_re": float(Fraction(int(row["re"]), m << 60)) if m else None,
             "f_im": float(Fraction(int(row["im"]), m << 60)) if m else None,
             "mean_lag_steps": float(Fraction(int(row["sum_steps"]), origins)) if origins else None}
+
+
+def four_point_summary(rows):
+    """What the rows of one (member, lag) of four_point() say, in float64 from the integers (pure Python ints; every
+    quotient is formed as one exact fraction and converted once).  `rows` is the list over the vectors, or one row.
+    With O = origins and Nbar = samples / O:  mean_overlap = overlap / samples, the fraction of the measured bots that
+    stayed within the radius;  chi4 = (overlap2 / O - (overlap / O)^2) / Nbar, the four-point susceptibility;  s4, per
+    vector, = (power / O - (re^2 + im^2) / O^2) / (2^60 Nbar), the structure factor of the slow bots;
+    mean_lag_steps = sum_steps / O.  All are None for a lag with no origins, and all but the last for one with no
+    measured pair."""
+    from fractions import Fraction
+    rows = [rows] if isinstance(rows, dict) else list(rows)
+    first = rows[0]
+    o, m = int(first["origins"]), int(first["samples"])
+    if not o or not m:
+        return {"mean_overlap": None, "chi4": None, "s4": [None] * len(rows),
+                "mean_lag_steps": float(Fraction(int(first["sum_steps"]), o)) if o else None}
+    q, q2 = int(first["overlap"]), int(first["overlap2"])
+    # (x / O - y / O^2) / (m / O) = (x O - y) / (O m)
+    s4 = [float(Fraction(int(r["power"]) * o - int(r["re"]) ** 2 - int(r["im"]) ** 2, (o * m) << 60)) for r in rows]
+    return {"mean_overlap": float(Fraction(q, m)), "chi4": float(Fraction(q2 * o - q * q, o * m)), "s4": s4,
+            "mean_lag_steps": float(Fraction(int(first["sum_steps"]), o))}
 
 
 def van_hove_summary(row, width):
@@ -1058,6 +1080,45 @@ class Sim:
     def coherent_scattering_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
         return self._span("pbSimGetCoherentTimes")
+
+    def set_four_point(self, interval, lags, overlap_radius, box_log2, vectors):
+        """Keep a device ring of `lags` records of every bot's quantised position, one taken in front of every step
+        whose start time passes the schedule's gate at `interval` (0: every step, -1: only by four_point_record())
+        while step() runs, and per pair of a record with one of the `lags` latest ones form the overlap count Q (bots
+        within `overlap_radius`, in [0, 2048), of where they were) and, per wavevector
+        k = (2 pi / 2^box_log2)(nx, ny) of `vectors`, an (nvec, 2) array of ints, nvec 1 ... 256, the density mode of the
+        overlapping bots at their earlier positions; Q, Q^2, the modes and their squared magnitudes are summed over the
+        origins as exact integers (pbSimSetFourPoint): chi_4 and S_4(k, lag).  Restarts at record 0; lags 0 switches it
+        off (vectors may then be None).  Recording changes no state bit."""
+        if int(lags) == 0 and vectors is None:
+            vectors = np.zeros((0, 2), np.int32)
+        held, nvec = _analysis.held_vectors(vectors)
+        _capi.check(_capi.lib().pbSimSetFourPoint(self._h, float(interval), int(lags), float(overlap_radius),
+                                                  int(box_log2), _capi.np_ptr(held), nvec), "pbSimSetFourPoint")
+
+    def four_point_record(self):
+        """One record now, of the state as it is (pbSimFourPointRecord)."""
+        _capi.check(_capi.lib().pbSimFourPointRecord(self._h), "pbSimFourPointRecord")
+
+    def four_point_info(self):
+        """A dict of interval, lags (0: off), overlap_radius, box_log2, nvec and records taken so far
+        (pbSimGetFourPointInfo)."""
+        return _analysis.read_info(_analysis.FOUR_POINT_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetFourPointInfo(self._h, *p), "pbSimGetFourPointInfo"))
+
+    def four_point(self):
+        """The table as it stands (pbSimGetFourPoint): per member a list over lags (lag 0 first) of lists over the
+        vectors (list order) of dicts of Python ints: lag, nx, ny, origins, sum_steps, samples, overlap, overlap2, re,
+        im (units of 2^-30), power (units of 2^-60).  four_point_summary() turns a lag's rows into chi_4 and S_4."""
+        info = self.four_point_info()
+        lags, nvec = info["lags"], info["nvec"]
+        rows = (_capi.pbFourPointRow * max(self.nsims * lags * nvec, 1))()
+        _capi.check(_capi.lib().pbSimGetFourPoint(self._h, rows), "pbSimGetFourPoint")
+        return _analysis.lag_table(self.nsims, lags, lambda g: _capi.four_point_row(rows[g]), nvec)
+
+    def four_point_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        return self._span("pbSimGetFourPointTimes")
 
 
 class Ensemble(Sim):

@@ -18,6 +18,8 @@ VAN_HOVE_INFO = (("interval", C.c_float), ("lags", C.c_uint), ("width", C.c_floa
                  ("records", C.c_ulonglong))
 VAN_HOVE_DISTINCT_INFO = VAN_HOVE_INFO
 COHERENT_INFO = SCATTERING_INFO
+FOUR_POINT_INFO = (("interval", C.c_float), ("lags", C.c_uint), ("overlap_radius", C.c_float), ("box_log2", C.c_int),
+                   ("nvec", C.c_uint), ("records", C.c_ulonglong))
 
 
 def read_info(spec, call):

@@ -318,6 +318,38 @@ def coherent_row(r):
     return d
 
 
+class pbFourPointRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("nx", C.c_int), ("ny", C.c_int), ("reserved", C.c_uint),
+                ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong), ("samples", C.c_ulonglong),
+                ("overlap", C.c_ulonglong), ("overlap2", C.c_ulonglong * 2), ("re", C.c_ulonglong * 2),
+                ("im", C.c_ulonglong * 2), ("power", C.c_ulonglong * 3), ("reserved2", C.c_ulonglong)]
+
+
+# pbFourPointRow as a numpy record
+FOUR_POINT_ROW_DTYPE = np.dtype([("lag", np.uint32), ("nx", np.int32), ("ny", np.int32), ("reserved", np.uint32),
+                                 ("origins", np.uint64), ("sum_steps", np.uint64), ("samples", np.uint64),
+                                 ("overlap", np.uint64), ("overlap2", np.uint64, (2,)), ("re", np.uint64, (2,)),
+                                 ("im", np.uint64, (2,)), ("power", np.uint64, (3,)), ("reserved2", np.uint64)])
+FOURPOINT_MAX_LAGS = 64
+FOURPOINT_MAX_VECTORS = 256
+
+
+def signed_128(limbs):
+    """The signed 128-bit two's-complement value of two little-endian 64-bit limbs as one Python int."""
+    v = int(limbs[0]) + (int(limbs[1]) << 64)
+    return v - (1 << 128) if v >> 127 else v
+
+
+def four_point_row(r):
+    """A pbFourPointRow as a dict of Python ints: row_dict(r) with overlap2 and power composed from their limbs as
+    unsigned values, re and im as signed 128-bit ones (units of 2^-30; power in units of 2^-60)."""
+    d = row_dict(r)
+    del d["reserved2"]
+    d["overlap2"] = int(d["overlap2"][0]) + (int(d["overlap2"][1]) << 64)
+    d["re"], d["im"], d["power"] = signed_128(d["re"]), signed_128(d["im"]), signed_192(d["power"])
+    return d
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -440,6 +472,12 @@ SYMBOLS = {
                                   C.POINTER(C.c_ulonglong)]),
     "pbSimGetCoherent": (_I, [_VP, C.POINTER(pbCoherentRow)]),
     "pbSimGetCoherentTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimSetFourPoint": (_I, [_VP, _F, _U, _F, _I, _VP, _U]),
+    "pbSimFourPointRecord": (_I, [_VP]),
+    "pbSimGetFourPointInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_F), C.POINTER(_I), C.POINTER(_U),
+                                   C.POINTER(C.c_ulonglong)]),
+    "pbSimGetFourPoint": (_I, [_VP, C.POINTER(pbFourPointRow)]),
+    "pbSimGetFourPointTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

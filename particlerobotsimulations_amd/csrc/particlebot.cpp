@@ -1661,6 +1661,38 @@ bool Particlebot::coherentRows(std::vector<pbCoherentRow> &rows) {
   });
 }
 
+bool Particlebot::setFourPoint(float interval, unsigned lags, float overlapRadius, int boxLog2,
+                               const std::vector<int> &vectors) {
+  return onFusedEngine("setFourPoint", "four-point recorder", [&] {
+    const size_t nvec = vectors.size() / 2;
+    const int none[2] = {0, 0};  // (the engine takes no NULL; it refuses an empty list and one that is too long)
+    const unsigned count = (unsigned)(nvec <= PB_FOURPOINT_MAX_VECTORS ? nvec : PB_FOURPOINT_MAX_VECTORS + 1u);
+    return pbSimSetFourPoint(sim, interval, lags, overlapRadius, boxLog2, nvec ? vectors.data() : none, count);
+  });
+}
+
+bool Particlebot::fourPointRecord() {
+  return onFusedEngine("fourPointRecord", "four-point recorder", [&] { return pbSimFourPointRecord(sim); });
+}
+
+bool Particlebot::fourPointInfo(float &interval, unsigned &lags, float &overlapRadius, int &boxLog2, unsigned &nvec,
+                                unsigned long long &records) {
+  auto call = [&] { return pbSimGetFourPointInfo(sim, &interval, &lags, &overlapRadius, &boxLog2, &nvec, &records); };
+  return onFusedEngine("fourPointInfo", "four-point recorder", call);
+}
+
+bool Particlebot::fourPointRows(std::vector<pbFourPointRow> &rows) {
+  return onFusedEngine("fourPointRows", "four-point recorder", [&] {
+    unsigned lags = 0, nvec = 0;
+    const int rc = pbSimGetFourPointInfo(sim, nullptr, &lags, nullptr, nullptr, &nvec, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? (size_t)lags * nvec : 1, pbFourPointRow());  // (the engine takes no NULL; with the recorder off it refuses)
+    const int got = pbSimGetFourPoint(sim, rows.data());
+    if (got != PB_OK) rows.clear();
+    return got;
+  });
+}
+
 bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
   return onFusedEngine("fieldMap", "field map", [&] {
     const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;

@@ -602,6 +602,47 @@ int pbHostCoherentRows(void *hv, pbCoherentRow *rows, unsigned long long cap, un
   return 0;
 }
 
+// four-point dynamics of the resident state (Particlebot::setFourPoint / fourPointRecord / fourPointInfo /
+// fourPointRows; fused engine only), shaped as the coherent recorder's: the 128-byte pbFourPointRow of every lag and
+// vector (cap entries of room; *count = how many there are).  -1 on the other engines, a bad interval, lags, radius, box
+// or list, a record or a read with the recorder off, or too little room.
+int pbHostSetFourPoint(void *hv, float interval, unsigned lags, float overlapRadius, int boxLog2, const int *vectors,
+                       unsigned nvec) {
+  if (!vectors && nvec) return -1;
+  if (nvec > PB_FOURPOINT_MAX_VECTORS) nvec = PB_FOURPOINT_MAX_VECTORS + 1u;  // (refused below all the same; a huge count is not read)
+  return ((HostSim *)hv)->bot->setFourPoint(interval, lags, overlapRadius, boxLog2,
+                                            std::vector<int>(vectors, vectors + 2 * (size_t)nvec))
+             ? 0
+             : -1;
+}
+
+int pbHostFourPointRecord(void *hv) { return ((HostSim *)hv)->bot->fourPointRecord() ? 0 : -1; }
+
+int pbHostFourPointInfo(void *hv, float *interval, unsigned *lags, float *overlapRadius, int *boxLog2, unsigned *nvec,
+                        unsigned long long *records) {
+  float i = 0.0f, a = 0.0f;
+  unsigned l = 0, k = 0;
+  int e = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->fourPointInfo(i, l, a, e, k, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (overlapRadius) *overlapRadius = a;
+  if (boxLog2) *boxLog2 = e;
+  if (nvec) *nvec = k;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostFourPointRows(void *hv, pbFourPointRow *rows, unsigned long long cap, unsigned long long *count) {
+  std::vector<pbFourPointRow> v;
+  if (!count || !((HostSim *)hv)->bot->fourPointRows(v)) return -1;
+  *count = v.size();
+  if (rows && cap < v.size()) return -1;
+  copyOut(rows, v);
+  return 0;
+}
+
 // a field map of the resident state (Particlebot::fieldMap; fused engine only): ny * nx 64-byte pbFieldCell entries and,
 // unless NULL, the 16-byte pbFieldTotals row.  -1 on the other engines and on a bad view.
 int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFieldTotals *totals) {

@@ -24,6 +24,9 @@
 //                    earlier position (pbSimSetVanHoveDistinct)
 //   pb_coherent.hip  coherent intermediate scattering: a ring of density modes per member and wavevector, and 192-bit
 //                    sums of their products per lag (pbSimSetCoherent); pb_coherent.hpp holds the arithmetic
+//   pb_fourpoint.hip four-point dynamics: masked density modes per origin pair over a lag ring, and the exact sums of the
+//                    overlap count, its square, the modes and their squared magnitudes per lag (pbSimSetFourPoint);
+//                    pb_fourpoint.hpp holds the arithmetic
 //   pb_strain.hip    local strain and D2min: the Falk-Langer fit of every bot's marked bonds onto its present ones, a
 //                    gather over the rearrangement analysis' mark (pbSimStrainStats); pb_strain.hpp holds the fit
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
@@ -100,7 +103,7 @@ struct PbSeries {
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
 // ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip,
-// pb_vanhove_distinct.hip, pb_coherent.hip) share ------------------------------------------------------------------------
+// pb_vanhove_distinct.hip, pb_coherent.hip, pb_fourpoint.hip) share ------------------------------------------------------
 // A ring of `lags` snapshots of the whole batch in ORIGINAL order, lags x total entries of Snap.  Record r goes into
 // slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1); all pairs of a record are added
 // into `table` by one launch over pbLagGrid() workgroups of PB_LAG_LANES lanes, which pbLagPair() takes apart again.
@@ -110,10 +113,12 @@ struct PbSeries {
 constexpr int PB_LAG_LANES = 256;
 constexpr unsigned PB_LAG_MAX_LAGS = 64u, PB_LAG_BLOCKS = 256u;  // (the public header states both per analysis)
 static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS &&
-                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS && PB_COHERENT_MAX_LAGS == PB_LAG_MAX_LAGS,
+                  PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS && PB_COHERENT_MAX_LAGS == PB_LAG_MAX_LAGS &&
+                  PB_FOURPOINT_MAX_LAGS == PB_LAG_MAX_LAGS,
               "one bound on the lags");  // (the distinct part uses the self part's)
 static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS &&
-                  PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS, "one bound on the blocks per lag");
+                  PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS && PB_FOURPOINT_BLOCKS == PB_LAG_BLOCKS,
+              "one bound on the blocks per lag");
 
 // the host's counters of a ring
 struct PbLagBook {
@@ -229,6 +234,22 @@ struct PbCoherent {
   int boxLog2 = 0;
 };
 
+// four-point dynamics (pb_fourpoint.hip): the scattering's int2 snapshots, nsims x lags x nvec cells of eight words (re,
+// im, power), then nsims x lags cells of four (samples, overlap, overlap2), and the per-record scratch of one origin's
+// modes and counts (pb_fourpoint.hpp; pbSimSetFourPoint)
+struct PbFourPoint {
+  PbLagRing<int2> lag;
+  PbDevBuf<unsigned long long> scratch;  // nsims x lags x nvec modes (A, B), then nsims x lags counts (m, Q)
+  PbDevBuf<int2> phasors;                // the 4096 (cos, sin) entries of pb_phasor.hpp
+  PbDevBuf<int2> vectors;                // nvec (nx, ny) pairs
+  std::vector<int> list;                 // the host's copy of the list, as passed
+  unsigned nvec = 0;
+  int boxLog2 = 0;
+  float radius = 0.0f;
+  long long qa = 0;           // rint(radius * 2^20) ...
+  unsigned long long a2 = 0;  // ... squared
+};
+
 // distinct van Hove function (pb_vanhove_distinct.hip): float2 (x, y) snapshots, NaN for an absent bot, and nsims x lags
 // cells of 2 + bins words, member-major: centres, partners, then the radial histogram of ordered pairs (pb_vanhove.hpp;
 // pbSimSetVanHoveDistinct)
@@ -326,6 +347,7 @@ struct pbSim {
   // k_coh_modes' lanes as (stripe, vector); false: one lane per vector, for A/B (PB_COHERENT_STRIPES=0 under
   // PB_ALLOW_ENV_OVERRIDES)
   bool coherentStripes = true;
+  PbFourPoint fp;
   pbSimStats stats{};
 };
 
@@ -380,7 +402,7 @@ int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words, siz
   PB_TRY(hipMemsetAsync(R.table, 0, sizeof(unsigned long long) * words, S->stream));
   return PB_OK;
 }
-// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd, S->co) off and, unless lags is 0, on again: a fresh value
+// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd, S->co, S->fp) off and, unless lags is 0, on again: a fresh value
 // with a ring of `lags` snapshots (of perSlot entries each; 0: one per bot of the batch), a zeroed table of wordsPerLag
 // words per member and lag, a book at record 0, and what fill(fresh) sets of the analysis' own.  When any of it fails,
 // what was made goes and the analysis stays off.
@@ -500,3 +522,4 @@ int pbScatteringRecord(pbSim *S);       // ... a quantised snapshot and its lags
 int pbVanHoveRecord(pbSim *S);          // ... a position snapshot and its lags (pbLagRecord)               pb_vanhove.hip
 int pbVanHoveDistinctRecord(pbSim *S);  // ... a filing, a snapshot and its lags (pbLagRecord)     pb_vanhove_distinct.hip
 int pbCoherentRecord(pbSim *S);         // ... the density modes and their products with the ring's         pb_coherent.hip
+int pbFourPointRecord(pbSim *S);        // ... a quantised snapshot, the masked modes of its lags, their fold  pb_fourpoint.hip

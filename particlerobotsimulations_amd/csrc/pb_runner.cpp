@@ -16,6 +16,8 @@
 //                   [--vanhove-distinct FILE [--vanhove-distinct-interval T] [--vanhove-distinct-lags N]
 //                    [--vanhove-distinct-width W] [--vanhove-distinct-bins B]]
 //                   [--coherent FILE [--coherent-interval T] [--coherent-lags N] [--coherent-box-log2 E] [--coherent-nmax M]]
+//                   [--fourpoint FILE [--fourpoint-interval T] [--fourpoint-lags N] [--fourpoint-overlap A]
+//                    [--fourpoint-box-log2 E] [--fourpoint-nmax M]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -122,6 +124,12 @@ struct RunOptions {
   float coherentInterval = -1.0f;                // below 0: dump_interval
   long coherentLags = 32, coherentNmax = 3;      // 24 wavevectors, as --scatter
   long coherentBoxLog2 = PB_SK_MIN_LOG2 - 1;     // below the range: boxLog2() chooses
+
+  std::string fourpointPath;
+  float fourpointInterval = -1.0f;               // below 0: dump_interval
+  float fourpointOverlap = -1.0f;                // below 0: min_radius, as --timecorr-overlap
+  long fourpointLags = 32, fourpointNmax = 3;    // 24 wavevectors and (0, 0)
+  long fourpointBoxLog2 = PB_SK_MIN_LOG2 - 1;    // below the range: boxLog2() chooses
 };
 
 using Choice = std::pair<const char *, int>;  // a word and what it stands for
@@ -237,6 +245,13 @@ const Flag kFlags[] = {
     {"--coherent-lags", &RunOptions::coherentLags, 1, PB_COHERENT_MAX_LAGS},
     {"--coherent-box-log2", &RunOptions::coherentBoxLog2, PB_SK_MIN_LOG2, PB_SK_MAX_LOG2},
     {"--coherent-nmax", &RunOptions::coherentNmax, 1, 10},  // (11: 264 vectors, past PB_COHERENT_MAX_VECTORS)
+
+    {"--fourpoint", &RunOptions::fourpointPath, "recorder"},
+    {"--fourpoint-interval", &RunOptions::fourpointInterval, 0.0f, false},
+    {"--fourpoint-lags", &RunOptions::fourpointLags, 1, PB_FOURPOINT_MAX_LAGS},
+    {"--fourpoint-overlap", &RunOptions::fourpointOverlap, 0.0f, false, 2048.0f},
+    {"--fourpoint-box-log2", &RunOptions::fourpointBoxLog2, PB_SK_MIN_LOG2, PB_SK_MAX_LOG2},
+    {"--fourpoint-nmax", &RunOptions::fourpointNmax, 1, 10},  // (11: 265 vectors, past PB_FOURPOINT_MAX_VECTORS)
 };
 
 // a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
@@ -354,6 +369,15 @@ long double real192(const unsigned long long (&w)[3]) {
   }
   const long double mag = ((long double)v[2] * 18446744073709551616.0L + (long double)v[1]) * 18446744073709551616.0L + (long double)v[0];
   return negative ? -mag : mag;
+}
+
+// a signed integer of two little-endian 64-bit limbs, two's complement
+__int128 signed128(const unsigned long long (&w)[2]) { return (__int128)(((unsigned __int128)w[1] << 64) | w[0]); }
+
+std::string decimalSigned128(const unsigned long long (&w)[2]) {
+  const __int128 v = signed128(w);
+  const unsigned __int128 mag = v < 0 ? -(unsigned __int128)v : (unsigned __int128)v;
+  return (v < 0 ? "-" : "") + decimal128((unsigned long long)(mag >> 64), (unsigned long long)mag);
 }
 
 // an analysis output; NULL after saying so
@@ -890,6 +914,54 @@ struct Run {
     }
     return fclose(f) == 0;
   }
+
+  // --fourpoint FILE: the device's four-point recorder (Particlebot::setFourPoint).  Records are taken as --scatter takes
+  // them, at --fourpoint-interval into a ring of --fourpoint-lags records of the quantised positions; per pair of
+  // records the bots within --fourpoint-overlap (default min_radius) of where they were are counted, and their density
+  // mode is formed over halfPlaneVectors(--fourpoint-nmax) and (0, 0), the list's last, in the box
+  // boxLog2(--fourpoint-box-log2).  Switched on behind a resume; refused by its record count alone, as --coherent.  At
+  // the end of the run one line per lag and vector, lag 0 first, the vectors in list order: the integers as they are
+  // (Overlap2, Re, Im and Power as exact decimals from their limbs), then Chi4 = (Overlap2 O - Overlap^2) / (O Samples),
+  // the numerator exact, and S4 = (Power O - Re^2 - Im^2) / (2^60 O Samples) in long double, both as %.9g (nan with no
+  // sample).
+  int startFourPoint() {
+    if (o.fourpointPath.empty()) return 0;
+    const float every = recordEvery(o.fourpointInterval, cfg);
+    if (const double records = recordsAhead(every); records >= 2147483648.0) {
+      fprintf(stderr, "--fourpoint: about %.0f records would pass 2^31 origins per lag: raise --fourpoint-interval or "
+                      "lower max_time\n", records);
+      return 2;
+    }
+    std::vector<int> vectors = halfPlaneVectors((int)o.fourpointNmax);
+    vectors.push_back(0), vectors.push_back(0);
+    const float overlap = o.fourpointOverlap < 0.0f ? sim.getParams().min_radius : o.fourpointOverlap;
+    return sim.setFourPoint(every, (unsigned)o.fourpointLags, overlap, boxLog2(o.fourpointBoxLog2, cfg), vectors) ? 0 : 1;
+  }
+
+  bool writeFourPoint() {
+    if (o.fourpointPath.empty()) return true;
+    std::vector<pbFourPointRow> rows;
+    if (!sim.fourPointRows(rows)) return false;
+    FILE *f = openWhole(o.fourpointPath,
+                        "Lag, Nx, Ny, Origins, SumSteps, Samples, Overlap, Overlap2, Re, Im, Power, Chi4, S4");
+    if (!f) return false;
+    for (const pbFourPointRow &c : rows) {
+      double chi4 = std::nan(""), s4 = std::nan("");
+      if (c.samples) {  // (then there are origins)
+        const long double scale = (long double)c.origins * (long double)c.samples;
+        // Overlap2 O < 2^118 and Overlap^2 < 2^118: the numerator is exact
+        const unsigned __int128 q2 = ((unsigned __int128)c.overlap2[1] << 64) | c.overlap2[0];
+        const __int128 num = (__int128)(q2 * c.origins) - (__int128)((unsigned __int128)c.overlap * c.overlap);
+        chi4 = (double)((long double)num / scale);
+        const long double re = (long double)signed128(c.re), im = (long double)signed128(c.im);
+        s4 = (double)((real192(c.power) * (long double)c.origins - re * re - im * im) / (scale * 1152921504606846976.0L));
+      }
+      fprintf(f, "%u, %d, %d, %llu, %llu, %llu, %llu, %s, %s, %s, %s, %.9g, %.9g\n", c.lag, c.nx, c.ny, c.origins,
+              c.sum_steps, c.samples, c.overlap, decimal128(c.overlap2[1], c.overlap2[0]).c_str(),
+              decimalSigned128(c.re).c_str(), decimalSigned128(c.im).c_str(), decimalSigned192(c.power).c_str(), chi4, s4);
+    }
+    return fclose(f) == 0;
+  }
 };
 
 }  // namespace
@@ -1027,6 +1099,7 @@ int main(int argc, char **argv) {
   if (const int refused = run.startVanHove()) return refused;
   if (const int refused = run.startVanHoveDistinct()) return refused;
   if (const int refused = run.startCoherent()) return refused;
+  if (const int refused = run.startFourPoint()) return refused;
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!o.ckptPath.empty() && run.stepsDone > lastCkptStep) {
@@ -1062,6 +1135,6 @@ int main(int argc, char **argv) {
   fclose(fp);
   const bool written = run.writeTrail() && run.writeContacts() && run.writeRdf() && run.writeTimeCorrelation() &&
                        run.writeScattering() && run.writeVanHove() && run.writeVanHoveDistinct() &&
-                       run.writeCoherent() && run.writeCorrelation();
+                       run.writeCoherent() && run.writeFourPoint() && run.writeCorrelation();
   return written ? 0 : 1;
 }

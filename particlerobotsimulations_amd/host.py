@@ -106,6 +106,10 @@ SYMBOLS = {
     "pbHostCoherentRecord": (_I, [_P]),
     "pbHostCoherentInfo": (_I, [_P, _P, _P, _P, _P, _P]),
     "pbHostCoherentRows": (_I, [_P, _P, _ULL, _PULL]),
+    "pbHostSetFourPoint": (_I, [_P, _F, _U, _F, _I, _P, _U]),
+    "pbHostFourPointRecord": (_I, [_P]),
+    "pbHostFourPointInfo": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "pbHostFourPointRows": (_I, [_P, _P, _ULL, _PULL]),
     "pbHostFieldMap": (_I, [_P, _P, _P, _P]),
     "pbHostStructureFactor": (_I, [_P, _I, _I, _P, _U, _P]),
     "pbHostSetDisplay": (None, [_P, _I]),
