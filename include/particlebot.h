@@ -320,6 +320,20 @@ class Particlebot {
   bool fourPointInfo(float &interval, unsigned &lags, float &overlapRadius, int &boxLog2, unsigned &nvec,
                      unsigned long long &records);
   bool fourPointRows(std::vector<pbFourPointRow> &rows);
+  /* Bond dynamics of the resident state on the device (pbSimSetBondDynamics / pbSimGetBondDynamics,
+   * include/particlebot_hip.h has the definitions), shaped as the time correlations above:
+   * setBondDynamics(interval, lags, linkGap, maxRadius, overlapRadius) keeps a device ring of `lags` records of every
+   * bot's quantised position and neighbour list and, per lag, the exact integer sums over all time origins of the
+   * surviving links and of the cage-relative and plain squared displacements; lags 0 switches it off.
+   * bondDynamicsRecord takes one record now; bondDynamicsInfo gives interval, lags, linkGap, maxRadius, overlapRadius and
+   * the records taken so far; bondDynamicsRows the `lags` rows, lag 0 first.  A bot whose radius is above maxRadius is
+   * absent.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Not part of a
+   * checkpoint. */
+  bool setBondDynamics(float interval, unsigned lags, float linkGap, float maxRadius, float overlapRadius);
+  bool bondDynamicsRecord();
+  bool bondDynamicsInfo(float &interval, unsigned &lags, float &linkGap, float &maxRadius, float &overlapRadius,
+                        unsigned long long &records);
+  bool bondDynamicsRows(std::vector<pbBondRow> &rows);
   /* A field map of the resident state on the device (pbSimFieldMap, include/particlebot_hip.h has the definition):
    * ny x nx cells, row 0 the lowest y, with count, dead and the integer sums of radius and velocity per cell, and the
    * totals row.  Fused engine only: Legacy and HostOnly instances return false with a message on stderr.  Also false on

@@ -1393,6 +1393,111 @@ int pbSimGetFourPointInfo(pbSim *sim, float *interval, unsigned *lags, float *ov
 int pbSimGetFourPoint(pbSim *sim, pbFourPointRow *rows /* nsims * lags * nvec: member, lag, vector */);
 int pbSimGetFourPointTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
 
+/* Bond dynamics on the device (csrc/pb_bonds.hip; the arithmetic is csrc/pb_bonds.hpp): relaxation measured on a bot's
+ * NEIGHBOURS instead of its own displacement.  The recorders above are all built on a bot's displacement, which for this
+ * system is the wrong observable twice over: a collective that translates, turns or breathes has a decaying MSD, F_s and
+ * overlap although no bot has changed its neighbours, and in two dimensions long-wavelength (Mermin-Wagner) fluctuations
+ * make the plain MSD and F_s decay even in a solid.  Per member and lag, over all time origins while pbSimStep runs:
+ *     the BOND-BREAKING correlation: the share of a bot's links at t that are still its links at t + tau
+ *     the CAGE-RELATIVE displacement: a bot's displacement minus the mean displacement of the neighbours it had at t
+ * and, on the same bots, the plain squared displacement, so that the two MSDs are compared on identical samples.  The
+ * book, the records, the interval rules and the pairing are the time correlation's (pbSimSetTimeCorrelation, above); the
+ * link rule is the cluster analysis' (pbSimClusterStats); the quantiser is the scattering's.  What this recorder adds is
+ * a ring of NEIGHBOUR LISTS.  Off by default: a run that does not ask for it makes the same launches, has the same
+ * pbSimStats and the same bits, and nothing is allocated.
+ * pbSimSetBondDynamics(sim, interval, lags, linkGap, maxRadius, overlapRadius).  interval and lags follow the other
+ * lagged recorders exactly: interval > 0 the schedule's gate, 0 every step, -1.0f manual only; lags is
+ * 1 ... PB_BOND_MAX_LAGS; lags == 0 switches off and frees everything (the gap and the radii are then not read).
+ * linkGap is the cluster analysis' gap, finite and >= 0.  maxRadius, finite and > 0, is the largest radius of a bot that
+ * takes part; 2 maxRadius + linkGap < 2048.  overlapRadius is in [0, 256).  Calling again restarts from record 0 with a
+ * zeroed table.  The filing's scratch is made at this call, so that no record allocates.
+ * A RECORD, of the state pbSimGetState would return in front of the step:
+ *   Bot i is PRESENT iff |x| < 2048 and |y| < 2048 (the scattering's rule; a NaN or an infinity fails it) and its radius
+ *   is finite and <= maxRadius.  Positions and radii are the state arrays' own bits.
+ *   Present bots i != j of one member are LINKED iff fl(dist - (ri + rj)) < linkGap in fp32 without contraction, dist the
+ *   correctly rounded root of fl(fl(dx dx) + fl(dy dy)): the cluster analysis' rule, order of operations included.  An
+ *   absent bot has no links and is nobody's neighbour.
+ *   The bots are filed on a grid of edge (2 maxRadius + linkGap)(1 + 2^-10).  A linked pair has
+ *   dist < ri + rj + linkGap <= 2 maxRadius + linkGap, so it is at most one cell apart and the walk over nine cells meets
+ *   it; and because the edge does not depend on the device's largest radius nothing is read back: a record never waits.
+ *   Per bot, in ORIGINAL order, slot r % lags of the ring keeps a HEAD of four 32-bit words (qx, qy, degree, 0), the
+ *   position quantised as rint(v 2^20), and (INT32_MIN, 0, 0, 0) for an absent bot (|q| <= 2^31 - 128: the value is
+ *   free); and a LIST of PB_BOND_WIDTH 32-bit words, the member-local original indices of its neighbours, strictly
+ *   ascending, padded with 0xFFFFFFFF.  A bot with degree > PB_BOND_WIDTH is CROWDED at that record: its degree is
+ *   stored, its list holds the first eight neighbours the walk met and is never read.  48 bytes per bot and slot, heads
+ *   and lists in arrays of their own: the neighbours' heads are gathered at random, from the dense 16-byte array.
+ * A PAIR of records (now; then = lag records earlier; lag 0 pairs a record with itself).  For each bot i:
+ *   SAMPLED iff i is present at both records and crowded at neither.  `crowded` counts the bots that are present at both
+ *   and crowded at either; such a bot takes part in nothing else.
+ *   For a sampled bot t = |N_then|, w = |N_now|, kept = |N_then n N_now|: they add into bonds_then, bonds_now and
+ *   bonds_kept (directed: a link counts once from each end that is sampled).  bots_unchanged counts kept == t && kept == w,
+ *   bots_lost kept < t, bots_gained kept < w.
+ *   CAGE.  Let k = t and dq_x = q_now(x) - q_then(x), as 64-bit integers, for any bot x.  Bot i is CAGED iff k >= 1,
+ *   every j in N_then(i) is present now, and cx = k dq_i.x - sum_j dq_j.x and cy likewise satisfy |cx|, |cy| < 2^31.
+ *   Then s = cx^2 + cy^2 is k^2 times the squared cage-relative displacement in units of 2^-40.  Per k = 1 ... 8 the cell
+ *   keeps cage_samples[k - 1]; cage_overlap[k - 1], the count with s < (k qa)^2, qa = rint(overlapRadius 2^20) formed
+ *   once on the host (equality does not overlap; overlapRadius == 0 overlaps nothing); and cage_q2[k - 1], the sum of s.
+ *   The caller divides by k^2; nothing on the device is divided.  plain_q2 is the sum of dq_i.x^2 + dq_i.y^2 over the same
+ *   caged bots, in units of 2^-40.
+ * EXACTNESS.  |q| <= 2^31 - 128, so |dq| <= 2^32 - 256 < 2^32; k <= 8, so |k dq| and |sum_j dq_j| are below 2^35 and c
+ * below 2^36 in magnitude: no 64-bit word wraps in front of the range test.  An accepted c has |c| < 2^31, hence
+ * s < 2^63, which is added as its low 32 bits and the rest (the time correlation's split); k qa <= 8 (2^28 - 16) < 2^31,
+ * so (k qa)^2 < 2^62.  dq^2 < 2^64 is one word, but dq_x^2 + dq_y^2 may pass 2^64: each square is split on its own, the
+ * two low halves (below 2^33 together) into one word, the two high halves (below 2^33 too) into another.  pbSimGetBondDynamics
+ * refuses a table in which a cell holds 2^31 samples or more ("a lag holds 2^31 samples or more: restart the bond
+ * recorder"), so every partial sum stays below 2^64 and the composed sums are exact: cage_q2[k - 1] < 2^94 and
+ * plain_q2 < 2^96.  (plain_q2.hi, a signed word, is below 2^63 while plain_q2 < 2^95: for fewer than 2^30 caged samples
+ * in the cell whatever they did, and for any count if no displacement reaches 2896 world units.)  Integer adds commute:
+ * results do not depend on slot order, on the kernel form that stepped or on the order in which the device adds.  No
+ * float atomics and no atomic wider than 64 bits.
+ * PER MEMBER AND LAG one pbBondRow: lag in RECORDS; origins and sum_steps as in pbTimeCorrelationRow; the counts; the
+ * 128-bit sums as pbMoment128 (value = hi 2^32 + lo, 0 <= lo < 2^32).  The caller forms
+ *     bond survival = bonds_kept / bonds_then          fraction lost = bots_lost / samples
+ *     cage MSD = (sum_k cage_q2[k - 1] / k^2) / (sum_k cage_samples[k - 1]) 2^-40
+ *     plain MSD = plain_q2 / (sum_k cage_samples[k - 1]) 2^-40.
+ * OTHER CALLS.  pbSimBondDynamicsRecord: one record now, of the state as it is, whatever the interval.
+ * pbSimGetBondDynamicsInfo: interval, lags (0: off), linkGap, maxRadius, overlapRadius and the records taken so far; any
+ * pointer may be NULL, not all.  pbSimGetBondDynamics: nsims * lags rows, member-major, lag 0 first; a lag that no record
+ * has reached yet has origins == 0 and zeros.  pbSimGetBondDynamicsTimes: records so far and the span of the last
+ * record's launches on the batch's stream in milliseconds (HIP events); either pointer may be NULL.
+ * ORDER.  The bond record is taken behind the four-point record and in front of the centroid trail and the phase update,
+ * of the same state as the other recorders' records.  No launch is fused across the gate and a resident stretch ends in
+ * front of it.
+ * The ring is not part of a checkpoint: pbSimSetState*, pbSimSetTime and pbSimSetLayoutOf leave it alone; pbSimDestroy
+ * frees it.  Recording never waits for the device.  It only reads the state, slot layout, keys, cell lists, pbSimStats,
+ * time, RNG, the mark and every other recorder's memory; it re-files the bots in the analysis layer's shared scratch, as a
+ * distinct van Hove record does, which every on-demand analysis re-files for itself.
+ * PB_ERR_ARG, before the device is touched: a NULL handle or rows; interval NaN, infinite, or negative other than -1;
+ * lags > PB_BOND_MAX_LAGS; linkGap or maxRadius negative, NaN or infinite; maxRadius == 0;
+ * 2 maxRadius + linkGap >= 2048; overlapRadius NaN or outside [0, 256); a batch of more than 65535 members or of 2^28
+ * bots or more; a ring above 2^33 bytes (lags x total x 48); the pointers of pbSimGetBondDynamicsInfo all NULL; a record
+ * or a read with the bond recorder off.
+ * Cost: a record files the bots (hash, sort, gather, cell starts), walks every bot's nine cells once (k_bond_snapshot)
+ * and pairs the record with its lags in one launch (k_bond_pairs): per bot and lag two coalesced 48-byte entries and
+ * 2 k random 16-byte gathers, k the bot's earlier degree.  Device memory: 48 bytes per bot and lag, 336 bytes per
+ * (member, lag).  Read back: the cells.  profiles/bond_dynamics.txt has the registers and the measurements.
+ * Out of scope: per-bot outputs; logarithmic lags; lists wider than 8; a rotation-corrected cage (the Falk-Langer fit per
+ * lag); neighbour exchange (T1) counting; the ensemble layer's summary rows; the legacy engine. */
+#define PB_BOND_MAX_LAGS 64u
+#define PB_BOND_BLOCKS 256u /* workgroups per member and lag: one pass covers 65536 bots of a member */
+#define PB_BOND_WIDTH 8u    /* neighbours a bot's list holds; a bot with more is crowded */
+typedef struct pbBondRow {             /* 360 bytes */
+  unsigned lag, reserved;              /* lag in RECORDS: record r against record r - lag; 0 */
+  unsigned long long origins, sum_steps;                 /* the book's columns */
+  unsigned long long samples, crowded; /* sampled bots; bots present at both records and crowded at either */
+  unsigned long long bonds_then, bonds_now, bonds_kept;  /* directed */
+  unsigned long long bots_unchanged, bots_lost, bots_gained;
+  pbMoment128 plain_q2;                /* sum of dq^2 over the caged bots, units of 2^-40 */
+  unsigned long long cage_samples[8], cage_overlap[8];   /* per k = 1 ... 8 earlier neighbours */
+  pbMoment128 cage_q2[8];              /* sum of s = k^2 x (cage-relative displacement)^2, units of 2^-40 */
+} pbBondRow;
+int pbSimSetBondDynamics(pbSim *sim, float interval, unsigned lags, float linkGap, float maxRadius, float overlapRadius);
+int pbSimBondDynamicsRecord(pbSim *sim);  /* one record now, of the state as it is */
+int pbSimGetBondDynamicsInfo(pbSim *sim, float *interval, unsigned *lags, float *linkGap, float *maxRadius,
+                             float *overlapRadius, unsigned long long *records);
+int pbSimGetBondDynamics(pbSim *sim, pbBondRow *rows /* nsims * lags, member-major, lag 0 first */);
+int pbSimGetBondDynamicsTimes(pbSim *sim, unsigned long long *records, float *last_device_ms);
+
 /* Local strain and non-affine displacement D2min on the device (csrc/pb_strain.hip; the fit itself is
  * csrc/pb_strain.hpp): the Falk-Langer fit against the mark of the rearrangement analysis.  For every bot, the best
  * local affine map that carries its MARKED bond vectors onto its present ones (the local deformation gradient: strain

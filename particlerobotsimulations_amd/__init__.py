@@ -19,7 +19,8 @@ __all__ = ["Sim", "Ensemble", "DeviceArray", "legacy", "SimParams", "make_params
            "radial_distribution", "mean_squared_displacement", "moments_summary", "correlation_values",
            "connected_correlation", "time_correlation_summary", "field_values", "structure_factor_values",
            "half_plane_vectors", "phasor_table", "scattering_summary", "van_hove_summary",
-           "deformation_gradient", "mean_d2min", "coherent_scattering_summary", "four_point_summary"]
+           "deformation_gradient", "mean_d2min", "coherent_scattering_summary", "four_point_summary",
+           "bond_dynamics_summary"]
 
 
 def phasor_table():
@@ -182,6 +183,30 @@ def four_point_summary(rows):
     s4 = [float(Fraction(int(r["power"]) * o - int(r["re"]) ** 2 - int(r["im"]) ** 2, (o * m) << 60)) for r in rows]
     return {"mean_overlap": float(Fraction(q, m)), "chi4": float(Fraction(q2 * o - q * q, o * m)), "s4": s4,
             "mean_lag_steps": float(Fraction(int(first["sum_steps"]), o))}
+
+
+def bond_dynamics_summary(row):
+    """What one row of bond_dynamics() says, in float64 from the integers (pure Python ints; every quotient is formed as
+    one exact fraction and converted once).  With C = sum_k cage_samples[k - 1], the caged bots:
+    bond_survival = bonds_kept / bonds_then, the bond-breaking correlation;  fraction_lost = bots_lost / samples;
+    cage_msd = (sum_k cage_q2[k - 1] / k^2) / (2^40 C), the mean squared cage-relative displacement in world units;
+    plain_msd = plain_q2 / (2^40 C), the plain one of the same bots;  cage_overlap = sum_k cage_overlap[k - 1] / C;
+    crowded_fraction = crowded / (samples + crowded);  mean_lag_steps = sum_steps / origins.  A value whose denominator
+    is 0 is None."""
+    from fractions import Fraction
+
+    def quotient(num, den):
+        return float(Fraction(num, den)) if den else None
+
+    caged = sum(int(c) for c in row["cage_samples"])
+    cage = sum(Fraction(int(q), k * k) for k, q in enumerate(row["cage_q2"], 1))
+    samples, crowded = int(row["samples"]), int(row["crowded"])
+    return {"bond_survival": quotient(int(row["bonds_kept"]), int(row["bonds_then"])),
+            "fraction_lost": quotient(int(row["bots_lost"]), samples),
+            "cage_msd": quotient(cage, caged << 40), "plain_msd": quotient(int(row["plain_q2"]), caged << 40),
+            "cage_overlap": quotient(sum(int(c) for c in row["cage_overlap"]), caged),
+            "crowded_fraction": quotient(crowded, samples + crowded),
+            "mean_lag_steps": quotient(int(row["sum_steps"]), int(row["origins"]))}
 
 
 def van_hove_summary(row, width):
@@ -1119,6 +1144,42 @@ class Sim:
     def four_point_times(self):
         """(records taken so far, device milliseconds of the last record's launches)."""
         return self._span("pbSimGetFourPointTimes")
+
+    def set_bond_dynamics(self, interval, lags, link_gap, max_radius, overlap_radius):
+        """Keep a device ring of `lags` records of every bot's quantised position and of the list of its up to 8
+        neighbours under the cluster analysis' link rule at `link_gap`, among the bots whose radius is at most
+        `max_radius`; one record is taken in front of every step whose start time passes the schedule's gate at
+        `interval` (0: every step, -1: only by bond_dynamics_record()) while step() runs.  Per pair of a record with one
+        of the `lags` latest ones the surviving links and, per bot, the displacement relative to the neighbours it had
+        are summed over the origins as exact integers (pbSimSetBondDynamics); a caged bot overlaps if that displacement
+        is shorter than `overlap_radius`, in [0, 256).  Restarts at record 0; lags 0 switches it off.  Recording changes
+        no state bit."""
+        _capi.check(_capi.lib().pbSimSetBondDynamics(self._h, float(interval), int(lags), float(link_gap),
+                                                     float(max_radius), float(overlap_radius)), "pbSimSetBondDynamics")
+
+    def bond_dynamics_record(self):
+        """One record now, of the state as it is (pbSimBondDynamicsRecord)."""
+        _capi.check(_capi.lib().pbSimBondDynamicsRecord(self._h), "pbSimBondDynamicsRecord")
+
+    def bond_dynamics_info(self):
+        """A dict of interval, lags (0: off), link_gap, max_radius, overlap_radius and records taken so far
+        (pbSimGetBondDynamicsInfo)."""
+        return _analysis.read_info(_analysis.BOND_DYNAMICS_INFO, lambda *p: _capi.check(
+            _capi.lib().pbSimGetBondDynamicsInfo(self._h, *p), "pbSimGetBondDynamicsInfo"))
+
+    def bond_dynamics(self):
+        """The table as it stands (pbSimGetBondDynamics): per member a list over lags (lag 0 first) of dicts of Python
+        ints: lag, origins, sum_steps, samples, crowded, bonds_then, bonds_now, bonds_kept, bots_unchanged, bots_lost,
+        bots_gained, plain_q2, and the lists over k = 1 ... 8 cage_samples, cage_overlap and cage_q2 (units of 2^-40,
+        k^2 times the cage-relative sum).  bond_dynamics_summary() turns a row into the quotients."""
+        lags = self.bond_dynamics_info()["lags"]
+        rows = (_capi.pbBondRow * max(self.nsims * lags, 1))()
+        _capi.check(_capi.lib().pbSimGetBondDynamics(self._h, rows), "pbSimGetBondDynamics")
+        return _analysis.lag_table(self.nsims, lags, lambda g: _capi.bond_row(rows[g]))
+
+    def bond_dynamics_times(self):
+        """(records taken so far, device milliseconds of the last record's launches)."""
+        return self._span("pbSimGetBondDynamicsTimes")
 
 
 class Ensemble(Sim):

@@ -20,6 +20,8 @@ VAN_HOVE_DISTINCT_INFO = VAN_HOVE_INFO
 COHERENT_INFO = SCATTERING_INFO
 FOUR_POINT_INFO = (("interval", C.c_float), ("lags", C.c_uint), ("overlap_radius", C.c_float), ("box_log2", C.c_int),
                    ("nvec", C.c_uint), ("records", C.c_ulonglong))
+BOND_DYNAMICS_INFO = (("interval", C.c_float), ("lags", C.c_uint), ("link_gap", C.c_float), ("max_radius", C.c_float),
+                      ("overlap_radius", C.c_float), ("records", C.c_ulonglong))
 
 
 def read_info(spec, call):

@@ -350,6 +350,45 @@ def four_point_row(r):
     return d
 
 
+class pbBondRow(C.Structure):
+    _fields_ = [("lag", C.c_uint), ("reserved", C.c_uint), ("origins", C.c_ulonglong), ("sum_steps", C.c_ulonglong),
+                ("samples", C.c_ulonglong), ("crowded", C.c_ulonglong), ("bonds_then", C.c_ulonglong),
+                ("bonds_now", C.c_ulonglong), ("bonds_kept", C.c_ulonglong), ("bots_unchanged", C.c_ulonglong),
+                ("bots_lost", C.c_ulonglong), ("bots_gained", C.c_ulonglong), ("plain_q2", pbMoment128),
+                ("cage_samples", C.c_ulonglong * 8), ("cage_overlap", C.c_ulonglong * 8), ("cage_q2", pbMoment128 * 8)]
+
+
+# pbBondRow as a numpy record: each 128-bit value is hi * 2^32 + lo, normalised to 0 <= lo < 2^32; cage_q2 is (8, 2)
+# words, (lo, hi) per k, the hi read as a signed word
+BOND_ROW_DTYPE = np.dtype([("lag", np.uint32), ("reserved", np.uint32), ("origins", np.uint64), ("sum_steps", np.uint64),
+                           ("samples", np.uint64), ("crowded", np.uint64), ("bonds_then", np.uint64),
+                           ("bonds_now", np.uint64), ("bonds_kept", np.uint64), ("bots_unchanged", np.uint64),
+                           ("bots_lost", np.uint64), ("bots_gained", np.uint64), ("plain_q2_lo", np.uint64),
+                           ("plain_q2_hi", np.int64), ("cage_samples", np.uint64, (8,)),
+                           ("cage_overlap", np.uint64, (8,)), ("cage_q2", np.uint64, (8, 2))])
+BOND_MAX_LAGS = 64
+BOND_WIDTH = 8
+
+
+def bond_row(r):
+    """A pbBondRow as a dict of Python ints: the counts as they are, plain_q2 and the eight cage_q2 composed as
+    hi * 2^32 + lo (units of 2^-40; cage_q2[k - 1] is k^2 times the cage-relative sum)."""
+    d = {}
+    for name, kind in r._fields_:
+        if name == "reserved":
+            continue
+        v = getattr(r, name)
+        if name == "cage_q2":
+            d[name] = [(int(m.hi) << 32) + int(m.lo) for m in v]
+        elif kind is pbMoment128:
+            d[name] = (int(v.hi) << 32) + int(v.lo)
+        elif issubclass(kind, C.Array):
+            d[name] = [int(x) for x in v]
+        else:
+            d[name] = int(v)
+    return d
+
+
 # pbContactLink as a numpy record
 CONTACT_LINK_DTYPE = np.dtype([("other", np.uint32), ("gap", np.float32), ("fx", np.float32), ("fy", np.float32)])
 
@@ -478,6 +517,12 @@ SYMBOLS = {
                                    C.POINTER(C.c_ulonglong)]),
     "pbSimGetFourPoint": (_I, [_VP, C.POINTER(pbFourPointRow)]),
     "pbSimGetFourPointTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
+    "pbSimSetBondDynamics": (_I, [_VP, _F, _U, _F, _F, _F]),
+    "pbSimBondDynamicsRecord": (_I, [_VP]),
+    "pbSimGetBondDynamicsInfo": (_I, [_VP, C.POINTER(_F), C.POINTER(_U), C.POINTER(_F), C.POINTER(_F), C.POINTER(_F),
+                                      C.POINTER(C.c_ulonglong)]),
+    "pbSimGetBondDynamics": (_I, [_VP, C.POINTER(pbBondRow)]),
+    "pbSimGetBondDynamicsTimes": (_I, [_VP, C.POINTER(C.c_ulonglong), C.POINTER(_F)]),
     "pbSimGetLayoutOf": (_I, [_VP, _U, _VP, _VP, C.POINTER(_I)]),
     "pbSimSetLayoutOf": (_I, [_VP, _U, _VP, _VP]),
     "pbSimSetForcesOf": (_I, [_VP, _U, _VP, _VP]),

@@ -1693,6 +1693,33 @@ bool Particlebot::fourPointRows(std::vector<pbFourPointRow> &rows) {
   });
 }
 
+bool Particlebot::setBondDynamics(float interval, unsigned lags, float linkGap, float maxRadius, float overlapRadius) {
+  return onFusedEngine("setBondDynamics", "bond recorder",
+                       [&] { return pbSimSetBondDynamics(sim, interval, lags, linkGap, maxRadius, overlapRadius); });
+}
+
+bool Particlebot::bondDynamicsRecord() {
+  return onFusedEngine("bondDynamicsRecord", "bond recorder", [&] { return pbSimBondDynamicsRecord(sim); });
+}
+
+bool Particlebot::bondDynamicsInfo(float &interval, unsigned &lags, float &linkGap, float &maxRadius,
+                                   float &overlapRadius, unsigned long long &records) {
+  auto call = [&] { return pbSimGetBondDynamicsInfo(sim, &interval, &lags, &linkGap, &maxRadius, &overlapRadius, &records); };
+  return onFusedEngine("bondDynamicsInfo", "bond recorder", call);
+}
+
+bool Particlebot::bondDynamicsRows(std::vector<pbBondRow> &rows) {
+  return onFusedEngine("bondDynamicsRows", "bond recorder", [&] {
+    unsigned lags = 0;
+    const int rc = pbSimGetBondDynamicsInfo(sim, nullptr, &lags, nullptr, nullptr, nullptr, nullptr);
+    if (rc != PB_OK) return rc;
+    rows.assign(lags ? lags : 1, pbBondRow());  // (the engine takes no NULL; with the recorder off it refuses)
+    const int got = pbSimGetBondDynamics(sim, rows.data());
+    if (got != PB_OK) rows.clear();
+    return got;
+  });
+}
+
 bool Particlebot::fieldMap(const pbFieldView &view, std::vector<pbFieldCell> &cells, pbFieldTotals &totals) {
   return onFusedEngine("fieldMap", "field map", [&] {
     const bool fits = view.nx >= 1 && view.nx <= PB_FIELD_MAX_AXIS && view.ny >= 1 && view.ny <= PB_FIELD_MAX_AXIS;

@@ -643,6 +643,40 @@ int pbHostFourPointRows(void *hv, pbFourPointRow *rows, unsigned long long cap, 
   return 0;
 }
 
+// bond dynamics of the resident state (Particlebot::setBondDynamics / bondDynamicsRecord / bondDynamicsInfo /
+// bondDynamicsRows; fused engine only), shaped as the four-point recorder's: the 360-byte pbBondRow of every lag (cap
+// entries of room; *count = how many there are).  -1 on the other engines, a bad interval, lags, gap or radius, a record
+// or a read with the recorder off, or too little room.
+int pbHostSetBondDynamics(void *hv, float interval, unsigned lags, float linkGap, float maxRadius, float overlapRadius) {
+  return ((HostSim *)hv)->bot->setBondDynamics(interval, lags, linkGap, maxRadius, overlapRadius) ? 0 : -1;
+}
+
+int pbHostBondDynamicsRecord(void *hv) { return ((HostSim *)hv)->bot->bondDynamicsRecord() ? 0 : -1; }
+
+int pbHostBondDynamicsInfo(void *hv, float *interval, unsigned *lags, float *linkGap, float *maxRadius,
+                           float *overlapRadius, unsigned long long *records) {
+  float i = 0.0f, g = 0.0f, m = 0.0f, a = 0.0f;
+  unsigned l = 0;
+  unsigned long long r = 0;
+  if (!((HostSim *)hv)->bot->bondDynamicsInfo(i, l, g, m, a, r)) return -1;
+  if (interval) *interval = i;
+  if (lags) *lags = l;
+  if (linkGap) *linkGap = g;
+  if (maxRadius) *maxRadius = m;
+  if (overlapRadius) *overlapRadius = a;
+  if (records) *records = r;
+  return 0;
+}
+
+int pbHostBondDynamicsRows(void *hv, pbBondRow *rows, unsigned long long cap, unsigned long long *count) {
+  std::vector<pbBondRow> v;
+  if (!count || !((HostSim *)hv)->bot->bondDynamicsRows(v)) return -1;
+  *count = v.size();
+  if (rows && cap < v.size()) return -1;
+  copyOut(rows, v);
+  return 0;
+}
+
 // a field map of the resident state (Particlebot::fieldMap; fused engine only): ny * nx 64-byte pbFieldCell entries and,
 // unless NULL, the 16-byte pbFieldTotals row.  -1 on the other engines and on a bad view.
 int pbHostFieldMap(void *hv, const pbFieldView *view, pbFieldCell *cells, pbFieldTotals *totals) {

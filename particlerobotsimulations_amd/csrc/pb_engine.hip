@@ -637,9 +637,9 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
   // The host events that are on, in firing order: the records of the time series (pb_moments.hip), the time
   // correlations (pb_timecorr.hip), the scattering (pb_scatter.hip), the van Hove function (pb_vanhove.hip) and its
   // distinct part (pb_vanhove_distinct.hip), the coherent scattering (pb_coherent.hip), the four-point recorder
-  // (pb_fourpoint.hip), the centroid trail, the phase update.  A new recorder is one more entry; the loop below does not
-  // name them.
-  PbHostEvent events[9];
+  // (pb_fourpoint.hip), the bond recorder (pb_bonds.hip), the centroid trail, the phase update.  A new recorder is one
+  // more entry; the loop below does not name them.
+  PbHostEvent events[10];
   int nEvents = 0;
   if (S->series.ring) events[nEvents++] = {true, true, S->series.interval, pbSeriesRecord};
   if (S->tc.lag.ring)
@@ -654,6 +654,8 @@ int stepMany(pbSim *S, float dt, float sortInterval, int nsteps, int *done) {
     events[nEvents++] = {true, true, S->co.lag.interval, [](pbSim *B, float) { return pbCoherentRecord(B); }};
   if (S->fp.lag.ring)
     events[nEvents++] = {true, true, S->fp.lag.interval, [](pbSim *B, float) { return pbFourPointRecord(B); }};
+  if (S->bd.lag.ring)
+    events[nEvents++] = {true, true, S->bd.lag.interval, [](pbSim *B, float) { return pbBondDynamicsRecord(B); }};
   if (S->trail.ring) events[nEvents++] = {false, false, S->trail.interval, trailRecord};
   if (lightWave)
     events[nEvents++] = {false, false, S->host.phase_update_interval, [](pbSim *B, float) { return phaseUpdate(B); }};

@@ -27,6 +27,9 @@
 //   pb_fourpoint.hip four-point dynamics: masked density modes per origin pair over a lag ring, and the exact sums of the
 //                    overlap count, its square, the modes and their squared magnitudes per lag (pbSimSetFourPoint);
 //                    pb_fourpoint.hpp holds the arithmetic
+//   pb_bonds.hip     bond dynamics: a ring of neighbour lists, and per lag the surviving links and the cage-relative
+//                    displacements of a record against the ring's (pbSimSetBondDynamics); pb_bonds.hpp holds the
+//                    arithmetic
 //   pb_strain.hip    local strain and D2min: the Falk-Langer fit of every bot's marked bonds onto its present ones, a
 //                    gather over the rearrangement analysis' mark (pbSimStrainStats); pb_strain.hpp holds the fit
 //   pb_selftest.hip  exhaustive / sampled on-device proofs of the fast exact math, shader-clock sampler
@@ -103,7 +106,7 @@ struct PbSeries {
   std::vector<unsigned long long> steps;  // per slot: stats.steps at that moment
 };
 // ---- the lag ring: what the lagged analyses (pb_timecorr.hip, pb_scatter.hip, pb_vanhove.hip,
-// pb_vanhove_distinct.hip, pb_coherent.hip, pb_fourpoint.hip) share ------------------------------------------------------
+// pb_vanhove_distinct.hip, pb_coherent.hip, pb_fourpoint.hip, pb_bonds.hip) share ----------------------------------------
 // A ring of `lags` snapshots of the whole batch in ORIGINAL order, lags x total entries of Snap.  Record r goes into
 // slot r % lags and is paired with the records r - l for l = 0 ... min(r, lags - 1); all pairs of a record are added
 // into `table` by one launch over pbLagGrid() workgroups of PB_LAG_LANES lanes, which pbLagPair() takes apart again.
@@ -114,10 +117,11 @@ constexpr int PB_LAG_LANES = 256;
 constexpr unsigned PB_LAG_MAX_LAGS = 64u, PB_LAG_BLOCKS = 256u;  // (the public header states both per analysis)
 static_assert(PB_TCORR_MAX_LAGS == PB_LAG_MAX_LAGS && PB_SCATTER_MAX_LAGS == PB_LAG_MAX_LAGS &&
                   PB_VANHOVE_MAX_LAGS == PB_LAG_MAX_LAGS && PB_COHERENT_MAX_LAGS == PB_LAG_MAX_LAGS &&
-                  PB_FOURPOINT_MAX_LAGS == PB_LAG_MAX_LAGS,
+                  PB_FOURPOINT_MAX_LAGS == PB_LAG_MAX_LAGS && PB_BOND_MAX_LAGS == PB_LAG_MAX_LAGS,
               "one bound on the lags");  // (the distinct part uses the self part's)
 static_assert(PB_TCORR_BLOCKS == PB_LAG_BLOCKS && PB_SCATTER_BLOCKS == PB_LAG_BLOCKS &&
-                  PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS && PB_FOURPOINT_BLOCKS == PB_LAG_BLOCKS,
+                  PB_VANHOVE_BLOCKS == PB_LAG_BLOCKS && PB_FOURPOINT_BLOCKS == PB_LAG_BLOCKS &&
+                  PB_BOND_BLOCKS == PB_LAG_BLOCKS,
               "one bound on the blocks per lag");
 
 // the host's counters of a ring
@@ -250,6 +254,16 @@ struct PbFourPoint {
   unsigned long long a2 = 0;  // ... squared
 };
 
+// bond dynamics (pb_bonds.hip): int4 heads (qx, qy, degree, 0), (INT32_MIN, 0, 0, 0) for an absent bot, in the ring; the
+// lists of eight neighbour indices beside it, two uint4 per bot and slot in the ring's order; and nsims x lags cells of
+// PB_BOND_WORDS words (pb_bonds.hpp; pbSimSetBondDynamics)
+struct PbBondDynamics {
+  PbLagRing<int4> lag;
+  PbDevBuf<uint4> lists;  // lags x total x 2
+  float gap = 0.0f, maxRadius = 0.0f, radius = 0.0f;
+  long long qa = 0;  // rint(radius * 2^20)
+};
+
 // distinct van Hove function (pb_vanhove_distinct.hip): float2 (x, y) snapshots, NaN for an absent bot, and nsims x lags
 // cells of 2 + bins words, member-major: centres, partners, then the radial histogram of ordered pairs (pb_vanhove.hpp;
 // pbSimSetVanHoveDistinct)
@@ -348,6 +362,7 @@ struct pbSim {
   // PB_ALLOW_ENV_OVERRIDES)
   bool coherentStripes = true;
   PbFourPoint fp;
+  PbBondDynamics bd;
   pbSimStats stats{};
 };
 
@@ -402,7 +417,7 @@ int pbLagAllocate(pbSim *S, PbLagRing<Snap> &R, unsigned lags, size_t words, siz
   PB_TRY(hipMemsetAsync(R.table, 0, sizeof(unsigned long long) * words, S->stream));
   return PB_OK;
 }
-// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd, S->co, S->fp) off and, unless lags is 0, on again: a fresh value
+// Switches the analysis `held` (S->tc, S->sc, S->vh, S->vd, S->co, S->fp, S->bd) off and, unless lags is 0, on again: a fresh value
 // with a ring of `lags` snapshots (of perSlot entries each; 0: one per bot of the batch), a zeroed table of wordsPerLag
 // words per member and lag, a book at record 0, and what fill(fresh) sets of the analysis' own.  When any of it fails,
 // what was made goes and the analysis stays off.
@@ -523,3 +538,4 @@ int pbVanHoveRecord(pbSim *S);          // ... a position snapshot and its lags 
 int pbVanHoveDistinctRecord(pbSim *S);  // ... a filing, a snapshot and its lags (pbLagRecord)     pb_vanhove_distinct.hip
 int pbCoherentRecord(pbSim *S);         // ... the density modes and their products with the ring's         pb_coherent.hip
 int pbFourPointRecord(pbSim *S);        // ... a quantised snapshot, the masked modes of its lags, their fold  pb_fourpoint.hip
+int pbBondDynamicsRecord(pbSim *S);     // ... a filing, the heads and lists, and their pairs with the ring's    pb_bonds.hip

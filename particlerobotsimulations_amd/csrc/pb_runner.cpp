@@ -18,6 +18,8 @@
 //                   [--coherent FILE [--coherent-interval T] [--coherent-lags N] [--coherent-box-log2 E] [--coherent-nmax M]]
 //                   [--fourpoint FILE [--fourpoint-interval T] [--fourpoint-lags N] [--fourpoint-overlap A]
 //                    [--fourpoint-box-log2 E] [--fourpoint-nmax M]]
+//                   [--bonds FILE [--bonds-interval T] [--bonds-lags N] [--bonds-gap G] [--bonds-max-radius R]
+//                    [--bonds-overlap A]]
 //                   [--resume FILE [--overwrite-csv]] [--checkpoint FILE [--checkpoint-every SECONDS] [--checkpoint-steps N]]
 //                   [--final-checkpoint FILE]
 //
@@ -130,6 +132,13 @@ struct RunOptions {
   float fourpointOverlap = -1.0f;                // below 0: min_radius, as --timecorr-overlap
   long fourpointLags = 32, fourpointNmax = 3;    // 24 wavevectors and (0, 0)
   long fourpointBoxLog2 = PB_SK_MIN_LOG2 - 1;    // below the range: boxLog2() chooses
+
+  std::string bondsPath;
+  float bondsInterval = -1.0f;                   // below 0: dump_interval
+  float bondsGap = 0.0f;
+  float bondsMaxRadius = 0.0f;                   // 0: max_radius of the cfg
+  float bondsOverlap = -1.0f;                    // below 0: min_radius, as --timecorr-overlap
+  long bondsLags = 32;
 };
 
 using Choice = std::pair<const char *, int>;  // a word and what it stands for
@@ -252,6 +261,13 @@ const Flag kFlags[] = {
     {"--fourpoint-overlap", &RunOptions::fourpointOverlap, 0.0f, false, 2048.0f},
     {"--fourpoint-box-log2", &RunOptions::fourpointBoxLog2, PB_SK_MIN_LOG2, PB_SK_MAX_LOG2},
     {"--fourpoint-nmax", &RunOptions::fourpointNmax, 1, 10},  // (11: 265 vectors, past PB_FOURPOINT_MAX_VECTORS)
+
+    {"--bonds", &RunOptions::bondsPath, "recorder"},
+    {"--bonds-interval", &RunOptions::bondsInterval, 0.0f, false},
+    {"--bonds-lags", &RunOptions::bondsLags, 1, PB_BOND_MAX_LAGS},
+    {"--bonds-gap", &RunOptions::bondsGap, 0.0f, false, 2048.0f},
+    {"--bonds-max-radius", &RunOptions::bondsMaxRadius, 0.0f, true, 1024.0f},
+    {"--bonds-overlap", &RunOptions::bondsOverlap, 0.0f, false, 256.0f},
 };
 
 // a flag's value: the whole string a finite float, >= lowest (> lowest when `above`)
@@ -962,6 +978,62 @@ struct Run {
     }
     return fclose(f) == 0;
   }
+
+  // --bonds FILE: the device's bond recorder (Particlebot::setBondDynamics).  Records are taken as --timecorr takes
+  // them, at --bonds-interval into a ring of --bonds-lags records of every bot's quantised position and neighbour list
+  // under the link rule at --bonds-gap, among the bots whose radius is at most --bonds-max-radius (default: max_radius of
+  // the configuration).  A payload bot larger than max_radius is ABSENT, with no links and nobody's neighbour, unless
+  // --bonds-max-radius is raised to hold it.  A caged bot overlaps if it moved less than --bonds-overlap (default
+  // min_radius) relative to the neighbours it had.  Switched on behind a resume; refused by its record count alone, as
+  // --timecorr.  At the end of the run one line per lag, lag 0 first: the row's integers as they are (the 128-bit sums
+  // as exact decimals), then BondSurvival = BondsKept / BondsThen, FractionLost = BotsLost / Samples,
+  // CageMsd = (sum_k CageQ2_k / k^2) / (2^40 C), PlainMsd = PlainQ2 / (2^40 C) and CageOverlap = (sum_k CageOverlap_k) / C
+  // with C = sum_k CageSamples_k, in long double, as %.9g (nan where the denominator is 0).
+  int startBonds() {
+    if (o.bondsPath.empty()) return 0;
+    const float every = recordEvery(o.bondsInterval, cfg);
+    if (const double records = recordsAhead(every); records >= 2147483648.0) {
+      fprintf(stderr, "--bonds: about %.0f records would pass 2^31 origins per lag: raise --bonds-interval or lower "
+                      "max_time\n", records);
+      return 2;
+    }
+    const float maxRadius = o.bondsMaxRadius > 0.0f ? o.bondsMaxRadius : sim.getParams().max_radius;
+    const float overlap = o.bondsOverlap < 0.0f ? sim.getParams().min_radius : o.bondsOverlap;
+    return sim.setBondDynamics(every, (unsigned)o.bondsLags, o.bondsGap, maxRadius, overlap) ? 0 : 1;
+  }
+
+  bool writeBonds() {
+    if (o.bondsPath.empty()) return true;
+    std::vector<pbBondRow> rows;
+    if (!sim.bondDynamicsRows(rows)) return false;
+    std::string header = "Lag, Origins, SumSteps, Samples, Crowded, BondsThen, BondsNow, BondsKept, BotsUnchanged, BotsLost, "
+                         "BotsGained, PlainQ2";
+    for (const char *column : {"CageSamples", "CageOverlap", "CageQ2"})
+      for (unsigned k = 1; k <= PB_BOND_WIDTH; k++) header += std::string(", ") + column + std::to_string(k);
+    header += ", BondSurvival, FractionLost, CageMsd, PlainMsd, CageOverlap";
+    FILE *f = openWhole(o.bondsPath, header.c_str());
+    if (!f) return false;
+    const auto real = [](const pbMoment128 &m) { return (long double)m.hi * 4294967296.0L + (long double)m.lo; };
+    const auto quotient = [](long double num, long double den) { return den > 0.0L ? (double)(num / den) : std::nan(""); };
+    for (const pbBondRow &r : rows) {
+      fprintf(f, "%u, %llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu, %llu, %s", r.lag, r.origins, r.sum_steps,
+              r.samples, r.crowded, r.bonds_then, r.bonds_now, r.bonds_kept, r.bots_unchanged, r.bots_lost, r.bots_gained,
+              decimal128(r.plain_q2).c_str());
+      long double caged = 0.0L, overlapping = 0.0L, cage = 0.0L;
+      for (unsigned k = 0; k < PB_BOND_WIDTH; k++) {
+        fprintf(f, ", %llu", r.cage_samples[k]);
+        caged += (long double)r.cage_samples[k], overlapping += (long double)r.cage_overlap[k];
+        cage += real(r.cage_q2[k]) / (long double)((k + 1u) * (k + 1u));
+      }
+      for (unsigned k = 0; k < PB_BOND_WIDTH; k++) fprintf(f, ", %llu", r.cage_overlap[k]);
+      for (unsigned k = 0; k < PB_BOND_WIDTH; k++) fprintf(f, ", %s", decimal128(r.cage_q2[k]).c_str());
+      const long double unit = 1099511627776.0L;  // 2^40
+      fprintf(f, ", %.9g, %.9g, %.9g, %.9g, %.9g\n", quotient((long double)r.bonds_kept, (long double)r.bonds_then),
+              quotient((long double)r.bots_lost, (long double)r.samples), quotient(cage, caged * unit),
+              quotient(real(r.plain_q2), caged * unit), quotient(overlapping, caged));
+    }
+    return fclose(f) == 0;
+  }
 };
 
 }  // namespace
@@ -1100,6 +1172,7 @@ int main(int argc, char **argv) {
   if (const int refused = run.startVanHoveDistinct()) return refused;
   if (const int refused = run.startCoherent()) return refused;
   if (const int refused = run.startFourPoint()) return refused;
+  if (const int refused = run.startBonds()) return refused;
   for (;;) {
     // a checkpoint is taken here, where the loop is about to dump: resuming re-enters at this very point
     if (!o.ckptPath.empty() && run.stepsDone > lastCkptStep) {
@@ -1135,6 +1208,6 @@ int main(int argc, char **argv) {
   fclose(fp);
   const bool written = run.writeTrail() && run.writeContacts() && run.writeRdf() && run.writeTimeCorrelation() &&
                        run.writeScattering() && run.writeVanHove() && run.writeVanHoveDistinct() &&
-                       run.writeCoherent() && run.writeFourPoint() && run.writeCorrelation();
+                       run.writeCoherent() && run.writeFourPoint() && run.writeBonds() && run.writeCorrelation();
   return written ? 0 : 1;
 }

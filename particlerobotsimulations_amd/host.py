@@ -110,6 +110,10 @@ SYMBOLS = {
     "pbHostFourPointRecord": (_I, [_P]),
     "pbHostFourPointInfo": (_I, [_P, _P, _P, _P, _P, _P, _P]),
     "pbHostFourPointRows": (_I, [_P, _P, _ULL, _PULL]),
+    "pbHostSetBondDynamics": (_I, [_P, _F, _U, _F, _F, _F]),
+    "pbHostBondDynamicsRecord": (_I, [_P]),
+    "pbHostBondDynamicsInfo": (_I, [_P, _P, _P, _P, _P, _P, _P]),
+    "pbHostBondDynamicsRows": (_I, [_P, _P, _ULL, _PULL]),
     "pbHostFieldMap": (_I, [_P, _P, _P, _P]),
     "pbHostStructureFactor": (_I, [_P, _I, _I, _P, _U, _P]),
     "pbHostSetDisplay": (None, [_P, _I]),
